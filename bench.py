@@ -6,6 +6,8 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --config {0,1,2,3,4}     # the other BASELINE.json configs (parity-test cases; extra bench lines)
+    python bench.py --dump-outputs DIR       # also write the last timed step's outputs as DIR/<name>.npy (seeded inputs:
+                                             # two builds can be compared array for array)
 
 One step = RGB->YCbCr, encode (DWT + subband auto-encoder), entropy-model forward (context CNNs + likelihood + -log2)
 for the 3 colour planes, sum of bits; eval mode, fp32, synthetic inputs resident in HBM, random-init weights.
@@ -103,7 +105,39 @@ def parse_args():
     ap.add_argument("--plc-mode", default="", help="override LLDWT_PLC_MODE (f16x3 | f32) for the dominant conv")
     ap.add_argument("--storage", default="", help="override LLDWT_STORAGE (fp32 | fp16): storage type of the tree-context tensor "
                                                   "(BASELINE configs[4] names fp16; its own tolerance class, never the headline)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the bits per coefficient that "
+                         "rate_planes returns) as DIR/<name>.npy, float32, at most 64 MB in all (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: [(name, numpy array)] -> d/<name>.npy as float32 (float64 stays float64).  If the whole set is larger than
+    `limit`, every array is cut to the same fixed, seeded sample fraction of its flattened elements (sorted positions, the
+    same for every run with the same shapes).  -> {name: {"shape", "saved"}} for the result line."""
+    import numpy as np
+    arrays = [(n, v if v.dtype == np.float64 else v.astype(np.float32, copy=False)) for n, v in arrays]
+    total = sum(v.nbytes for _, v in arrays)
+    room = limit - 1024 * len(arrays)                       # the .npy headers count against the limit too
+    frac = min(1.0, room / total) if total else 1.0
+    os.makedirs(d, exist_ok=True)
+    info = {}
+    for i, (n, v) in enumerate(arrays):
+        flat = v.reshape(-1)
+        if frac < 1.0:
+            k = int(flat.size * frac)
+            idx = np.sort(np.random.RandomState(1337 + i).choice(flat.size, k, replace=False))
+            flat = flat[idx]
+        out = flat.reshape(v.shape) if frac == 1.0 else flat
+        np.save(os.path.join(d, n + ".npy"), out)
+        info[n] = {"shape": list(v.shape), "saved": int(out.size)}
+    return info
 
 
 # LLDWT_BENCH_REHEARSE=1: rehearsal of the N > 1 flow on a box with fewer GPUs than ranks -- the ranks share the visible
@@ -469,13 +503,17 @@ def main():
         roof = {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                 "kernel": "fixed CDF 9/7 %d-level forward (k_cdf97_* launches of one call)" % c["levels"]}
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         with torch.no_grad():
             y = ops.rgb_to_ycc(x)
             si_xe, si_xo = rate_planes(nets, y, False)
             ops.sum_into(si_xe, bit_acc)
             for t in si_xo:
                 ops.sum_into(t, bit_acc)
+        if keep:                                             # --dump-outputs: the last timed step's results
+            last["si_xe"], last["si_xo"] = si_xe, si_xo
 
     for i in range(a.warmup):
         step()
@@ -485,8 +523,8 @@ def main():
     torch.cuda.synchronize()
     dom["on"] = True
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
+    for i in range(a.steps):
+        step(keep=bool(a.dump_outputs) and i == a.steps - 1)
     torch.cuda.synchronize()
     parallel.barrier()
     torch.cuda.synchronize()
@@ -494,6 +532,13 @@ def main():
     dom["on"] = False
     log("timed region done: %.3f s for %d steps" % (dt, a.steps))
     dt = parallel.max_over_ranks(dt, dev)                    # the slowest rank defines the step time
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        arrays = [("si_xe", last["si_xe"])] + [("si_xo_%d" % i, t) for i, t in enumerate(last["si_xo"])]
+        dumped = dump_outputs(a.dump_outputs, [(n, (t if t.dtype == torch.float64 else t.float()).detach().cpu().numpy())
+                                               for n, t in arrays])
+        log("outputs of the last timed step written to %s" % a.dump_outputs)
+    last.clear()
 
     traffic, traffic_src = None, None
     tpath = os.path.join(REPO, "profiles", "traffic_current.json")
@@ -586,6 +631,8 @@ def main():
                    **({"rehearsal": True} if REHEARSE else {})},
         "roofline": roof,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if dom2["events"]:
         ms2 = sum(e0.elapsed_time(e1) for e0, e1 in dom2["events"])
         tf2 = dom2["work"] / (ms2 * 1e-3) / 1e12

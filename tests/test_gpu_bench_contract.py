@@ -50,3 +50,23 @@ def test_bench_other_config_is_labelled_truthfully():
     assert "configs[1]" in d["config"]["workload"] and "factorized" in d["config"]["workload"]
     assert d["config"]["per_gpu_images"] == 16 and d["config"]["image_hw"] == [256, 256]
     assert d["cpu_baseline"] is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's bits per coefficient; the inputs and weights are seeded, so runs with a
+    different number of timed steps leave the same arrays, and --steps sets the number of timed steps."""
+    import numpy as np
+    common = ("--config", "1", "--warmup", "1", "--train-steps", "0", "--no-cpu-baseline", "--no-hbm-kernels")
+    runs = []
+    for steps in (1, 3):
+        d = tmp_path / ("s%d" % steps)
+        line = _run(*common, "--steps", str(steps), "--dump-outputs", str(d))
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert set(line["dump_outputs"]["arrays"]) == {"si_xe", "si_xo_0", "si_xo_1", "si_xo_2"}
+        runs.append({f: np.load(d / f) for f in os.listdir(d)})
+    assert set(runs[0]) == {"si_xe.npy", "si_xo_0.npy", "si_xo_1.npy", "si_xo_2.npy"}
+    assert sum(v.nbytes for v in runs[0].values()) <= 64 * 1024 * 1024
+    for f, v in runs[0].items():
+        assert v.dtype == np.float32 and v.shape[:2] == (3, 16) and np.isfinite(v).all(), f
+        assert (v == runs[1][f]).all(), f
+    assert float(runs[0]["si_xe.npy"].sum()) > 0

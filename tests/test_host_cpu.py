@@ -226,3 +226,28 @@ def test_precision_names_and_traffic_hashes(monkeypatch):
     assert not bench.traffic_is_current({}, ("conv_f16x3.hip",))
     tj = json.load(open(os.path.join(REPO, "profiles", "traffic_current.json")))
     assert set(tj["source_hashes"]) >= {"conv_f16x3.hip", "lifting_f16.hip"}
+
+
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: arrays within the limit are written whole as float32; a larger set is cut to the same seeded
+    sample on every call, within the limit."""
+    import numpy as np
+    import bench
+    a = np.arange(24, dtype=np.float16).reshape(2, 3, 4)
+    b = np.linspace(0, 1, 1000)
+    info = bench.dump_outputs(str(tmp_path / "whole"), [("a", a), ("b", b)])
+    assert info == {"a": {"shape": [2, 3, 4], "saved": 24}, "b": {"shape": [1000], "saved": 1000}}
+    ga, gb = np.load(tmp_path / "whole" / "a.npy"), np.load(tmp_path / "whole" / "b.npy")
+    assert ga.dtype == np.float32 and (ga == a).all() and gb.dtype == np.float64 and (gb == b).all()
+    big = [("x", np.random.RandomState(0).rand(50000).astype(np.float32)), ("y", np.arange(30000, dtype=np.float32))]
+    limit = 40000 * 4 + 2048
+    bench.dump_outputs(str(tmp_path / "s1"), big, limit=limit)
+    bench.dump_outputs(str(tmp_path / "s2"), big, limit=limit)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["x.npy", "y.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= limit
+    for f in files:
+        s1, s2 = np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)
+        assert s1.size > 0 and (s1 == s2).all()
+    y = np.load(tmp_path / "s1" / "y.npy")
+    assert (np.diff(y) > 0).all()                     # sorted positions of the flattened array
