@@ -53,7 +53,15 @@ constexpr int F1_PP = 3 * 6 * 18;               // parent values under a tile (s
 constexpr int F1_LDS = F3_LDS + F1_COL + 1536;  // + the parent patch: 159,552 B
 // behind the (hi, lo) fp16 fragments: a bf16 copy of the scaled weights, half a step's bytes per step (one-product bf16 mode)
 static inline int64_t f1_bf_off(int cmid) { return F1_HDR + (int64_t)cdiv(cmid, F3_CK) * F1_CHUNK_BYTES; }
-static inline int64_t f1_plane_bytes(int cmid) { return f1_bf_off(cmid) + (int64_t)cdiv(cmid, F3_CK) * (F1_CHUNK_BYTES / 2); }
+// then the 16x16x32 fragments of the Winograd kernel (k_plc_wino): [chunk of 16 channels][hi|lo][lane][8 x fp16],
+// A[row = channel lane&15][k = 8*(lane>>4) + j]
+constexpr int W3_CK = 16;                       // input channels per chunk of the Winograd kernel
+static inline __host__ __device__ int w3_nch(int cin) { return (cin + W3_CK - 1) / W3_CK; }
+static inline __host__ __device__ int64_t f1_w16_off(int cmid) {
+    const int nch = (cmid + F3_CK - 1) / F3_CK;
+    return F1_HDR + (int64_t)nch * F1_CHUNK_BYTES + (int64_t)nch * (F1_CHUNK_BYTES / 2);
+}
+static inline int64_t f1_plane_bytes(int cmid) { return f1_w16_off(cmid) + (int64_t)w3_nch(cmid) * F3_STEP_BYTES; }
 
 static inline int f3_nch(int cin) { return (int)cdiv(cin, F3_CK); }
 static inline int f3_nocb(int cout) { return (int)cdiv(cout, F3_OCB); }
@@ -61,9 +69,15 @@ static inline __host__ __device__ int64_t f3_bf_off_n(int nocb, int nch) {
     // + 5 steps of padding: the kernel prefetches weight fragments 5 steps ahead without a bounds branch
     return F3_HDR + (int64_t)nocb * 4 * nch * F3_CHUNK_BYTES + 5 * F3_STEP_BYTES;
 }
+// the (hi, lo) fp16 steps, then a bf16 copy at half the bytes per step (same 5 steps of padding), then the Winograd section of
+// k_plc_wino: [hdr: s_u][ocb][wave][chunk of 16][12 steps (dy, xi)][hi|lo][lane][8 x fp16] + 5 steps of padding
+constexpr int W3_NST = 12;                       // weight steps (dy, xi) per chunk
+static inline __host__ __device__ int64_t f3_wino_off(int cin, int cout) {
+    const int nocb = (cout + F3_OCB - 1) / F3_OCB, nch = (cin + F3_CK - 1) / F3_CK;
+    return f3_bf_off_n(nocb, nch) + (int64_t)nocb * 4 * nch * (F3_CHUNK_BYTES / 2) + 5 * (F3_STEP_BYTES / 2);
+}
 static inline int64_t f3_plane_bytes(int cin, int cout) {
-    // the (hi, lo) fp16 steps, then a bf16 copy at half the bytes per step (same 5 steps of padding)
-    return f3_bf_off_n(f3_nocb(cout), f3_nch(cin)) + (int64_t)f3_nocb(cout) * 4 * f3_nch(cin) * (F3_CHUNK_BYTES / 2) + 5 * (F3_STEP_BYTES / 2);
+    return f3_wino_off(cin, cout) + F3_HDR + (int64_t)f3_nocb(cout) * 4 * w3_nch(cin) * W3_NST * F3_STEP_BYTES + 5 * F3_STEP_BYTES;
 }
 
 __device__ __forceinline__ float pow2_scale_for(float amax) {
@@ -194,6 +208,16 @@ __global__ void k_f1_pack(const float* __restrict__ w1, const float* __restrict_
         fr[(chunk * 2 + ks) * 1024 + lane * 8 + j] = hi;
         fr[(chunk * 2 + ks) * 1024 + 512 + lane * 8 + j] = (_Float16)(v - (float)hi);
         reinterpret_cast<__bf16*>(pp + F1_HDR + (int64_t)nch * F1_CHUNK_BYTES)[(chunk * 2 + ks) * 512 + lane * 8 + j] = (__bf16)v;
+    }
+    _Float16* f16 = reinterpret_cast<_Float16*>(pp + f1_w16_off(cmid));
+    for (int i = tid; i < w3_nch(cmid) * 512; i += 256) {
+        const int j = i & 7, lane = (i >> 3) & 63, chunk = i >> 9;
+        const int c = chunk * W3_CK + (lane & 15), k = 8 * (lane >> 4) + j;
+        float v = 0.f;
+        if (c < cmid && k < 27) v = wp[c * 27 + k] * sw1;
+        const _Float16 hi = (_Float16)v;
+        f16[chunk * 1024 + lane * 8 + j] = hi;
+        f16[chunk * 1024 + 512 + lane * 8 + j] = (_Float16)(v - (float)hi);
     }
 }
 
@@ -753,6 +777,379 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     F3_STAMP(11)
     F3_STAMP(15)
 }
+
+// ======================================================================================================================
+// Row-wise Winograd F(2,3) form of the fused pair (MODE 2, PREC 0; the default -- LLDWT_PLC_ALGO=direct keeps the kernel
+// above).  Two outputs of a 3-tap row filter from four products instead of six: for a pixel pair (x, x+1) of an output row
+// and one filter row dy, with the input window d0..d3 = row dy, pixels x-1 .. x+2, and the weight row g0..g2
+//     U = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2)           (weights, formed in fp64 at pack time, k_f3w_pack)
+//     V = (d0-d2, d1+d2, d2-d1, d1-d3)                    (activations, formed in fp32 before the split)
+//     M_xi = sum_ic sum_dy U_xi V_xi,   y_x = M0+M1+M2,   y_x+1 = M1-M2-M3
+// The main conv issues 3 dy x 4 xi MFMA k-steps per pixel PAIR instead of 9 taps per pixel: two thirds of the MFMAs.
+// Scales: |V| <= 2 max|d|, so the activation scale is half the direct kernel's; the weight scale comes from max|U|
+// (<= 1.5 max|g|).  tools/winograd_numerics.py emulates both forms: the error stays at the direct form's level.
+//
+// Kernel shape: the direct kernel's workgroup tile (128 output channels x 8 rows x 32 pixels = 16 pixel pairs per row);
+//   wave w owns channels 32w..32w+31 x all 128 pairs = 4 xi x 4 N-tiles of 32 pairs (2 rows x 16 pairs) = 16 accumulator
+//   tiles of 32x32 (256 registers).  K loop: chunks of 16 input channels (one 32x32x16 k-step): 12 units (dy, xi) of
+//   4 N-tiles x 3 products per chunk.
+//   V image in LDS: [10 patch rows][4 xi][16 pairs][16 ch] fp16, hi and lo, double-buffered (80 KB).  The 16-byte halves of
+//      an entry swap places on bit 3 of the pair index: each 16-lane group of a ds_read_b128 hits 16 distinct slots.
+//   The first conv (3 -> cmid, K = 27 -> 32) is RECOMPUTED on four pixel sets shifted by s = 0..3 (pixel 2p + s of pair p),
+//      so that d0..d3 of a pair land in one lane and V is lane-local arithmetic -- no cross-lane moves.  It runs on
+//      v_mfma_f32_16x16x32_f16 (16 channels x 16 pairs, K = 32 in one step): 4 shifts x 3 products per patch row, 10 patch
+//      rows per chunk (waves 0, 1 take three, waves 2, 3 two and one dead row).  Its B operand is the split im2col of the
+//      parent patch, built once per tile in LDS as [pixel parity][row][17 pixels] at a 144-byte pitch (9 slots: the 16
+//      pairs one read touches map to 16 distinct slots).
+constexpr int W3_NE = F3_IH * 4 * 16;            // V entries: 10 rows x 4 xi x 16 pairs = 640
+constexpr int W3_PART = W3_NE * 32;              // 20,480 B: one V image (hi or lo)
+constexpr int W3_BUF = 2 * W3_PART;
+constexpr int W3_DUMP = 2 * W3_BUF;              // 64-byte slot: dead conv1 rows write here; [32, 48) the amax reduction
+constexpr int W3_COLP = 144;                     // im2col pitch
+constexpr int W3_COL = W3_DUMP + 64;
+constexpr int W3_PP = W3_COL + 2 * F3_IH * 17 * W3_COLP;   // parent patch (F1_PP floats)
+constexpr int W3_LDS = W3_PP + 1536;             // 132,480 B
+constexpr int W3_RING = 6;                       // weight steps in flight + 1 (12 % W3_RING == 0: the ring slot of a unit is
+                                                 // the same in every chunk)
+static_assert(12 % W3_RING == 0 && W3_RING <= 6, "weight ring");
+static_assert(W3_PP % 16 == 0 && F1_PP * 4 <= 1536, "LDS layout");
+
+// The first conv's 12 MFMAs of one patch row (4 shifted pixel sets x 3 products) with their results in VGPRs.  As builtins their
+// results take accumulator registers, and the main loop's 16 tiles fill all 256 of them: the compiler then moves main tiles
+// in and out around every row.  Hazards inside the statement: each chain takes the previous result whole as C (0 wait
+// states); the trailing 21 states cover the read of D by whatever follows (12 for this 8-pass MFMA).
+__device__ __forceinline__ void w3_row_mma(f4_t (&t)[4], const h8_t& wh, const h8_t& wl, const h8_t (&ch)[4], const h8_t (&cl)[4]) {
+    asm volatile(
+        "v_mfma_f32_16x16x32_f16 %0, %4, %6, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %4, %7, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %2, %4, %8, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %3, %4, %9, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %0, %5, %10, %0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %5, %11, %1\n\t"
+        "v_mfma_f32_16x16x32_f16 %2, %5, %12, %2\n\t"
+        "v_mfma_f32_16x16x32_f16 %3, %5, %13, %3\n\t"
+        "v_mfma_f32_16x16x32_f16 %0, %5, %6, %0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %5, %7, %1\n\t"
+        "v_mfma_f32_16x16x32_f16 %2, %5, %8, %2\n\t"
+        "v_mfma_f32_16x16x32_f16 %3, %5, %9, %3\n\t"
+        "s_nop 7\n\ts_nop 7\n\ts_nop 4"
+        : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
+        : "v"(wl), "v"(wh), "v"(ch[0]), "v"(ch[1]), "v"(ch[2]), "v"(ch[3]), "v"(cl[0]), "v"(cl[1]), "v"(cl[2]), "v"(cl[3]));
+}
+
+__device__ __forceinline__ void wino_u(const float* g, double (&u)[4]) {
+    const double g0 = g[0], g1 = g[1], g2 = g[2];
+    u[0] = g0; u[1] = (g0 + g1 + g2) * 0.5; u[2] = (g0 - g1 + g2) * 0.5; u[3] = g2;
+}
+
+// max |U| per plane into the Winograd header's [1]
+__global__ void k_f3w_umax(const float* __restrict__ w, int64_t nrows, uint8_t* __restrict__ packed, int64_t plane_bytes, int64_t woff) {
+    const int plane = blockIdx.y;
+    float m = 0.f;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
+        double u[4];
+        wino_u(w + ((int64_t)plane * nrows + i) * 3, u);
+        for (int k = 0; k < 4; ++k) m = fmaxf(m, fabsf((float)u[k]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
+    float* hdr = reinterpret_cast<float*>(packed + (int64_t)plane * plane_bytes + woff);
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(reinterpret_cast<int*>(hdr + 1), __float_as_int(m));
+}
+
+// U fragments: step (ocb, wave, chunk, st = dy*4 + xi), A[row = oc lane&31][k = ic 8*(lane>>5) + j]
+__global__ void k_f3w_pack(const float* __restrict__ w, uint8_t* __restrict__ packed, int cin, int cout, int64_t plane_bytes, int64_t woff) {
+    const int plane = blockIdx.y;
+    uint8_t* pp = packed + (int64_t)plane * plane_bytes + woff;
+    float* hdr = reinterpret_cast<float*>(pp);
+    const double su = pow2_scale_for(hdr[1]);
+    const int nch = w3_nch(cin), nocb = (cout + F3_OCB - 1) / F3_OCB;
+    const int64_t n = (int64_t)nocb * 4 * nch * W3_NST * 64 * 8;
+    const float* wp = w + (int64_t)plane * cout * cin * 9;
+    _Float16* out = reinterpret_cast<_Float16*>(pp + F3_HDR);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t r = i;
+        const int j = (int)(r % 8); r /= 8;
+        const int lane = (int)(r % 64); r /= 64;
+        const int st = (int)(r % W3_NST); r /= W3_NST;
+        const int chunk = (int)(r % nch); r /= nch;
+        const int wv = (int)(r % 4); r /= 4;
+        const int ocb = (int)r;
+        const int oc = ocb * F3_OCB + wv * 32 + (lane & 31), ic = chunk * W3_CK + 8 * (lane >> 5) + j;
+        const int dy = st >> 2, xi = st & 3;
+        float v = 0.f;
+        if (oc < cout && ic < cin) {
+            double u[4];
+            wino_u(wp + ((int64_t)oc * cin + ic) * 9 + dy * 3, u);
+            v = (float)(u[xi] * su);
+        }
+        const _Float16 hi = (_Float16)v;
+        const int64_t step = ((int64_t)(ocb * 4 + wv) * nch + chunk) * W3_NST + st;
+        out[step * 1024 + lane * 8 + j] = hi;
+        out[step * 1024 + 512 + lane * 8 + j] = (_Float16)(v - (float)hi);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) hdr[0] = (float)su;
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_plc_wino(F3Args a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t z = blockIdx.z;
+    const int plane = (int)(z / a.batch);
+    const int ocb = blockIdx.y;
+    const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+    const int y0 = ty * F3_TH, x0 = tx * F3_TW;
+    const int h = a.h, w = a.w;
+    const int64_t hw = (int64_t)h * w;
+
+    F3_STAMP(0)
+    F3_STAMP(14)
+    const uint8_t* pp = a.packed + (int64_t)plane * a.plane_bytes + f3_wino_off(a.cin, a.cout);
+    const float su = *reinterpret_cast<const float*>(pp);
+    const uint8_t* pk1 = a.packed1 + (int64_t)plane * a.plane_bytes1;
+    const float* h1 = reinterpret_cast<const float*>(pk1);
+    const float* bias1 = h1 + 16;
+    // the weight ring's first steps and the first conv's chunk-0 operands: in flight during the whole prologue
+    const uint8_t* wbase = pp + F3_HDR + ((int64_t)(ocb * 4 + wave) * a.nch) * (W3_NST * F3_STEP_BYTES) + lane * 16;
+    half8 ah[W3_RING], al[W3_RING];
+#pragma unroll
+    for (int i = 0; i < W3_RING - 1; ++i) {
+        ah[i] = *reinterpret_cast<const half8*>(wbase + i * F3_STEP_BYTES);
+        al[i] = *reinterpret_cast<const half8*>(wbase + i * F3_STEP_BYTES + 1024);
+    }
+    half8 w1h, w1l;
+    f4_t b1r, b1v;
+#define W3_FUSED_LOAD(C1)                                                                                             \
+    {                                                                                                                 \
+        const uint8_t* w1_ = pk1 + f1_w16_off(a.cin) + (int64_t)((C1) / W3_CK) * F3_STEP_BYTES + lane * 16;           \
+        w1h = *reinterpret_cast<const half8*>(w1_);                                                                   \
+        w1l = *reinterpret_cast<const half8*>(w1_ + 1024);                                                            \
+        b1r = *reinterpret_cast<const f4_t*>(bias1 + (C1) + 4 * (lane >> 4));                                        \
+    }
+    W3_FUSED_LOAD(0)
+
+    // ---- the parent patch (as in the direct kernel), then its split im2col for every patch pixel, once per tile
+    const int hp = h >> 1, wp_ = w >> 1;
+    const float* par = a.parent + z * 3 * (int64_t)hp * wp_;
+    float* PP = reinterpret_cast<float*>(lds + W3_PP);
+    float amax = 0.f;
+#pragma unroll
+    for (int i = tid; i < F1_PP; i += 256) {
+        const int ci = i / 108, rem = i - ci * 108, r = rem / 18, c = rem - r * 18;
+        const int Yp = (y0 >> 1) - 1 + r, Xp = (x0 >> 1) - 1 + c;
+        const bool in = Yp >= 0 && Yp < hp && Xp >= 0 && Xp < wp_;
+        const float v = par[(int64_t)ci * hp * wp_ + min(max(Yp, 0), hp - 1) * wp_ + min(max(Xp, 0), wp_ - 1)];
+        const float vz = in ? v : 0.f;
+        PP[i] = vz;
+        amax = fmaxf(amax, fabsf(vz));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    float* red = reinterpret_cast<float*>(lds + W3_DUMP + 32);
+    if (lane == 0) red[wave] = amax;
+    __syncthreads();
+    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float s_p = pow2_scale_for(amax);
+    // V spans twice the activation bound: half the direct kernel's scale keeps max|V * sx| below 2^15
+    const float sx = 0.5f * pow2_scale_for(amax * h1[1] + h1[2]);
+    const float out_scale = (1.f / sx) * (1.f / su);
+    const float inv1sx = (1.f / s_p) * (1.f / h1[0]) * sx;
+    for (int px = tid; px < F3_NPX; px += 256) {
+        const int ly = px / F3_IW, lx = px - ly * F3_IW;
+        uint8_t* dst = lds + W3_COL + ((lx & 1) * (F3_IH * 17) + ly * 17 + (lx >> 1)) * W3_COLP;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float v8[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = 8 * g + j, q = k < 27 ? k : 26;         // k >= 27 meets zero weights
+                const int dy = (q % 9) / 3, dx = q % 3;
+                v8[j] = PP[(q / 9) * 108 + ((ly + dy) >> 1) * 18 + ((lx + dx) >> 1)] * s_p;
+            }
+            half8 ch_, cl_;
+            split8v(v8, ch_, cl_);
+            *reinterpret_cast<half8*>(dst + g * 16) = ch_;
+            *reinterpret_cast<half8*>(dst + 64 + g * 16) = cl_;
+        }
+    }
+
+    // ---- this wave's first-conv rows (wave, wave + 4, wave + 8; the last one dead for waves 2, 3): pair p = lane&15,
+    // channel group g = lane>>4 (D rows 4g .. 4g+3 of the 16x16 tile)
+    const int p = lane & 15, g = lane >> 4;
+    int colw[3], vw[3];
+    unsigned pinm = 0;                 // bit 4*B + s: pixel 2p + s of row B inside the image
+#pragma unroll
+    for (int B = 0; B < 3; ++B) {
+        const int r = wave + 4 * B;
+        const bool live = r < F3_IH;
+        const int rr = live ? r : 0;
+        colw[B] = W3_COL + (rr * 17 + p) * W3_COLP + g * 16;
+        vw[B] = live ? ((rr * 4) * 16 + p) * 32 + (((g >> 1) ^ (p >> 3)) * 16) + (g & 1) * 8 : -1;
+        const int gy = y0 - 1 + r;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int gx = x0 - 1 + 2 * p + s;
+            if (live && gy >= 0 && gy < h && gx >= 0 && gx < w) pinm |= 1u << (4 * B + s);
+        }
+    }
+    // row B of the first conv for channels C1 .. C1+15 on the 4 shifted pixel sets, in four stages that run in consecutive
+    // units of the chunk loop (one wave per SIMD: nothing else hides an LDS read, an MFMA result or a block of vector
+    // instructions): READ the im2col fragments, MMA, ACT = bias + LeakyReLU, STORE = V (4 xi) -> split -> the LDS image at DST
+    half8 c1h[4], c1l[4];
+    f4_t t1[4];
+    float d1[4][4];                    // [shift][channel]: LeakyReLU(conv1) of the row, zero outside the image
+#define W3_ROW_READ(B)                                                                                                \
+    {                                                                                                                 \
+        _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                                               \
+            const uint8_t* c_ = lds + colw[B] + ((s & 1) * (F3_IH * 17) + (s >> 1)) * W3_COLP;                        \
+            c1h[s] = *reinterpret_cast<const half8*>(c_);                                                             \
+            c1l[s] = *reinterpret_cast<const half8*>(c_ + 64);                                                        \
+        }                                                                                                             \
+    }
+#define W3_ROW_MMA() w3_row_mma(t1, w1h, w1l, c1h, c1l);
+#define W3_ROW_ACT(B)                                                                                                 \
+    {                                                                                                                 \
+        if ((B) == 0) b1v = b1r * sx;                                                                                 \
+        _Pragma("unroll") for (int s = 0; s < 4; ++s)                                                                 \
+            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                           \
+                const float v_ = __builtin_fmaf(t1[s][q], inv1sx, b1v[q]);                                            \
+                d1[s][q] = (pinm >> (4 * (B) + s)) & 1 ? fmaxf(v_, 0.01f * v_) : 0.f;                                 \
+            }                                                                                                         \
+    }
+#define W3_ROW_STORE(B, DST)                                                                                          \
+    {                                                                                                                 \
+        const bool livev_ = vw[B] >= 0;                                                                               \
+        uint8_t* d0_ = livev_ ? (DST) + vw[B] : lds + W3_DUMP;                                                        \
+        const int xs_ = livev_ ? 16 * 32 : 0, lo_ = livev_ ? W3_PART : 8;                                             \
+        _Pragma("unroll") for (int xi = 0; xi < 4; ++xi) {                                                            \
+            float v4_[4];                                                                                             \
+            _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                             \
+                v4_[q] = xi == 0 ? d1[0][q] - d1[2][q] : xi == 1 ? d1[1][q] + d1[2][q]                                \
+                       : xi == 2 ? d1[2][q] - d1[1][q] : d1[1][q] - d1[3][q];                                         \
+            h4_t hi_, lo4_;                                                                                           \
+            split4v(v4_, hi_, lo4_);                                                                                  \
+            *reinterpret_cast<h4_t*>(d0_ + xi * xs_) = hi_;                                                           \
+            *reinterpret_cast<h4_t*>(d0_ + xi * xs_ + lo_) = lo4_;                                                    \
+        }                                                                                                             \
+    }
+    __syncthreads();                   // the im2col is read across lanes
+
+    floatx16 acc[4][4];                // [xi][N-tile]
+#pragma unroll
+    for (int xi = 0; xi < 4; ++xi)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[xi][n][q] = 0.f;
+
+#pragma unroll
+    for (int B = 0; B < 3; ++B) {
+        W3_ROW_READ(B)
+        W3_ROW_MMA()
+        W3_ROW_ACT(B)
+        W3_ROW_STORE(B, lds)
+    }
+    __syncthreads();
+
+    // B fragment of N-tile n, filter row dy, xi: pair p of output row 2n + ((lane>>4)&1), channel half lane>>5
+    const int boff = (((lane >> 4) & 1) * 64 + p) * 32 + (((lane >> 5) ^ (p >> 3)) * 16);
+    F3_STAMP(1)
+    // Per chunk: 12 units (dy, xi), 12 MFMAs each (384 matrix cycles); interleaved between them as in the direct kernel: the
+    // 8 fragment reads of unit u+1, the weight step u+5 (ring of 6, continuous across chunks, pack padded by 5 steps), the
+    // next chunk's first-conv operands (unit 0) and its three rows into the idle buffer, each row over four units (READ at
+    // 2, 5, 8; MMA at 3, 6, 9; ACT at 4, 7, 10; STORE at 5, 8, 11).  One barrier per chunk.
+    for (int chunk = 0; chunk < a.nch; ++chunk) {
+        if (chunk < 16 && !(chunk & 1)) F3_STAMP(2 + (chunk >> 1))
+        const int buf = chunk & 1;
+        const uint8_t* wp = wbase + (int64_t)chunk * (W3_NST * F3_STEP_BYTES);
+        const uint8_t* bb = lds + buf * W3_BUF + boff;
+        uint8_t* sdst = lds + (buf ^ 1) * W3_BUF;
+        const int c1 = (chunk + 1 < a.nch ? chunk + 1 : chunk) * W3_CK;     // chunk being staged (last: itself, unused)
+        half8 bh[2][4], bl[2][4];
+#define W3_BLOAD(U, SET)                                                                               \
+        {                                                                                              \
+            const int dy_ = (U) >> 2, xi_ = (U) & 3;                                                   \
+            _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                            \
+                const int off = ((2 * n + dy_) * 4 + xi_) * 512;                                       \
+                bh[SET][n] = *reinterpret_cast<const half8*>(bb + off);                                \
+                bl[SET][n] = *reinterpret_cast<const half8*>(bb + W3_PART + off);                      \
+            }                                                                                          \
+        }
+        W3_BLOAD(0, 0)
+        // all 8 reads of unit 0 in flight before its first MFMA: interleaved by the unit's schedule, each would wait alone
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < W3_NST; ++u) {
+            const int xi = u & 3;
+            ah[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES);
+            al[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES + 1024);
+            if (u + 1 < W3_NST) W3_BLOAD(u + 1, (u + 1) & 1)
+            if (u == 0) W3_FUSED_LOAD(c1)
+            if (u == 2 || u == 5 || u == 8) W3_ROW_READ((u - 2) / 3)
+            if (u == 3 || u == 6 || u == 9) W3_ROW_MMA()
+            if (u == 4 || u == 7 || u == 10) W3_ROW_ACT((u - 4) / 3)
+            if (u == 5 || u == 8 || u == 11) W3_ROW_STORE((u - 5) / 3, sdst)
+            const half8 A_h = ah[u % W3_RING], A_l = al[u % W3_RING];
+            // product-major: the three MFMAs of one accumulator are 4 apart (no back-to-back dependent pair)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[xi][n] = mma32<0>(A_l, bh[u & 1][n], acc[xi][n]);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[xi][n] = mma32<0>(A_h, bl[u & 1][n], acc[xi][n]);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[xi][n] = mma32<0>(A_h, bh[u & 1][n], acc[xi][n]);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        // one LDS read
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                        // one global load
+                __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);                        // a few vector ALU instructions
+                __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                        // one LDS write
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#undef W3_BLOAD
+        __syncthreads();
+    }
+#undef W3_ROW_READ
+#undef W3_ROW_MMA
+#undef W3_ROW_ACT
+#undef W3_ROW_STORE
+#undef W3_FUSED_LOAD
+
+    F3_STAMP(10)
+    // ---- epilogue: the inverse transform is lane-local (the four M_xi tiles share one layout): D col = lane&31 = pair p of
+    // row 2n + ((lane>>4)&1), D row = (q&3) + 8*(q>>2) + 4*(lane>>5) = channel of the wave's 32.  Two adjacent pixels per
+    // store (w is even, so a pair is either inside the image or wholly outside it)
+    const int ocw = ocb * F3_OCB + __builtin_amdgcn_readfirstlane(wave) * 32;
+    const int och = 4 * (lane >> 5), orow = (lane >> 4) & 1;
+    float* ybase = a.y + (z * a.cout + ocw) * hw + (int64_t)y0 * w;                  // wave-uniform
+    const unsigned loff = (unsigned)och * (unsigned)hw + (unsigned)(orow * w + x0 + 2 * p);
+    const bool full = y0 + F3_TH <= h && x0 + F3_TW <= w;                            // uniform
+    // the activation and the bounds resolved outside the store loops (as in the direct kernel's epilogue)
+#define W3_EPI(COND, ACT0, ACT1)                                                                                      \
+    _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                                  \
+        const int ocq = (q & 3) + 8 * (q >> 2);                                                                       \
+        if (ocw + ocq + och < a.cout) {                                                                               \
+            const float bq = a.bias ? a.bias[plane * a.cout + ocw + ocq + och] : 0.f;                                 \
+            float* yq = ybase + (int64_t)ocq * hw + loff;                                                             \
+            _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                                           \
+                const float v0 = (acc[0][n][q] + acc[1][n][q] + acc[2][n][q]) * out_scale + bq;                       \
+                const float v1 = (acc[1][n][q] - acc[2][n][q] - acc[3][n][q]) * out_scale + bq;                       \
+                if (COND) *reinterpret_cast<f2_t*>(yq + 2 * n * w) = f2_t{ACT0, ACT1};                                \
+            }                                                                                                         \
+        }                                                                                                             \
+    }
+    if (full && a.act != LLDWT_ACT_TANH) {
+        const float slope = a.act == LLDWT_ACT_LRELU ? 0.01f : (a.act == LLDWT_ACT_RELU ? 0.f : 1.f);   // none: max(v, v)
+        W3_EPI(true, fmaxf(v0, v0 * slope), fmaxf(v1, v1 * slope))
+    } else {
+        const bool colin = x0 + 2 * p < w;        // w is even: a pair is either inside the image or wholly outside it
+        W3_EPI(colin && y0 + 2 * n + orow < h, act_apply(v0, a.act), act_apply(v1, a.act))
+    }
+#undef W3_EPI
+    F3_STAMP(11)
+    F3_STAMP(15)
+}
 #undef F3_STAMP
 
 }  // namespace lldwt
@@ -765,6 +1162,13 @@ using namespace lldwt;
 static const int g_f3_shape16 = [] { const char* e = getenv("LLDWT_PLC_SHAPE"); return (e && !strcmp(e, "16")) ? 1 : 0; }();
 static int f3_shape16() { return g_f3_shape16; }
 extern "C" int lldwt_plc_shape16(void) { return g_f3_shape16; }
+
+// Algorithm of the fused pair at PREC 0 with the 32x32x16 shape, fixed for the process: row-wise Winograd F(2,3) (k_plc_wino,
+// the default: two thirds of the direct kernel's MFMAs) or the direct kernel (LLDWT_PLC_ALGO=direct, kept for A/B timing and
+// the tests).  The other modes and the S16 shape always run the direct kernel.
+static const int g_plc_wino = [] { const char* e = getenv("LLDWT_PLC_ALGO"); return (e && !strcmp(e, "direct")) ? 0 : 1; }();
+static bool plc_wino_active() { return g_plc_wino && !g_f3_shape16; }
+extern "C" int lldwt_plc_winograd(void) { return plc_wino_active() ? 1 : 0; }
 
 extern "C" int64_t lldwt_conv_f16x3_packed_bytes(int cin, int cout) {
     if (cin <= 0 || cout <= 0) return -1;
@@ -784,6 +1188,18 @@ extern "C" int lldwt_conv_f16x3_pack(const float* w, void* packed, int cin, int 
     hipLaunchKernelGGL(k_f3_wmax, dim3(64, (unsigned)planes), dim3(256), 0, st, w, nw, reinterpret_cast<float*>(packed), pb);
     hipLaunchKernelGGL(k_f3_pack, dim3(1024, (unsigned)planes), dim3(256), 0, st, w, reinterpret_cast<uint8_t*>(packed), cin, cout, pb,
                        f3_shape16());
+    if (plc_wino_active()) {          // the fused pair's Winograd weights (the section stays unwritten when nothing reads it)
+        const int64_t wo = f3_wino_off(cin, cout);
+        for (int64_t p = 0; p < planes; ++p)
+            if (hipMemsetAsync(reinterpret_cast<char*>(packed) + p * pb + wo, 0, F3_HDR, st) != hipSuccess) {
+                set_error("conv_f16x3_pack: memset failed");
+                return LLDWT_EHIP;
+            }
+        hipLaunchKernelGGL(k_f3w_umax, dim3(64, (unsigned)planes), dim3(256), 0, st, w, (int64_t)cout * cin * 3,
+                           reinterpret_cast<uint8_t*>(packed), pb, wo);
+        hipLaunchKernelGGL(k_f3w_pack, dim3(1024, (unsigned)planes), dim3(256), 0, st, w, reinterpret_cast<uint8_t*>(packed), cin, cout,
+                           pb, wo);
+    }
     return check_launch("conv_f16x3_pack");
 }
 
@@ -917,7 +1333,18 @@ extern "C" int lldwt_plc_fused(const float* parent, float* y, const void* packed
     }
     dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)f3_nocb(cout), (unsigned)(planes * batch));
     const int prec = split_precision();
-    if (g_f3_shape16) {
+    if (prec == 0 && plc_wino_active()) {
+        static bool wattr_set = false;
+        if (!wattr_set) {
+            if (hipFuncSetAttribute((const void*)k_plc_wino, hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS) != hipSuccess) {
+                set_error("plc_fused: cannot reserve %d bytes of LDS", W3_LDS);
+                return LLDWT_EHIP;
+            }
+            wattr_set = true;
+        }
+        a.nch = w3_nch(cmid);
+        hipLaunchKernelGGL(k_plc_wino, grid, dim3(256), W3_LDS, (hipStream_t)stream, a);
+    } else if (g_f3_shape16) {
         if (prec == 1) hipLaunchKernelGGL((k_conv3_f16x3<2, 1, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);
         else if (prec == 2) hipLaunchKernelGGL((k_conv3_f16x3<2, 2, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);
         else hipLaunchKernelGGL((k_conv3_f16x3<2, 0, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);

@@ -513,6 +513,12 @@ def plc_shape():
     return 16 if _lib.load().lldwt_plc_shape16() else 32
 
 
+def plc_algo():
+    """Algorithm of plc_fused's split-fp16 32x32x16 path in this process: 'winograd' (row-wise F(2,3), default) or 'direct'
+    (LLDWT_PLC_ALGO=direct, or the 16x16x32 shape)."""
+    return "winograd" if _lib.load().lldwt_plc_winograd() else "direct"
+
+
 def conv_f16x3_pack(w):
     """(P,cout,cin,3,3) fp32 -> packed split-fp16 weights (uint8 tensor (P, bytes)) for conv3x3_f16x3."""
     lib = _lib.load()

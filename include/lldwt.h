@@ -381,6 +381,10 @@ int64_t lldwt_plc_fused_pack1_bytes(int cmid);
 /* 1 when this process packs and runs the split-fp16 3x3 conv kernels in the 16x16x32 MFMA shape (LLDWT_PLC_SHAPE=16, read when
  * the library loads), 0 for the default 32x32x16. */
 int lldwt_plc_shape16(void);
+/* 1 when lldwt_plc_fused runs its split-fp16 (precision 0) 32x32x16 path as row-wise Winograd F(2,3) (the default), 0 for the
+ * direct kernel (LLDWT_PLC_ALGO=direct, read when the library loads) or the 16x16x32 shape.  The packed sizes of
+ * lldwt_conv_f16x3_packed_bytes and lldwt_plc_fused_pack1_bytes include the Winograd sections either way. */
+int lldwt_plc_winograd(void);
 int lldwt_plc_fused_pack1(const float* w1, const float* b1, void* packed1, int cmid, int64_t planes, void* stream);
 int lldwt_plc_fused(const float* parent, float* y, const void* packed1, const void* packed2, const float* bias2, int cmid,
                     int cout, int act, int64_t planes, int64_t batch, int64_t h, int64_t w_, void* stream);

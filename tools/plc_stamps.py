@@ -37,7 +37,9 @@ def main():
     torch.cuda.synchronize()
     ops.set_diagnostics(1, None)
     s = st.cpu().numpy().astype(np.int64)
-    res = {"workgroups": nwg}
+    # k_plc_wino (the default, ops.plc_algo() == "winograd") stamps every second of its 16-channel chunks: a "chunk" below is 32
+    # channels either way; ideal_cycles_per_chunk is the direct kernel's
+    res = {"workgroups": nwg, "algo": ops.plc_algo()}
     d = np.diff(s[..., :12], axis=-1)
     names = ["prologue (gather, scales, chunk 0 staging, ring fill)"] + ["chunk %d" % i for i in range(8)] + ["epilogue stores"]
     cols = [0] + list(range(1, 9)) + [10 - 0]

@@ -57,11 +57,11 @@ def main():
             w.writerow([k, nf[k], "%.1f" % (fetch[k]["FETCH_SIZE"] / n), "%.1f" % (write.get(k, {}).get("WRITE_SIZE", 0.0) / max(nw[k], 1))] +
                        ["%.4g" % s.get(c, 0.0) for c in ("SQ_BUSY_CYCLES", "SQ_WAVE_CYCLES", "SQ_INSTS_MFMA", "SQ_INSTS_VALU",
                                                         "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY")])
-    dom = sorted((k for k in fetch if "k_conv3_f16x3" in k), key=lambda k: -nf[k])
+    dom = sorted((k for k in fetch if "k_conv3_f16x3" in k or "k_plc_wino" in k), key=lambda k: -nf[k])
     if dom:
         k = dom[0]
         fk, wk = fetch[k]["FETCH_SIZE"] / max(nf[k], 1), write[k]["WRITE_SIZE"] / max(nw[k], 1)
-        tj = {"kernel": k, "plc_mode": "f16x3", "fused": ("<2" in k or "ILi2E" in k), "launches": nf[k],
+        tj = {"kernel": k, "plc_mode": "f16x3", "fused": ("<2" in k or "ILi2E" in k or "k_plc_wino" in k), "launches": nf[k],
               "avg_fetch_KB_per_launch": fk, "avg_write_KB_per_launch": wk,
               "traffic_bytes_per_launch": (fk + wk) * 1024.0,
               "traffic_bytes_per_launch_if_every_fetch_were_16B_per_lane": (2.0 * fk + wk) * 1024.0,
