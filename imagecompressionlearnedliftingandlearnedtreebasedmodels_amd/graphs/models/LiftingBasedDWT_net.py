@@ -8,7 +8,9 @@ planes and the whole batch (plane-major tensors, per-plane weights stacked), ins
 
 Real entropy coding (``compress`` / ``test`` / ``compress_ar`` / ``decompress_ar``, :76-99,136-152,374-556) is built for
 the layer the reference builds it for, ``DWTConditioned2EntropyLayerZTsepSubbands``: the per-pixel Python loops become a
-wavefront schedule on the GPU (entropy_coding.py) and the range coder is the C-ABI's host rANS (ans.py).
+wavefront schedule on the GPU (entropy_coding.py) and the range coder is the C-ABI's host rANS (ans.py).  As extensions,
+``onlyEZWT`` (one parallel pass per level) and ``DWTConditioned2EntropyLayerZTBlock`` (four polyphase passes per level on the
+fused phase kernel, csrc/ztblock.hip) are coded too.
 """
 import math
 
@@ -543,6 +545,99 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return si_xe, si_list, xe_q, q_list
 
 
+    # ---------------------------------------------------------------- real entropy coding (EXTENSION: the reference has no
+    # test() for this layer).  compressai's contract, as for the other coded layers: xe and the coarsest level with the
+    # factorized priors; each finer level phase by phase (entropy_coding.code_ztblock_level), the contexts being the decoded
+    # parent and the decoded phases round(y - mu) + mu, symbols round(y - mu) under the Gaussian tables of get_scale_table().
+    # A level needs 4 host round trips in the decoder.  One rANS stream per (plane, image, tensor).
+    @staticmethod
+    def _require_clrch1(layers):
+        if layers[0].clrch != 1:
+            raise NotImplementedError("DWTConditioned2EntropyLayerZTBlock codes clrch == 1 only: with clrch == 3 its forward "
+                                      "rates 3 of the 9 subband channels (LiftingBasedDWT_net.py:716-744), so no coding is "
+                                      "defined")
+
+    @staticmethod
+    def _level_models(layers, i, L):
+        """GaussianConditional of subband j at finer level i (i = 0 next to the coarsest): ent_out_xo_list[(L-i-1)*3-j-1], the
+        reference's indexing; all carry get_scale_table() and bound 0.11, hence one set of host tables."""
+        idx = [(L - i - 1) * 3 - j - 1 for j in range(3)]
+        for l in layers:
+            for n in idx:
+                l.ent_out_xo_list[n].update_scale_table(get_scale_table())
+        from .entropy_coding import _Tables
+        ems = [layers[0].ent_out_xo_list[n] for n in idx]
+        return ems, _Tables(ems[0], get_scale_table())
+
+    @staticmethod
+    def _phase_packs(layers, i):
+        """ops.ztblock_pack of the phase-k nets of finer level i (k = 1..4): dep_k_list_{sigma,mu}[j + 3 i], every plane."""
+        packs = []
+        for k in range(1, 5):
+            nets = [[[getattr(l, "dep_%d_list_%s" % (k, kind))[j + 3 * i] for kind in ("sigma", "mu")] for j in range(3)]
+                    for l in layers]
+            srcs = [t for pl in nets for sub in pl for nt in sub for n in (0, 2, 4, 6, 8) for t in (nt[n].weight, nt[n].bias)]
+
+            def build(nets=nets):
+                return ops.ztblock_pack([torch.stack([torch.stack([torch.stack([getattr(nt[n], a) for nt in sub]) for sub in pl])
+                                                      for pl in nets]) for n in (0, 2, 4, 6, 8) for a in ("weight", "bias")])
+            packs.append(cached(layers[0], ("ztblock", i, k), srcs, build))
+        return packs
+
+    @staticmethod
+    def compress_planes(layers, out_xe, out_xo_list):
+        """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first), *_q the decoder's values."""
+        from . import entropy_coding as ec
+        cls = DWTConditioned2EntropyLayerZTBlock
+        cls._require_clrch1(layers)
+        L = len(out_xo_list)
+        with torch.no_grad():
+            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape)
+            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape)
+            s_list, q_list = [s], [q]
+            for i in range(L - 1):
+                x = out_xo_list[L - i - 2]
+                ems, tabs = cls._level_models(layers, i, L)
+                s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs)
+                s_list.append(s)
+                q_list.append(q)
+        s_list.reverse()
+        q_list.reverse()
+        return s_xe, s_list, xe_q, q_list
+
+    @staticmethod
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo):
+        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors."""
+        from . import entropy_coding as ec
+        cls = DWTConditioned2EntropyLayerZTBlock
+        cls._require_clrch1(layers)
+        L = len(shapes_xo)
+        with torch.no_grad():
+            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe)
+            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1])
+            q_list = [q]
+            for i in range(L - 1):
+                ems, tabs = cls._level_models(layers, i, L)
+                _, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, None, shapes_xo[L - i - 2], tabs,
+                                             strings_xo_list[L - i - 2])
+                q_list.append(q)
+        q_list.reverse()
+        return xe, q_list
+
+    @staticmethod
+    def test_planes(layers, out_xe, out_xo_list):
+        """Encode, then decode FROM THE STRINGS (same contract as the other coded layers' test_planes)."""
+        cls = DWTConditioned2EntropyLayerZTBlock
+        s_xe, s_xo, _, _ = cls.compress_planes(layers, out_xe, out_xo_list)
+        xe, xo = cls.decompress_planes(layers, s_xe, s_xo, out_xe.shape, [t.shape for t in out_xo_list])
+        return s_xe, s_xo, xe, xo
+
+    def test(self, out_xe, out_xo_list):
+        s_xe, s_xo, xe, xo = self.test_planes([self], out_xe[None].contiguous(), [t[None].contiguous() for t in out_xo_list])
+        one = lambda rows: rows[0][0] if len(rows[0]) == 1 else rows[0]
+        return one(s_xe), [one(r) for r in s_xo], xe[0], [t[0] for t in xo]
+
+
 # ------------------------------------------------------------------------------------------------ training path
 # Same maths as the eval path, but every op is a differentiable autograd.Function (forward AND backward are HIP
 # kernels; torch only keeps the tape and un-stacks the per-plane parameter gradients).  Built for the headline
@@ -888,9 +983,9 @@ def compress_planes(nets, x):
     x (P,B,C,H,W) -> (xhat, strings_xe[p][b], [strings_xo[p][b] per level])."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "test_planes"):
-        raise NotImplementedError("real entropy coding exists for conditioned2ZTsepSubbands (as in the reference) and, as an "
-                                  "extension, onlyEZWT; the other entropy layers have no test() (LiftingBasedDWT_net.py:"
-                                  "145-146 would fail there too)")
+        raise NotImplementedError("real entropy coding exists for conditioned2ZTsepSubbands (as in the reference) and, as "
+                                  "extensions, onlyEZWT and DWTConditioned2EntropyLayerZTBlock; the factorized layer has no "
+                                  "test() (LiftingBasedDWT_net.py:145-146 would fail there too)")
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
     s_xe, s_xo, xe_q, xo_q = type(em[0]).test_planes(em, out_xe, out_xo)
     xhat = decode_planes([n.autoencoder for n in nets], xe_q, xo_q)

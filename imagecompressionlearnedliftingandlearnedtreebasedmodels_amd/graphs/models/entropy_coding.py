@@ -259,6 +259,35 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
     return (None if sink.decoding else sink.flush()), out
 
 
+ZT_PHASES = ((0, 0), (0, 1), (1, 0), (1, 1))        # ee, eo, oe, oo: (row, column) offset of phase k in the level
+
+
+def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None):
+    """One finer level of DWTConditioned2EntropyLayerZTBlock (the reference's forward, LiftingBasedDWT_net.py:716-744, coded
+    with compressai's GaussianConditional contract).  parent (P,B,3,h,w): the DECODED coarser level; y (P,B,3,2h,2w) the
+    coefficients (encoder) or None (decoder); emodels: the GaussianConditional of each subband (build_indexes); packs[k]:
+    ops.ztblock_pack of the phase-(k+1) nets.
+
+    The four phases ee, eo, oe, oo run in sequence; each is ONE launch of lldwt_ztblock_phase for every plane, image and
+    subband (its contexts are the parent and the phases already decoded, round(y - mu) + mu), then one pass of the range
+    coder over every stream.  Symbols inside a stream: phase ascending, then subband, then raster order over the phase grid.
+    -> (strings or None, dequantised (P,B,3,2h,2w))."""
+    P, B, G, H, W = shape
+    h2, w2 = H // 2, W // 2
+    lev = torch.zeros(P, B, G, H, W, device=parent.device, dtype=torch.float32)
+    sink = _Sink(P, B, tables, strings)
+    for k, (r, c) in enumerate(ZT_PHASES):
+        params = ops.ztblock_phase(parent, lev, packs[k], k + 1)
+        sigma, mu = params[:, :, 0::2], params[:, :, 1::2]
+        idx = torch.stack([emodels[j].build_indexes(sigma[:, :, j]) for j in range(G)], 2)          # (P,B,3,h2,w2)
+        sym = None
+        if y is not None:
+            sym = torch.round(y[:, :, :, r::2, c::2] - mu).int().reshape(P, B, G * h2 * w2, 1)
+        sym = sink.step(idx.reshape(P, B, G * h2 * w2, 1), sym)
+        lev[:, :, :, r::2, c::2] = sym.reshape(P, B, G, h2, w2).float() + mu
+    return (None if sink.decoding else sink.flush()), lev
+
+
 class _FactorizedTables:
     """The per-channel CDF tables of one EntropyBottleneck as host int32 arrays."""
 

@@ -669,6 +669,53 @@ def gauss_rate(x, params, noise=None, want_q=False, bit_sum=None):
     return bits, q
 
 
+def ztblock_pack(ws):
+    """Pack the phase nets of DWTConditioned2EntropyLayerZTBlock for lldwt_ztblock_phase.  ws: the 10 tensors w1, b1, ..., w5,
+    b5 of the 5-layer net, each with leading dims (P, 3, 2) = (plane, subband, head 0 sigma / 1 mu): w1 (.., 32, k, 3, 3),
+    w2 (.., 32, 32, 3, 3), w3 / w4 (.., 32, 32, 1, 1), w5 (.., 1, 32, 1, 1), biases (.., 32) / (.., 1).
+    -> flat fp32 device tensor of P*3*2 records (csrc/ztblock.hip): MFMA B fragments of conv2 and the two 32 -> 32 1x1 layers
+    (lane l of k-step s holds W[16 nb + (l & 15)][4 s + (l >> 4)], K ordered tap-major / channel-minor), conv1 as rows
+    ci*9 + tap, then the biases and the last layer."""
+    w1, b1, w2, b2, w3, b3, w4, b4, w5, b5 = [t.detach().float() for t in ws]
+    lead = w1.shape[:3]
+    if lead[1:] != (3, 2) or w1.shape[3:] not in [(32, k, 3, 3) for k in range(1, 5)] or w2.shape[3:] != (32, 32, 3, 3) or \
+            w3.shape[3:] != (32, 32, 1, 1) or w4.shape[3:] != (32, 32, 1, 1) or w5.shape[3:] != (1, 32, 1, 1):
+        raise _lib.LLDWTError("ztblock_pack: expected the (P,3,2)-stacked 3x3 k->32, 3x3 32->32, 1x1 32->32 x2, 1x1 32->1 "
+                              "nets (got %s)" % [tuple(t.shape) for t in ws])
+    R = int(lead[0]) * 6
+    k = w1.shape[4]
+
+    def frag(wk, nks):                                   # (R, K, 32) [k][n] -> (R, nks, 2, 64)
+        return wk.reshape(R, nks, 4, 2, 16).permute(0, 1, 3, 2, 4).reshape(R, nks * 128)
+    w1r = torch.zeros(R, 36, 32, device=w1.device)
+    w1r[:, :9 * k] = w1.reshape(R, 32, k, 3, 3).permute(0, 2, 3, 4, 1).reshape(R, 9 * k, 32)
+    parts = [frag(w2.reshape(R, 32, 32, 3, 3).permute(0, 3, 4, 2, 1).reshape(R, 288, 32), 72),
+             frag(w3.reshape(R, 32, 32).transpose(1, 2), 8), frag(w4.reshape(R, 32, 32).transpose(1, 2), 8),
+             w1r.reshape(R, 36 * 32), b1.reshape(R, 32), b2.reshape(R, 32), b3.reshape(R, 32), b4.reshape(R, 32),
+             w5.reshape(R, 32), torch.nn.functional.pad(b5.reshape(R, 1), (0, 31))]
+    packed = torch.cat(parts, 1).contiguous()
+    assert packed.shape[1] == _lib.load().lldwt_ztblock_packed_floats()
+    return packed.reshape(-1)
+
+
+def ztblock_phase(parent, level, packed, k, out=None):
+    """(sigma, mu) of polyphase phase k (1 ee, 2 eo, 3 oe, 4 oo) of a ZTBlock level: parent (P,B,3,h2,w2) decoded coarser
+    level, level (P,B,3,2h2,2w2) the finer level (phases < k decoded; unused for k == 1), packed = ztblock_pack of the phase-k
+    nets.  -> params (P,B,6,h2,w2): sigma of subband j on channel 2j, mu on 2j+1."""
+    P, B, G, h2, w2 = parent.shape
+    H, W = (level.shape[3], level.shape[4]) if level is not None else (2 * h2, 2 * w2)
+    if G != 3 or (level is not None and tuple(level.shape[:3]) != (P, B, 3)):
+        raise _lib.LLDWTError("ztblock_phase: parent / level must be (P,B,3,.,.) (got %s, %s)" % (
+            tuple(parent.shape), None if level is None else tuple(level.shape)))
+    if packed.numel() != P * 6 * _lib.load().lldwt_ztblock_packed_floats():
+        raise _lib.LLDWTError("ztblock_phase: packed holds %d floats, %d planes need %d" % (
+            packed.numel(), P, P * 6 * _lib.load().lldwt_ztblock_packed_floats()))
+    params = torch.empty(P, B, 6, h2, w2, device=parent.device, dtype=torch.float32) if out is None else out
+    check(_lib.load().lldwt_ztblock_phase(_chk(parent, "parent"), _opt(level, "level"), _chk(packed, "packed"),
+                                          _chk(params, "params"), P, B, h2, w2, H, W, int(k), _stream()), "ztblock_phase")
+    return params
+
+
 def cgp_pack(ws, bs, groups):
     """ws: 4 stacked 1x1 conv weights (P, groups*c_{l+1}, c_l, 1, 1); bs: 4 biases (P, groups*c_{l+1})."""
     lib = _lib.load()

@@ -455,6 +455,16 @@ int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const float* y, co
                                int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, void* stream);
 int lldwt_wavefront_apply(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h, int64_t w,
                           int groups, int K, int t, int64_t ntot, int64_t off, void* stream);
+/* Real entropy coding of DWTConditioned2EntropyLayerZTBlock (csrc/ztblock.hip; nets: LiftingBasedDWT_net.py:618-624,716-744):
+ * (sigma, mu) of ONE polyphase phase k (1 ee, 2 eo, 3 oe, 4 oo) of every plane, image and of the 3 subbands, both heads, in
+ * one launch.  parent (planes, batch, 3, h2, w2): the decoded coarser level; level (planes, batch, 3, 2*h2, 2*w2): the
+ * decoded finer level, of which only the phases before k are read (strided, in place; may be null for k == 1).
+ * packed: planes * 3 * 2 records of lldwt_ztblock_packed_floats() floats, record (plane, subband, head 0 sigma / 1 mu)
+ * (ops.ztblock_pack).  params (planes, batch, 6, h2, w2): sigma of subband j on channel 2j, mu on 2j+1.  Exact fp32
+ * (v_mfma_f32_16x16x4_f32), every output's reduction order fixed: bitwise deterministic and batch invariant.          */
+int64_t lldwt_ztblock_packed_floats(void);
+int lldwt_ztblock_phase(const float* parent, const float* level, const float* packed, float* params, int64_t planes,
+                        int64_t batch, int64_t h2, int64_t w2, int64_t H, int64_t W, int k, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Real entropy coding (reference: compress_ar / decompress_ar, LiftingBasedDWT_net.py:458-556, on
