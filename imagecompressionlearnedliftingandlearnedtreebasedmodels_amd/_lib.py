@@ -51,6 +51,8 @@ SIGNATURES = {
     "lldwt_rgb_to_ycc": (_i, [_p, _p, _i64, _i64, _i64, _p]),
     "lldwt_u8hwc_to_f32chw": (_i, [_p, _p, _i64, _i64, _i64, _p]),
     "lldwt_ycc_to_rgb": (_i, [_p, _p, _i64, _i64, _i64, _i, _p]),
+    "lldwt_u8hwc_to_ycc_pad": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
+    "lldwt_ycc_to_u8hwc_crop": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "lldwt_pblock_packed_floats": (_i64, [_i, _i]),
     "lldwt_set_lift_mode": (_i, [_i]),
     "lldwt_set_diagnostics": (_i, [_i, _p, _i64, _i]),

@@ -1,0 +1,330 @@
+"""Standalone image codec: uint8 RGB images <-> self-describing byte containers (one per image).
+
+``encode_images(net, images)`` and ``decode_images(net, blobs)`` wrap the coded entropy layers
+(conditioned2ZTsepSubbands, onlyEZWT, DWTConditioned2EntropyLayerZTBlock) of a ``LiftingBasedDWTNetWrapper`` in eval mode.
+The decoder needs nothing but the container and a net with the same weights: the shapes, the model identity and the
+coding arithmetic are in the header and are checked on the host before any GPU work.  ``read_header`` is CPU only.
+
+Container format, version 1 (all integers little-endian):
+
+    magic             4 bytes   b"LLDW"
+    format version    u8        1
+    entropy layer     u8        1 conditioned2ZTsepSubbands, 2 onlyEZWT, 3 DWTConditioned2EntropyLayerZTBlock
+    netType           u8        1 CDF97, 2 LiftingBasedNeuralWaveletv4
+    dwtlevels L       u8
+    H, W              u32, u32  size of the original image
+    numerics version  u16       CODING_NUMERICS_VERSION of the encoder
+    arithmetic        u8 length + ASCII: canonical "key=value,..." of the switches that select the coding arithmetic
+    weights digest    16 bytes  sha256 of the parameters (weights_digest), first 16 bytes
+    stream count      u8        3 * (L + 1)
+    stream lengths    LEB128 varints, one per stream
+    payload           the rANS streams, plane-major; per plane: xe, then xo finest -> coarsest
+    CRC32             u32       zlib.crc32 of every byte before it
+
+The image is coded at the padded size padded_size(H, W) (replicate-edge padding, lifting_dwt_nets.padded_size) and
+cropped back to H x W after decoding.
+"""
+import hashlib
+import struct
+import zlib
+
+MAGIC = b"LLDW"
+FORMAT_VERSION = 1
+# Bump whenever a change alters the bits of any kernel on the coding context path (the tree-context pair, the crop-stack
+# conv engine path, lldwt_cgp16_wavefront_step, lldwt_ztblock_phase, the rate tables, the range coder): a container
+# written before such a change must be refused, not silently mis-decoded.
+CODING_NUMERICS_VERSION = 1
+
+LAYER_CODES = {"conditioned2ZTsepSubbands": 1, "onlyEZWT": 2, "DWTConditioned2EntropyLayerZTBlock": 3}
+NETTYPE_CODES = {"CDF97": 1, "LiftingBasedNeuralWaveletv4": 2}
+_LAYER_NAMES = {v: k for k, v in LAYER_CODES.items()}
+_NETTYPE_NAMES = {v: k for k, v in NETTYPE_CODES.items()}
+_FIXED = struct.Struct("<4sBBBBIIH")          # magic .. numerics version
+_PLANES = 3
+
+
+# ------------------------------------------------------------------------------------------------ byte level (host only)
+def leb128_encode(n):
+    """Unsigned LEB128: 7 bits per byte, low groups first, high bit = more bytes follow."""
+    if n < 0:
+        raise ValueError("LEB128: negative value %d" % n)
+    out = bytearray()
+    while True:
+        b = n & 0x7F
+        n >>= 7
+        if n:
+            out.append(b | 0x80)
+        else:
+            out.append(b)
+            return bytes(out)
+
+
+def leb128_decode(buf, pos, end=None):
+    """-> (value, next position); ValueError if the varint runs past ``end`` or beyond 9 bytes (63 bits)."""
+    end = len(buf) if end is None else end
+    n = shift = 0
+    for i in range(9):
+        if pos + i >= end:
+            raise ValueError("container truncated inside the stream lengths")
+        b = buf[pos + i]
+        n |= (b & 0x7F) << shift
+        shift += 7
+        if not b & 0x80:
+            return n, pos + i + 1
+    raise ValueError("stream lengths: varint longer than 9 bytes")
+
+
+def pack_container(hdr, streams):
+    """hdr: dict with layer, netType, dwtlevels, H, W, numerics, arithmetic, digest; streams: list of bytes -> container."""
+    arith = hdr["arithmetic"].encode("ascii")
+    if len(arith) > 255:
+        raise ValueError("arithmetic string longer than 255 bytes")
+    if len(hdr["digest"]) != 16:
+        raise ValueError("weights digest must be 16 bytes")
+    if len(streams) > 255:
+        raise ValueError("more than 255 streams")
+    head = _FIXED.pack(MAGIC, FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], hdr["dwtlevels"],
+                       hdr["H"], hdr["W"], hdr["numerics"])
+    body = bytearray(head)
+    body += bytes([len(arith)]) + arith + hdr["digest"] + bytes([len(streams)])
+    for s in streams:
+        body += leb128_encode(len(s))
+    for s in streams:
+        body += s
+    return bytes(body) + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def parse_container(blob):
+    """Container -> (header dict, list of stream bytes).  Every structural check (magic, version, CRC, truncation, stream
+    count, lengths) raises ValueError naming the field; nothing here touches the GPU library."""
+    if not isinstance(blob, (bytes, bytearray, memoryview)):
+        raise ValueError("container must be bytes (got %s)" % type(blob).__name__)
+    blob = bytes(blob)
+    if len(blob) < 4 or blob[:4] != MAGIC:
+        raise ValueError("bad magic: not an LLDW container")
+    if len(blob) < 5:
+        raise ValueError("container truncated before the format version")
+    if blob[4] != FORMAT_VERSION:
+        raise ValueError("unsupported format version %d (this decoder reads %d)" % (blob[4], FORMAT_VERSION))
+    end = len(blob) - 4
+    if end < _FIXED.size + 1 + 16 + 1:
+        raise ValueError("container truncated: %d bytes is shorter than the smallest header" % len(blob))
+    if struct.unpack_from("<I", blob, end)[0] != zlib.crc32(blob[:end]) & 0xFFFFFFFF:
+        raise ValueError("CRC32 mismatch: the container is corrupted or truncated")
+    _, _, layer, nettype, L, H, W, numerics = _FIXED.unpack_from(blob, 0)
+    pos = _FIXED.size
+    if layer not in _LAYER_NAMES:
+        raise ValueError("unknown entropy layer code %d" % layer)
+    if nettype not in _NETTYPE_NAMES:
+        raise ValueError("unknown netType code %d" % nettype)
+    if L < 1 or H < 1 or W < 1:
+        raise ValueError("bad dwtlevels / H / W in the header (%d, %d, %d)" % (L, H, W))
+    alen = blob[pos]
+    pos += 1
+    if pos + alen + 16 + 1 > end:
+        raise ValueError("container truncated inside the arithmetic string / weights digest")
+    try:
+        arith = blob[pos:pos + alen].decode("ascii")
+    except UnicodeDecodeError:
+        raise ValueError("arithmetic string is not ASCII") from None
+    pos += alen
+    digest = blob[pos:pos + 16]
+    pos += 16
+    count = blob[pos]
+    pos += 1
+    if count != _PLANES * (L + 1):
+        raise ValueError("stream count %d does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    lengths = []
+    for _ in range(count):
+        n, pos = leb128_decode(blob, pos, end)
+        lengths.append(n)
+    if pos + sum(lengths) != end:
+        raise ValueError("stream lengths: payload is %d bytes, the lengths add up to %d" % (end - pos, sum(lengths)))
+    streams = []
+    for n in lengths:
+        streams.append(blob[pos:pos + n])
+        pos += n
+    hdr = dict(version=FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
+               numerics=numerics, arithmetic=arith, digest=digest, stream_lengths=lengths,
+               header_bytes=end - sum(lengths))
+    return hdr, streams
+
+
+def read_header(blob):
+    """The header of a container as a dict (CPU only; the library is never loaded).  Raises ValueError as parse_container."""
+    return parse_container(blob)[0]
+
+
+# ------------------------------------------------------------------------------------------------ model identity
+def arithmetic_string():
+    """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path.
+    Which reach which layer (the others are carried along, harmlessly):
+      plc_mode, plc_fuse, plc_algo, plc_shape, storage -- the tree-context pair: conditioned2ZTsepSubbands, onlyEZWT;
+      precision -- the split-fp16 pair and cgp chain (conditioned2ZTsepSubbands, onlyEZWT) and the lifting steps (all);
+      cgp -- the training path only: the coding wavefront step always runs the split-fp16 register chain.
+    DWTConditioned2EntropyLayerZTBlock's phase kernel and the crop-stack conv engine have no switch."""
+    from . import ops
+    kv = (("cgp", ops.cgp_mode()), ("plc_algo", ops.plc_algo()), ("plc_fuse", int(ops.plc_fuse())),
+          ("plc_mode", ops.plc_mode()), ("plc_shape", ops.plc_shape()), ("precision", ops.get_precision()),
+          ("storage", ops.storage_dtype()))
+    return ",".join("%s=%s" % p for p in kv)
+
+
+def _batch_invariant(arith):
+    """True when the coding path is per image in this arithmetic, so images can be coded together.  Not so when the
+    non-fused split-fp16 pair takes its operand scale from an absmax over the whole batch (plc_fuse=0), or with fp16
+    storage (a bound over the batch's parents); the one-product precisions are not verified.  Otherwise: one image per call."""
+    d = dict(p.split("=") for p in arith.split(","))
+    if d["precision"] != "f16x3" or d["storage"] != "fp32":
+        return False
+    return d["plc_mode"] == "f32" or d["plc_fuse"] == "1"
+
+
+def weights_digest(net):
+    """First 16 bytes of sha256 over net.named_parameters() sorted by name: name, dtype, shape, contiguous CPU bytes of each.
+    Parameters only: the buffers (quantized_cdf, offset, cdf_length, scale_table) are derived from them and rewritten by
+    update() during coding."""
+    import torch
+    from .graphs.layers.masked_conv2d import MaskedConv2d
+    h = hashlib.sha256()
+    # a MaskedConv2d weight is hashed masked (exact: x * 1 and x * 0), as every forward leaves it; so the digest is the same
+    # before and after coding, and is taken on the host before any GPU work of the decoder
+    masks = {name + ".weight": m.mask for name, m in net.named_modules() if isinstance(m, MaskedConv2d)}
+
+    def put(b):
+        h.update(struct.pack("<Q", len(b)))
+        h.update(b)
+    for name, p in sorted(net.named_parameters(), key=lambda kv: kv[0]):
+        t = p.detach().to("cpu")
+        if name in masks:
+            t = t * masks[name].to("cpu")
+        t = t.contiguous()
+        put(name.encode())
+        put(str(t.dtype).encode())
+        put(struct.pack("<%dq" % t.dim(), *t.shape))
+        put(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+    return h.digest()[:16]
+
+
+def _prepare(net):
+    """Bring the net to the state coding leaves it in: MaskedConv2d zeroes its masked taps on every forward (apply_mask_, as
+    the reference does), and EntropyBottleneck.update() keeps the CDF tables it finds in its buffers (a checkpoint may carry
+    stale ones), so rebuild them from the parameters.  Then what the weights digest pins is what the coder uses."""
+    import torch
+    from .entropy_models import EntropyBottleneck
+    from .graphs.layers.masked_conv2d import MaskedConv2d
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, MaskedConv2d):
+                m.apply_mask_()
+            elif isinstance(m, EntropyBottleneck):
+                m.update(force=True)
+
+
+def describe(net):
+    """-> (layer name, netType name, dwtlevels) of a LiftingBasedDWTNetWrapper; refuses what cannot be coded."""
+    from .graphs.models.LiftingBasedDWT_net import LiftingBasedDWTNetWrapper
+    from .graphs.layers.lifting_dwt_nets import DWTPytorchWaveletsLayer
+    if not isinstance(net, LiftingBasedDWTNetWrapper):
+        raise TypeError("the codec takes a LiftingBasedDWTNetWrapper (got %s)" % type(net).__name__)
+    if net.clrch == 3:
+        raise NotImplementedError("the codec codes clrch == 1 only: with clrch == 3 the coded layers define no coding "
+                                  "(DWTConditioned2EntropyLayerZTBlock rates 3 of the 9 subband channels)")
+    if net.training:
+        raise NotImplementedError("the codec needs the net in eval mode: training mode adds quantisation noise")
+    n0 = net.nets()[0]
+    if n0.entropy_layer not in LAYER_CODES:
+        from .graphs.models.LiftingBasedDWT_net import _NOT_CODED
+        raise NotImplementedError(_NOT_CODED)
+    ae = n0.autoencoder
+    if isinstance(ae, DWTPytorchWaveletsLayer):
+        return n0.entropy_layer, "CDF97", ae.dwtlevels
+    return n0.entropy_layer, "LiftingBasedNeuralWaveletv4", ae.waveletLevel
+
+
+# ------------------------------------------------------------------------------------------------ public API
+def encode_images(net, images_u8):
+    """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes)."""
+    import torch
+    from . import ops
+    from .graphs.layers.lifting_dwt_nets import padded_size
+    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    layer, nettype, L = describe(net)
+    if not (isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
+            and images_u8.shape[3] == 3):
+        raise ValueError("images must be a (B,H,W,3) uint8 tensor")
+    B, H, W, _ = images_u8.shape
+    if B < 1 or H < 1 or W < 1 or H >= 1 << 32 or W >= 1 << 32:
+        raise ValueError("bad image batch shape %s" % (tuple(images_u8.shape),))
+    nets = net.nets()
+    Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
+    arith = arithmetic_string()
+    _prepare(net)
+    hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, numerics=CODING_NUMERICS_VERSION, arithmetic=arith,
+               digest=weights_digest(net))
+    dev = next(net.parameters()).device
+    x = ops.u8hwc_to_ycc_pad(images_u8.to(dev).contiguous(), Hp, Wp)                  # (3,B,1,Hp,Wp)
+    groups = [(0, B)] if _batch_invariant(arith) else [(b, b + 1) for b in range(B)]
+    blobs = []
+    with torch.no_grad():
+        for a, e in groups:
+            s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous())
+            for b in range(e - a):
+                streams = [s for p in range(_PLANES) for s in [s_xe[p][b]] + [lev[p][b] for lev in s_xo]]
+                blobs.append(pack_container(hdr, streams))
+    return blobs
+
+
+def check_header(hdr, layer, nettype, L, digest, arith):
+    """The identity checks of a parsed header against the decoding net and process (ValueError naming the field)."""
+    if hdr["layer"] != layer:
+        raise ValueError("entropy layer: the container holds %s, the net is %s" % (hdr["layer"], layer))
+    if hdr["netType"] != nettype:
+        raise ValueError("netType: the container holds %s, the net is %s" % (hdr["netType"], nettype))
+    if hdr["dwtlevels"] != L:
+        raise ValueError("dwtlevels: the container holds %d, the net has %d" % (hdr["dwtlevels"], L))
+    if hdr["digest"] != digest:
+        raise ValueError("weights digest: the container was encoded with other weights (%s != %s)"
+                         % (hdr["digest"].hex(), digest.hex()))
+    if hdr["numerics"] != CODING_NUMERICS_VERSION:
+        raise ValueError("numerics version: the container was written with coding numerics version %d, this decoder has %d"
+                         % (hdr["numerics"], CODING_NUMERICS_VERSION))
+    if hdr["arithmetic"] != arith:
+        got = dict(p.split("=", 1) for p in hdr["arithmetic"].split(",") if "=" in p)
+        have = dict(p.split("=", 1) for p in arith.split(","))
+        diff = sorted(k for k in set(got) | set(have) if got.get(k) != have.get(k))
+        raise ValueError("arithmetic: the container was coded with %s, this process has %s (differs in: %s)"
+                         % (hdr["arithmetic"], arith, ", ".join(diff)))
+
+
+def decode_images(net, blobs):
+    """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
+    first; then containers of equal (H, W) are decoded together."""
+    import torch
+    from . import ops
+    from .graphs.layers.lifting_dwt_nets import padded_size
+    from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
+    layer, nettype, L = describe(net)
+    parsed = [parse_container(b) for b in blobs]
+    digest, arith = weights_digest(net), arithmetic_string()
+    for hdr, _ in parsed:
+        check_header(hdr, layer, nettype, L, digest, arith)
+    _prepare(net)
+    nets = net.nets()
+    by_size = {}
+    for i, (hdr, _) in enumerate(parsed):
+        by_size.setdefault((hdr["H"], hdr["W"]), []).append(i)
+    out = [None] * len(parsed)
+    with torch.no_grad():
+        for (H, W), idx in by_size.items():
+            Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
+            groups = [idx] if _batch_invariant(arith) else [[i] for i in idx]
+            for g in groups:
+                per = L + 1                                   # streams per plane: xe, xo finest -> coarsest
+                s_xe = [[parsed[i][1][p * per] for i in g] for p in range(_PLANES)]
+                s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(L)]
+                xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g))
+                img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W).cpu()
+                for j, i in enumerate(g):
+                    out[i] = img[j]
+    return out

@@ -67,6 +67,49 @@ __global__ void k_ycc_to_rgb(const float* __restrict__ ycc, float* __restrict__ 
     }
 }
 
+// Image codec I/O.  uint8 HWC (B,H,W,3) RGB -> plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5, padded to Hp x Wp by replicating
+// the last row / column (the source coordinate is clamped).  The same expressions as k_u8hwc_to_f32chw then k_rgb_to_ycc, so
+// every value is bitwise equal to that composition.  Grid (cdiv(Wp,256), Hp, B): one thread per output pixel, every plane row
+// written coalesced.
+__global__ void k_u8hwc_to_ycc_pad(const uint8_t* __restrict__ src, float* __restrict__ ycc, int64_t B, int64_t H, int64_t W,
+                                   int64_t Hp, int64_t Wp) {
+    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (x >= Wp) return;
+    const int64_t y = blockIdx.y, b = blockIdx.z;
+    const int64_t sy = y < H ? y : H - 1, sx = x < W ? x : W - 1;
+    const uint8_t* s = src + ((b * H + sy) * W + sx) * 3;
+    const float r = (float)s[0] / 255.0f, g = (float)s[1] / 255.0f, bl = (float)s[2] / 255.0f;
+    const float yy = KR * r + KG * g + KB * bl;
+    const float cb = 0.5f * (bl - yy) / (1.f - KB) + 0.5f;
+    const float cr = 0.5f * (r - yy) / (1.f - KR) + 0.5f;
+    const int64_t hw = Hp * Wp, p = y * Wp + x;
+    ycc[(0 * B + b) * hw + p] = yy - 0.5f;
+    ycc[(1 * B + b) * hw + p] = cb;
+    ycc[(2 * B + b) * hw + p] = cr;
+}
+
+// plane-major (3,B,1,Hp,Wp) YCbCr -> uint8 HWC (B,H,W,3) RGB of the top-left H x W: k_ycc_to_rgb(clamp=1), then
+// floor((v + 0.5) * 255 + 0.5) in fp32 (v in [-0.5, 0.5], so the byte is in [0, 255]).  Grid (cdiv(W,256), H, B).
+__global__ void k_ycc_to_u8hwc_crop(const float* __restrict__ ycc, uint8_t* __restrict__ dst, int64_t B, int64_t H, int64_t W,
+                                    int64_t Hp, int64_t Wp) {
+    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (x >= W) return;
+    const int64_t y_ = blockIdx.y, b = blockIdx.z;
+    const int64_t hw = Hp * Wp, p = y_ * Wp + x;
+    const float y = ycc[(0 * B + b) * hw + p] + 0.5f, cb = ycc[(1 * B + b) * hw + p], cr = ycc[(2 * B + b) * hw + p];
+    float r = y + (2.f - 2.f * KR) * (cr - 0.5f);
+    float bl = y + (2.f - 2.f * KB) * (cb - 0.5f);
+    float g = (y - KR * r - KB * bl) / KG;
+    r -= 0.5f; g -= 0.5f; bl -= 0.5f;
+    r = fminf(fmaxf(r, -0.5f), 0.5f);
+    g = fminf(fmaxf(g, -0.5f), 0.5f);
+    bl = fminf(fmaxf(bl, -0.5f), 0.5f);
+    uint8_t* d = dst + ((b * H + y_) * W + x) * 3;
+    d[0] = (uint8_t)floorf((r + 0.5f) * 255.0f + 0.5f);
+    d[1] = (uint8_t)floorf((g + 0.5f) * 255.0f + 0.5f);
+    d[2] = (uint8_t)floorf((bl + 0.5f) * 255.0f + 0.5f);
+}
+
 // ------------------------------------------------------------------------------------------ subband MLP
 // SubbandAutoEncoder (lifting_dwt_nets.py:99-110): 1 -> 32 -> 32 -> 32 -> 1 per coefficient, tanh between, on the matrix
 // cores: the two 32x32 layers run on v_mfma_f32_16x16x4_f32 with everything in registers.
@@ -1130,6 +1173,22 @@ extern "C" int lldwt_ycc_to_rgb(const float* ycc, float* rgb, int64_t B, int64_t
     LLDWT_REQUIRE(rgb && ycc && B > 0 && H > 0 && W > 0, "ycc_to_rgb: bad arguments");
     hipLaunchKernelGGL(k_ycc_to_rgb, dim3(ew_grid(B * H * W)), dim3(256), 0, (hipStream_t)stream, ycc, rgb, B, H * W, clamp);
     return check_launch("ycc_to_rgb");
+}
+extern "C" int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
+                                      void* stream) {
+    LLDWT_REQUIRE(src && ycc && B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W, "u8hwc_to_ycc_pad: bad arguments");
+    LLDWT_REQUIRE(B <= 65535 && Hp <= 65535 && Wp <= (1ll << 30), "u8hwc_to_ycc_pad: grid too large");
+    hipLaunchKernelGGL(k_u8hwc_to_ycc_pad, dim3((unsigned)cdiv(Wp, 256), (unsigned)Hp, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, src, ycc, B, H, W, Hp, Wp);
+    return check_launch("u8hwc_to_ycc_pad");
+}
+extern "C" int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
+                                       void* stream) {
+    LLDWT_REQUIRE(ycc && dst && B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W, "ycc_to_u8hwc_crop: bad arguments");
+    LLDWT_REQUIRE(B <= 65535 && H <= 65535 && W <= (1ll << 30), "ycc_to_u8hwc_crop: grid too large");
+    hipLaunchKernelGGL(k_ycc_to_u8hwc_crop, dim3((unsigned)cdiv(W, 256), (unsigned)H, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, ycc, dst, B, H, W, Hp, Wp);
+    return check_launch("ycc_to_u8hwc_crop");
 }
 
 extern "C" int lldwt_subband_mlp(const float* x, float* y, int64_t planes, int64_t batch, int C, int64_t hw, int Hd,

@@ -267,6 +267,31 @@ def encode_planes(nets, x):
     return out_xe, out_xo
 
 
+def _levels(n0):
+    return n0.dwtlevels if isinstance(n0, DWTPytorchWaveletsLayer) else n0.waveletLevel
+
+
+def padded_size(nets, H, W):
+    """Smallest (Hp, Wp) >= (H, W) the transform of these plane modules accepts: multiples of 2^L (lifting_args_ok /
+    cdf_args); CDF 9/7 also refuses a deepest level input shorter than its 10 taps (cdf_args, csrc/cdf97.hip:547), i.e.
+    min(Hp, Wp) >> (L-1) >= 10, so both sides are at least 5 * 2^L (no short levels, whatever set_cdf97_short_levels says)."""
+    n0 = nets[0]
+    m = 1 << _levels(n0)
+    lo = 5 * m if isinstance(n0, DWTPytorchWaveletsLayer) else m
+    up = lambda v: max(lo, -(-v // m) * m)
+    return up(H), up(W)
+
+
+def encode_shapes(nets, B, H, W):
+    """Shapes encode_planes produces for x (P,B,C,H,W) without running it -> (shape_xe, [shape_xo] finest first): the
+    transform's ll (P,B,C,H>>L,W>>L) and yh_i (P,B,3C,H>>(i+1),W>>(i+1)) (ops.cdf97_forward / ops.lifting_forward), which the
+    subband auto-encoders keep (SubbandAutoEncoder: per coefficient; Berk: 3x3 convs with padding 1, in_ch channels out)."""
+    n0 = nets[0]
+    L, Cc = _levels(n0), n0.clrch
+    P = len(nets)
+    return (P, B, Cc, H >> L, W >> L), [(P, B, 3 * Cc, H >> (i + 1), W >> (i + 1)) for i in range(L)]
+
+
 def decode_planes(nets, out_xe, out_xo_list):
     """autoencoder.decode for a list of per-plane transform modules -> xhat (P,B,C,H,W)."""
     n0 = nets[0]

@@ -26,7 +26,7 @@ from ...entropy_models import EntropyBottleneck, GaussianConditional
 from ...packed_cache import PackedOwnerMixin, cached
 from ... import param_arena
 from ..layers.lifting_dwt_nets import (DWTPytorchWaveletsLayer, LiftingBasedNeuralWaveletv4, _stack,
-                                       decode_planes, encode_planes, lifting_coeff)
+                                       decode_planes, encode_planes, encode_shapes, lifting_coeff)
 from ..layers.masked_conv2d import MaskedConv2d
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
@@ -978,18 +978,44 @@ def rate_planes(nets, x, training=False):
     return si_xe, si_xo
 
 
+_NOT_CODED = ("real entropy coding exists for conditioned2ZTsepSubbands (as in the reference) and, as extensions, onlyEZWT and "
+              "DWTConditioned2EntropyLayerZTBlock; the factorized layer has no test() (LiftingBasedDWT_net.py:145-146 would "
+              "fail there too)")
+
+
 def compress_planes(nets, x):
     """encode -> real entropy coding (compress + decompress from the strings) -> decode, for a list of per-plane nets;
     x (P,B,C,H,W) -> (xhat, strings_xe[p][b], [strings_xo[p][b] per level])."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "test_planes"):
-        raise NotImplementedError("real entropy coding exists for conditioned2ZTsepSubbands (as in the reference) and, as "
-                                  "extensions, onlyEZWT and DWTConditioned2EntropyLayerZTBlock; the factorized layer has no "
-                                  "test() (LiftingBasedDWT_net.py:145-146 would fail there too)")
+        raise NotImplementedError(_NOT_CODED)
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
     s_xe, s_xo, xe_q, xo_q = type(em[0]).test_planes(em, out_xe, out_xo)
     xhat = decode_planes([n.autoencoder for n in nets], xe_q, xo_q)
     return xhat, s_xe, s_xo
+
+
+def encode_strings_planes(nets, x):
+    """The encoder half of compress_planes: encode -> the entropy layer's compress_planes, no decoding.
+    x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first)."""
+    em = [n.entropymodel for n in nets]
+    if not hasattr(type(em[0]), "compress_planes"):
+        raise NotImplementedError(_NOT_CODED)
+    out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
+    s_xe, s_xo, _, _ = type(em[0]).compress_planes(em, out_xe, out_xo)
+    return s_xe, s_xo
+
+
+def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B):
+    """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them) -> xhat (P,B,C,Hp,Wp).
+    Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes)."""
+    em = [n.entropymodel for n in nets]
+    if not hasattr(type(em[0]), "decompress_planes"):
+        raise NotImplementedError(_NOT_CODED)
+    aenc = [n.autoencoder for n in nets]
+    shape_xe, shapes_xo = encode_shapes(aenc, B, Hp, Wp)
+    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo)
+    return decode_planes(aenc, xe, xo)
 
 
 class LiftingBasedDWTNet(PackedOwnerMixin, nn.Module):

@@ -117,6 +117,29 @@ def ycc_to_rgb(y, clamp=False):
     return x
 
 
+def u8hwc_to_ycc_pad(src, Hp, Wp):
+    """(B,H,W,3) uint8 RGB device tensor -> plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5, replicate-edge padded
+    (lldwt_u8hwc_to_ycc_pad; inside the image bitwise equal to rgb_to_ycc(u8hwc_to_f32chw(src)))."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+            and src.dim() == 4 and src.shape[3] == 3):
+        raise _lib.LLDWTError("u8hwc_to_ycc_pad: expected a contiguous (B,H,W,3) uint8 device tensor")
+    B, H, W, _ = src.shape
+    y = torch.empty(3, B, 1, Hp, Wp, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u8hwc_to_ycc_pad(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, Hp, Wp, _stream()),
+          "u8hwc_to_ycc_pad")
+    return y
+
+
+def ycc_to_u8hwc_crop(y, H, W):
+    """plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5 -> (B,H,W,3) uint8 RGB of the top-left H x W
+    (lldwt_ycc_to_u8hwc_crop: floor((v + 0.5) * 255 + 0.5) of v = ycc_to_rgb(y, clamp=True))."""
+    _, B, _, Hp, Wp = y.shape
+    dst = torch.empty(B, H, W, 3, device=y.device, dtype=torch.uint8)
+    check(_lib.load().lldwt_ycc_to_u8hwc_crop(_chk(y, "y"), C.c_void_p(dst.data_ptr()), B, H, W, Hp, Wp, _stream()),
+          "ycc_to_u8hwc_crop")
+    return dst
+
+
 def pblock_packed_floats(Cc, K):
     return int(_lib.load().lldwt_pblock_packed_floats(Cc, K))
 

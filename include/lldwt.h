@@ -67,6 +67,17 @@ int lldwt_ycc_to_rgb_bwd(const float* grgb, float* gycc, int64_t B, int64_t H, i
  * ToTensor's arithmetic (x / 255 in fp32), bit-exact.                                                          */
 int lldwt_u8hwc_to_f32chw(const uint8_t* src, float* dst, int64_t B, int64_t H, int64_t W, void* stream);
 
+/* Image codec I/O (the package's codec.py; the reference has no file codec).
+ * lldwt_u8hwc_to_ycc_pad: src (B,H,W,3) uint8 RGB -> ycc plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5, Hp >= H, Wp >= W;
+ *   positions outside the image take the value of the clamped source pixel (replicate-edge padding).  Inside the image
+ *   bitwise equal to lldwt_u8hwc_to_f32chw followed by lldwt_rgb_to_ycc.  B, Hp <= 65535.
+ * lldwt_ycc_to_u8hwc_crop: ycc (3,B,1,Hp,Wp) -> dst (B,H,W,3) uint8 RGB of the top-left H x W:
+ *   floor((v + 0.5f) * 255.0f + 0.5f) of v = lldwt_ycc_to_rgb(..., clamp=1).  B, H <= 65535.                      */
+int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
+                           void* stream);
+int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * P/U block parameters (graphs/layers/P_block_v2.py:15-33) packed for the kernels.
  * lldwt_pack_pblock: in = the four conv weights/biases of `planes` stacked blocks in PyTorch layout

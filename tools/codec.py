@@ -1,0 +1,94 @@
+"""Command-line image codec on the HIP path (imagecompressionlearnedliftingandlearnedtreebasedmodels_amd/codec.py).
+
+    python tools/codec.py encode --config cfg.json [--checkpoint ckpt.pth.tar] in.png out.lld
+    python tools/codec.py decode --config cfg.json [--checkpoint ckpt.pth.tar] in.lld out.png
+    python tools/codec.py info in.lld                      (CPU only: prints the header)
+
+The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
+read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
+Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
+decoder must then use the same config (and seed).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import codec  # noqa: E402
+
+
+def build_net(config_path, checkpoint=None, device="cuda:0"):
+    import torch
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.graphs.models.LiftingBasedDWT_net import \
+        LiftingBasedDWTNetWrapper
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.utils.config import make_config
+    with open(config_path) as f:
+        cfg = make_config(**json.load(f))
+    torch.manual_seed(int(cfg.get("seed", 1337)))
+    net = LiftingBasedDWTNetWrapper(cfg)
+    if checkpoint:
+        ckpt = torch.load(checkpoint, map_location="cpu", weights_only=True)
+        sd = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
+        missing, unexpected = net.load_state_dict(sd, strict=False)
+        if missing or unexpected:
+            raise RuntimeError("checkpoint %s does not match the model: %d missing keys (e.g. %s), %d unexpected (e.g. %s)"
+                               % (checkpoint, len(missing), missing[:3], len(unexpected), unexpected[:3]))
+    return net.to(device).eval()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    for name in ("encode", "decode"):
+        p = sub.add_parser(name)
+        p.add_argument("--config", required=True)
+        p.add_argument("--checkpoint")
+        p.add_argument("src")
+        p.add_argument("dst")
+    p = sub.add_parser("info")
+    p.add_argument("src")
+    a = ap.parse_args(argv)
+
+    if a.cmd == "info":
+        with open(a.src, "rb") as f:
+            hdr = codec.read_header(f.read())
+        for k, v in hdr.items():
+            print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
+        return 0
+
+    import numpy as np
+    import torch
+    from PIL import Image
+    net = build_net(a.config, a.checkpoint)
+    if a.cmd == "encode":
+        img = np.asarray(Image.open(a.src).convert("RGB"), dtype=np.uint8)
+        x = torch.from_numpy(np.ascontiguousarray(img))[None]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        blob = codec.encode_images(net, x)[0]
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        with open(a.dst, "wb") as f:
+            f.write(blob)
+        H, W = img.shape[:2]
+        print("encoded %dx%d: %d bytes, %.4f bpp, %.3f s" % (W, H, len(blob), len(blob) * 8 / (H * W), dt))
+    else:
+        with open(a.src, "rb") as f:
+            blob = f.read()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        img = codec.decode_images(net, [blob])[0]
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        Image.fromarray(img.numpy()).save(a.dst)
+        print("decoded %dx%d: %.3f s" % (img.shape[1], img.shape[0], dt))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
