@@ -53,6 +53,8 @@ SIGNATURES = {
     "lldwt_ycc_to_rgb": (_i, [_p, _p, _i64, _i64, _i64, _i, _p]),
     "lldwt_u8hwc_to_ycc_pad": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "lldwt_ycc_to_u8hwc_crop": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
+    "lldwt_u8hwc_to_ycc_tiles": (_i, [_p, _p] + [_i64] * 9 + [_p]),
+    "lldwt_ycc_tiles_to_u8hwc": (_i, [_p, _p] + [_i64] * 13 + [_p, _p]),
     "lldwt_pblock_packed_floats": (_i64, [_i, _i]),
     "lldwt_set_lift_mode": (_i, [_i]),
     "lldwt_set_diagnostics": (_i, [_i, _p, _i64, _i]),
@@ -163,6 +165,8 @@ SIGNATURES = {
     "lldwt_rans_decoder_new": (_p, [_p, _i64]),
     "lldwt_rans_decode": (_i, [_p, _p, _i64, _p, C.c_int32, C.c_int32, _p, _p, _p]),
     "lldwt_rans_decoder_free": (None, [_p]),
+    "lldwt_rans_encode_multi": (_i, [_p, _p, _i64, _i64, _i64, _p, C.c_int32, C.c_int32, _p, _p, _p, _i64, _p]),
+    "lldwt_rans_set_parallel": (_i, [_i, _i64]),
     "lldwt_sq_err_sum": (_i, [_p, _p, _i64, _p, _p]),
     "lldwt_sum": (_i, [_p, _i64, _p, _p]),
     "lldwt_cdf97_ws_bytes": (_i64, [_i64, _i64, _i64]),

@@ -145,6 +145,48 @@ class RansDecoder:
             pass
 
 
+def set_parallel(threads=0, min_symbols=-1):
+    """The stream-parallel host coder of encode_streams / decode_streams / lldwt_rans_decode_multi (lldwt_rans_set_parallel):
+    threads > 0 forces that many threads (1 = sequential), 0 = min(16, OMP_NUM_THREADS, streams); min_symbols >= 0 replaces
+    the per-call symbol threshold of the parallel path, -1 restores it.  The bytes and symbols do not depend on either."""
+    _lib.check(_lib.load().lldwt_rans_set_parallel(int(threads), int(min_symbols)), "rans_set_parallel")
+
+
+def encode_streams(symbols, indexes, cdfs, cdfs_sizes, offsets):
+    """S independent streams with one table set in one call: symbols / indexes (S, n) -> list of S byte strings, each equal
+    to BufferedRansEncoder().encode_with_indexes(symbols[k], indexes[k], ...) + flush().  Runs the streams in parallel."""
+    s, i = _i32(symbols), _i32(indexes)
+    if s.ndim != 2 or s.shape != i.shape:
+        raise _lib.LLDWTError("encode_streams: symbols and indexes must be (streams, n) of one shape")
+    S, n = s.shape
+    cdf, sizes, offs = _tables(cdfs, cdfs_sizes, offsets)
+    cap = 16 * n + 64                                     # as BufferedRansEncoder.flush
+    out = np.empty((S, cap), dtype=np.uint8)
+    nbytes = np.zeros(S, dtype=np.int64)
+    _lib.check(_lib.load().lldwt_rans_encode_multi(_p(s), _p(i), S, n, n, _p(cdf), cdf.shape[0], cdf.shape[1], _p(sizes),
+                                                   _p(offs), _p(out), cap, _p(nbytes)), "rans_encode_multi")
+    return [out[k, :nbytes[k]].tobytes() for k in range(S)]
+
+
+def decode_streams(streams, indexes, cdfs, cdfs_sizes, offsets):
+    """S streams, indexes (S, n) -> (S, n) int32 symbols: RansDecoder().set_stream(streams[k]) + decode_stream(indexes[k])
+    for every k, in one lldwt_rans_decode_multi call (streams in parallel)."""
+    i = _i32(indexes)
+    if i.ndim != 2 or i.shape[0] != len(streams):
+        raise _lib.LLDWTError("decode_streams: indexes must be (streams, n)")
+    cdf, sizes, offs = _tables(cdfs, cdfs_sizes, offsets)
+    decs = []
+    for st in streams:
+        d = RansDecoder()
+        d.set_stream(st)
+        decs.append(d)
+    handles = (C.c_void_p * len(decs))(*[d._h for d in decs])
+    out = np.empty(i.shape, dtype=np.int32)
+    _lib.check(_lib.load().lldwt_rans_decode_multi(handles, len(decs), _p(i), i.shape[1], i.shape[1], _p(cdf), cdf.shape[0],
+                                                   cdf.shape[1], _p(sizes), _p(offs), _p(out)), "rans_decode_multi")
+    return out
+
+
 def pmf_to_quantized_cdf(pmf, precision=16):
     """compressai._CXX.pmf_to_quantized_cdf: list / 1-D tensor of float -> list of len(pmf)+1 ints."""
     a = np.ascontiguousarray(np.asarray(pmf.detach().cpu().numpy() if isinstance(pmf, torch.Tensor) else pmf, dtype=np.float32))

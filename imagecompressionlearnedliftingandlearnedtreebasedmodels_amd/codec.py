@@ -23,6 +23,23 @@ Container format, version 1 (all integers little-endian):
 
 The image is coded at the padded size padded_size(H, W) (replicate-edge padding, lifting_dwt_nets.padded_size) and
 cropped back to H x W after decoding.
+
+Tiled coding (``encode_tiled`` / ``decode_tiled``): a large image is cut into a grid of ny x nx tiles of
+th x tw (tile_grid), each coded as an independent image -- its streams are byte-identical to those of
+``encode_images(net, padded_tile)`` -- and a region decodes from the tiles it touches.  Tiled container, version 1:
+
+    magic             4 bytes   b"LLDT"
+    format version    u8        1
+    entropy layer, netType, dwtlevels   u8 x 3, as LLDW
+    H, W              u32, u32  size of the original image
+    th, tw            u32, u32  tile size (padded_size(th, tw) == (th, tw))
+    ny, nx            u16, u16  grid (ceil(H / th), ceil(W / tw))
+    numerics version  u16
+    arithmetic, weights digest          as LLDW
+    streams per tile  u8        3 * (L + 1)
+    stream lengths    LEB128 varints, tile-major in raster order of (ty, tx); inside a tile the LLDW order
+    payload           the streams in the same order
+    CRC32             u32       zlib.crc32 of every byte before it
 """
 import hashlib
 import struct
@@ -40,6 +57,9 @@ NETTYPE_CODES = {"CDF97": 1, "LiftingBasedNeuralWaveletv4": 2}
 _LAYER_NAMES = {v: k for k, v in LAYER_CODES.items()}
 _NETTYPE_NAMES = {v: k for k, v in NETTYPE_CODES.items()}
 _FIXED = struct.Struct("<4sBBBBIIH")          # magic .. numerics version
+TILED_MAGIC = b"LLDT"
+TILED_FORMAT_VERSION = 1
+_TFIXED = struct.Struct("<4sBBBBIIIIHHH")     # magic .. H, W, th, tw, ny, nx, numerics version
 _PLANES = 3
 
 
@@ -74,51 +94,60 @@ def leb128_decode(buf, pos, end=None):
     raise ValueError("stream lengths: varint longer than 9 bytes")
 
 
-def pack_container(hdr, streams):
-    """hdr: dict with layer, netType, dwtlevels, H, W, numerics, arithmetic, digest; streams: list of bytes -> container."""
+def _pack_identity(hdr):
+    """The arithmetic string and weights digest fields (u8 length + ASCII, 16 bytes), shared by LLDW and LLDT."""
     arith = hdr["arithmetic"].encode("ascii")
     if len(arith) > 255:
         raise ValueError("arithmetic string longer than 255 bytes")
     if len(hdr["digest"]) != 16:
         raise ValueError("weights digest must be 16 bytes")
-    if len(streams) > 255:
-        raise ValueError("more than 255 streams")
-    head = _FIXED.pack(MAGIC, FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], hdr["dwtlevels"],
-                       hdr["H"], hdr["W"], hdr["numerics"])
-    body = bytearray(head)
-    body += bytes([len(arith)]) + arith + hdr["digest"] + bytes([len(streams)])
+    return bytes([len(arith)]) + arith + hdr["digest"]
+
+
+def _pack_streams(streams):
+    """LEB128 stream lengths, then the payload."""
+    body = bytearray()
     for s in streams:
         body += leb128_encode(len(s))
     for s in streams:
         body += s
+    return bytes(body)
+
+
+def _seal(body):
     return bytes(body) + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
 
 
-def parse_container(blob):
-    """Container -> (header dict, list of stream bytes).  Every structural check (magic, version, CRC, truncation, stream
-    count, lengths) raises ValueError naming the field; nothing here touches the GPU library."""
+def _open(blob, magic, version, min_header):
+    """The checks every container starts with: type, magic, version, minimum length, CRC32 -> (bytes, end of payload)."""
     if not isinstance(blob, (bytes, bytearray, memoryview)):
         raise ValueError("container must be bytes (got %s)" % type(blob).__name__)
     blob = bytes(blob)
-    if len(blob) < 4 or blob[:4] != MAGIC:
-        raise ValueError("bad magic: not an LLDW container")
+    if len(blob) < 4 or blob[:4] != magic:
+        raise ValueError("bad magic: not an %s container" % magic.decode())
     if len(blob) < 5:
         raise ValueError("container truncated before the format version")
-    if blob[4] != FORMAT_VERSION:
-        raise ValueError("unsupported format version %d (this decoder reads %d)" % (blob[4], FORMAT_VERSION))
+    if blob[4] != version:
+        raise ValueError("unsupported format version %d (this decoder reads %d)" % (blob[4], version))
     end = len(blob) - 4
-    if end < _FIXED.size + 1 + 16 + 1:
+    if end < min_header:
         raise ValueError("container truncated: %d bytes is shorter than the smallest header" % len(blob))
     if struct.unpack_from("<I", blob, end)[0] != zlib.crc32(blob[:end]) & 0xFFFFFFFF:
         raise ValueError("CRC32 mismatch: the container is corrupted or truncated")
-    _, _, layer, nettype, L, H, W, numerics = _FIXED.unpack_from(blob, 0)
-    pos = _FIXED.size
+    return blob, end
+
+
+def _check_model_fields(layer, nettype, L, H, W):
     if layer not in _LAYER_NAMES:
         raise ValueError("unknown entropy layer code %d" % layer)
     if nettype not in _NETTYPE_NAMES:
         raise ValueError("unknown netType code %d" % nettype)
     if L < 1 or H < 1 or W < 1:
         raise ValueError("bad dwtlevels / H / W in the header (%d, %d, %d)" % (L, H, W))
+
+
+def _parse_identity(blob, pos, end):
+    """-> (arithmetic string, digest, count byte, position after the count byte)."""
     alen = blob[pos]
     pos += 1
     if pos + alen + 16 + 1 > end:
@@ -130,10 +159,11 @@ def parse_container(blob):
     pos += alen
     digest = blob[pos:pos + 16]
     pos += 16
-    count = blob[pos]
-    pos += 1
-    if count != _PLANES * (L + 1):
-        raise ValueError("stream count %d does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    return arith, digest, blob[pos], pos + 1
+
+
+def _parse_streams(blob, pos, end, count):
+    """count LEB128 lengths, then the payload up to end -> (list of stream bytes, lengths)."""
     lengths = []
     for _ in range(count):
         n, pos = leb128_decode(blob, pos, end)
@@ -144,14 +174,86 @@ def parse_container(blob):
     for n in lengths:
         streams.append(blob[pos:pos + n])
         pos += n
+    return streams, lengths
+
+
+def pack_container(hdr, streams):
+    """hdr: dict with layer, netType, dwtlevels, H, W, numerics, arithmetic, digest; streams: list of bytes -> container."""
+    ident = _pack_identity(hdr)
+    if len(streams) > 255:
+        raise ValueError("more than 255 streams")
+    head = _FIXED.pack(MAGIC, FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], hdr["dwtlevels"],
+                       hdr["H"], hdr["W"], hdr["numerics"])
+    return _seal(head + ident + bytes([len(streams)]) + _pack_streams(streams))
+
+
+def parse_container(blob):
+    """Container -> (header dict, list of stream bytes).  Every structural check (magic, version, CRC, truncation, stream
+    count, lengths) raises ValueError naming the field; nothing here touches the GPU library."""
+    blob, end = _open(blob, MAGIC, FORMAT_VERSION, _FIXED.size + 1 + 16 + 1)
+    _, _, layer, nettype, L, H, W, numerics = _FIXED.unpack_from(blob, 0)
+    _check_model_fields(layer, nettype, L, H, W)
+    arith, digest, count, pos = _parse_identity(blob, _FIXED.size, end)
+    if count != _PLANES * (L + 1):
+        raise ValueError("stream count %d does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    streams, lengths = _parse_streams(blob, pos, end, count)
     hdr = dict(version=FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
                numerics=numerics, arithmetic=arith, digest=digest, stream_lengths=lengths,
                header_bytes=end - sum(lengths))
     return hdr, streams
 
 
+def _check_grid(nettype, L, H, W, th, tw, ny, nx):
+    """The grid fields of an LLDT header against the image size and the transform (ValueError naming the field)."""
+    from .graphs.layers.lifting_dwt_nets import padded_dims
+    if th < 1 or tw < 1 or ny < 1 or nx < 1:
+        raise ValueError("tile grid: th, tw, ny, nx must be positive (got %d, %d, %d, %d)" % (th, tw, ny, nx))
+    if ny * th < H or (ny - 1) * th >= H:
+        raise ValueError("tile grid rows: %d tiles of %d rows do not fit an image of %d rows" % (ny, th, H))
+    if nx * tw < W or (nx - 1) * tw >= W:
+        raise ValueError("tile grid columns: %d tiles of %d columns do not fit an image of %d columns" % (nx, tw, W))
+    if padded_dims(L, nettype == "CDF97", th, tw) != (th, tw):
+        raise ValueError("tile size: %d x %d is not a size the %s transform at %d levels accepts" % (th, tw, nettype, L))
+
+
+def pack_tiled(hdr, tile_streams):
+    """hdr: as pack_container plus th, tw, ny, nx; tile_streams: ny * nx lists of 3 (L + 1) streams in raster order of
+    (ty, tx) -> LLDT container."""
+    L, ny, nx = hdr["dwtlevels"], hdr["ny"], hdr["nx"]
+    _check_grid(hdr["netType"], L, hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx)
+    if ny > 0xFFFF or nx > 0xFFFF:
+        raise ValueError("tile grid: ny, nx must fit 16 bits")
+    if len(tile_streams) != ny * nx or any(len(t) != _PLANES * (L + 1) for t in tile_streams):
+        raise ValueError("stream count: expected %d tiles of %d streams" % (ny * nx, _PLANES * (L + 1)))
+    head = _TFIXED.pack(TILED_MAGIC, TILED_FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], L,
+                        hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx, hdr["numerics"])
+    return _seal(head + _pack_identity(hdr) + bytes([_PLANES * (L + 1)])
+                 + _pack_streams([s for t in tile_streams for s in t]))
+
+
+def parse_tiled(blob):
+    """LLDT container -> (header dict, list of ny * nx lists of stream bytes).  The structural checks of parse_container plus
+    the grid (ValueError naming the field); host only."""
+    blob, end = _open(blob, TILED_MAGIC, TILED_FORMAT_VERSION, _TFIXED.size + 1 + 16 + 1)
+    _, _, layer, nettype, L, H, W, th, tw, ny, nx, numerics = _TFIXED.unpack_from(blob, 0)
+    _check_model_fields(layer, nettype, L, H, W)
+    _check_grid(_NETTYPE_NAMES[nettype], L, H, W, th, tw, ny, nx)
+    arith, digest, count, pos = _parse_identity(blob, _TFIXED.size, end)
+    if count != _PLANES * (L + 1):
+        raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
+    tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
+    hdr = dict(version=TILED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
+               W=W, th=th, tw=tw, ny=ny, nx=nx, numerics=numerics, arithmetic=arith, digest=digest,
+               streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
+    return hdr, tiles
+
+
 def read_header(blob):
-    """The header of a container as a dict (CPU only; the library is never loaded).  Raises ValueError as parse_container."""
+    """The header of a container (LLDW or LLDT) as a dict (CPU only; the library is never loaded).  Raises ValueError as
+    parse_container / parse_tiled."""
+    if isinstance(blob, (bytes, bytearray, memoryview)) and bytes(blob[:4]) == TILED_MAGIC:
+        return parse_tiled(blob)[0]
     return parse_container(blob)[0]
 
 
@@ -243,6 +345,17 @@ def describe(net):
 
 
 # ------------------------------------------------------------------------------------------------ public API
+def _check_images(images_u8):
+    import torch
+    if not (isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
+            and images_u8.shape[3] == 3):
+        raise ValueError("images must be a (B,H,W,3) uint8 tensor")
+    B, H, W, _ = images_u8.shape
+    if B < 1 or H < 1 or W < 1 or H >= 1 << 32 or W >= 1 << 32:
+        raise ValueError("bad image batch shape %s" % (tuple(images_u8.shape),))
+    return B, H, W
+
+
 def encode_images(net, images_u8):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes)."""
     import torch
@@ -250,12 +363,7 @@ def encode_images(net, images_u8):
     from .graphs.layers.lifting_dwt_nets import padded_size
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
     layer, nettype, L = describe(net)
-    if not (isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
-            and images_u8.shape[3] == 3):
-        raise ValueError("images must be a (B,H,W,3) uint8 tensor")
-    B, H, W, _ = images_u8.shape
-    if B < 1 or H < 1 or W < 1 or H >= 1 << 32 or W >= 1 << 32:
-        raise ValueError("bad image batch shape %s" % (tuple(images_u8.shape),))
+    B, H, W = _check_images(images_u8)
     nets = net.nets()
     Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
     arith = arithmetic_string()
@@ -328,3 +436,105 @@ def decode_images(net, blobs):
                 for j, i in enumerate(g):
                     out[i] = img[j]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ tiled coding
+def tile_grid(nets, H, W, tile=512):
+    """The tile grid of an H x W image for a target tile side -> (th, tw, ny, nx).  nets: the per-plane transform modules
+    (padded_size).  Every tile has the size padded_size gives for ceil(H / ny) x ceil(W / nx), and the grid is recounted
+    with it (rounding up to 2^L, or to CDF 9/7's 5 * 2^L, can otherwise leave whole tile rows or columns outside)."""
+    from .graphs.layers.lifting_dwt_nets import padded_size
+    if int(tile) < 1 or H < 1 or W < 1:
+        raise ValueError("tile grid: tile, H and W must be positive (got %d, %d, %d)" % (tile, H, W))
+    nx, ny = -(-W // tile), -(-H // tile)
+    th, tw = padded_size(nets, -(-H // ny), -(-W // nx))
+    return th, tw, -(-H // th), -(-W // tw)
+
+
+def _tile_streams(s_xe, s_xo, j):
+    """The 3 (L + 1) streams of image j of an encode_strings_planes result, in the LLDW order."""
+    return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
+
+
+def encode_tiled(net, images_u8, tile=512, tiles_per_call=32):
+    """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers.  Every tile is coded as an independent image: its streams
+    are those of encode_images(net, padded_tile).  The images are uploaded once; groups of tiles_per_call tiles (over all
+    images of the batch) are cut out on the device (lldwt_u8hwc_to_ycc_tiles) and coded together, which bounds the device
+    memory; one tile per call in the arithmetics that are not batch invariant.  The bytes do not depend on tiles_per_call."""
+    import torch
+    from . import ops
+    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    layer, nettype, L = describe(net)
+    B, H, W = _check_images(images_u8)
+    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
+        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
+    nets = net.nets()
+    th, tw, ny, nx = tile_grid([n.autoencoder for n in nets], H, W, int(tile))
+    if ny > 0xFFFF or nx > 0xFFFF:
+        raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
+    arith = arithmetic_string()
+    _prepare(net)
+    hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx,
+               numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
+    dev = next(net.parameters()).device
+    img = images_u8.to(dev).contiguous()
+    T = B * ny * nx
+    g = int(tiles_per_call) if _batch_invariant(arith) else 1
+    tiles = []
+    with torch.no_grad():
+        for first in range(0, T, g):
+            n = min(g, T - first)
+            x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)                 # (3,n,1,th,tw)
+            s_xe, s_xo = encode_strings_planes(nets, x)
+            tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
+    per = ny * nx
+    return [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
+
+
+def _decode_tiles(nets, s_xe, s_xo, th, tw, n):
+    """One group of n tiles -> xhat (3,n,1,th,tw) (decode_strings_planes; a module-level hook so the number of tiles a
+    decode touches can be counted)."""
+    from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
+    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n)
+
+
+def _region(region, H, W):
+    if region is None:
+        return 0, 0, H, W
+    try:
+        y0, x0, h, w = (int(v) for v in region)
+    except (TypeError, ValueError):
+        raise ValueError("region must be (y0, x0, h, w) (got %r)" % (region,)) from None
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+        raise ValueError("region (%d, %d, %d, %d) is not inside the %d x %d image" % (y0, x0, h, w, H, W))
+    return y0, x0, h, w
+
+
+def decode_tiled(net, blob, region=None, tiles_per_call=32):
+    """LLDT container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
+    intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
+    Every check (container, identity, region) runs on the host before any GPU work."""
+    import torch
+    from . import ops
+    layer, nettype, L = describe(net)
+    hdr, tiles = parse_tiled(blob)
+    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
+    H, W, th, tw, ny, nx = (hdr[k] for k in ("H", "W", "th", "tw", "ny", "nx"))
+    y0, x0, h, w = _region(region, H, W)
+    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
+        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
+    _prepare(net)
+    nets = net.nets()
+    dev = next(net.parameters()).device
+    want = [ty * nx + tx for ty in range(y0 // th, (y0 + h - 1) // th + 1) for tx in range(x0 // tw, (x0 + w - 1) // tw + 1)]
+    g = int(tiles_per_call) if _batch_invariant(hdr["arithmetic"]) else 1
+    per = L + 1
+    out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
+    with torch.no_grad():
+        for a in range(0, len(want), g):
+            grp = want[a:a + g]
+            s_xe = [[tiles[t][p * per] for t in grp] for p in range(_PLANES)]
+            s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(L)]
+            xhat = _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp))
+            ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=grp, out=out)
+    return out[0].cpu()

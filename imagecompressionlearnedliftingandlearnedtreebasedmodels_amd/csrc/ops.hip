@@ -67,47 +67,82 @@ __global__ void k_ycc_to_rgb(const float* __restrict__ ycc, float* __restrict__ 
     }
 }
 
-// Image codec I/O.  uint8 HWC (B,H,W,3) RGB -> plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5, padded to Hp x Wp by replicating
-// the last row / column (the source coordinate is clamped).  The same expressions as k_u8hwc_to_f32chw then k_rgb_to_ycc, so
-// every value is bitwise equal to that composition.  Grid (cdiv(Wp,256), Hp, B): one thread per output pixel, every plane row
-// written coalesced.
-__global__ void k_u8hwc_to_ycc_pad(const uint8_t* __restrict__ src, float* __restrict__ ycc, int64_t B, int64_t H, int64_t W,
-                                   int64_t Hp, int64_t Wp) {
+// Image codec I/O over a tile grid.  The (B,H,W,3) uint8 batch is cut into a grid of ny x nx tiles of th x tw per image,
+// tile index t = (b * ny + ty) * nx + tx covering rows [ty*th, (ty+1)*th) and columns [tx*tw, (tx+1)*tw); positions past
+// the last row / column take the clamped source pixel (replicate-edge padding).  The untiled codec is the 1x1 grid
+// (th, tw) = (Hp, Wp).
+
+// uint8 HWC RGB -> plane-major (3,n,1,th,tw) YCbCr with Y-0.5 for the tiles first .. first+n-1.  The same expressions as
+// k_u8hwc_to_f32chw then k_rgb_to_ycc, so every value is bitwise equal to that composition on the padded tile.
+// Grid (cdiv(tw,256), th, n): one thread per output pixel, every plane row written coalesced.  GRID = false: the 1 x 1 grid
+// (tile = image), without the tile index arithmetic (the kernel is bandwidth-bound and the untiled codec's path).
+template <bool GRID>
+__global__ void k_u8hwc_to_ycc_tiles(const uint8_t* __restrict__ src, float* __restrict__ ycc, int64_t H, int64_t W,
+                                     int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t first, int64_t n) {
     const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (x >= Wp) return;
-    const int64_t y = blockIdx.y, b = blockIdx.z;
-    const int64_t sy = y < H ? y : H - 1, sx = x < W ? x : W - 1;
+    if (x >= tw) return;
+    const int64_t y = blockIdx.y, j = blockIdx.z;
+    int64_t b = first + j, gy = y, gx = x;
+    if (GRID) {                                   // block-uniform: 32-bit (the launcher bounds B * ny * nx)
+        const uint32_t t = (uint32_t)(first + j), per = (uint32_t)(ny * nx), b32 = t / per, r = t - b32 * per;
+        const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
+        b = b32;
+        gy += (int64_t)ty * th;
+        gx += (int64_t)tx * tw;
+    }
+    const int64_t sy = gy < H ? gy : H - 1, sx = gx < W ? gx : W - 1;
     const uint8_t* s = src + ((b * H + sy) * W + sx) * 3;
-    const float r = (float)s[0] / 255.0f, g = (float)s[1] / 255.0f, bl = (float)s[2] / 255.0f;
-    const float yy = KR * r + KG * g + KB * bl;
+    const float rr = (float)s[0] / 255.0f, g = (float)s[1] / 255.0f, bl = (float)s[2] / 255.0f;
+    const float yy = KR * rr + KG * g + KB * bl;
     const float cb = 0.5f * (bl - yy) / (1.f - KB) + 0.5f;
-    const float cr = 0.5f * (r - yy) / (1.f - KR) + 0.5f;
-    const int64_t hw = Hp * Wp, p = y * Wp + x;
-    ycc[(0 * B + b) * hw + p] = yy - 0.5f;
-    ycc[(1 * B + b) * hw + p] = cb;
-    ycc[(2 * B + b) * hw + p] = cr;
+    const float cr = 0.5f * (rr - yy) / (1.f - KR) + 0.5f;
+    const int64_t hw = th * tw, p = y * tw + x;
+    ycc[(0 * n + j) * hw + p] = yy - 0.5f;
+    ycc[(1 * n + j) * hw + p] = cb;
+    ycc[(2 * n + j) * hw + p] = cr;
 }
 
-// plane-major (3,B,1,Hp,Wp) YCbCr -> uint8 HWC (B,H,W,3) RGB of the top-left H x W: k_ycc_to_rgb(clamp=1), then
-// floor((v + 0.5) * 255 + 0.5) in fp32 (v in [-0.5, 0.5], so the byte is in [0, 255]).  Grid (cdiv(W,256), H, B).
-__global__ void k_ycc_to_u8hwc_crop(const float* __restrict__ ycc, uint8_t* __restrict__ dst, int64_t B, int64_t H, int64_t W,
-                                    int64_t Hp, int64_t Wp) {
-    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (x >= W) return;
-    const int64_t y_ = blockIdx.y, b = blockIdx.z;
-    const int64_t hw = Hp * Wp, p = y_ * Wp + x;
-    const float y = ycc[(0 * B + b) * hw + p] + 0.5f, cb = ycc[(1 * B + b) * hw + p], cr = ycc[(2 * B + b) * hw + p];
-    float r = y + (2.f - 2.f * KR) * (cr - 0.5f);
+// One pixel of plane-major YCbCr (slot j of n, offset p in its plane) -> 3 bytes of uint8 RGB: k_ycc_to_rgb(clamp=1), then
+// floor((v + 0.5) * 255 + 0.5) in fp32 (v in [-0.5, 0.5], so the byte is in [0, 255]).
+__device__ __forceinline__ void ycc_px_to_u8(const float* __restrict__ ycc, int64_t n, int64_t j, int64_t hw, int64_t p,
+                                             uint8_t* __restrict__ d) {
+    const float y = ycc[(0 * n + j) * hw + p] + 0.5f, cb = ycc[(1 * n + j) * hw + p], cr = ycc[(2 * n + j) * hw + p];
+    float rr = y + (2.f - 2.f * KR) * (cr - 0.5f);
     float bl = y + (2.f - 2.f * KB) * (cb - 0.5f);
-    float g = (y - KR * r - KB * bl) / KG;
-    r -= 0.5f; g -= 0.5f; bl -= 0.5f;
-    r = fminf(fmaxf(r, -0.5f), 0.5f);
+    float g = (y - KR * rr - KB * bl) / KG;
+    rr -= 0.5f; g -= 0.5f; bl -= 0.5f;
+    rr = fminf(fmaxf(rr, -0.5f), 0.5f);
     g = fminf(fmaxf(g, -0.5f), 0.5f);
     bl = fminf(fmaxf(bl, -0.5f), 0.5f);
-    uint8_t* d = dst + ((b * H + y_) * W + x) * 3;
-    d[0] = (uint8_t)floorf((r + 0.5f) * 255.0f + 0.5f);
+    d[0] = (uint8_t)floorf((rr + 0.5f) * 255.0f + 0.5f);
     d[1] = (uint8_t)floorf((g + 0.5f) * 255.0f + 0.5f);
     d[2] = (uint8_t)floorf((bl + 0.5f) * 255.0f + 0.5f);
+}
+
+// plane-major (3,n,1,th,tw) YCbCr of n tiles (tile of slot j: tiles[j], or first + j when tiles is null) -> uint8 HWC RGB
+// of the pixels inside the image and inside the region [y0, y0+h) x [x0, x0+w), written to dst (B,h,w,3) at the image of
+// the tile (ycc_px_to_u8).  GRID = true: grid (cdiv(tw,256), th, n), one thread per tile pixel; a tile index outside the
+// B x ny x nx grid writes nothing.  GRID = false: the 1 x 1 grid (tile = image, tiles == NULL, the untiled codec's crop):
+// grid (cdiv(w,256), h, n), one thread per region pixel.
+template <bool GRID>
+__global__ void k_ycc_tiles_to_u8hwc(const float* __restrict__ ycc, const int32_t* __restrict__ tiles, int64_t first, int64_t n,
+                                     int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx,
+                                     int64_t y0, int64_t x0, int64_t h, int64_t w, uint8_t* __restrict__ dst) {
+    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, j = blockIdx.z, hw = th * tw;
+    if (!GRID) {
+        if (x >= w) return;
+        const int64_t ry = blockIdx.y, b = first + j;
+        ycc_px_to_u8(ycc, n, j, hw, (y0 + ry) * tw + x0 + x, dst + ((b * h + ry) * w + x) * 3);
+        return;
+    }
+    if (x >= tw) return;
+    const int64_t t = tiles ? (int64_t)tiles[j] : first + j;
+    if (t < 0 || t >= B * ny * nx) return;
+    const uint32_t per = (uint32_t)(ny * nx), b = (uint32_t)t / per, r = (uint32_t)t - b * per;
+    const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
+    const int64_t gy = (int64_t)ty * th + blockIdx.y, gx = (int64_t)tx * tw + x;
+    if (gy >= H || gx >= W || gy < y0 || gy >= y0 + h || gx < x0 || gx >= x0 + w) return;
+    ycc_px_to_u8(ycc, n, j, hw, (int64_t)blockIdx.y * tw + x, dst + (((int64_t)b * h + (gy - y0)) * w + (gx - x0)) * 3);
 }
 
 // ------------------------------------------------------------------------------------------ subband MLP
@@ -1174,21 +1209,53 @@ extern "C" int lldwt_ycc_to_rgb(const float* ycc, float* rgb, int64_t B, int64_t
     hipLaunchKernelGGL(k_ycc_to_rgb, dim3(ew_grid(B * H * W)), dim3(256), 0, (hipStream_t)stream, ycc, rgb, B, H * W, clamp);
     return check_launch("ycc_to_rgb");
 }
+extern "C" int lldwt_u8hwc_to_ycc_tiles(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th,
+                                        int64_t tw, int64_t ny, int64_t nx, int64_t first, int64_t n, void* stream) {
+    LLDWT_REQUIRE(src && ycc && B > 0 && H > 0 && W > 0 && th > 0 && tw > 0 && ny > 0 && nx > 0,
+                  "u8hwc_to_ycc_tiles: bad arguments");
+    LLDWT_REQUIRE(first >= 0 && n > 0 && first + n <= B * ny * nx, "u8hwc_to_ycc_tiles: tile range [%lld, %lld) outside the "
+                  "%lld tiles", (long long)first, (long long)(first + n), (long long)(B * ny * nx));
+    LLDWT_REQUIRE(ny * th >= H && nx * tw >= W, "u8hwc_to_ycc_tiles: the grid does not cover the image");
+    LLDWT_REQUIRE(n <= 65535 && th <= 65535 && tw <= (1ll << 30) && B * ny * nx < (1ll << 31),
+                  "u8hwc_to_ycc_tiles: grid too large");
+    const bool grid = ny * nx > 1;
+    hipLaunchKernelGGL(grid ? k_u8hwc_to_ycc_tiles<true> : k_u8hwc_to_ycc_tiles<false>, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
+                       (hipStream_t)stream, src, ycc, H, W, th, tw, ny, nx, first, n);
+    return check_launch("u8hwc_to_ycc_tiles");
+}
+extern "C" int lldwt_ycc_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H,
+                                        int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
+                                        int64_t h, int64_t w, uint8_t* dst, void* stream) {
+    LLDWT_REQUIRE(ycc && dst && B > 0 && H > 0 && W > 0 && th > 0 && tw > 0 && ny > 0 && nx > 0 && n > 0,
+                  "ycc_tiles_to_u8hwc: bad arguments");
+    LLDWT_REQUIRE(tiles || (first >= 0 && first + n <= B * ny * nx), "ycc_tiles_to_u8hwc: tile range outside the grid");
+    LLDWT_REQUIRE(y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && y0 + h <= H && x0 + w <= W,
+                  "ycc_tiles_to_u8hwc: region (%lld, %lld, %lld, %lld) outside the %lld x %lld image", (long long)y0,
+                  (long long)x0, (long long)h, (long long)w, (long long)H, (long long)W);
+    LLDWT_REQUIRE(ny * th >= H && nx * tw >= W, "ycc_tiles_to_u8hwc: the grid does not cover the image");
+    const bool grid = ny * nx > 1 || tiles;
+    LLDWT_REQUIRE(n <= 65535 && (grid ? th : h) <= 65535 && tw <= (1ll << 30) && B * ny * nx < (1ll << 31),
+                  "ycc_tiles_to_u8hwc: grid too large");
+    if (grid)
+        hipLaunchKernelGGL(k_ycc_tiles_to_u8hwc<true>, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
+                           (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst);
+    else
+        hipLaunchKernelGGL(k_ycc_tiles_to_u8hwc<false>, dim3((unsigned)cdiv(w, 256), (unsigned)h, (unsigned)n), dim3(256), 0,
+                       (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst);
+    return check_launch("ycc_tiles_to_u8hwc");
+}
+// the untiled codec's I/O: the 1 x 1 grid of one Hp x Wp tile per image
 extern "C" int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
                                       void* stream) {
     LLDWT_REQUIRE(src && ycc && B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W, "u8hwc_to_ycc_pad: bad arguments");
     LLDWT_REQUIRE(B <= 65535 && Hp <= 65535 && Wp <= (1ll << 30), "u8hwc_to_ycc_pad: grid too large");
-    hipLaunchKernelGGL(k_u8hwc_to_ycc_pad, dim3((unsigned)cdiv(Wp, 256), (unsigned)Hp, (unsigned)B), dim3(256), 0,
-                       (hipStream_t)stream, src, ycc, B, H, W, Hp, Wp);
-    return check_launch("u8hwc_to_ycc_pad");
+    return lldwt_u8hwc_to_ycc_tiles(src, ycc, B, H, W, Hp, Wp, 1, 1, 0, B, stream);
 }
 extern "C" int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
                                        void* stream) {
     LLDWT_REQUIRE(ycc && dst && B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W, "ycc_to_u8hwc_crop: bad arguments");
     LLDWT_REQUIRE(B <= 65535 && H <= 65535 && W <= (1ll << 30), "ycc_to_u8hwc_crop: grid too large");
-    hipLaunchKernelGGL(k_ycc_to_u8hwc_crop, dim3((unsigned)cdiv(W, 256), (unsigned)H, (unsigned)B), dim3(256), 0,
-                       (hipStream_t)stream, ycc, dst, B, H, W, Hp, Wp);
-    return check_launch("ycc_to_u8hwc_crop");
+    return lldwt_ycc_tiles_to_u8hwc(ycc, nullptr, 0, B, B, H, W, Hp, Wp, 1, 1, 0, 0, H, W, dst, stream);
 }
 
 extern "C" int lldwt_subband_mlp(const float* x, float* y, int64_t planes, int64_t batch, int C, int64_t hw, int Hd,

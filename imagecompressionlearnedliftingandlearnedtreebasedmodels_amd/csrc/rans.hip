@@ -11,12 +11,23 @@
 // Also pmf_to_quantized_cdf (compressai _CXX): float pmf -> 16-bit CDF with every symbol given a non-zero frequency.
 // parity unpinned against compressai's bytes (package absent, the reference holds no bitstream fixture); pinned instead by
 // an independent pure-Python restatement held by the tests, by decode(encode(x)) == x and by the code length.
+//
+// The multi-stream calls (lldwt_rans_encode_multi, lldwt_rans_decode_multi) code independent streams on a persistent pool of
+// host threads.  Every stream still runs through the same sequential state machine; only which thread runs it changes, so
+// the bytes and symbols are those of the one-stream calls.
+#include <pthread.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <functional>
+#include <mutex>
 #include <numeric>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "common.h"
@@ -86,7 +97,145 @@ struct Decoder {
     }
 };
 
+// ------------------------------------------------------------------------------------------ stream-parallel pool
+// Threads for a call: min(16, OMP_NUM_THREADS if set (read once), number of streams) -- never the machine's core count (a
+// process may own a share of a much larger host).  Calls with fewer symbols in all than the threshold stay on the calling
+// thread: handing a call to the pool costs ~10 us of wake-up, and the wavefront decoder makes ~2 000 small calls per
+// 512 x 512 image.  Break-even measured on one MI355X host with tools/bench_rans_parallel.py: ~3 000-6 000
+// symbols per decode call, ~12 000 per encode call.
+constexpr int kMaxThreads = 16;
+constexpr int64_t kParallelMinDecode = 4096;
+constexpr int64_t kParallelMinEncode = 12288;
+std::atomic<int> g_threads_override{0};                     // lldwt_rans_set_parallel: 0 = the rule above
+std::atomic<int64_t> g_min_symbols{-1};                     // -1: the per-direction thresholds above
+
+int env_threads() {
+    static const int n = [] {
+        const char* e = getenv("OMP_NUM_THREADS");
+        if (!e || !*e) return kMaxThreads;
+        const int v = atoi(e);
+        return v < 1 ? 1 : std::min(v, kMaxThreads);
+    }();
+    return n;
+}
+
+// Workers sleep on a condition variable between jobs; a job hands out stream indexes through an atomic counter and the
+// calling thread takes part.  One job at a time.  The pool is never destroyed (workers blocked at exit die with the
+// process); a fork()ed child starts a new one.
+class Pool {
+  public:
+    void run(int64_t nitems, int nthreads, const std::function<void(int64_t)>& fn) {
+        std::lock_guard<std::mutex> job(job_);
+        while ((int)workers_.size() < nthreads - 1) {
+            const int id = (int)workers_.size();
+            const uint64_t gen = gen_;                  // a new worker waits for the NEXT job (gen_ only moves under job_)
+            workers_.emplace_back([this, id, gen] { work(id, gen); });
+            workers_.back().detach();
+        }
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            fn_ = &fn;
+            nitems_ = nitems;
+            next_.store(0);
+            wanted_ = nthreads - 1;
+            running_ = nthreads - 1;
+            ++gen_;
+        }
+        cv_.notify_all();
+        drain();
+        std::unique_lock<std::mutex> lk(m_);
+        done_.wait(lk, [this] { return running_ == 0; });
+        fn_ = nullptr;
+    }
+
+  private:
+    void drain() {
+        for (int64_t k; (k = next_.fetch_add(1)) < nitems_;) (*fn_)(k);
+    }
+    void work(int id, uint64_t seen) {
+        std::unique_lock<std::mutex> lk(m_);
+        for (;;) {
+            cv_.wait(lk, [&] { return gen_ != seen; });
+            seen = gen_;
+            if (id >= wanted_) continue;
+            lk.unlock();
+            drain();
+            lk.lock();
+            if (--running_ == 0) done_.notify_one();
+        }
+    }
+    std::mutex job_, m_;
+    std::condition_variable cv_, done_;
+    std::vector<std::thread> workers_;
+    const std::function<void(int64_t)>* fn_ = nullptr;
+    int64_t nitems_ = 0;
+    std::atomic<int64_t> next_{0};
+    int wanted_ = 0, running_ = 0;
+    uint64_t gen_ = 0;
+};
+
+std::atomic<Pool*> g_pool{nullptr};
+std::once_flag g_atfork_once;
+
+Pool& pool() {
+    std::call_once(g_atfork_once, [] { pthread_atfork(nullptr, nullptr, [] { g_pool.store(nullptr); }); });
+    Pool* p = g_pool.load();
+    if (!p) {
+        Pool* fresh = new Pool();
+        if (g_pool.compare_exchange_strong(p, fresh))
+            p = fresh;
+        else
+            delete fresh;
+    }
+    return *p;
+}
+
+int threads_for(int64_t nstreams, int64_t nsymbols, int64_t min_symbols) {
+    const int over = g_threads_override.load();
+    const int cap = over > 0 ? std::min(over, kMaxThreads) : env_threads();
+    const int64_t m = g_min_symbols.load();
+    if (nstreams < 2 || cap < 2 || (over <= 0 && nsymbols < (m >= 0 ? m : min_symbols))) return 1;
+    return (int)std::min<int64_t>(cap, nstreams);
+}
+
+// Runs fn(k) for k < nstreams (fn returns an LLDWT status).  The error of the lowest failing stream is reported, as the
+// sequential loop would report it; the sequential loop stops there, the pool finishes the other streams.
+int for_streams(int64_t nstreams, int64_t nsymbols, int64_t min_symbols, const std::function<int(int64_t)>& fn) {
+    const int nt = threads_for(nstreams, nsymbols, min_symbols);
+    if (nt <= 1) {
+        for (int64_t k = 0; k < nstreams; ++k) {
+            const int r = fn(k);
+            if (r) return r;
+        }
+        return LLDWT_OK;
+    }
+    std::mutex em;
+    int64_t bad_k = -1;
+    int bad_r = LLDWT_OK;
+    std::string bad_msg;
+    pool().run(nstreams, nt, [&](int64_t k) {
+        const int r = fn(k);
+        if (r) {
+            std::lock_guard<std::mutex> lk(em);
+            if (bad_k < 0 || k < bad_k) {
+                bad_k = k;
+                bad_r = r;
+                bad_msg = lldwt_last_error();          // the worker's thread-local message
+            }
+        }
+    });
+    if (bad_k >= 0) lldwt::set_error("%s", bad_msg.c_str());
+    return bad_r;
+}
+
 }  // namespace
+
+extern "C" int lldwt_rans_set_parallel(int threads, int64_t min_symbols) {
+    LLDWT_REQUIRE(threads >= 0 && min_symbols >= -1, "rans_set_parallel: bad arguments");
+    g_threads_override.store(threads);
+    g_min_symbols.store(min_symbols);
+    return LLDWT_OK;
+}
 
 extern "C" int lldwt_pmf_to_quantized_cdf(const float* pmf, int n, int precision, uint32_t* cdf) {
     LLDWT_REQUIRE(pmf && cdf && n > 0 && precision > 0 && precision <= 16, "pmf_to_quantized_cdf: bad arguments");
@@ -127,7 +276,18 @@ extern "C" int64_t lldwt_rans_encode(const int32_t* symbols, const int32_t* inde
         lldwt::set_error("rans_encode: bad arguments");
         return LLDWT_EINVAL;
     }
-    std::vector<Sym> syms;
+    // per-thread scratch kept across calls: a fresh allocation per stream costs page faults, which serialise the threads of
+    // a multi-stream call
+    static thread_local std::vector<Sym> syms;
+    static thread_local std::vector<uint32_t> words;
+    struct Trim {                                  // do not hold more than 64 MB per thread between calls
+        ~Trim() {
+            if (syms.capacity() * sizeof(Sym) > (64u << 20)) std::vector<Sym>().swap(syms);
+            if (words.capacity() * 4 > (64u << 20)) std::vector<uint32_t>().swap(words);
+        }
+    } trim;
+    syms.clear();
+    words.clear();
     syms.reserve((size_t)n + 16);
     for (int64_t i = 0; i < n; ++i) {
         const int32_t ci = indexes[i];
@@ -166,7 +326,6 @@ extern "C" int64_t lldwt_rans_encode(const int32_t* symbols, const int32_t* inde
             }
         }
     }
-    std::vector<uint32_t> words;
     words.reserve(syms.size() / 2 + 4);
     uint64_t x = kRansL;
     for (size_t k = syms.size(); k-- > 0;) {
@@ -249,14 +408,28 @@ extern "C" int lldwt_rans_decode(void* dec, const int32_t* indexes, int64_t n, c
 
 // One call for a whole wavefront step: stream k (of nstreams decoders) pops n symbols for the indexes at indexes + k * stride,
 // into symbols + k * stride.  The same tables for every stream.  (A Python loop over the streams of a step cost more than the
-// decoding itself: ~10 us of call overhead per stream and step.)
+// decoding itself: ~10 us of call overhead per stream and step.)  Streams in parallel above the pool's threshold.
 extern "C" int lldwt_rans_decode_multi(void* const* decs, int64_t nstreams, const int32_t* indexes, int64_t n, int64_t stride,
                                        const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride, const int32_t* cdf_sizes,
                                        const int32_t* offsets, int32_t* symbols) {
     LLDWT_REQUIRE(decs && nstreams >= 0 && stride >= n, "rans_decode_multi: bad arguments");
-    for (int64_t k = 0; k < nstreams; ++k) {
-        const int r = lldwt_rans_decode(decs[k], indexes + k * stride, n, cdfs, ncdf, cdf_stride, cdf_sizes, offsets, symbols + k * stride);
-        if (r) return r;
-    }
-    return LLDWT_OK;
+    return for_streams(nstreams, nstreams * n, kParallelMinDecode, [&](int64_t k) {
+        return lldwt_rans_decode(decs[k], indexes + k * stride, n, cdfs, ncdf, cdf_stride, cdf_sizes, offsets, symbols + k * stride);
+    });
+}
+
+// nstreams independent encodes with the same tables: stream k codes the n symbols at symbols + k * stride (indexes
+// likewise) into out + k * out_stride (at most out_stride bytes) and stores its length in nbytes[k].  Each stream's bytes
+// are those of lldwt_rans_encode on it.
+extern "C" int lldwt_rans_encode_multi(const int32_t* symbols, const int32_t* indexes, int64_t nstreams, int64_t n, int64_t stride,
+                                       const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride, const int32_t* cdf_sizes,
+                                       const int32_t* offsets, uint8_t* out, int64_t out_stride, int64_t* nbytes) {
+    LLDWT_REQUIRE(symbols && indexes && out && nbytes && nstreams >= 0 && n >= 0 && stride >= n && out_stride > 0,
+                  "rans_encode_multi: bad arguments");
+    return for_streams(nstreams, nstreams * n, kParallelMinEncode, [&](int64_t k) {
+        const int64_t r = lldwt_rans_encode(symbols + k * stride, indexes + k * stride, n, cdfs, ncdf, cdf_stride, cdf_sizes,
+                                            offsets, out + k * out_stride, out_stride);
+        nbytes[k] = r;
+        return r < 0 ? (int)r : LLDWT_OK;
+    });
 }

@@ -276,8 +276,13 @@ def padded_size(nets, H, W):
     cdf_args); CDF 9/7 also refuses a deepest level input shorter than its 10 taps (cdf_args, csrc/cdf97.hip:547), i.e.
     min(Hp, Wp) >> (L-1) >= 10, so both sides are at least 5 * 2^L (no short levels, whatever set_cdf97_short_levels says)."""
     n0 = nets[0]
-    m = 1 << _levels(n0)
-    lo = 5 * m if isinstance(n0, DWTPytorchWaveletsLayer) else m
+    return padded_dims(_levels(n0), isinstance(n0, DWTPytorchWaveletsLayer), H, W)
+
+
+def padded_dims(L, cdf97, H, W):
+    """padded_size from the level count and the transform kind alone (what a container header holds)."""
+    m = 1 << L
+    lo = 5 * m if cdf97 else m
     up = lambda v: max(lo, -(-v // m) * m)
     return up(H), up(W)
 

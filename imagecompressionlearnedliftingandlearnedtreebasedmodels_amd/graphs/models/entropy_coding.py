@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from ...ans import BufferedRansEncoder, RansDecoder
+from ...ans import RansDecoder, decode_streams, encode_streams
 
 _WF_CACHE = {}
 
@@ -105,18 +105,12 @@ class _Sink:
         A hook for diagnostics (the code-length test replaces it); does nothing."""
 
     def flush(self):
-        """Encoder: -> strings[p][b]."""
+        """Encoder: -> strings[p][b] (the P * B streams in one parallel call)."""
         idx = torch.cat(self.idx, 2).cpu().numpy()          # (P,B,Npix,g) in wavefront order
         sym = torch.cat(self.sym, 2).cpu().numpy()
-        out = []
-        for p in range(self.P):
-            row = []
-            for b in range(self.B):
-                e = BufferedRansEncoder()
-                e.encode_with_indexes(sym[p, b].reshape(-1), idx[p, b].reshape(-1), self.t.cdf, self.t.sizes, self.t.offsets)
-                row.append(e.flush())
-            out.append(row)
-        return out
+        flat = encode_streams(sym.reshape(self.P * self.B, -1), idx.reshape(self.P * self.B, -1), self.t.cdf, self.t.sizes,
+                              self.t.offsets)
+        return [flat[p * self.B:(p + 1) * self.B] for p in range(self.P)]
 
 
 def _finish_step(emodel, sink, sigma, mu, yv):
@@ -311,21 +305,12 @@ def code_factorized(emodels, y, shape, strings=None):
         if strings is None:
             sym, idx = em.symbols_and_indexes(y[p])                                     # (B,C,h,w)
             sh, ih = sym.cpu().numpy(), idx.cpu().numpy()
-            row = []
-            for b in range(B):
-                e = BufferedRansEncoder()
-                e.encode_with_indexes(sh[b].reshape(-1), ih[b].reshape(-1), tabs.cdf, tabs.sizes, tabs.offsets)
-                row.append(e.flush())
-            strs.append(row)
+            strs.append(encode_streams(sh.reshape(B, -1), ih.reshape(B, -1), tabs.cdf, tabs.sizes, tabs.offsets))
             out.append(em.dequantize_symbols(sym))
         else:
             dev = em.quantiles.device
-            idx = np.broadcast_to(np.arange(Cc, dtype=np.int32).reshape(Cc, 1, 1), (Cc, H, W)).reshape(-1)
-            syms = np.empty((B, Cc, H, W), dtype=np.int32)
-            for b in range(B):
-                d = RansDecoder()
-                d.set_stream(strings[p][b])
-                syms[b] = d.decode_stream(idx, tabs.cdf, tabs.sizes, tabs.offsets, as_numpy=True).reshape(Cc, H, W)
+            idx = np.broadcast_to(np.arange(Cc, dtype=np.int32).reshape(1, Cc, 1, 1), (B, Cc, H, W)).reshape(B, -1)
+            syms = decode_streams(strings[p], idx, tabs.cdf, tabs.sizes, tabs.offsets).reshape(B, Cc, H, W)
             out.append(em.dequantize_symbols(torch.from_numpy(syms).to(dev)))
     return (strs if strings is None else None), torch.stack(out, 0)
 
@@ -341,22 +326,10 @@ def code_gaussian_parallel(emodels, params, y, shape, tables, strings=None):
     if strings is None:
         sym = torch.round(y - mu).int()
         sh = sym.cpu().numpy()
-        strs = []
-        for p in range(P):
-            row = []
-            for b in range(B):
-                e = BufferedRansEncoder()
-                e.encode_with_indexes(sh[p, b].reshape(-1), ih[p, b].reshape(-1), tables.cdf, tables.sizes, tables.offsets)
-                row.append(e.flush())
-            strs.append(row)
-        return strs, sym.float() + mu
-    syms = np.empty(ih.shape, dtype=np.int32)
-    for p in range(P):
-        for b in range(B):
-            d = RansDecoder()
-            d.set_stream(strings[p][b])
-            syms[p, b] = d.decode_stream(ih[p, b].reshape(-1), tables.cdf, tables.sizes, tables.offsets,
-                                         as_numpy=True).reshape(ih.shape[2:])
+        flat = encode_streams(sh.reshape(P * B, -1), ih.reshape(P * B, -1), tables.cdf, tables.sizes, tables.offsets)
+        return [flat[p * B:(p + 1) * B] for p in range(P)], sym.float() + mu
+    syms = decode_streams([strings[p][b] for p in range(P) for b in range(B)], ih.reshape(P * B, -1), tables.cdf,
+                          tables.sizes, tables.offsets).reshape(ih.shape)
     return None, torch.from_numpy(syms).to(mu.device).float() + mu
 
 

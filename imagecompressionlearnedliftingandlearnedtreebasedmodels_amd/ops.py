@@ -130,6 +130,45 @@ def u8hwc_to_ycc_pad(src, Hp, Wp):
     return y
 
 
+def u8hwc_to_ycc_tiles(src, th, tw, ny, nx, first, n):
+    """(B,H,W,3) uint8 RGB device tensor -> plane-major (3,n,1,th,tw) YCbCr with Y-0.5 of the tiles first .. first+n-1 of a
+    ny x nx grid of th x tw tiles per image (index (b * ny + ty) * nx + tx), replicate-edge padded past the image
+    (lldwt_u8hwc_to_ycc_tiles; bitwise u8hwc_to_ycc_pad of the cropped tile)."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+            and src.dim() == 4 and src.shape[3] == 3):
+        raise _lib.LLDWTError("u8hwc_to_ycc_tiles: expected a contiguous (B,H,W,3) uint8 device tensor")
+    B, H, W, _ = src.shape
+    y = torch.empty(3, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u8hwc_to_ycc_tiles(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, th, tw, ny, nx, first, n,
+                                               _stream()), "u8hwc_to_ycc_tiles")
+    return y
+
+
+def ycc_tiles_to_u8hwc(y, grid, region, tiles=None, first=0, B=1, out=None):
+    """plane-major (3,n,1,th,tw) decoded tiles -> the uint8 RGB pixels of those tiles inside the image and the region,
+    written into out (B,h,w,3) (allocated when None; pixels no tile covers are left as they are) and returned.
+    grid = (H, W, th, tw, ny, nx); region = (y0, x0, h, w) inside the image; tiles: the n tile indexes (list), or None for
+    first .. first+n-1 (lldwt_ycc_tiles_to_u8hwc: bytes as ycc_to_u8hwc_crop)."""
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    _, n, _, yh, yw = y.shape
+    if (yh, yw) != (th, tw):
+        raise _lib.LLDWTError("ycc_tiles_to_u8hwc: tiles are %d x %d, the grid says %d x %d" % (yh, yw, th, tw))
+    tptr = C.c_void_p(0)
+    if tiles is not None:
+        if len(tiles) != n or any(t < 0 or t >= B * ny * nx for t in tiles):
+            raise _lib.LLDWTError("ycc_tiles_to_u8hwc: need %d tile indexes in [0, %d)" % (n, B * ny * nx))
+        tiles = torch.tensor(list(tiles), dtype=torch.int32).to(y.device)
+        tptr = C.c_void_p(tiles.data_ptr())
+    if out is None:
+        out = torch.empty(B, h, w, 3, device=y.device, dtype=torch.uint8)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)):
+        raise _lib.LLDWTError("ycc_tiles_to_u8hwc: out must be a contiguous (%d,%d,%d,3) uint8 device tensor" % (B, h, w))
+    check(_lib.load().lldwt_ycc_tiles_to_u8hwc(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w,
+                                               C.c_void_p(out.data_ptr()), _stream()), "ycc_tiles_to_u8hwc")
+    return out
+
+
 def ycc_to_u8hwc_crop(y, H, W):
     """plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5 -> (B,H,W,3) uint8 RGB of the top-left H x W
     (lldwt_ycc_to_u8hwc_crop: floor((v + 0.5) * 255 + 0.5) of v = ycc_to_rgb(y, clamp=True))."""

@@ -67,12 +67,25 @@ int lldwt_ycc_to_rgb_bwd(const float* grgb, float* gycc, int64_t B, int64_t H, i
  * ToTensor's arithmetic (x / 255 in fp32), bit-exact.                                                          */
 int lldwt_u8hwc_to_f32chw(const uint8_t* src, float* dst, int64_t B, int64_t H, int64_t W, void* stream);
 
-/* Image codec I/O (the package's codec.py; the reference has no file codec).
- * lldwt_u8hwc_to_ycc_pad: src (B,H,W,3) uint8 RGB -> ycc plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5, Hp >= H, Wp >= W;
- *   positions outside the image take the value of the clamped source pixel (replicate-edge padding).  Inside the image
- *   bitwise equal to lldwt_u8hwc_to_f32chw followed by lldwt_rgb_to_ycc.  B, Hp <= 65535.
- * lldwt_ycc_to_u8hwc_crop: ycc (3,B,1,Hp,Wp) -> dst (B,H,W,3) uint8 RGB of the top-left H x W:
- *   floor((v + 0.5f) * 255.0f + 0.5f) of v = lldwt_ycc_to_rgb(..., clamp=1).  B, H <= 65535.                      */
+/* Image codec I/O (the package's codec.py; the reference has no file codec), on a tile grid: each of the B images of a
+ * (B,H,W,3) uint8 RGB batch is cut into ny x nx tiles of th x tw; tile index t = (b * ny + ty) * nx + tx covers rows
+ * [ty*th, (ty+1)*th) and columns [tx*tw, (tx+1)*tw); positions past the last row / column take the value of the clamped
+ * source pixel (replicate-edge padding).  The untiled codec is the 1 x 1 grid with (th, tw) = (Hp, Wp).
+ * lldwt_u8hwc_to_ycc_tiles: the tiles first .. first+n-1 -> ycc plane-major (3,n,1,th,tw) YCbCr with Y-0.5; every value
+ *   bitwise equal to lldwt_u8hwc_to_f32chw followed by lldwt_rgb_to_ycc on the padded tile.  n, th <= 65535.
+ * lldwt_ycc_tiles_to_u8hwc: ycc (3,n,1,th,tw) of the tiles tiles[0..n-1] (a device int32 array; NULL: first .. first+n-1)
+ *   -> the pixels of those tiles inside the image and inside the region [y0, y0+h) x [x0, x0+w) (which must lie in the
+ *   image), written to dst (B,h,w,3) uint8 RGB at the tile's image b: floor((v + 0.5f) * 255.0f + 0.5f) of
+ *   v = lldwt_ycc_to_rgb(..., clamp=1).  Pixels of the region no listed tile covers are left as they are.  n, th <= 65535.
+ * lldwt_u8hwc_to_ycc_pad: src (B,H,W,3) -> ycc (3,B,1,Hp,Wp), Hp >= H, Wp >= W: the 1 x 1 grid.  B, Hp <= 65535.
+ * lldwt_ycc_to_u8hwc_crop: ycc (3,B,1,Hp,Wp) -> dst (B,H,W,3) of the top-left H x W: the 1 x 1 grid, region = the image.
+ *   B, H <= 65535.
+ * Both tile entry points require ny * th >= H and nx * tw >= W.                                                                                                  */
+int lldwt_u8hwc_to_ycc_tiles(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw,
+                             int64_t ny, int64_t nx, int64_t first, int64_t n, void* stream);
+int lldwt_ycc_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                             int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                             uint8_t* dst, void* stream);
 int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
                            void* stream);
 int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
@@ -498,10 +511,22 @@ void* lldwt_rans_decoder_new(const uint8_t* stream, int64_t nbytes);
 int lldwt_rans_decode(void* dec, const int32_t* indexes, int64_t n, const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride,
                       const int32_t* cdf_sizes, const int32_t* offsets, int32_t* symbols);
 /* The same for nstreams decoders in one call (one wavefront step of every (plane, image) stream): stream k reads its n
- * indexes at indexes + k * stride and writes symbols + k * stride; one table set for all. */
+ * indexes at indexes + k * stride and writes symbols + k * stride; one table set for all.
+ * lldwt_rans_encode_multi: nstreams independent lldwt_rans_encode calls with one table set: stream k codes the n symbols
+ *   at symbols + k * stride (indexes likewise) into out + k * out_stride (capacity out_stride bytes), its length goes to
+ *   nbytes[k].
+ * Both run their streams on a persistent pool of host threads when the call holds at least 4 096 (decode) / 12 288
+ * (encode) symbols: min(16, OMP_NUM_THREADS if set, nstreams) threads.  Each stream runs the same state machine as the one-stream call, so bytes and
+ * symbols do not depend on the thread count.  On failure the error of the lowest failing stream is reported.
+ * lldwt_rans_set_parallel: threads > 0 forces that many threads (at most 16) on every multi-stream call, 1 = sequential;
+ *   threads = 0 restores the rule above; min_symbols >= 0 replaces both thresholds, -1 restores them.             */
 int lldwt_rans_decode_multi(void* const* decs, int64_t nstreams, const int32_t* indexes, int64_t n, int64_t stride,
                             const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride, const int32_t* cdf_sizes,
                             const int32_t* offsets, int32_t* symbols);
+int lldwt_rans_encode_multi(const int32_t* symbols, const int32_t* indexes, int64_t nstreams, int64_t n, int64_t stride,
+                            const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride, const int32_t* cdf_sizes,
+                            const int32_t* offsets, uint8_t* out, int64_t out_stride, int64_t* nbytes);
+int lldwt_rans_set_parallel(int threads, int64_t min_symbols);
 void lldwt_rans_decoder_free(void* dec);
 
 /* ---------------------------------------------------------------------------------------------------------

@@ -1,0 +1,200 @@
+"""Host (CPU) tests of tiled coding (codec.py): the tile grid rule, the LLDT container (round trip, every structural refusal
+with its field named) and the stream-parallel host rANS coder against the sequential path and the pure-Python oracle."""
+import struct
+import zlib
+
+import numpy as np
+import pytest
+
+from oracle import rans as orans
+from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import ans, codec
+
+
+def _autoencoders(netType, L):
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.graphs.models.LiftingBasedDWT_net import \
+        LiftingBasedDWTNetWrapper
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.utils.config import make_config
+    net = LiftingBasedDWTNetWrapper(make_config(dwtlevels=L, netType=netType, entropy_layer="onlyEZWT"))
+    return [n.autoencoder for n in net.nets()]
+
+
+# ------------------------------------------------------------------------------------------------ grid
+@pytest.mark.parametrize("netType,L,H,W,tile,want", [
+    ("LiftingBasedNeuralWaveletv4", 4, 2160, 3840, 512, (432, 480, 5, 8)),     # exact fit: no padding
+    ("LiftingBasedNeuralWaveletv4", 3, 200, 300, 96, (72, 80, 3, 4)),          # ragged on both sides
+    ("LiftingBasedNeuralWaveletv4", 3, 100, 90, 512, (104, 96, 1, 1)),        # single tile = padded_size of the image
+    ("LiftingBasedNeuralWaveletv4", 4, 512, 512, 512, (512, 512, 1, 1)),
+    ("CDF97", 3, 100, 100, 16, (40, 40, 3, 3)),                                # 5 * 2^L minimum: the grid is recounted
+    ("CDF97", 4, 37, 1000, 100, (80, 112, 1, 9)),
+])
+def test_tile_grid_rule(netType, L, H, W, tile, want):
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.graphs.layers.lifting_dwt_nets import padded_size
+    aes = _autoencoders(netType, L)
+    th, tw, ny, nx = codec.tile_grid(aes, H, W, tile)
+    assert (th, tw, ny, nx) == want
+    assert padded_size(aes, th, tw) == (th, tw)
+    assert ny * th >= H and (ny - 1) * th < H and nx * tw >= W and (nx - 1) * tw < W
+    if ny * nx == 1:
+        assert (th, tw) == padded_size(aes, H, W)
+
+
+# ------------------------------------------------------------------------------------------------ container
+def _hdr(L=1, H=37, W=53, th=24, tw=32, ny=2, nx=2, netType="LiftingBasedNeuralWaveletv4"):
+    return dict(layer="onlyEZWT", netType=netType, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx, numerics=7,
+                arithmetic="plc_mode=f16x3,storage=fp32", digest=bytes(range(16)))
+
+
+def _tiles(hdr, seed=0):
+    g = np.random.default_rng(seed)
+    per = 3 * (hdr["dwtlevels"] + 1)
+    return [[bytes(g.integers(0, 256, int(g.integers(0, 140))).astype(np.uint8).tobytes()) for _ in range(per)]
+            for _ in range(hdr["ny"] * hdr["nx"])]
+
+
+def _raw(hdr, tile_streams, count=None, magic=b"LLDT", version=1):
+    """An LLDT container packed WITHOUT pack_tiled's checks (to build inconsistent ones)."""
+    head = codec._TFIXED.pack(magic, version, codec.LAYER_CODES[hdr["layer"]], codec.NETTYPE_CODES[hdr["netType"]],
+                              hdr["dwtlevels"], hdr["H"], hdr["W"], hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"],
+                              hdr["numerics"])
+    count = 3 * (hdr["dwtlevels"] + 1) if count is None else count
+    body = head + codec._pack_identity(hdr) + bytes([count]) + codec._pack_streams([s for t in tile_streams for s in t])
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def test_tiled_pack_parse_round_trip():
+    hdr = _hdr()
+    tiles = _tiles(hdr)
+    blob = codec.pack_tiled(hdr, tiles)
+    assert blob[:4] == b"LLDT" and blob[4] == 1
+    assert blob == _raw(hdr, tiles)
+    got, got_tiles = codec.parse_tiled(blob)
+    for k, v in hdr.items():
+        assert got[k] == v, k
+    assert got_tiles == tiles
+    assert got["streams_per_tile"] == 6
+    assert got["stream_lengths"] == [len(s) for t in tiles for s in t]
+    assert len(blob) == got["header_bytes"] + sum(got["stream_lengths"]) + 4
+    assert codec.read_header(blob) == got
+    # LLDW headers read as before
+    lldw = codec.pack_container(dict(hdr, H=37, W=53), tiles[0])
+    assert codec.read_header(lldw) == codec.parse_container(lldw)[0] and "ny" not in codec.read_header(lldw)
+
+
+def test_formats_refuse_each_other():
+    hdr = _hdr()
+    blob = codec.pack_tiled(hdr, _tiles(hdr))
+    lldw = codec.pack_container(hdr, _tiles(hdr)[0])
+    with pytest.raises(ValueError, match="magic"):
+        codec.parse_container(blob)
+    with pytest.raises(ValueError, match="magic"):
+        codec.parse_tiled(lldw)
+
+
+def test_tiled_structural_refusals_name_the_field():
+    hdr = _hdr()
+    tiles = _tiles(hdr)
+    blob = codec.pack_tiled(hdr, tiles)
+    with pytest.raises(ValueError, match="magic"):
+        codec.parse_tiled(b"PNG0" + blob[4:])
+    with pytest.raises(ValueError, match="version"):
+        codec.parse_tiled(_raw(hdr, tiles, version=2))
+    with pytest.raises(ValueError, match="CRC"):
+        codec.parse_tiled(blob[:-5] + bytes([blob[-5] ^ 1]) + blob[-4:])
+    with pytest.raises(ValueError, match="stream count"):
+        codec.parse_tiled(_raw(hdr, [t[:-1] for t in tiles], count=5))
+    with pytest.raises(ValueError, match="stream count"):
+        codec.pack_tiled(hdr, tiles[:-1])
+    # grids that do not fit the image: too few / too many rows or columns, a tile size the transform refuses
+    for bad, field in [(dict(ny=1), "rows"), (dict(ny=3), "rows"), (dict(th=16), "rows"),
+                       (dict(nx=1), "columns"), (dict(nx=3), "columns"), (dict(tw=56), "columns"),
+                       (dict(th=19, ny=2), "tile size"), (dict(H=20, W=30, th=24, tw=32, ny=1, nx=1, netType="CDF97",
+                                                               dwtlevels=3), "tile size")]:
+        h = dict(hdr, **bad)
+        t = _tiles(h)
+        with pytest.raises(ValueError, match=field):
+            codec.parse_tiled(_raw(h, t))
+        with pytest.raises(ValueError, match=field):
+            codec.pack_tiled(h, t)
+
+
+def test_tiled_truncations_and_byte_flips_are_value_errors():
+    hdr = _hdr(L=1, ny=2, nx=1, W=30)
+    blob = codec.pack_tiled(hdr, _tiles(hdr, 3))
+    for n in range(len(blob)):
+        with pytest.raises(ValueError):
+            codec.parse_tiled(blob[:n])
+    for i in range(0, len(blob), 3):
+        bad = bytearray(blob)
+        bad[i] ^= 0x41
+        with pytest.raises(ValueError):
+            codec.parse_tiled(bytes(bad))
+
+
+# ------------------------------------------------------------------------------------------------ parallel host rANS
+def _tables(seed, ncdf=6):
+    g = np.random.default_rng(seed)
+    cdfs, sizes, offs = [], [], []
+    for _ in range(ncdf):
+        n = int(g.integers(3, 40))
+        pmf = g.random(n).astype(np.float32) ** 3 + 1e-7
+        pmf /= pmf.sum()
+        c = orans.pmf_to_quantized_cdf(pmf.tolist())
+        cdfs.append(c)
+        sizes.append(len(c))
+        offs.append(-int(g.integers(0, n)))
+    return cdfs, sizes, offs
+
+
+@pytest.fixture
+def restore_parallel():
+    yield
+    ans.set_parallel(0, -1)
+
+
+@pytest.mark.parametrize("S,n", [(48, 700), (64, 300), (3, 5000)])
+def test_parallel_rans_equals_sequential_and_oracle(S, n, restore_parallel):
+    cdfs, sizes, offs = _tables(S)
+    g = np.random.default_rng(n)
+    idx = g.integers(0, len(cdfs), (S, n)).astype(np.int32)
+    sym = np.array([[int(g.integers(offs[i] - 3, offs[i] + sizes[i] + 1)) for i in r] for r in idx], dtype=np.int32)
+    sym[1, 5], sym[S - 1, n - 1] = 100000, -77777                         # long bypass runs
+    ans.set_parallel(1)
+    seq = ans.encode_streams(sym, idx, cdfs, sizes, offs)
+    ans.set_parallel(16, 0)                                                # every call on the pool, 16 threads
+    par = ans.encode_streams(sym, idx, cdfs, sizes, offs)
+    assert par == seq
+    for k in range(S):
+        e = ans.BufferedRansEncoder()
+        e.encode_with_indexes(sym[k], idx[k], cdfs, sizes, offs)
+        assert e.flush() == par[k], k
+    for k in (0, 1, S // 2, S - 1):
+        assert par[k] == orans.encode(sym[k].tolist(), idx[k].tolist(), cdfs, sizes, offs), k
+        assert orans.Decoder(par[k]).decode(idx[k].tolist(), cdfs, sizes, offs) == sym[k].tolist()
+    got = ans.decode_streams(par, idx, cdfs, sizes, offs)
+    assert np.array_equal(got, sym)
+    ans.set_parallel(1)
+    assert np.array_equal(ans.decode_streams(par, idx, cdfs, sizes, offs), sym)
+    ans.set_parallel(0, -1)                                                # the default rule (threshold from the symbol count)
+    assert ans.encode_streams(sym, idx, cdfs, sizes, offs) == seq
+    assert np.array_equal(ans.decode_streams(par, idx, cdfs, sizes, offs), sym)
+
+
+def test_parallel_rans_reports_the_first_failing_stream(restore_parallel):
+    cdfs, sizes, offs = _tables(5)
+    S, n = 48, 200
+    idx = np.zeros((S, n), dtype=np.int32)
+    sym = np.zeros((S, n), dtype=np.int32)
+    idx[20, 3] = idx[40, 0] = len(cdfs) + 2                                # out-of-table indexes in two streams
+    msgs = []
+    for threads in (1, 16):
+        ans.set_parallel(threads, 0)
+        with pytest.raises(Exception, match="cdf index") as e:
+            ans.encode_streams(sym, idx, cdfs, sizes, offs)
+        msgs.append(str(e.value))
+    assert msgs[0] == msgs[1] and "symbol 3" in msgs[0]
+    # a truncated stream: read past the end, in either mode
+    good = ans.encode_streams(np.zeros((S, n), np.int32), np.zeros((S, n), np.int32), cdfs, sizes, offs)
+    bad = list(good)
+    bad[7] = bad[7][:8]
+    with pytest.raises(Exception, match="past the end|corrupt"):
+        ans.decode_streams(bad, np.zeros((S, n * 50), np.int32), cdfs, sizes, offs)

@@ -1,5 +1,7 @@
 """Times the image codec's I/O kernels (lldwt_u8hwc_to_ycc_pad, lldwt_ycc_to_u8hwc_crop) with HIP events and prints one JSON
-line of GB/s (bytes read + written once).  Default 8 x 2048 x 2048, padded by 16 rows / columns."""
+line of GB/s (bytes read + written once).  Default 8 x 2048 x 2048, padded by 16 rows / columns.
+--tiled times the tile-grid kernels instead (lldwt_u8hwc_to_ycc_tiles over every tile of the batch,
+lldwt_ycc_tiles_to_u8hwc writing the whole image from them): default 8 x 3840 x 2160 at tile 512 (480 x 432 tiles)."""
 import argparse
 import json
 import os
@@ -29,7 +31,14 @@ def main():
     ap.add_argument("--size", type=int, default=2048)
     ap.add_argument("--pad", type=int, default=16)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--tiled", action="store_true")
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--th", type=int, default=432)
+    ap.add_argument("--tw", type=int, default=480)
     a = ap.parse_args()
+    if a.tiled:
+        return tiled(a)
     B, H = a.batch, a.size
     Hp = H + a.pad
     img = torch.randint(0, 256, (B, H, H, 3), dtype=torch.uint8, device="cuda:0")
@@ -41,6 +50,24 @@ def main():
     print(json.dumps({"shape": [B, H, H, 3], "padded": [Hp, Hp],
                       "u8hwc_to_ycc_pad": {"ms": t_in * 1e3, "GB/s": bytes_in / t_in / 1e9},
                       "ycc_to_u8hwc_crop": {"ms": t_out * 1e3, "GB/s": bytes_out / t_out / 1e9}}))
+
+
+def tiled(a):
+    B, H, W, th, tw = a.batch, a.height, a.width, a.th, a.tw
+    ny, nx = -(-H // th), -(-W // tw)
+    T = B * ny * nx
+    img = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device="cuda:0")
+    y = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, 0, T)
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device="cuda:0")
+    grid = (H, W, th, tw, ny, nx)
+    t_in = timeit(lambda: ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, 0, T), a.iters)
+    t_out = timeit(lambda: ops.ycc_tiles_to_u8hwc(y, grid, (0, 0, H, W), B=B, out=out), a.iters)
+    tile_px = T * th * tw
+    bytes_in = B * H * W * 3 + 3 * tile_px * 4         # each source byte read once (no padding at the default grid)
+    bytes_out = 3 * B * H * W * 4 + B * H * W * 3      # the scatter reads the in-image part of every tile
+    print(json.dumps({"shape": [B, H, W, 3], "tile": [th, tw], "grid": [ny, nx], "tiles": T,
+                      "u8hwc_to_ycc_tiles": {"ms": t_in * 1e3, "GB/s": bytes_in / t_in / 1e9},
+                      "ycc_tiles_to_u8hwc": {"ms": t_out * 1e3, "GB/s": bytes_out / t_out / 1e9}}))
 
 
 if __name__ == "__main__":

@@ -4,6 +4,9 @@
     python tools/codec.py decode --config cfg.json [--checkpoint ckpt.pth.tar] in.lld out.png
     python tools/codec.py info in.lld                      (CPU only: prints the header)
 
+    encode --tile N [--tiles-per-call K]   writes a tiled (LLDT) container: N x N target tiles, each an independent image
+    decode --region y0,x0,h,w              decodes only that region (tiled containers only)
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -48,8 +51,11 @@ def main(argv=None):
         p = sub.add_parser(name)
         p.add_argument("--config", required=True)
         p.add_argument("--checkpoint")
+        p.add_argument("--tiles-per-call", type=int, default=32)
         p.add_argument("src")
         p.add_argument("dst")
+    sub.choices["encode"].add_argument("--tile", type=int, help="write a tiled container with this target tile side")
+    sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
     p = sub.add_parser("info")
     p.add_argument("src")
     a = ap.parse_args(argv)
@@ -59,6 +65,8 @@ def main(argv=None):
             hdr = codec.read_header(f.read())
         for k, v in hdr.items():
             print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
+        if "ny" in hdr:
+            print("%-15s %d x %d tiles of %d x %d (rows x columns)" % ("grid", hdr["ny"], hdr["nx"], hdr["th"], hdr["tw"]))
         return 0
 
     import numpy as np
@@ -70,19 +78,35 @@ def main(argv=None):
         x = torch.from_numpy(np.ascontiguousarray(img))[None]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        blob = codec.encode_images(net, x)[0]
+        if a.tile is None:
+            blob = codec.encode_images(net, x)[0]
+        else:
+            blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         with open(a.dst, "wb") as f:
             f.write(blob)
         H, W = img.shape[:2]
         print("encoded %dx%d: %d bytes, %.4f bpp, %.3f s" % (W, H, len(blob), len(blob) * 8 / (H * W), dt))
+        if a.tile is not None:
+            hdr = codec.read_header(blob)
+            print("tiles: %d x %d of %dx%d" % (hdr["ny"], hdr["nx"], hdr["tw"], hdr["th"]))
     else:
         with open(a.src, "rb") as f:
             blob = f.read()
+        tiled = blob[:4] == codec.TILED_MAGIC
+        region = None
+        if a.region is not None:
+            if not tiled:
+                print("--region needs a tiled container (encode --tile)", file=sys.stderr)
+                return 2
+            region = tuple(int(v) for v in a.region.split(","))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        img = codec.decode_images(net, [blob])[0]
+        if tiled:
+            img = codec.decode_tiled(net, blob, region=region, tiles_per_call=a.tiles_per_call)
+        else:
+            img = codec.decode_images(net, [blob])[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         Image.fromarray(img.numpy()).save(a.dst)
