@@ -167,6 +167,14 @@ SIGNATURES = {
     "lldwt_rans_decoder_free": (None, [_p]),
     "lldwt_rans_encode_multi": (_i, [_p, _p, _i64, _i64, _i64, _p, C.c_int32, C.c_int32, _p, _p, _p, _i64, _p]),
     "lldwt_rans_set_parallel": (_i, [_i, _i64]),
+    "lldwt_irans_lanes": (_i, [_i64]),
+    "lldwt_irans_capacity": (_i64, [_i64]),
+    "lldwt_irans_state_words": (_i, []),
+    "lldwt_irans_rcp_table": (_i, [_p]),
+    "lldwt_irans_lut": (_i, [_p, C.c_int32, C.c_int32, _p, _p]),
+    "lldwt_irans_encode": (_i, [_p, _p, _i64, _i64, _i64, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "lldwt_irans_decode": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, C.c_int32, C.c_int32, _p, _p,
+                                _p, _p, _p]),
     "lldwt_sq_err_sum": (_i, [_p, _p, _i64, _p, _p]),
     "lldwt_sum": (_i, [_p, _i64, _p, _p]),
     "lldwt_cdf97_ws_bytes": (_i64, [_i64, _i64, _i64]),

@@ -21,6 +21,10 @@ Container format, version 1 (all integers little-endian):
     payload           the rANS streams, plane-major; per plane: xe, then xo finest -> coarsest
     CRC32             u32       zlib.crc32 of every byte before it
 
+The streams are coded by the host range coder (rans64, csrc/rans.hip) unless the arithmetic string holds a ``coder`` key:
+``coder=irans32`` selects the interleaved device coder (``encode_images(..., coder="gpu")``).  The key is
+absent for the host coder, so host-coded containers are those of the format as first defined, byte for byte.
+
 The image is coded at the padded size padded_size(H, W) (replicate-edge padding, lifting_dwt_nets.padded_size) and
 cropped back to H x W after decoding.
 
@@ -61,6 +65,9 @@ TILED_MAGIC = b"LLDT"
 TILED_FORMAT_VERSION = 1
 _TFIXED = struct.Struct("<4sBBBBIIIIHHH")     # magic .. H, W, th, tw, ny, nx, numerics version
 _PLANES = 3
+# coder name of the API -> value of the arithmetic string's "coder" key (None: the key is absent)
+CODER_KEYS = {"host": None, "gpu": "irans32"}
+_CODER_NAMES = {v: k for k, v in CODER_KEYS.items() if v is not None}
 
 
 # ------------------------------------------------------------------------------------------------ byte level (host only)
@@ -162,6 +169,20 @@ def _parse_identity(blob, pos, end):
     return arith, digest, blob[pos], pos + 1
 
 
+def _split_coder(arith):
+    """arithmetic string -> (coder name, the string without the coder key).  ValueError naming coder if its value is
+    unknown."""
+    parts = arith.split(",") if arith else []
+    rest = [p for p in parts if not p.startswith("coder=")]
+    vals = [p[len("coder="):] for p in parts if p.startswith("coder=")]
+    if not vals:
+        return "host", arith
+    if len(vals) > 1 or vals[0] not in _CODER_NAMES:
+        raise ValueError("coder: unknown entropy coder %r in the arithmetic string (this decoder reads: %s)"
+                         % (",".join(vals), ", ".join(sorted(_CODER_NAMES))))
+    return _CODER_NAMES[vals[0]], ",".join(rest)
+
+
 def _parse_streams(blob, pos, end, count):
     """count LEB128 lengths, then the payload up to end -> (list of stream bytes, lengths)."""
     lengths = []
@@ -196,9 +217,10 @@ def parse_container(blob):
     arith, digest, count, pos = _parse_identity(blob, _FIXED.size, end)
     if count != _PLANES * (L + 1):
         raise ValueError("stream count %d does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    coder, _ = _split_coder(arith)
     streams, lengths = _parse_streams(blob, pos, end, count)
     hdr = dict(version=FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
-               numerics=numerics, arithmetic=arith, digest=digest, stream_lengths=lengths,
+               numerics=numerics, arithmetic=arith, coder=coder, digest=digest, stream_lengths=lengths,
                header_bytes=end - sum(lengths))
     return hdr, streams
 
@@ -241,10 +263,11 @@ def parse_tiled(blob):
     arith, digest, count, pos = _parse_identity(blob, _TFIXED.size, end)
     if count != _PLANES * (L + 1):
         raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    coder, _ = _split_coder(arith)
     streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
     tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
     hdr = dict(version=TILED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
-               W=W, th=th, tw=tw, ny=ny, nx=nx, numerics=numerics, arithmetic=arith, digest=digest,
+               W=W, th=th, tw=tw, ny=ny, nx=nx, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
                streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
     return hdr, tiles
 
@@ -258,18 +281,23 @@ def read_header(blob):
 
 
 # ------------------------------------------------------------------------------------------------ model identity
-def arithmetic_string():
-    """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path.
+def arithmetic_string(coder="host"):
+    """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path, plus the
+    entropy coder: ``coder=irans32`` for coder="gpu", no key for the host coder (so the host string is unchanged).
     Which reach which layer (the others are carried along, harmlessly):
       plc_mode, plc_fuse, plc_algo, plc_shape, storage -- the tree-context pair: conditioned2ZTsepSubbands, onlyEZWT;
       precision -- the split-fp16 pair and cgp chain (conditioned2ZTsepSubbands, onlyEZWT) and the lifting steps (all);
       cgp -- the training path only: the coding wavefront step always runs the split-fp16 register chain.
     DWTConditioned2EntropyLayerZTBlock's phase kernel and the crop-stack conv engine have no switch."""
     from . import ops
-    kv = (("cgp", ops.cgp_mode()), ("plc_algo", ops.plc_algo()), ("plc_fuse", int(ops.plc_fuse())),
+    if coder not in CODER_KEYS:
+        raise ValueError("coder must be one of %s (got %r)" % (", ".join(sorted(CODER_KEYS)), coder))
+    kv = [("cgp", ops.cgp_mode()), ("plc_algo", ops.plc_algo()), ("plc_fuse", int(ops.plc_fuse())),
           ("plc_mode", ops.plc_mode()), ("plc_shape", ops.plc_shape()), ("precision", ops.get_precision()),
-          ("storage", ops.storage_dtype()))
-    return ",".join("%s=%s" % p for p in kv)
+          ("storage", ops.storage_dtype())]
+    if CODER_KEYS[coder] is not None:
+        kv.append(("coder", CODER_KEYS[coder]))
+    return ",".join("%s=%s" % p for p in sorted(kv))
 
 
 def _batch_invariant(arith):
@@ -356,8 +384,9 @@ def _check_images(images_u8):
     return B, H, W
 
 
-def encode_images(net, images_u8):
-    """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes)."""
+def encode_images(net, images_u8, coder="host"):
+    """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
+    default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string)."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
@@ -366,7 +395,7 @@ def encode_images(net, images_u8):
     B, H, W = _check_images(images_u8)
     nets = net.nets()
     Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
-    arith = arithmetic_string()
+    arith = arithmetic_string(coder)
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, numerics=CODING_NUMERICS_VERSION, arithmetic=arith,
                digest=weights_digest(net))
@@ -376,7 +405,7 @@ def encode_images(net, images_u8):
     blobs = []
     with torch.no_grad():
         for a, e in groups:
-            s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous())
+            s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder)
             for b in range(e - a):
                 streams = [s for p in range(_PLANES) for s in [s_xe[p][b]] + [lev[p][b] for lev in s_xo]]
                 blobs.append(pack_container(hdr, streams))
@@ -384,7 +413,9 @@ def encode_images(net, images_u8):
 
 
 def check_header(hdr, layer, nettype, L, digest, arith):
-    """The identity checks of a parsed header against the decoding net and process (ValueError naming the field)."""
+    """The identity checks of a parsed header against the decoding net and process (ValueError naming the field).  arith:
+    the process's arithmetic string without a coder key; the header's coder key is checked and set aside first."""
+    _, hdr_arith = _split_coder(hdr["arithmetic"])
     if hdr["layer"] != layer:
         raise ValueError("entropy layer: the container holds %s, the net is %s" % (hdr["layer"], layer))
     if hdr["netType"] != nettype:
@@ -397,17 +428,17 @@ def check_header(hdr, layer, nettype, L, digest, arith):
     if hdr["numerics"] != CODING_NUMERICS_VERSION:
         raise ValueError("numerics version: the container was written with coding numerics version %d, this decoder has %d"
                          % (hdr["numerics"], CODING_NUMERICS_VERSION))
-    if hdr["arithmetic"] != arith:
-        got = dict(p.split("=", 1) for p in hdr["arithmetic"].split(",") if "=" in p)
+    if hdr_arith != arith:
+        got = dict(p.split("=", 1) for p in hdr_arith.split(",") if "=" in p)
         have = dict(p.split("=", 1) for p in arith.split(","))
         diff = sorted(k for k in set(got) | set(have) if got.get(k) != have.get(k))
         raise ValueError("arithmetic: the container was coded with %s, this process has %s (differs in: %s)"
-                         % (hdr["arithmetic"], arith, ", ".join(diff)))
+                         % (hdr_arith, arith, ", ".join(diff)))
 
 
 def decode_images(net, blobs):
     """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
-    first; then containers of equal (H, W) are decoded together."""
+    first; then containers of equal (H, W) and coder are decoded together (the coder comes from each header)."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
@@ -421,17 +452,17 @@ def decode_images(net, blobs):
     nets = net.nets()
     by_size = {}
     for i, (hdr, _) in enumerate(parsed):
-        by_size.setdefault((hdr["H"], hdr["W"]), []).append(i)
+        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"]), []).append(i)
     out = [None] * len(parsed)
     with torch.no_grad():
-        for (H, W), idx in by_size.items():
+        for (H, W, coder), idx in by_size.items():
             Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             groups = [idx] if _batch_invariant(arith) else [[i] for i in idx]
             for g in groups:
                 per = L + 1                                   # streams per plane: xe, xo finest -> coarsest
                 s_xe = [[parsed[i][1][p * per] for i in g] for p in range(_PLANES)]
                 s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(L)]
-                xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g))
+                xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder)
                 img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W).cpu()
                 for j, i in enumerate(g):
                     out[i] = img[j]
@@ -456,11 +487,12 @@ def _tile_streams(s_xe, s_xo, j):
     return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
 
 
-def encode_tiled(net, images_u8, tile=512, tiles_per_call=32):
+def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host"):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers.  Every tile is coded as an independent image: its streams
     are those of encode_images(net, padded_tile).  The images are uploaded once; groups of tiles_per_call tiles (over all
     images of the batch) are cut out on the device (lldwt_u8hwc_to_ycc_tiles) and coded together, which bounds the device
-    memory; one tile per call in the arithmetics that are not batch invariant.  The bytes do not depend on tiles_per_call."""
+    memory; one tile per call in the arithmetics that are not batch invariant.  The bytes do not depend on tiles_per_call.
+    coder: as encode_images."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
@@ -472,7 +504,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32):
     th, tw, ny, nx = tile_grid([n.autoencoder for n in nets], H, W, int(tile))
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
-    arith = arithmetic_string()
+    arith = arithmetic_string(coder)
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx,
                numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
@@ -485,17 +517,17 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32):
         for first in range(0, T, g):
             n = min(g, T - first)
             x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)                 # (3,n,1,th,tw)
-            s_xe, s_xo = encode_strings_planes(nets, x)
+            s_xe, s_xo = encode_strings_planes(nets, x, coder=coder)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
     per = ny * nx
     return [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
 
 
-def _decode_tiles(nets, s_xe, s_xo, th, tw, n):
+def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host"):
     """One group of n tiles -> xhat (3,n,1,th,tw) (decode_strings_planes; a module-level hook so the number of tiles a
     decode touches can be counted)."""
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
-    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n)
+    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder)
 
 
 def _region(region, H, W):
@@ -535,6 +567,7 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32):
             grp = want[a:a + g]
             s_xe = [[tiles[t][p * per] for t in grp] for p in range(_PLANES)]
             s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(L)]
-            xhat = _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp))
+            kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}     # host: the call as it has always been
+            xhat = _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp), **kw)
             ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=grp, out=out)
     return out[0].cpu()

@@ -224,13 +224,13 @@ class onlyEZWT(_EntropyLayerBase):
         return _conv([s[4] for s in seqs], t)                                       # (P,B,6,h,w): sigma even, mu odd
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host"):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first)."""
         from . import entropy_coding as ec
         L = len(out_xo_list)
         with torch.no_grad():
-            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape)
-            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape)
+            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
+            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
             s_list, q_list = [s], [q]
             for i in range(L - 2, -1, -1):
                 tabs = ec._Tables(layers[0].ent_out_xo_list[i], get_scale_table())
@@ -238,7 +238,7 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 s, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, out_xo_list[i],
-                                                 out_xo_list[i].shape, tabs)
+                                                 out_xo_list[i].shape, tabs, coder=coder)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -246,13 +246,13 @@ class onlyEZWT(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host"):
         """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors."""
         from . import entropy_coding as ec
         L = len(shapes_xo)
         with torch.no_grad():
-            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe)
-            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1])
+            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
+            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1], coder=coder)
             q_list = [q]
             for i in range(L - 2, -1, -1):
                 tabs = ec._Tables(layers[0].ent_out_xo_list[i], get_scale_table())
@@ -260,7 +260,7 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 _, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, None, shapes_xo[i], tabs,
-                                                 strings_xo_list[i])
+                                                 strings_xo_list[i], coder=coder)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -413,7 +413,7 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return plc, (packed, packed16), dims, cs[0].kernel_size[0], cs[0].tap_bits()
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host"):
         """compress_ar for every tensor (:386-417): -> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q])
         with *_q = round(y - mu) + mu, the values the decoder reconstructs."""
         from . import entropy_coding as ec
@@ -421,18 +421,18 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         L = len(out_xo_list)
         with torch.no_grad():
             s_xe, xe_q = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], out_xe,
-                                            out_xe.shape, tabs)
+                                            out_xe.shape, tabs, coder=coder)
             s, q = ec.code_crop_stack(stack, [l.ent_out_xo_list[L - 1] for l in layers], [l.csc_list[L - 1] for l in layers],
-                                      out_xo_list[L - 1], out_xo_list[L - 1].shape, tabs)
+                                      out_xo_list[L - 1], out_xo_list[L - 1].shape, tabs, coder=coder)
             s_list, q_list = [s], [q]
             for i in range(L - 2, -1, -1):
                 x = out_xo_list[i]
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, x.shape[2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
                 if packed[1] is not None:       # the reference's cgp widths: one fused launch per wavefront step
-                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs)
+                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder)
                 else:
-                    s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs)
+                    s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs, coder=coder)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -440,7 +440,7 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host"):
         """decompress_ar for every tensor (:419-454): strings -> (xe, [xo] finest first), bit-identical to compress_planes'
         dequantised tensors."""
         from . import entropy_coding as ec
@@ -448,18 +448,18 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         L = len(shapes_xo)
         with torch.no_grad():
             _, xe = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], None, shape_xe, tabs,
-                                       strings_xe)
+                                       strings_xe, coder=coder)
             _, q = ec.code_crop_stack(stack, [l.ent_out_xo_list[L - 1] for l in layers], [l.csc_list[L - 1] for l in layers],
-                                      None, shapes_xo[L - 1], tabs, strings_xo_list[L - 1])
+                                      None, shapes_xo[L - 1], tabs, strings_xo_list[L - 1], coder=coder)
             q_list = [q]
             for i in range(L - 2, -1, -1):
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, shapes_xo[i][2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
                 if packed[1] is not None:
-                    _, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, None, shapes_xo[i], tabs, strings_xo_list[i])
+                    _, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, None, shapes_xo[i], tabs, strings_xo_list[i], coder=coder)
                 else:
                     _, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, None, shapes_xo[i], tabs,
-                                                      strings_xo_list[i])
+                                                      strings_xo_list[i], coder=coder)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -585,20 +585,20 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return packs
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host"):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first), *_q the decoder's values."""
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(out_xo_list)
         with torch.no_grad():
-            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape)
-            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape)
+            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
+            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
             s_list, q_list = [s], [q]
             for i in range(L - 1):
                 x = out_xo_list[L - i - 2]
                 ems, tabs = cls._level_models(layers, i, L)
-                s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs)
+                s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs, coder=coder)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -606,20 +606,20 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host"):
         """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors."""
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(shapes_xo)
         with torch.no_grad():
-            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe)
-            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1])
+            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
+            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1], coder=coder)
             q_list = [q]
             for i in range(L - 1):
                 ems, tabs = cls._level_models(layers, i, L)
                 _, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, None, shapes_xo[L - i - 2], tabs,
-                                             strings_xo_list[L - i - 2])
+                                             strings_xo_list[L - i - 2], coder=coder)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -995,26 +995,28 @@ def compress_planes(nets, x):
     return xhat, s_xe, s_xo
 
 
-def encode_strings_planes(nets, x):
+def encode_strings_planes(nets, x, coder="host"):
     """The encoder half of compress_planes: encode -> the entropy layer's compress_planes, no decoding.
-    x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first)."""
+    x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first).  coder: "host" (rans64 on the host) or "gpu"
+    (irans32 on the device); the symbols are the same, the bytes differ."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "compress_planes"):
         raise NotImplementedError(_NOT_CODED)
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
-    s_xe, s_xo, _, _ = type(em[0]).compress_planes(em, out_xe, out_xo)
+    s_xe, s_xo, _, _ = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder)
     return s_xe, s_xo
 
 
-def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B):
-    """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them) -> xhat (P,B,C,Hp,Wp).
+def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host"):
+    """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them, with the same coder) ->
+    xhat (P,B,C,Hp,Wp).
     Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes)."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "decompress_planes"):
         raise NotImplementedError(_NOT_CODED)
     aenc = [n.autoencoder for n in nets]
     shape_xe, shapes_xo = encode_shapes(aenc, B, Hp, Wp)
-    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo)
+    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder)
     return decode_planes(aenc, xe, xo)
 
 

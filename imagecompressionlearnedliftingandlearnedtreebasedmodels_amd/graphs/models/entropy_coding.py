@@ -27,8 +27,10 @@ hold 0 on both sides (the reference's encoder holds the unquantised value there,
 import numpy as np
 import torch
 
-from ... import ops
+from ... import irans, ops
 from ...ans import RansDecoder, decode_streams, encode_streams
+
+CODERS = ("host", "gpu")         # host: ans.py (rans64 on the host, the default); gpu: irans.py (irans32)
 
 _WF_CACHE = {}
 
@@ -104,6 +106,9 @@ class _Sink:
         """Decoder of code_tree_level: called with every step's (indexes, symbols) as host int32 arrays once they are decoded.
         A hook for diagnostics (the code-length test replaces it); does nothing."""
 
+    def finish(self):
+        """Decoder: the end of a tensor (the host coder checks its streams symbol by symbol)."""
+
     def flush(self):
         """Encoder: -> strings[p][b] (the P * B streams in one parallel call)."""
         idx = torch.cat(self.idx, 2).cpu().numpy()          # (P,B,Npix,g) in wavefront order
@@ -111,6 +116,50 @@ class _Sink:
         flat = encode_streams(sym.reshape(self.P * self.B, -1), idx.reshape(self.P * self.B, -1), self.t.cdf, self.t.sizes,
                               self.t.offsets)
         return [flat[p * self.B:(p + 1) * self.B] for p in range(self.P)]
+
+
+class _DeviceSink:
+    """_Sink's interface over the irans32 device coder: the encoder buffers the steps on the device and codes every stream
+    in one launch at flush(); the decoder pops each step on the device (no synchronisation) and checks the streams once in
+    finish().  n: symbols per stream (decoder)."""
+
+    def __init__(self, P, B, tables, strings=None, n=None, device=None):
+        self.P, self.B, self.t = P, B, tables
+        self.decoding = strings is not None
+        self.dt = irans.device_tables(tables, device)
+        if self.decoding:
+            self.dec = irans.Decoder([strings[p][b] for p in range(P) for b in range(B)], n, self.dt, device)
+        else:
+            self.sym, self.idx = [], []
+
+    def step(self, idx, sym=None):
+        if not self.decoding:
+            self.idx.append(idx)
+            self.sym.append(sym)
+            return sym
+        return self.dec.pop(idx.contiguous())
+
+    def note(self, idx_host, sym_host):
+        pass
+
+    def finish(self):
+        self.dec.finish()
+
+    def flush(self):
+        Z = self.P * self.B
+        idx = torch.cat([t.reshape(Z, -1) for t in self.idx], 1)
+        sym = torch.cat([t.reshape(Z, -1) for t in self.sym], 1)
+        flat = irans.encode(sym.int(), idx.int(), self.dt)
+        return [flat[p * self.B:(p + 1) * self.B] for p in range(self.P)]
+
+
+def _make_sink(coder, P, B, tables, strings, n, device):
+    """The sink of a tensor for the chosen coder (n: symbols per stream; device: where the coder runs)."""
+    if coder == "host":
+        return _Sink(P, B, tables, strings)
+    if coder == "gpu":
+        return _DeviceSink(P, B, tables, strings, n, device)
+    raise ValueError("coder must be one of %s (got %r)" % (", ".join(CODERS), coder))
 
 
 def _finish_step(emodel, sink, sigma, mu, yv):
@@ -123,13 +172,13 @@ def _finish_step(emodel, sink, sigma, mu, yv):
     return sym.permute(0, 1, 3, 2).float() + mu                                         # dequantize: symbol + mu
 
 
-def code_crop_stack(seq_stack, emodels, seqs, y, shape, tables, strings=None):
+def code_crop_stack(seq_stack, emodels, seqs, y, shape, tables, strings=None, coder="host"):
     """The 3x3-crop context (LiftingBasedDWT_net.py:388-401 / :424-433 with compress_ar / decompress_ar at
     network_kernel_size 3).  y: (P,B,g,H,W) coefficients (encoder) or None (decoder); -> (strings or None, dequantised)."""
     P, B, g, H, W = shape
     dev = y.device if y is not None else next(seqs[0].parameters()).device
     hs, ws, starts = wavefront(H, W, 2, dev)
-    sink = _Sink(P, B, tables, strings)
+    sink = _make_sink(coder, P, B, tables, strings, H * W * g, dev)
     yhat = torch.zeros(P, B, g, H + 2, W + 2, device=dev, dtype=torch.float32)       # 1-pixel zero frame = the crop padding
     ar = torch.arange(3, device=dev)
     for t in range(len(starts) - 1):
@@ -148,6 +197,8 @@ def code_crop_stack(seq_stack, emodels, seqs, y, shape, tables, strings=None):
         yv = y[:, :, :, h, w] if y is not None else None
         yhat[:, :, :, h + 1, w + 1] = _finish_step(emodels[0], sink, sigma, mu, yv)
     out = yhat[:, :, :, 1:-1, 1:-1].contiguous()
+    if sink.decoding:
+        sink.finish()
     return (None if sink.decoding else sink.flush()), out
 
 
@@ -159,7 +210,7 @@ def _step_offsets(H, W, slope):
     return np.searchsorted(t, np.arange(W + slope * (H - 1) + 1)).tolist()
 
 
-def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strings=None):
+def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strings=None, coder="host"):
     """A level with tree context + masked KxK context + cgp (:402-417 / :440-454 with kernel size 5).  plc: (P,B,G*81,H,W)
     tree-context features of the (decoded) parent; packed16: the cgp stack with the masked conv folded into its first layer,
     packed for the register-chain kernel (_fold_csc_into_cgp).
@@ -169,7 +220,8 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     index, symbol and dequantised value -- no per-step tensor ops on the host side.  Encoder: the launches are queued back to
     back (no synchronisation until the streams are written).  Decoder: per step one launch, the step's indexes down to the
     host (pinned buffer), ONE C call that pops the step's symbols from every (plane, image) stream, the symbols up, one
-    small launch that writes symbol + mu."""
+    small launch that writes symbol + mu.  With coder="gpu" the decoder never waits: per step the step kernel, the irans32 pop
+    of every stream and the apply launch are queued back to back, and the streams are checked once at the end of the level."""
     import ctypes as C
     from ... import _lib
     lib = _lib.load()
@@ -181,7 +233,7 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     table63 = emodels[0].scale_table.to(dev).float()[:63].contiguous()
     yhat = torch.zeros(P, B, G, H, W, device=dev, dtype=torch.float32)
-    sink = _Sink(P, B, tables, strings)
+    sink = _make_sink(coder, P, B, tables, strings, ntot * G, dev)
     ptr = lambda t_: C.c_void_p(t_.data_ptr())
     if not sink.decoding:
         yc = y.contiguous()
@@ -198,6 +250,17 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     idx_d = torch.empty(Z * nmax * G, device=dev, dtype=torch.int32)
     sym_d = torch.empty(Z * nmax * G, device=dev, dtype=torch.int32)
     mu_d = torch.empty(Z * G * nmax, device=dev, dtype=torch.float32)
+    if coder == "gpu":
+        for t in range(nsteps):
+            n = starts[t + 1] - starts[t]
+            if n == 0:
+                continue
+            ops.check(lib.lldwt_cgp16_wavefront_step(ptr(plc), ptr(yhat), None, ptr(packed16), ptr(table63), ptr(idx_d), None,
+                                                     ptr(mu_d), P, B, H, W, G, K, int(tap_bits), t, n, 0, st), "cgp16_wavefront_step")
+            sink.dec.pop(idx_d, n * G, n * G, sym_d)
+            ops.check(lib.lldwt_wavefront_apply(ptr(sym_d), ptr(mu_d), ptr(yhat), P, B, H, W, G, K, t, n, 0, st), "wavefront_apply")
+        sink.finish()
+        return None, yhat
     idx_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
     sym_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
     handles = (C.c_void_p * Z)(*[sink.dec[p][b]._h for p in range(P) for b in range(B)])
@@ -220,7 +283,7 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     return None, yhat
 
 
-def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, shape, tables, strings=None):
+def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, shape, tables, strings=None, coder="host"):
     """A level with tree context + masked KxK context + cgp (:402-417 / :440-454 with kernel size 5).  plc: (P,B,G*81,H,W)
     tree-context features of the (decoded) parent; cgp_packed/dims: the cgp stack with the masked conv folded into its
     first layer (_fold_csc_into_cgp).  The host-stepped schedule (a handful of tensor ops and launches per step) for cgp widths
@@ -231,7 +294,7 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
     taps = _live_taps(tap_bits, K)
     cpl = plc.shape[2] // G
     hs, ws, starts = wavefront(H, W, R + 1, dev)
-    sink = _Sink(P, B, tables, strings)
+    sink = _make_sink(coder, P, B, tables, strings, H * W * G, dev)
     yhat = torch.zeros(P, B, G, H + 2 * R, W + 2 * R, device=dev, dtype=torch.float32)
     dy = torch.tensor([t[0] for t in taps], device=dev)
     dx = torch.tensor([t[1] for t in taps], device=dev)
@@ -250,13 +313,15 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
         sigma, mu = params[:, :, 0::2, 0, :], params[:, :, 1::2, 0, :]
         yhat[:, :, :, h + R, w + R] = _finish_step(emodels[0], sink, sigma, mu, yv)
     out = yhat[:, :, :, R:-R, R:-R].contiguous()
+    if sink.decoding:
+        sink.finish()
     return (None if sink.decoding else sink.flush()), out
 
 
 ZT_PHASES = ((0, 0), (0, 1), (1, 0), (1, 1))        # ee, eo, oe, oo: (row, column) offset of phase k in the level
 
 
-def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None):
+def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None, coder="host"):
     """One finer level of DWTConditioned2EntropyLayerZTBlock (the reference's forward, LiftingBasedDWT_net.py:716-744, coded
     with compressai's GaussianConditional contract).  parent (P,B,3,h,w): the DECODED coarser level; y (P,B,3,2h,2w) the
     coefficients (encoder) or None (decoder); emodels: the GaussianConditional of each subband (build_indexes); packs[k]:
@@ -269,7 +334,7 @@ def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None):
     P, B, G, H, W = shape
     h2, w2 = H // 2, W // 2
     lev = torch.zeros(P, B, G, H, W, device=parent.device, dtype=torch.float32)
-    sink = _Sink(P, B, tables, strings)
+    sink = _make_sink(coder, P, B, tables, strings, G * H * W, parent.device)
     for k, (r, c) in enumerate(ZT_PHASES):
         params = ops.ztblock_phase(parent, lev, packs[k], k + 1)
         sigma, mu = params[:, :, 0::2], params[:, :, 1::2]
@@ -279,6 +344,8 @@ def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None):
             sym = torch.round(y[:, :, :, r::2, c::2] - mu).int().reshape(P, B, G * h2 * w2, 1)
         sym = sink.step(idx.reshape(P, B, G * h2 * w2, 1), sym)
         lev[:, :, :, r::2, c::2] = sym.reshape(P, B, G, h2, w2).float() + mu
+    if sink.decoding:
+        sink.finish()
     return (None if sink.decoding else sink.flush()), lev
 
 
@@ -292,11 +359,14 @@ class _FactorizedTables:
         self.offsets = emodel.offset.cpu().numpy().astype(np.int32)
 
 
-def code_factorized(emodels, y, shape, strings=None):
+def code_factorized(emodels, y, shape, strings=None, coder="host"):
     """A tensor coded with a factorized prior (EntropyBottleneck; compressai compress / decompress): every coefficient is
     independent, so symbols and indexes of the whole tensor are produced in one pass; one rANS stream per (plane, image),
-    raster order, channels outermost.  emodels: one per plane.  -> (strings or None, dequantised (P,B,C,h,w))."""
+    raster order, channels outermost.  emodels: one per plane.  -> (strings or None, dequantised (P,B,C,h,w)).
+    coder="gpu": symbols and indexes stay on the device (irans32)."""
     P, B, Cc, H, W = shape
+    if coder != "host":
+        return _code_factorized_device(emodels, y, shape, strings, coder)
     out = []
     strs = []
     for p in range(P):
@@ -315,13 +385,44 @@ def code_factorized(emodels, y, shape, strings=None):
     return (strs if strings is None else None), torch.stack(out, 0)
 
 
-def code_gaussian_parallel(emodels, params, y, shape, tables, strings=None):
+def _code_factorized_device(emodels, y, shape, strings, coder):
+    P, B, Cc, H, W = shape
+    out, strs = [], []
+    for p in range(P):
+        em = emodels[p]
+        dev = em.quantiles.device
+        tabs = _FactorizedTables(em)
+        if strings is None:
+            sym, idx = em.symbols_and_indexes(y[p])                                     # (B,C,h,w)
+            sink = _make_sink(coder, 1, B, tabs, None, None, dev)
+            sink.step(idx.int().reshape(1, B, -1), sym.int().reshape(1, B, -1))
+            strs.append(sink.flush()[0])
+            out.append(em.dequantize_symbols(sym))
+        else:
+            sink = _make_sink(coder, 1, B, tabs, [strings[p]], Cc * H * W, dev)
+            idx = torch.arange(Cc, device=dev, dtype=torch.int32).reshape(1, Cc, 1, 1).expand(B, Cc, H, W).contiguous()
+            syms = sink.step(idx)
+            sink.finish()
+            out.append(em.dequantize_symbols(syms))
+    return (strs if strings is None else None), torch.stack(out, 0)
+
+
+def code_gaussian_parallel(emodels, params, y, shape, tables, strings=None, coder="host"):
     """A level whose (sigma, mu) depend only on already decoded tensors (onlyEZWT: the tree context of the parent level,
     LiftingBasedDWT_net.py:822-835): fully parallel -- indexes and symbols of the whole tensor in one pass, raster order.
     params (P,B,2C,h,w): sigma on the even, mu on the odd channels.  -> (strings or None, dequantised (P,B,C,h,w))."""
     P, B, Cc, H, W = shape
     sigma, mu = params[:, :, 0::2].contiguous(), params[:, :, 1::2].contiguous()
     idx = emodels[0].build_indexes(sigma)                                               # (P,B,C,h,w) int32
+    if coder != "host":
+        sink = _make_sink(coder, P, B, tables, strings, Cc * H * W, mu.device)
+        if strings is None:
+            sym = torch.round(y - mu).int()
+            sink.step(idx.int(), sym)
+            return sink.flush(), sym.float() + mu
+        syms = sink.step(idx.int().contiguous())
+        sink.finish()
+        return None, syms.float() + mu
     ih = idx.cpu().numpy()
     if strings is None:
         sym = torch.round(y - mu).int()

@@ -529,6 +529,31 @@ int lldwt_rans_encode_multi(const int32_t* symbols, const int32_t* indexes, int6
 int lldwt_rans_set_parallel(int threads, int64_t min_symbols);
 void lldwt_rans_decoder_free(void* dec);
 
+/* The interleaved rANS coder "irans32" (csrc/rans_gpu.hip; format: DESIGN.md 7.1.2, definition: tools/irans_ref.py).  Same
+ * symbols, order and tables as lldwt_rans_*; a stream of n symbols has lldwt_irans_lanes(n) 32-bit lanes (1..32).
+ *   lldwt_irans_encode: nstreams streams, one wave each; stream k codes the n device symbols / indexes at + k * stride into
+ *     out + k * out_stride (out_stride >= lldwt_irans_capacity(n)); its bytes END at out + (k + 1) * out_stride and
+ *     nbytes[k] (device) is their number, -1 on failure (bad index, no room), which also sets *flag != 0.  rcp: the device
+ *     copy of lldwt_irans_rcp_table (65537 u32).  Host-side tables (cdfs, cdf_sizes, offsets) are device arrays here.
+ *   lldwt_irans_decode: pops symbols [pos, pos + cnt) of every stream: indexes at indexes + k * idx_stride, symbols to
+ *     symbols + k * sym_stride.  state: nstreams * lldwt_irans_state_words() u32, written by the launch with pos == 0 and
+ *     carried between launches (queue them in order on one stream).  Stream k's bytes: bytes + byte_offsets[k], of length
+ *     byte_lengths[k] (device int64); reads at or past the length return 0 and set *flag.  When pos + cnt == n, every lane
+ *     must be back at 2^23 and the cursor at the length, else *flag is set.  lut: lldwt_irans_lut of the tables (device).
+ *   lldwt_irans_rcp_table / lldwt_irans_lut: HOST helpers that fill the host arrays the two kernels read.              */
+int lldwt_irans_lanes(int64_t n);
+int64_t lldwt_irans_capacity(int64_t n);
+int lldwt_irans_state_words(void);
+int lldwt_irans_rcp_table(uint32_t* rcp);
+int lldwt_irans_lut(const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride, const int32_t* cdf_sizes, int32_t* lut);
+int lldwt_irans_encode(const int32_t* symbols, const int32_t* indexes, int64_t nstreams, int64_t n, int64_t stride,
+                       const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                       const uint32_t* rcp, uint8_t* out, int64_t out_stride, int64_t* nbytes, int32_t* flag, void* stream);
+int lldwt_irans_decode(uint32_t* state, const uint8_t* bytes, const int64_t* byte_offsets, const int64_t* byte_lengths,
+                       int64_t nstreams, int64_t n, int64_t pos, int64_t cnt, const int32_t* indexes, int64_t idx_stride,
+                       int32_t* symbols, int64_t sym_stride, const int32_t* cdfs, int32_t ncdf, int32_t cdf_stride,
+                       const int32_t* cdf_sizes, const int32_t* offsets, const int32_t* lut, int32_t* flag, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Rate estimation, fused quantise + likelihood + both LowerBounds + -log2 + sum of bits.
  * Gaussian (compressai GaussianConditional.forward as called at LiftingBasedDWT_net.py:334,345,364,832):

@@ -6,6 +6,8 @@
 
     encode --tile N [--tiles-per-call K]   writes a tiled (LLDT) container: N x N target tiles, each an independent image
     decode --region y0,x0,h,w              decodes only that region (tiled containers only)
+    encode --coder gpu                     codes the streams with the interleaved device coder (irans32); decode reads the
+                                           coder from the header
 
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
@@ -55,6 +57,8 @@ def main(argv=None):
         p.add_argument("src")
         p.add_argument("dst")
     sub.choices["encode"].add_argument("--tile", type=int, help="write a tiled container with this target tile side")
+    sub.choices["encode"].add_argument("--coder", choices=("host", "gpu"), default="host",
+                                       help="entropy coder: host (rans64, the default) or gpu (irans32 on the device)")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
     p = sub.add_parser("info")
     p.add_argument("src")
@@ -79,9 +83,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tile is None:
-            blob = codec.encode_images(net, x)[0]
+            blob = codec.encode_images(net, x, coder=a.coder)[0]
         else:
-            blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call)[0]
+            blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, coder=a.coder)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         with open(a.dst, "wb") as f:
