@@ -367,17 +367,24 @@ _BUF_X, _BUF_LROW, _BUF_HROW, _BUF_TMPL, _BUF_TMPH, _BUF_LL0, _BUF_LL1, _BUF_LL,
 
 
 _W_KEYS = ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")
-_PACK_MEMO = {"key": None, "val": None}
+_PACK_MEMO = {"key": None, "val": None, "refs": None}
+
+
+def _memo_key(W, keys):
+    return tuple((k, W[k].data_ptr(), W[k]._version, tuple(W[k].shape), W[k].stride()) for k in keys)
 
 
 def _pack_forward(W, nblocks):
     """W: dict of 8 stacked tensors (nblocks,2,P,...) -> packed (P,nblocks,2,total) for the lifting step kernels.
 
     One training step asks for the same pack four times (encode and decode share their P/U blocks -- lifting_dwt_nets.py:
-    695-707 -- and each backward reads the forward pack again): the last result is kept and reused while every tensor is
-    the same object at the same version (an optimizer step or load_state_dict bumps ``_version``).  With the fused training
-    forward the pack includes the composed 9x9 kernels (0.4 ms per block and call: 6.7 ms per step without the memo)."""
-    key = tuple((k, W[k].data_ptr(), W[k]._version, tuple(W[k].shape)) for k in _W_KEYS) + (nblocks, ops.train_lift_f16())
+    695-707 -- and each backward reads the forward pack again): the last result is kept and reused while every tensor
+    has the same address, version and layout (an optimizer step through the parameter arena bumps ``_version``:
+    FlatGradBucket.bump_version).  The memo holds the tensors themselves ("refs"): a torch.stack fallback (no arena) makes
+    a fresh tensor at version 0 on every forward, and without the reference its memory could be freed and handed to the
+    next step's stack, whose key would then match the previous weights' pack.  With the fused training forward the pack
+    includes the composed 9x9 kernels (0.4 ms per block and call: 6.7 ms per step without the memo)."""
+    key = _memo_key(W, _W_KEYS) + (nblocks, ops.train_lift_f16())
     if _PACK_MEMO["key"] == key:
         return _PACK_MEMO["val"]
     blocks = []
@@ -388,22 +395,23 @@ def _pack_forward(W, nblocks):
                               train=not ops.train_lift_f16(), compose=False) for u in range(2)]
         blocks.append(torch.stack(pu, 1))
     out = torch.stack(blocks, 1).contiguous()
-    _PACK_MEMO["key"], _PACK_MEMO["val"] = key, out
+    _PACK_MEMO["key"], _PACK_MEMO["val"], _PACK_MEMO["refs"] = key, out, [W[k] for k in _W_KEYS]
     return out
 
 
-_BPACK_MEMO = {"key": None, "val": None}
+_BPACK_MEMO = {"key": None, "val": None, "refs": None}
 
 
 def _pack_backward(W, nblocks):
     """Backward packs (transposed, mirrored weights; ops.pack_pblock_bwd) of every P/U block, (P,nblocks,2,total) like
-    _pack_forward's result, kept while the weights are unchanged (the encode and the decode backward of a step share it)."""
-    key = tuple((k, W[k].data_ptr(), W[k]._version, tuple(W[k].shape)) for k in ("w1", "w2", "w3", "w4")) + (nblocks,)
+    _pack_forward's result, kept while the weights are unchanged (the encode and the decode backward of a step share it;
+    the memo holds the tensors, as _pack_forward's does)."""
+    key = _memo_key(W, ("w1", "w2", "w3", "w4")) + (nblocks,)
     if _BPACK_MEMO["key"] == key:
         return _BPACK_MEMO["val"]
     out = torch.stack([torch.stack([ops.pack_pblock_bwd(*[W[k][b, u] for k in ("w1", "w2", "w3", "w4")]) for u in range(2)], 1)
                        for b in range(nblocks)], 1).contiguous()
-    _BPACK_MEMO["key"], _BPACK_MEMO["val"] = key, out
+    _BPACK_MEMO["key"], _BPACK_MEMO["val"], _BPACK_MEMO["refs"] = key, out, [W[k] for k in ("w1", "w2", "w3", "w4")]
     return out
 
 

@@ -256,5 +256,16 @@ def test_parameter_arena_matches_plain_tensors(monkeypatch, tmp_path):
     ag1.model.load_state_dict(sd)
     for n, p in ag1.model.named_parameters():
         assert lo <= p.data_ptr() < hi and torch.equal(p.detach().cpu(), sd[n].cpu()), n
-    l_next = float(ag1.train_step(x)[0])
+    def seeded_noise():
+        gen = torch.Generator(device=DEV).manual_seed(78)
+        return lambda t: torch.rand(t.shape, device=t.device, generator=gen) - 0.5
+    monkeypatch.setattr(la, "_USE_ARENA", True)                     # run(False) left it off: this step runs on the arena
+    l_next = float(ag1.train_step(x, noise_fn=seeded_noise())[0])
     assert l_next == l_next and len(b.group_views) > 50            # still on the fast path after the reload
+    # ... and the arena path after a reload computes what a freshly built agent (its first step: the torch.stack path) loaded
+    # with the same state_dict computes, for the same noise; float-atomic order only
+    ag2 = _agent(dwtlevels=2, mode="train", patch_size=64, batch_size=2)
+    ag2.model.load_state_dict(sd)
+    ag2.model.train()
+    l_fresh = float(ag2.train_step(x, noise_fn=seeded_noise())[0])
+    assert abs(l_next - l_fresh) <= 1e-6 * abs(l_fresh), (l_next, l_fresh)
