@@ -44,6 +44,13 @@ th x tw (tile_grid), each coded as an independent image -- its streams are byte-
     stream lengths    LEB128 varints, tile-major in raster order of (ty, tx); inside a tile the LLDW order
     payload           the streams in the same order
     CRC32             u32       zlib.crc32 of every byte before it
+
+Reduced-resolution decoding (``decode_images(..., reduce=k)``, ``decode_tiled(..., reduce=k)``): for
+0 <= k <= L the output is the image at 1/2^k of each side, ceil(H / 2^k) x ceil(W / 2^k).  Only the xe streams and the xo
+streams of levels k .. L-1 are decoded (the streams of finer levels are never handed to a coder), the inverse transform runs
+for the top L-k levels, and the LL band at level k is brought to the image's scale by lifting_dwt_nets.ll_affine before the
+colour conversion.  reduce=0 is the full decode.  ``reduce_bytes`` gives, per factor, the header plus stream bytes such a
+decode reads.  The container format is the same.
 """
 import hashlib
 import struct
@@ -280,6 +287,21 @@ def read_header(blob):
     return parse_container(blob)[0]
 
 
+def reduce_bytes(hdr):
+    """-> list of L + 1 ints: entry k is the number of container bytes a decode at reduce=k reads, the header (every byte
+    before the payload) plus the xe streams and the xo streams of levels k .. L-1 of every plane (for LLDT, of every tile).
+    The 4-byte CRC32 trailer is not counted.  hdr: read_header's dict (LLDW or LLDT); CPU only."""
+    L, lengths = hdr["dwtlevels"], hdr["stream_lengths"]
+    per = L + 1                                       # streams per plane: xe, xo finest -> coarsest
+    if len(lengths) % per:
+        raise ValueError("stream lengths: %d streams are not a whole number of planes of %d" % (len(lengths), per))
+    out = []
+    for k in range(L + 1):
+        need = sum(n for i, n in enumerate(lengths) if i % per == 0 or i % per - 1 >= k)
+        out.append(hdr["header_bytes"] + need)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ model identity
 def arithmetic_string(coder="host"):
     """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path, plus the
@@ -436,14 +458,43 @@ def check_header(hdr, layer, nettype, L, digest, arith):
                          % (hdr_arith, arith, ", ".join(diff)))
 
 
-def decode_images(net, blobs):
+def _reduce(reduce, L):
+    """The reduce factor of a decode, checked on the host (ValueError naming reduce)."""
+    try:
+        k = int(reduce)
+    except (TypeError, ValueError):
+        raise ValueError("reduce must be an integer in [0, %d] (got %r)" % (L, reduce)) from None
+    if k != reduce or not 0 <= k <= L:
+        raise ValueError("reduce must be an integer in [0, %d], the net's dwtlevels (got %r)" % (L, reduce))
+    return k
+
+
+def _reduced(v, k):
+    """ceil(v / 2^k): a side of the image at reduce=k."""
+    return -(-v >> k)
+
+
+def ll_norm(net, k):
+    """-> (inv_a, b), 3 floats each, rounded to fp32: the per-plane map (LL_k - b) * inv_a of a reduce=k decode, with
+    (a, b) = lifting_dwt_nets.ll_affine of the net's transforms and inv_a = fp32(1 / a) computed here on the host."""
+    import torch
+    from .graphs.layers.lifting_dwt_nets import ll_affine
+    a, b = ll_affine([n.autoencoder for n in net.nets()], k)
+    inv = [1.0 / v if v != 0 else float("inf") for v in a]
+    return torch.tensor(inv, dtype=torch.float32).tolist(), torch.tensor(b, dtype=torch.float32).tolist()
+
+
+def decode_images(net, blobs, reduce=0):
     """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
-    first; then containers of equal (H, W) and coder are decoded together (the coder comes from each header)."""
+    first; then containers of equal (H, W) and coder are decoded together (the coder comes from each header).
+    reduce = k in [0, L]: the image at 1/2^k of each side, (ceil(H / 2^k), ceil(W / 2^k), 3), decoded from the xe streams
+    and the levels k .. L-1 only (the module docstring); reduce=0 is the full decode."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
     layer, nettype, L = describe(net)
+    k = _reduce(reduce, L)
     parsed = [parse_container(b) for b in blobs]
     digest, arith = weights_digest(net), arithmetic_string()
     for hdr, _ in parsed:
@@ -455,15 +506,23 @@ def decode_images(net, blobs):
         by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"]), []).append(i)
     out = [None] * len(parsed)
     with torch.no_grad():
+        if k:
+            inv_a, b = ll_norm(net, k)
         for (H, W, coder), idx in by_size.items():
             Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             groups = [idx] if _batch_invariant(arith) else [[i] for i in idx]
             for g in groups:
                 per = L + 1                                   # streams per plane: xe, xo finest -> coarsest
                 s_xe = [[parsed[i][1][p * per] for i in g] for p in range(_PLANES)]
-                s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(L)]
-                xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder)
-                img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W).cpu()
+                s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(k, L)]
+                if k == 0:
+                    xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder)
+                    img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W).cpu()
+                else:
+                    ll = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, first_level=k)
+                    Hr, Wr = _reduced(H, k), _reduced(W, k)
+                    img = ops.ll_tiles_to_u8hwc(ll.contiguous(), (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr), inv_a,
+                                                b, B=len(g)).cpu()
                 for j, i in enumerate(g):
                     out[i] = img[j]
     return out
@@ -523,10 +582,12 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host"):
     return [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
 
 
-def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host"):
-    """One group of n tiles -> xhat (3,n,1,th,tw) (decode_strings_planes; a module-level hook so the number of tiles a
-    decode touches can be counted)."""
+def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0):
+    """One group of n tiles -> xhat (3,n,1,th,tw), or at first_level = k the LL band (3,n,1,th>>k,tw>>k)
+    (decode_strings_planes; a module-level hook so the number of tiles a decode touches can be counted)."""
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
+    if first_level:
+        return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level)
     return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder)
 
 
@@ -542,19 +603,23 @@ def _region(region, H, W):
     return y0, x0, h, w
 
 
-def decode_tiled(net, blob, region=None, tiles_per_call=32):
+def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
     """LLDT container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
-    Every check (container, identity, region) runs on the host before any GPU work."""
+    reduce = k in [0, L]: the image at 1/2^k of each side (decode_images); region is then in the coordinates of the reduced
+    image, each tile covers th>>k x tw>>k of its pixels and is written by lldwt_ll_tiles_to_u8hwc.
+    Every check (container, region, identity) runs on the host before any GPU work."""
     import torch
     from . import ops
     layer, nettype, L = describe(net)
+    k = _reduce(reduce, L)
     hdr, tiles = parse_tiled(blob)
-    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
-    H, W, th, tw, ny, nx = (hdr[k] for k in ("H", "W", "th", "tw", "ny", "nx"))
+    H, W, th, tw, ny, nx = (hdr[key] for key in ("H", "W", "th", "tw", "ny", "nx"))
+    H, W, th, tw = _reduced(H, k), _reduced(W, k), th >> k, tw >> k          # tile sides are multiples of 2^L
     y0, x0, h, w = _region(region, H, W)
     if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
         raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
+    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
     _prepare(net)
     nets = net.nets()
     dev = next(net.parameters()).device
@@ -563,11 +628,19 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32):
     per = L + 1
     out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
     with torch.no_grad():
+        if k:
+            inv_a, b = ll_norm(net, k)
         for a in range(0, len(want), g):
             grp = want[a:a + g]
             s_xe = [[tiles[t][p * per] for t in grp] for p in range(_PLANES)]
-            s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(L)]
+            s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(k, L)]
             kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}     # host: the call as it has always been
-            xhat = _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp), **kw)
-            ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=grp, out=out)
+            if k:
+                kw["first_level"] = k
+            xhat = _decode_tiles(nets, s_xe, s_xo, hdr["th"], hdr["tw"], len(grp), **kw)
+            if k == 0:
+                ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=grp, out=out)
+            else:
+                ops.ll_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), inv_a, b, tiles=grp,
+                                      out=out)
     return out[0].cpu()

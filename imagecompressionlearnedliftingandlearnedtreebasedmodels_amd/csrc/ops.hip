@@ -102,11 +102,25 @@ __global__ void k_u8hwc_to_ycc_tiles(const uint8_t* __restrict__ src, float* __r
     ycc[(2 * n + j) * hw + p] = cr;
 }
 
+// Per-plane affine map of a reduced-resolution decode (lldwt_ll_tiles_to_u8hwc): sample s of plane p -> (s - b[p]) * inv_a[p],
+// the LL band at level k on the image's scale (lifting_dwt_nets.ll_affine).  Six floats passed by value.
+struct LLAffine {
+    float inv_a[3], b[3];
+};
+
 // One pixel of plane-major YCbCr (slot j of n, offset p in its plane) -> 3 bytes of uint8 RGB: k_ycc_to_rgb(clamp=1), then
-// floor((v + 0.5) * 255 + 0.5) in fp32 (v in [-0.5, 0.5], so the byte is in [0, 255]).
+// floor((v + 0.5) * 255 + 0.5) in fp32 (v in [-0.5, 0.5], so the byte is in [0, 255]).  AFFINE: each plane's sample goes
+// through the LLAffine map first.
+template <bool AFFINE>
 __device__ __forceinline__ void ycc_px_to_u8(const float* __restrict__ ycc, int64_t n, int64_t j, int64_t hw, int64_t p,
-                                             uint8_t* __restrict__ d) {
-    const float y = ycc[(0 * n + j) * hw + p] + 0.5f, cb = ycc[(1 * n + j) * hw + p], cr = ycc[(2 * n + j) * hw + p];
+                                             uint8_t* __restrict__ d, LLAffine af) {
+    float s0 = ycc[(0 * n + j) * hw + p], cb = ycc[(1 * n + j) * hw + p], cr = ycc[(2 * n + j) * hw + p];
+    if (AFFINE) {
+        s0 = (s0 - af.b[0]) * af.inv_a[0];
+        cb = (cb - af.b[1]) * af.inv_a[1];
+        cr = (cr - af.b[2]) * af.inv_a[2];
+    }
+    const float y = s0 + 0.5f;
     float rr = y + (2.f - 2.f * KR) * (cr - 0.5f);
     float bl = y + (2.f - 2.f * KB) * (cb - 0.5f);
     float g = (y - KR * rr - KB * bl) / KG;
@@ -123,16 +137,16 @@ __device__ __forceinline__ void ycc_px_to_u8(const float* __restrict__ ycc, int6
 // of the pixels inside the image and inside the region [y0, y0+h) x [x0, x0+w), written to dst (B,h,w,3) at the image of
 // the tile (ycc_px_to_u8).  GRID = true: grid (cdiv(tw,256), th, n), one thread per tile pixel; a tile index outside the
 // B x ny x nx grid writes nothing.  GRID = false: the 1 x 1 grid (tile = image, tiles == NULL, the untiled codec's crop):
-// grid (cdiv(w,256), h, n), one thread per region pixel.
-template <bool GRID>
+// grid (cdiv(w,256), h, n), one thread per region pixel.  AFFINE: the samples are a reduced-resolution LL band (LLAffine).
+template <bool GRID, bool AFFINE>
 __global__ void k_ycc_tiles_to_u8hwc(const float* __restrict__ ycc, const int32_t* __restrict__ tiles, int64_t first, int64_t n,
                                      int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx,
-                                     int64_t y0, int64_t x0, int64_t h, int64_t w, uint8_t* __restrict__ dst) {
+                                     int64_t y0, int64_t x0, int64_t h, int64_t w, uint8_t* __restrict__ dst, LLAffine af) {
     const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, j = blockIdx.z, hw = th * tw;
     if (!GRID) {
         if (x >= w) return;
         const int64_t ry = blockIdx.y, b = first + j;
-        ycc_px_to_u8(ycc, n, j, hw, (y0 + ry) * tw + x0 + x, dst + ((b * h + ry) * w + x) * 3);
+        ycc_px_to_u8<AFFINE>(ycc, n, j, hw, (y0 + ry) * tw + x0 + x, dst + ((b * h + ry) * w + x) * 3, af);
         return;
     }
     if (x >= tw) return;
@@ -142,7 +156,8 @@ __global__ void k_ycc_tiles_to_u8hwc(const float* __restrict__ ycc, const int32_
     const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
     const int64_t gy = (int64_t)ty * th + blockIdx.y, gx = (int64_t)tx * tw + x;
     if (gy >= H || gx >= W || gy < y0 || gy >= y0 + h || gx < x0 || gx >= x0 + w) return;
-    ycc_px_to_u8(ycc, n, j, hw, (int64_t)blockIdx.y * tw + x, dst + (((int64_t)b * h + (gy - y0)) * w + (gx - x0)) * 3);
+    ycc_px_to_u8<AFFINE>(ycc, n, j, hw, (int64_t)blockIdx.y * tw + x, dst + (((int64_t)b * h + (gy - y0)) * w + (gx - x0)) * 3,
+                         af);
 }
 
 // ------------------------------------------------------------------------------------------ subband MLP
@@ -1223,26 +1238,51 @@ extern "C" int lldwt_u8hwc_to_ycc_tiles(const uint8_t* src, float* ycc, int64_t 
                        (hipStream_t)stream, src, ycc, H, W, th, tw, ny, nx, first, n);
     return check_launch("u8hwc_to_ycc_tiles");
 }
+// the checks and the launch of both tile output entry points (who: the name their messages carry)
+template <bool AFFINE>
+static int ycc_tiles_to_u8hwc(const char* who, const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B,
+                              int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
+                              int64_t h, int64_t w, uint8_t* dst, LLAffine af, void* stream) {
+    LLDWT_REQUIRE(ycc && dst && B > 0 && H > 0 && W > 0 && th > 0 && tw > 0 && ny > 0 && nx > 0 && n > 0,
+                  "%s: bad arguments", who);
+    LLDWT_REQUIRE(tiles || (first >= 0 && first + n <= B * ny * nx), "%s: tile range outside the grid", who);
+    LLDWT_REQUIRE(y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && y0 + h <= H && x0 + w <= W,
+                  "%s: region (%lld, %lld, %lld, %lld) outside the %lld x %lld image", who, (long long)y0,
+                  (long long)x0, (long long)h, (long long)w, (long long)H, (long long)W);
+    LLDWT_REQUIRE(ny * th >= H && nx * tw >= W, "%s: the grid does not cover the image", who);
+    const bool grid = ny * nx > 1 || tiles;
+    LLDWT_REQUIRE(n <= 65535 && (grid ? th : h) <= 65535 && tw <= (1ll << 30) && B * ny * nx < (1ll << 31),
+                  "%s: grid too large", who);
+    if (grid)
+        hipLaunchKernelGGL((k_ycc_tiles_to_u8hwc<true, AFFINE>), dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n),
+                           dim3(256), 0, (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst,
+                           af);
+    else
+        hipLaunchKernelGGL((k_ycc_tiles_to_u8hwc<false, AFFINE>), dim3((unsigned)cdiv(w, 256), (unsigned)h, (unsigned)n),
+                           dim3(256), 0, (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst,
+                           af);
+    return check_launch(who);
+}
 extern "C" int lldwt_ycc_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H,
                                         int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
                                         int64_t h, int64_t w, uint8_t* dst, void* stream) {
-    LLDWT_REQUIRE(ycc && dst && B > 0 && H > 0 && W > 0 && th > 0 && tw > 0 && ny > 0 && nx > 0 && n > 0,
-                  "ycc_tiles_to_u8hwc: bad arguments");
-    LLDWT_REQUIRE(tiles || (first >= 0 && first + n <= B * ny * nx), "ycc_tiles_to_u8hwc: tile range outside the grid");
-    LLDWT_REQUIRE(y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && y0 + h <= H && x0 + w <= W,
-                  "ycc_tiles_to_u8hwc: region (%lld, %lld, %lld, %lld) outside the %lld x %lld image", (long long)y0,
-                  (long long)x0, (long long)h, (long long)w, (long long)H, (long long)W);
-    LLDWT_REQUIRE(ny * th >= H && nx * tw >= W, "ycc_tiles_to_u8hwc: the grid does not cover the image");
-    const bool grid = ny * nx > 1 || tiles;
-    LLDWT_REQUIRE(n <= 65535 && (grid ? th : h) <= 65535 && tw <= (1ll << 30) && B * ny * nx < (1ll << 31),
-                  "ycc_tiles_to_u8hwc: grid too large");
-    if (grid)
-        hipLaunchKernelGGL(k_ycc_tiles_to_u8hwc<true>, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
-                           (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst);
-    else
-        hipLaunchKernelGGL(k_ycc_tiles_to_u8hwc<false>, dim3((unsigned)cdiv(w, 256), (unsigned)h, (unsigned)n), dim3(256), 0,
-                       (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst);
-    return check_launch("ycc_tiles_to_u8hwc");
+    return ycc_tiles_to_u8hwc<false>("ycc_tiles_to_u8hwc", ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst,
+                                     LLAffine{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}}, stream);
+}
+extern "C" int lldwt_ll_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H,
+                                       int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
+                                       int64_t h, int64_t w, const float* inv_a, const float* b, uint8_t* dst, void* stream) {
+    LLDWT_REQUIRE(inv_a && b, "ll_tiles_to_u8hwc: null inv_a / b");
+    LLAffine af;
+    for (int p = 0; p < 3; ++p) {
+        LLDWT_REQUIRE(isfinite(inv_a[p]) && inv_a[p] != 0.f && isfinite(b[p]),
+                      "ll_tiles_to_u8hwc: plane %d: inv_a = %g, b = %g (inv_a must be finite and non-zero, b finite)", p,
+                      (double)inv_a[p], (double)b[p]);
+        af.inv_a[p] = inv_a[p];
+        af.b[p] = b[p];
+    }
+    return ycc_tiles_to_u8hwc<true>("ll_tiles_to_u8hwc", ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst, af,
+                                    stream);
 }
 // the untiled codec's I/O: the 1 x 1 grid of one Hp x Wp tile per image
 extern "C" int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,

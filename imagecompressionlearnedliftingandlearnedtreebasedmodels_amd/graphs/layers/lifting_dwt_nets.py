@@ -297,12 +297,46 @@ def encode_shapes(nets, B, H, W):
     return (P, B, Cc, H >> L, W >> L), [(P, B, 3 * Cc, H >> (i + 1), W >> (i + 1)) for i in range(L)]
 
 
-def decode_planes(nets, out_xe, out_xo_list):
-    """autoencoder.decode for a list of per-plane transform modules -> xhat (P,B,C,H,W)."""
+def decode_planes(nets, out_xe, out_xo_list, first_level=0):
+    """autoencoder.decode for a list of per-plane transform modules -> xhat (P,B,C,H,W).  first_level = k: out_xo_list holds
+    the levels k .. L-1 only (finest first) and the result is the decoded LL band at level k, (P,B,C,H>>k,W>>k): the inverse
+    of the top L-k levels (for k = L, the decoded xe).  Its scale is not the image's (ll_affine)."""
     n0 = nets[0]
+    k = int(first_level)
     Yl = ae_planes([n.Yl_ae for n in nets], out_xe, True)
-    Yh = [ae_planes([n.Yh_ae[i] for n in nets], out_xo_list[i], True) for i in range(len(out_xo_list))]
+    Yh = [ae_planes([n.Yh_ae[k + i] for n in nets], out_xo_list[i], True) for i in range(len(out_xo_list))]
+    if not Yh:
+        return Yl
     if isinstance(n0, DWTPytorchWaveletsLayer):
         Yh6 = [t.reshape(t.shape[0], t.shape[1], t.shape[2] // 3, 3, t.shape[3], t.shape[4]) for t in Yh]
         return ops.cdf97_inverse(Yl, Yh6)
     return lifting_inverse_planes(nets, Yl, Yh)
+
+
+def ll_affine(nets, k):
+    """The normalisation of a reduced-resolution decode: -> (a, b), lists of P floats, such that the LL
+    band at level k of plane p maps to the image's plane domain (Y - 0.5, Cb, Cr) as v = (LL_k - b[p]) / a[p].
+    Measured with the transform's own forward kernels: k levels of it on constant planes at 0 and at 1 of the smallest square
+    side it accepts whose LL is at least 8 x 8; m(c) = mean of that LL, b = m(0), a = m(1) - m(0).  k = 0: a = 1, b = 0.
+    For CDF 9/7 (periodization) a = 2^k and b = 0; the learned lifting's P/U blocks are nonlinear, so this is the affine
+    map a constant plane sees.  Cached on the transform's parameters (one small forward per (model, k))."""
+    n0 = nets[0]
+    L, P = _levels(n0), len(nets)
+    k = int(k)
+    if not 0 <= k <= L:
+        raise ValueError("ll_affine: level k must be in [0, %d] (got %d)" % (L, k))
+    if k == 0:
+        return [1.0] * P, [0.0] * P
+    cdf = isinstance(n0, DWTPytorchWaveletsLayer)
+    srcs = [] if cdf else [p for n in nets for name, p in n.named_parameters() if not name.startswith(("Yl_ae.", "Yh_ae."))]
+
+    def build():
+        side = padded_dims(k, cdf, 8 << k, 8 << k)[0]
+        dev = next(n0.parameters()).device
+        c = torch.zeros(P, 2, 1, side, side, device=dev, dtype=torch.float32)
+        c[:, 1] = 1.0
+        ll = ops.cdf97_forward(c, k)[0] if cdf else lifting_forward_planes(nets, c, levels=k)[0]
+        m = ll.double().mean(dim=(2, 3, 4)).cpu()                                   # (P, 2): m(0), m(1)
+        return [float(v) for v in m[:, 1] - m[:, 0]], [float(v) for v in m[:, 0]]
+    with torch.no_grad():
+        return cached(n0, ("ll_affine", k, tuple(id(n) for n in nets[1:])), srcs, build)

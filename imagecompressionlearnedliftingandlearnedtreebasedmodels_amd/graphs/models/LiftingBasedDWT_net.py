@@ -122,6 +122,18 @@ def _eb_packed(ebs):
 
 
 # ------------------------------------------------------------------------------------------------ entropy layers
+def _coarse_strings(strings_xo_list, L, first_level):
+    """The per-level strings of a decode that stops at level first_level = k, indexed by level (finest first): the input holds
+    either all L levels or only the levels k .. L-1; the entries below k are None and are never read."""
+    k = int(first_level)
+    if not 0 <= k <= L:
+        raise ValueError("first_level must be in [0, %d] (got %d)" % (L, k))
+    s = list(strings_xo_list)
+    if len(s) not in (L, L - k):
+        raise ValueError("first_level %d: expected the strings of %d or %d levels (got %d)" % (k, L, L - k, len(s)))
+    return [None] * k + s[len(s) - (L - k):]
+
+
 class _EntropyLayerBase(PackedOwnerMixin, nn.Module):
     def _level_channels(self, config):
         self.num_lifting_layers = config.dwtlevels
@@ -246,15 +258,20 @@ class onlyEZWT(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host"):
-        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors."""
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0):
+        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
+        xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]); shapes_xo has all L levels, strings_xo_list all L or the
+        levels k .. L-1 (_coarse_strings)."""
         from . import entropy_coding as ec
         L = len(shapes_xo)
+        strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
+            if first_level == L:
+                return xe, []
             _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1], coder=coder)
             q_list = [q]
-            for i in range(L - 2, -1, -1):
+            for i in range(L - 2, first_level - 1, -1):
                 tabs = ec._Tables(layers[0].ent_out_xo_list[i], get_scale_table())
                 for l in layers[1:]:
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
@@ -440,19 +457,23 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host"):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0):
         """decompress_ar for every tensor (:419-454): strings -> (xe, [xo] finest first), bit-identical to compress_planes'
-        dequantised tensors."""
+        dequantised tensors.  first_level = k: decode xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}])
+        (_coarse_strings; onlyEZWT.decompress_planes)."""
         from . import entropy_coding as ec
         tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
         L = len(shapes_xo)
+        strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], None, shape_xe, tabs,
                                        strings_xe, coder=coder)
+            if first_level == L:
+                return xe, []
             _, q = ec.code_crop_stack(stack, [l.ent_out_xo_list[L - 1] for l in layers], [l.csc_list[L - 1] for l in layers],
                                       None, shapes_xo[L - 1], tabs, strings_xo_list[L - 1], coder=coder)
             q_list = [q]
-            for i in range(L - 2, -1, -1):
+            for i in range(L - 2, first_level - 1, -1):
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, shapes_xo[i][2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
                 if packed[1] is not None:
@@ -606,17 +627,21 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host"):
-        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors."""
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0):
+        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
+        xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]) (_coarse_strings; onlyEZWT.decompress_planes)."""
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(shapes_xo)
+        strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
+            if first_level == L:
+                return xe, []
             _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1], coder=coder)
             q_list = [q]
-            for i in range(L - 1):
+            for i in range(L - 1 - first_level):          # i counts from the coarse end: level L - i - 2 >= first_level
                 ems, tabs = cls._level_models(layers, i, L)
                 _, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, None, shapes_xo[L - i - 2], tabs,
                                              strings_xo_list[L - i - 2], coder=coder)
@@ -1007,17 +1032,21 @@ def encode_strings_planes(nets, x, coder="host"):
     return s_xe, s_xo
 
 
-def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host"):
+def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0):
     """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them, with the same coder) ->
     xhat (P,B,C,Hp,Wp).
-    Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes)."""
+    Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes).
+    first_level = k: strings_xo holds all L levels or only the levels k .. L-1, which are the only ones decoded, and the result
+    is the decoded LL band at level k, (P,B,C,Hp>>k,Wp>>k) (decode_planes; lifting_dwt_nets.ll_affine gives its scale)."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "decompress_planes"):
         raise NotImplementedError(_NOT_CODED)
     aenc = [n.autoencoder for n in nets]
+    k = int(first_level)
     shape_xe, shapes_xo = encode_shapes(aenc, B, Hp, Wp)
-    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder)
-    return decode_planes(aenc, xe, xo)
+    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder, first_level=k)
+    assert [tuple(t.shape) for t in xo] == [tuple(sh) for sh in shapes_xo[k:]]
+    return decode_planes(aenc, xe, xo, first_level=k)
 
 
 class LiftingBasedDWTNet(PackedOwnerMixin, nn.Module):

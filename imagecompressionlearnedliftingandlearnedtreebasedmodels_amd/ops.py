@@ -169,6 +169,35 @@ def ycc_tiles_to_u8hwc(y, grid, region, tiles=None, first=0, B=1, out=None):
     return out
 
 
+def ll_tiles_to_u8hwc(y, grid, region, inv_a, b, tiles=None, first=0, B=1, out=None):
+    """ycc_tiles_to_u8hwc for a reduced-resolution decode: y (3,n,1,th,tw) holds each tile's decoded LL band at level k, grid
+    and region are in reduced coordinates, and plane p's samples become (s - b[p]) * inv_a[p] before the colour and u8 rule
+    (lldwt_ll_tiles_to_u8hwc; inv_a, b: 3 floats each, lifting_dwt_nets.ll_affine).  The untiled decode is the 1 x 1 grid."""
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    _, n, _, yh, yw = y.shape
+    if (yh, yw) != (th, tw):
+        raise _lib.LLDWTError("ll_tiles_to_u8hwc: tiles are %d x %d, the grid says %d x %d" % (yh, yw, th, tw))
+    if len(inv_a) != 3 or len(b) != 3:
+        raise _lib.LLDWTError("ll_tiles_to_u8hwc: inv_a and b need 3 values each")
+    tptr = C.c_void_p(0)
+    if tiles is not None:
+        if len(tiles) != n or any(t < 0 or t >= B * ny * nx for t in tiles):
+            raise _lib.LLDWTError("ll_tiles_to_u8hwc: need %d tile indexes in [0, %d)" % (n, B * ny * nx))
+        tiles = torch.tensor(list(tiles), dtype=torch.int32).to(y.device)
+        tptr = C.c_void_p(tiles.data_ptr())
+    if out is None:
+        out = torch.empty(B, h, w, 3, device=y.device, dtype=torch.uint8)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)):
+        raise _lib.LLDWTError("ll_tiles_to_u8hwc: out must be a contiguous (%d,%d,%d,3) uint8 device tensor" % (B, h, w))
+    ia = (C.c_float * 3)(*[float(v) for v in inv_a])
+    bb = (C.c_float * 3)(*[float(v) for v in b])
+    check(_lib.load().lldwt_ll_tiles_to_u8hwc(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w,
+                                              C.cast(ia, C.c_void_p), C.cast(bb, C.c_void_p), C.c_void_p(out.data_ptr()),
+                                              _stream()), "ll_tiles_to_u8hwc")
+    return out
+
+
 def ycc_to_u8hwc_crop(y, H, W):
     """plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5 -> (B,H,W,3) uint8 RGB of the top-left H x W
     (lldwt_ycc_to_u8hwc_crop: floor((v + 0.5) * 255 + 0.5) of v = ycc_to_rgb(y, clamp=True))."""

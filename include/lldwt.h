@@ -80,12 +80,20 @@ int lldwt_u8hwc_to_f32chw(const uint8_t* src, float* dst, int64_t B, int64_t H, 
  * lldwt_u8hwc_to_ycc_pad: src (B,H,W,3) -> ycc (3,B,1,Hp,Wp), Hp >= H, Wp >= W: the 1 x 1 grid.  B, Hp <= 65535.
  * lldwt_ycc_to_u8hwc_crop: ycc (3,B,1,Hp,Wp) -> dst (B,H,W,3) of the top-left H x W: the 1 x 1 grid, region = the image.
  *   B, H <= 65535.
- * Both tile entry points require ny * th >= H and nx * tw >= W.                                                                                                  */
+ * lldwt_ll_tiles_to_u8hwc: lldwt_ycc_tiles_to_u8hwc for a reduced-resolution decode: ycc holds the decoded LL band at level
+ *   k of each tile (3,n,1,th,tw) with th, tw, H, W the reduced tile and image sizes; every sample s of plane p becomes
+ *   (s - b[p]) * inv_a[p] (inv_a, b: 3 host floats each, lifting_dwt_nets.ll_affine) before the same colour and u8 rule.
+ *   Refuses a non-finite or zero inv_a, a non-finite b, and every grid / region lldwt_ycc_tiles_to_u8hwc refuses.
+ *   With inv_a = 1, b = 0 the bytes are those of lldwt_ycc_tiles_to_u8hwc.
+ * Every tile entry point requires ny * th >= H and nx * tw >= W.                                                                                                   */
 int lldwt_u8hwc_to_ycc_tiles(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw,
                              int64_t ny, int64_t nx, int64_t first, int64_t n, void* stream);
 int lldwt_ycc_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
                              int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
                              uint8_t* dst, void* stream);
+int lldwt_ll_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                            int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                            const float* inv_a, const float* b, uint8_t* dst, void* stream);
 int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
                            void* stream);
 int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,

@@ -2,10 +2,13 @@
 
     python tools/codec.py encode --config cfg.json [--checkpoint ckpt.pth.tar] in.png out.lld
     python tools/codec.py decode --config cfg.json [--checkpoint ckpt.pth.tar] in.lld out.png
-    python tools/codec.py info in.lld                      (CPU only: prints the header)
+    python tools/codec.py info in.lld                      (CPU only: prints the header and the bytes a decode reads
+                                                            at each reduce factor)
 
     encode --tile N [--tiles-per-call K]   writes a tiled (LLDT) container: N x N target tiles, each an independent image
     decode --region y0,x0,h,w              decodes only that region (tiled containers only)
+    decode --reduce k                      decodes the image at 1/2^k of each side from the coarse levels only (0 <= k <=
+                                           dwtlevels; with --region, the region is in the reduced image's coordinates)
     encode --coder gpu                     codes the streams with the interleaved device coder (irans32); decode reads the
                                            coder from the header
 
@@ -60,6 +63,8 @@ def main(argv=None):
     sub.choices["encode"].add_argument("--coder", choices=("host", "gpu"), default="host",
                                        help="entropy coder: host (rans64, the default) or gpu (irans32 on the device)")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
+    sub.choices["decode"].add_argument("--reduce", type=int, default=0,
+                                       help="decode at 1/2^k of each side from the coarse wavelet levels (default 0: full)")
     p = sub.add_parser("info")
     p.add_argument("src")
     a = ap.parse_args(argv)
@@ -71,6 +76,8 @@ def main(argv=None):
             print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
         if "ny" in hdr:
             print("%-15s %d x %d tiles of %d x %d (rows x columns)" % ("grid", hdr["ny"], hdr["nx"], hdr["th"], hdr["tw"]))
+        for k, n in enumerate(codec.reduce_bytes(hdr)):
+            print("%-15s %d x %d: %d bytes" % ("reduce %d" % k, -(-hdr["W"] >> k), -(-hdr["H"] >> k), n))
         return 0
 
     import numpy as np
@@ -108,9 +115,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if tiled:
-            img = codec.decode_tiled(net, blob, region=region, tiles_per_call=a.tiles_per_call)
+            img = codec.decode_tiled(net, blob, region=region, tiles_per_call=a.tiles_per_call, reduce=a.reduce)
         else:
-            img = codec.decode_images(net, [blob])[0]
+            img = codec.decode_images(net, [blob], reduce=a.reduce)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         Image.fromarray(img.numpy()).save(a.dst)
