@@ -107,6 +107,8 @@ SIGNATURES = {
     "lldwt_conv_pack": (_i, [_p, _p, C.POINTER(ConvDesc), _i64, _p]),
     "lldwt_conv_pack_ex": (_i, [_p, _p, C.POINTER(ConvDesc), _i64, _i, _p]),
     "lldwt_conv2d": (_i, [_p, _p, _p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
+    "lldwt_conv_stack_pair": (_i, [_p, _p, _p, _p, C.POINTER(_p), C.POINTER(_p), C.POINTER(ConvDesc), _i, _i, _p, _p, _i64, _i64, _i64,
+                                   _i64, _i64, _i64, _p]),
     "lldwt_conv2d_absmax": (_i, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
     "lldwt_conv2d_f16out": (_i, [_p, _p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
     "lldwt_conv3x3_f16in": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _i64, _i64, _i64, _p]),
@@ -178,6 +180,7 @@ SIGNATURES = {
                                 _p, _p, _p]),
     "lldwt_sq_err_sum": (_i, [_p, _p, _i64, _p, _p]),
     "lldwt_sum": (_i, [_p, _i64, _p, _p]),
+    "lldwt_tail_legacy": (_i, []),
     "lldwt_cdf97_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "lldwt_cdf97_forward": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i, _p, _i64, _p]),
     "lldwt_cdf97_inverse": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i, _p, _i64, _p]),

@@ -112,6 +112,11 @@ struct ConvArgs {
     lldwt_conv_desc d;
     ConvPlan p;
     int batch, h, w, tiles_x, tiles_y;
+    // pair launch (lldwt_conv_stack_pair): the groups from g2 on read x2 and / or write y2, dense tensors that hold those
+    // groups only; x and y then hold the groups below g2 only.  Null = every group in x / y.
+    const float* x2 = nullptr;
+    float* y2 = nullptr;
+    int g2 = 0;
 };
 
 template <int KS, int WM, int WN, int WVM, int WVN, int TWS, int CK>
@@ -153,8 +158,10 @@ __global__ __launch_bounds__(64 * WVM * WVN) void k_conv_mfma(ConvArgs a) {
     const int h = a.h, w = a.w;
     const int hi = d.upsample2 ? h >> 1 : h, wi = d.upsample2 ? w >> 1 : w;
     const int64_t hwi = (int64_t)hi * wi;
-    const int xtot = d.ic_block > 0 ? d.xtot : d.cin;
-    const float* xg = a.x + (z * xtot) * hwi;               // + mapped channel * hwi
+    const bool in2 = a.x2 && g >= a.g2, out2 = a.y2 && g >= a.g2;     // workgroup-uniform
+    const int gi = in2 ? g - a.g2 : g;                      // this group's index inside its input tensor
+    const int xtot = d.ic_block > 0 ? d.xtot : (a.x2 ? (in2 ? d.groups - a.g2 : a.g2) * cin_g : d.cin);
+    const float* xg = (in2 ? a.x2 : a.x) + (z * xtot) * hwi;   // + mapped channel * hwi
     const int icb = d.ic_block > 0 ? d.ic_block : d.cin, ics = d.ic_block > 0 ? d.ic_stride : 0, ico = d.ic_block > 0 ? d.ic_off : 0;
     const float* pk = a.packed + (int64_t)plane * a.p.plane_floats +
                       ((int64_t)(g * a.p.nocb + ocb) * a.p.nchunk) * a.p.chunk_floats;
@@ -191,7 +198,7 @@ __global__ __launch_bounds__(64 * WVM * WVN) void k_conv_mfma(ConvArgs a) {
     for (int ic = tid; ic < a.p.nchunk * CK; ic += G::NT) {
         int v = -1;
         if (ic < cin_g) {
-            const int icg = g * cin_g + ic;
+            const int icg = gi * cin_g + ic;
             v = (icg / icb) * ics + ico + icg % icb;
         }
         s_icm[ic] = v;
@@ -216,7 +223,7 @@ __global__ __launch_bounds__(64 * WVM * WVN) void k_conv_mfma(ConvArgs a) {
 #define LLDWT_STAGE_LOAD(CHUNK)                                                                             \
     {                                                                                                       \
         if (plain_in && (CHUNK) < full_chunks) {                                                            \
-            const float* cb = xg + (int64_t)(g * cin_g + (CHUNK) * CK) * hwi;      /* wave-uniform */        \
+            const float* cb = xg + (int64_t)(gi * cin_g + (CHUNK) * CK) * hwi;     /* wave-uniform */        \
             _Pragma("unroll") for (int r = 0; r < G::NIN; ++r)                                              \
                 xin[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(cb) + voff[r]);      \
         } else {                                                                                            \
@@ -325,6 +332,8 @@ __global__ __launch_bounds__(64 * WVM * WVN) void k_conv_mfma(ConvArgs a) {
     // ---- epilogue: bias, residual, activation, channel placement
     const int64_t hw = (int64_t)h * w;
     float omax = 0.f;
+    float* const ybase = out2 ? a.y2 : a.y;
+    const int ytot = out2 ? (d.groups - a.g2) * cout_g : d.ytot;
 #pragma unroll
     for (int m = 0; m < WM; ++m) {
 #pragma unroll
@@ -332,13 +341,13 @@ __global__ __launch_bounds__(64 * WVM * WVN) void k_conv_mfma(ConvArgs a) {
             const int ocl = (ocb * G::OCT + wm * WM + m) * 16 + kk * 4 + r;
             if (ocl >= cout_g) continue;
             const int oc = g * cout_g + ocl;
-            const int ocp = (oc / d.oc_block) * d.oc_stride + d.oc_off + oc % d.oc_block;
+            const int ocp = out2 ? (g - a.g2) * cout_g + ocl : (oc / d.oc_block) * d.oc_stride + d.oc_off + oc % d.oc_block;
             const float bv = a.bias ? a.bias[plane * d.cout + oc] : 0.f;
-            float* yp = a.y16 ? nullptr : a.y + (z * d.ytot + ocp) * hw;
-            _Float16* yp16 = a.y16 ? a.y16 + (z * d.ytot + ocp) * hw : nullptr;
+            float* yp = a.y16 ? nullptr : ybase + (z * ytot + ocp) * hw;
+            _Float16* yp16 = a.y16 ? a.y16 + (z * ytot + ocp) * hw : nullptr;
             const float osc = a.y16 ? a.oscale[plane] : 1.f;
-            const float* rp = a.residual ? a.residual + (z * d.ytot + ocp) * hw : nullptr;
-            const float* ap = (a.aux && d.epi) ? a.aux + (z * d.ytot + ocp) * hw : nullptr;
+            const float* rp = a.residual ? a.residual + (z * ytot + ocp) * hw : nullptr;
+            const float* ap = (a.aux && d.epi) ? a.aux + (z * ytot + ocp) * hw : nullptr;
 #pragma unroll
             for (int n = 0; n < WN; ++n) {
                 const int j = wn * WN + n;
@@ -478,6 +487,56 @@ extern "C" int lldwt_conv2d_f16out(const float* x, void* y16, const float* packe
     a.x = x; a.y = nullptr; a.packed = packed; a.bias = bias; a.residual = nullptr; a.aux = nullptr; a.absmax = nullptr;
     a.y16 = reinterpret_cast<_Float16*>(y16); a.oscale = oscale;
     return conv2d_launch(a, d, planes, batch, h, w_, stream);
+}
+
+// Two independent grouped conv stacks of the same per-group shapes (the coarsest level's context stacks: g -> 81g -> 81g ->
+// 27g -> 9g -> 2g, LiftingBasedDWT_net.py:299-305,311-317) as ONE grouped problem per layer: stack A's groups_a groups first,
+// then stack B's.  Each stack alone leaves most of the chip idle at 32 x 32 pixels and a launch costs one workgroup's
+// latency whatever its size, so the pair costs about what stack A costs alone.  A workgroup computes one group's outputs
+// exactly as in the single launch (same plan, same chunk order): the results are bit-identical.
+extern "C" int lldwt_conv_stack_pair(const float* xa, const float* xb, float* ya, float* yb, const float* const* packed,
+                                     const float* const* bias, const lldwt_conv_desc* descs, int nlayers, int groups_a,
+                                     float* ws0, float* ws1, int64_t ws0_floats, int64_t ws1_floats, int64_t planes, int64_t batch, int64_t h,
+                                     int64_t w_, void* stream) {
+    LLDWT_REQUIRE(xa && xb && ya && yb && packed && bias && descs && ws0 && ws1, "conv_stack_pair: null pointer");
+    LLDWT_REQUIRE(nlayers >= 2 && nlayers <= 16, "conv_stack_pair: %d layers unsupported", nlayers);
+    const int groups = descs[0].groups;
+    LLDWT_REQUIRE(groups_a > 0 && groups_a < groups, "conv_stack_pair: bad group split (%d of %d)", groups_a, groups);
+    int64_t mid[2] = {0, 0};      // widest layer written to ws0 (even layers) / ws1 (odd layers)
+    for (int i = 0; i < nlayers; ++i) {
+        const lldwt_conv_desc& d = descs[i];
+        int r = conv_desc_ok("conv_stack_pair", &d, planes, batch, h, w_);
+        if (r) return r;
+        LLDWT_REQUIRE(packed[i], "conv_stack_pair: null weights of layer %d", i);
+        LLDWT_REQUIRE(d.groups == groups && !d.upsample2 && !d.transposed && d.ic_block == 0 && d.epi == 0 &&
+                      d.oc_block == d.cout && d.oc_off == 0 && d.ytot == d.cout,
+                      "conv_stack_pair: layer %d must be a plain grouped conv of %d groups", i, groups);
+        LLDWT_REQUIRE(i == 0 || d.cin == descs[i - 1].cout, "conv_stack_pair: layer %d reads %d channels, layer %d writes %d", i,
+                      d.cin, i - 1, descs[i - 1].cout);
+        if (i + 1 < nlayers && d.cout > mid[i & 1]) mid[i & 1] = d.cout;
+    }
+    LLDWT_REQUIRE(ws0_floats >= planes * batch * mid[0] * h * w_ && ws1_floats >= planes * batch * mid[1] * h * w_,
+                  "conv_stack_pair: workspaces too small");
+    const float* src = xa;
+    for (int i = 0; i < nlayers; ++i) {
+        const bool first = i == 0, last = i == nlayers - 1;
+        lldwt_conv_desc d = descs[i];
+        ConvArgs a;
+        a.x = src; a.packed = packed[i]; a.bias = bias[i]; a.residual = nullptr; a.aux = nullptr; a.absmax = nullptr;
+        a.y16 = nullptr; a.oscale = nullptr;
+        a.g2 = groups_a;
+        if (first) a.x2 = xb;
+        if (last) {
+            a.y = ya; a.y2 = yb;
+            d.ytot = d.oc_block = d.cout / groups * groups_a;       // ya holds stack A's channels only (oc' = oc below g2)
+        } else {
+            a.y = (i & 1) ? ws1 : ws0;
+        }
+        int r = conv2d_launch(a, &d, planes, batch, h, w_, stream);
+        if (r) return r;
+        src = a.y;
+    }
+    return LLDWT_OK;
 }
 
 static int conv2d_launch_impl(ConvArgs& a, const lldwt_conv_desc* d, int64_t planes, int64_t batch, int64_t h, int64_t w_,

@@ -116,6 +116,26 @@ def _seq_stack(seqs, x, idxs):
     return t
 
 
+def _seq_stack_pair(seqs_a, seqs_b, xa, xb, idxs):
+    """_seq_stack of two independent stacks with the same per-group layers (the coarsest level's csc_list[L-1] and csc_xe) in
+    one launch per layer instead of two (ops.conv_stack_pair): -> (ya, yb), bit-identical to the two _seq_stack calls."""
+    ga, gb = seqs_a[0][idxs[0]].groups, seqs_b[0][idxs[0]].groups
+    layers = []
+    for n in idxs:
+        ma, mb = seqs_a[0][n], seqs_b[0][n]
+        _, ba, pa, mask = _conv_params([s[n] for s in seqs_a], "w")
+        _, bb, pb, mask_b = _conv_params([s[n] for s in seqs_b], "w")
+        same = (ma.kernel_size == mb.kernel_size and mask == mask_b and ma.in_channels * gb == mb.in_channels * ga and
+                ma.out_channels * gb == mb.out_channels * ga and ma.groups == ga and mb.groups == gb)
+        if not same:
+            return _seq_stack(seqs_a, xa, idxs), _seq_stack(seqs_b, xb, idxs)
+        packed, bias = cached(ma, ("conv_pair", n), [p for m in [s[n] for s in seqs_a + seqs_b] for p in (m.weight, m.bias)],
+                              lambda: (torch.cat([pa, pb], 1).contiguous(), torch.cat([ba, bb], 1).contiguous()))
+        layers.append((packed, bias, ma.in_channels + mb.in_channels, ma.out_channels + mb.out_channels, ma.kernel_size[0],
+                       ops.ACT_NONE if n == idxs[-1] else ops.ACT_LRELU, mask))
+    return ops.conv_stack_pair(xa, xb, layers, ga, gb)
+
+
 def _eb_packed(ebs):
     return cached(ebs[0], ("eb",), [p for e in ebs for p in e.parameters()],
                       lambda: torch.stack([e.packed() for e in ebs], 0).contiguous())
@@ -344,13 +364,20 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         idx5 = (0, 2, 4, 6, 8)
         # xe: decoder / context see quantize(x) WITHOUT means (:330); the rate uses an independent noise sample (:334)
         xe_q = ops.quantize(out_xe, _noise(out_xe, training))
-        ms = _seq_stack([l.csc_xe for l in layers], xe_q, idx5)
-        si_xe, _ = ops.gauss_rate(out_xe, ms, _noise(out_xe, training))
         q_list, si_list = [], []
         i = L - 1
-        xo_q = ops.quantize(out_xo_list[i], _noise(out_xo_list[i], training))
-        ms = _seq_stack([l.csc_list[i] for l in layers], xo_q, idx5)
-        bits, _ = ops.gauss_rate(out_xo_list[i], ms, _noise(out_xo_list[i], training))
+        if not training and ops.tail_mode() != "legacy" and out_xe.shape[3:] == out_xo_list[i].shape[3:]:
+            # the two stacks are independent and each leaves most of the chip idle: one launch per layer for both
+            xo_q = ops.quantize(out_xo_list[i])
+            ms, ms_xe = _seq_stack_pair([l.csc_list[i] for l in layers], [l.csc_xe for l in layers], xo_q, xe_q, idx5)
+            si_xe, _ = ops.gauss_rate(out_xe, ms_xe)
+            bits, _ = ops.gauss_rate(out_xo_list[i], ms)
+        else:
+            ms = _seq_stack([l.csc_xe for l in layers], xe_q, idx5)
+            si_xe, _ = ops.gauss_rate(out_xe, ms, _noise(out_xe, training))
+            xo_q = ops.quantize(out_xo_list[i], _noise(out_xo_list[i], training))
+            ms = _seq_stack([l.csc_list[i] for l in layers], xo_q, idx5)
+            bits, _ = ops.gauss_rate(out_xo_list[i], ms, _noise(out_xo_list[i], training))
         si_list.append(bits)
         q_list.append(xo_q)
         parent = xo_q

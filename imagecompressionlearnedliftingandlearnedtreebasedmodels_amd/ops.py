@@ -446,6 +446,39 @@ def conv2d(x, w, bias, K, groups=1, act=ACT_NONE, upsample2=False, transposed=Fa
     return out
 
 
+def tail_mode():
+    """'fused' (default) or 'legacy' (LLDWT_TAIL=legacy, read when the library loads): the earlier launches of the small
+    end-of-step work -- one launch per layer and per stack of the coarsest level's context stacks, the scalar sum kernel."""
+    return "legacy" if _lib.load().lldwt_tail_legacy() else "fused"
+
+
+def conv_stack_pair(xa, xb, layers, groups_a, groups_b):
+    """Two independent grouped masked-conv stacks with the same per-group shapes as one grouped problem per layer
+    (include/lldwt.h lldwt_conv_stack_pair).  xa: (P,B,groups_a*c,h,w), xb: (P,B,groups_b*c,h,w); layers: one
+    (packed, bias, cin, cout, K, act, tap_mask) per layer of the MERGED problem (stack A's groups first).  -> (ya, yb), each
+    bit-identical to conv2d run layer by layer on its stack alone."""
+    lib = _lib.load()
+    P, B, _, h, w = xa.shape
+    if xb.shape[:2] != (P, B) or xb.shape[3:] != (h, w):
+        raise _lib.LLDWTError("conv_stack_pair: inputs of different planes / batch / size")
+    groups, n = groups_a + groups_b, len(layers)
+    descs = (ConvDesc * n)(*[conv_desc(cin, cout, K, groups, act, tap_mask=mask) for _, _, cin, cout, K, act, mask in layers])
+    if xa.shape[2] * groups != layers[0][2] * groups_a or xb.shape[2] * groups != layers[0][2] * groups_b:
+        raise _lib.LLDWTError("conv_stack_pair: input channels do not match the first layer")
+    packed = (C.c_void_p * n)(*[_chk(l[0], "packed").value for l in layers])
+    bias = (C.c_void_p * n)(*[_opt(l[1], "bias").value for l in layers])
+    cout = layers[-1][3] // groups
+    ya = torch.empty(P, B, cout * groups_a, h, w, device=xa.device, dtype=torch.float32)
+    yb = torch.empty(P, B, cout * groups_b, h, w, device=xa.device, dtype=torch.float32)
+    mid = [l[3] for l in layers[:-1]]                      # even layers write ws0, odd layers ws1
+    n0, n1 = P * B * h * w * max(mid[0::2]), P * B * h * w * max(mid[1::2] or [1])
+    ws0 = torch.empty(n0, device=xa.device, dtype=torch.float32)
+    ws1 = torch.empty(n1, device=xa.device, dtype=torch.float32)
+    check(lib.lldwt_conv_stack_pair(_chk(xa, "xa"), _chk(xb, "xb"), _chk(ya), _chk(yb), packed, bias, descs, n, groups_a,
+                                    _chk(ws0), _chk(ws1), n0, n1, P, B, h, w, _stream()), "conv_stack_pair")
+    return ya, yb
+
+
 def storage_dtype():
     """Storage type of the tree-context tensor between the two tree convs: 'fp32' (default, the reference's) or 'fp16'
     (BASELINE configs[4]: half the bytes, two MFMA products instead of three, 1e-2 tolerance class).  LLDWT_STORAGE."""

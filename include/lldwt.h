@@ -330,6 +330,16 @@ int lldwt_conv_pack_ex(const float* w, float* packed, const lldwt_conv_desc* d, 
 int lldwt_conv2d(const float* x, float* y, const float* packed, const float* bias, const float* residual,
                  const float* aux, const lldwt_conv_desc* d, int64_t planes, int64_t batch, int64_t h, int64_t w_,
                  void* stream);
+/* Two independent stacks of grouped convs with the same per-group layer shapes, run as one grouped problem per layer (nlayers
+ * launches instead of 2 * nlayers): stack A's groups_a groups first, then stack B's.  descs[i] / packed[i] / bias[i] describe
+ * layer i of the MERGED problem (groups = groups_a + groups_b; packed and bias are stack A's per-plane block followed by stack
+ * B's; descs[i].act is applied as given).  xa (planes,batch,groups_a*cin_g,h,w) and xb (planes,batch,groups_b*cin_g,h,w) are
+ * the two inputs, ya / yb the two outputs of the last layer in the same manner; ws0 (ws0_floats) receives the even layers'
+ * outputs and ws1 (ws1_floats) the odd ones': each >= planes*batch*h*w * the widest layer it receives (the last layer writes ya / yb).  Every output is bit-identical to the one lldwt_conv2d
+ * gives for its stack alone.  Plain placement only (no upsample2 / transposed / ic_block / oc placement / epi).               */
+int lldwt_conv_stack_pair(const float* xa, const float* xb, float* ya, float* yb, const float* const* packed,
+                          const float* const* bias, const lldwt_conv_desc* descs, int nlayers, int groups_a, float* ws0,
+                          float* ws1, int64_t ws0_floats, int64_t ws1_floats, int64_t planes, int64_t batch, int64_t h, int64_t w_, void* stream);
 /* As lldwt_conv2d; additionally absmax_slots (planes,64), if not null, receives max |y| of each plane spread over 64
  * slots (the consumer takes their maximum): the activation scale of a following lldwt_conv3x3_f16x3, produced in the
  * epilogue instead of by a separate pass over y.                                                                  */
@@ -661,6 +671,10 @@ int lldwt_factorized_rate_bwd(const float* x, const float* eb, const float* nois
 /* sum((a-b)^2) and sum(x) into a double (graphs/losses/rate_dist.py:36-41). */
 int lldwt_sq_err_sum(const float* a, const float* b, int64_t n, double* out, void* stream);
 int lldwt_sum(const float* x, int64_t n, double* out, void* stream);
+/* 1 when the process runs the earlier launches of the small end-of-step work (LLDWT_TAIL=legacy, read when the library loads):
+ * the scalar sum kernel; the model then runs the coarsest level's two context stacks layer by layer with lldwt_conv2d instead of
+ * lldwt_conv_stack_pair (the entry itself works in either mode). */
+int lldwt_tail_legacy(void);
 /* out = alpha*a + beta*b elementwise (b optional): gradient glue of the loss (d mse = 2(xhat-x)/N). */
 int lldwt_axpby(const float* a, const float* b, float* out, int64_t n, float alpha, float beta, void* stream);
 
