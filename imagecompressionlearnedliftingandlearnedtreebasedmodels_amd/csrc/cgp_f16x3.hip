@@ -22,6 +22,8 @@
 // activations' bounds come from the wave's input maximum and the layers' max row L1 norms (fp16's exponent keeps the full
 // 22-bit split precision over 18 binades, so a loose bound costs nothing).
 // Output: params (planes, batch, 2*groups, h, w) = (sigma, mu) interleaved per subband, consumed by lldwt_gauss_rate.
+#include <stdlib.h>
+#include <string.h>
 #include "common.h"
 #include "split_f16.h"
 #include "lifting_f16.h"      // split_precision()
@@ -54,6 +56,11 @@ __device__ __forceinline__ float pow2_scale(float amax) {      // s = 2^k with a
     int k = 15 - e;
     k = k > 120 ? 120 : (k < -120 ? -120 : k);
     return ldexpf(1.f, k);
+}
+
+// base[elem] with the BYTE offset formed in 32 bits (elem < 2^30): scalar base + 32-bit lane offset, one address register per load
+__device__ __forceinline__ float ld_off32(const float* base, uint32_t elem) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (elem << 2));
 }
 
 // row of a 32x32 D tile held by (register q, lane half h)
@@ -164,11 +171,23 @@ struct Cgp16Args {
     // TRAIN: the hidden activations after LeakyReLU in the layout of the unfused convs, h1 (Z, groups*162, hw), h2 (Z, groups*54,
     // hw), h3 (Z, groups*18, hw): what lldwt_cgp_bwd_split gates with and the 1x1 weight-gradient GEMMs read
     float* h1; float* h2; float* h3;
+    // PERS: pairs = planes * groups; workgroup i of the grid serves pair ((i + 1) * pairs - 1) / gridDim.x (see k_cgp16)
+    int pairs;
 };
 #define CGP_STAMP(i)                                                                                                    \
-    if (a.stamps && lane == 0)                                                                                          \
-        a.stamps[(((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * a.cols + col) * 8 + (i)] =                           \
-            (i) >= 6 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
+    if constexpr (!PERS)                                                                                            \
+        if (a.stamps && lane == 0)                                                                                      \
+            a.stamps[(((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * a.cols + col) * 8 + (i)] =                       \
+                (i) >= 6 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
+// PERS: per wave [workgroup][wave][8] = start | end of the prologue | cycles summed over the wave's blocks: waiting for the inputs
+// (up to the split), layers 0 + 1, the rest | blocks | s_memrealtime at start, end
+#define CGP_PSTAMP(ACC)                                                                                                 \
+    if constexpr (PERS)                                                                                            \
+        if (a.stamps) {                                                                                                 \
+            const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                               \
+            ACC += now_ - t_last;                                                                                       \
+            t_last = now_;                                                                                              \
+        }
 
 // bias + LeakyReLU + rescale + split of one D tile into the two B fragments (k-steps 0 and 1) of the next layer.
 // The next layer's power-of-two scale commutes with LeakyReLU, so it is folded into the dequantisation factor and into the
@@ -207,94 +226,175 @@ __device__ __forceinline__ void next_frags(const floatx16& acc, float k, const f
 // WF: one wavefront step of the real entropy coder (see Cgp16Args): the pixel list is the step's anti-diagonal and the epilogue
 // turns (sigma, mu) into CDF index + symbol + dequantised value (LiftingBasedDWT_net.py:458-506: compress_ar's per-pixel work)
 // TRAIN: the training forward -- also writes the hidden activations (see Cgp16Args); always the fp32-accurate PREC 0
-template <int PREC, bool WF = false, bool TRAIN = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 : 3, TRAIN ? 2 : 3))) void k_cgp16(Cgp16Args a) {
+// PERS (whole-image eval only): the persistent form.  The streaming form (PERS 0) reads all NSTEP weight steps from L2 for every
+// 32-pixel block: 135 KB per block, the same 135 KB for every wave of a (plane, group).  Here a workgroup stays on its CU, is bound
+// to ONE (plane, group), copies that pair's weight steps into LDS once (141 KB, the pack's own layout: lane * 16 inside a 1 KB
+// fragment, so the chain's ds_read_b128 are conflict-free) and its waves stride over the pair's blocks of all images.  The chain per
+// block is the streaming one instruction for instruction -- same blocks (col * 32), same scales, same MFMA order, same bits.
+// 12 waves (three per SIMD); a block's inputs are loaded when the block starts.  A variant with 8 waves (two per SIMD, 256 registers)
+// that issued the NEXT block's 48 input loads before the current block's chain was measured and dropped: 901 / 233 / 67 us against
+// 883 / 233 / 74 us for levels 0 / 1 / 2 of configs[2] -- the third wave hides the input wait as well as the prefetch does.
+// DIAG (streaming form, lldwt_set_diagnostics: timing only, WRONG results): 1 = every step reads the weight fragments of step 0
+// (same instruction stream, L1-resident weights), 2 = the inputs are constants instead of loads.  Addresses: a subset of the real ones.
+template <int PREC, bool WF = false, bool TRAIN = false, bool PERS = false, int DIAG = 0>
+__global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 : 3, TRAIN ? 2 : 3))) void k_cgp16(Cgp16Args a) {
     // (TRAIN: two waves per SIMD -- the store addresses do not fit the 168 registers of three)
     static_assert(!TRAIN || (PREC == 0 && !WF), "the training forward runs the split-fp16 arithmetic on whole images");
+    static_assert(!PERS || (!WF && !TRAIN), "the persistent form is the whole-image eval chain");
+    static_assert(DIAG == 0 || (!PERS && PREC == 0 && !WF && !TRAIN), "the bound-only variants are of the streaming eval chain");
     constexpr int SB = PREC == 2 ? STEP_BYTES / 2 : STEP_BYTES;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int NW = PERS ? 12 : 4;                       // waves per workgroup
+    // (PERS: the wave number as a scalar, so that its block, image and the loads' base addresses are scalars too)
+    const int lane = threadIdx.x & 63, wave = PERS ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int h5 = lane >> 5, pl = lane & 31;
-    const int64_t z = blockIdx.z;
-    const int plane = (int)(z / a.batch), g = blockIdx.y;
-    const int col = blockIdx.x * 4 + wave;
     const int64_t hw = (int64_t)a.h * a.w;
+    int64_t z;
+    int plane, g, col;
+    int blk = 0, nblk = 0, bstride = 0;                          // PERS: this wave's block, the pair's blocks (batch * cols), the stride
+    if constexpr (!PERS) {
+        z = blockIdx.z;
+        plane = (int)(z / a.batch);
+        g = blockIdx.y;
+        col = blockIdx.x * 4 + wave;
+    } else {
+        // the grid's W workgroups are dealt to the pairs in proportion: pair p owns [p W / pairs, (p + 1) W / pairs), W >= pairs
+        const int W = gridDim.x, i = blockIdx.x;
+        const int pair = ((i + 1) * a.pairs - 1) / W;
+        const int first = pair * W / a.pairs, cnt = (pair + 1) * W / a.pairs - first;
+        plane = pair / a.groups;
+        g = pair - plane * a.groups;
+        nblk = a.batch * a.cols;
+        blk = (i - first) * NW + wave;
+        bstride = cnt * NW;
+        z = (int64_t)plane * a.batch;
+        col = 0;
+    }
+    unsigned long long t_last = 0, t_pro = 0, t_start = 0, rt_start = 0, t_in = 0, t_l01 = 0, t_rest = 0;   // PERS stamps (uniform)
+    int blocks_done = 0;
+    if constexpr (PERS)
+        if (a.stamps) { t_start = __builtin_amdgcn_s_memtime(); rt_start = __builtin_amdgcn_s_memrealtime(); }
     const uint8_t* grp = a.packed + ((int64_t)plane * a.groups + g) * GROUP_BYTES;
     const float* hdr = reinterpret_cast<const float*>(grp);
     __shared__ float sbias[320];                                 // header floats 64 .. 383: the four layers' biases
-    for (int i = threadIdx.x; i < 320; i += 256) sbias[i] = hdr[64 + i];
+    __shared__ uint4 swt[PERS ? (NSTEP + 3) * SB / 16 : 1]; // PERS: every weight step of the pair (+ the ring's 3 steps of padding)
+    for (int i = threadIdx.x; i < 320; i += NW * 64) sbias[i] = hdr[64 + i];
+    if constexpr (PERS) {
+        const uint4* src = reinterpret_cast<const uint4*>(grp + (PREC == 2 ? BF_OFF : HDR_FLOATS * 4));
+        constexpr int N16 = (NSTEP + 3) * SB / 16, NT = NW * 64;
+#pragma unroll
+        for (int i0 = 0; i0 < N16; i0 += 4 * NT) {               // four loads in flight per lane
+            uint4 t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                t[u] = src[min(i0 + u * NT + (int)threadIdx.x, N16 - 1)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u * NT + (int)threadIdx.x < N16) swt[i0 + u * NT + threadIdx.x] = t[u];
+        }
+    }
     __syncthreads();                                             // the only barrier: before any wave can leave
-    if (col >= a.cols) return;                                   // whole wave
+    if constexpr (!PERS) {
+        if (col >= a.cols) return;                               // whole wave
+    } else {
+        if (blk >= nblk) return;                                 // whole wave: a pair with fewer blocks than its share of waves
+        if (a.stamps) t_pro = t_last = __builtin_amdgcn_s_memtime();
+    }
     const float* bias0 = sbias, * bias1 = sbias + 192, * bias2 = sbias + 256, * bias3 = sbias + 288;
-    const uint8_t* wst = grp + (PREC == 2 ? BF_OFF : HDR_FLOATS * 4) + lane * 16;
+    const uint8_t* wst = (PERS ? reinterpret_cast<const uint8_t*>(swt) : grp + (PREC == 2 ? BF_OFF : HDR_FLOATS * 4)) + lane * 16;
+    // the header's scalars: the persistent loop reads them once (its stores to params could alias them for all the compiler knows)
+    float hs[12];
+    if constexpr (PERS) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) hs[i] = hdr[i];
+    }
+#define CGP_H(i) (PERS ? hs[i] : hdr[i])
     CGP_STAMP(0)
     CGP_STAMP(6)
 
     // ---- layer-0 B fragments straight from global memory
-    const float* plc = a.plc + (z * a.groups * CPLC + (int64_t)g * CPLC) * hw;
-    const float* xq = a.xq + (z * a.groups + g) * hw;
     const int R = a.K / 2;
     float xin[NB][NK0][8];
     int pix[NB];
     bool valid[NB];
     float amax = 0.f;
+    // the 48 loads per lane of block cc of image-plane zz
+    auto load_inputs = [&](int64_t zz, int cc, int (&pix_o)[NB], bool (&valid_o)[NB]) {
+        const float* plc = a.plc + (zz * a.groups * CPLC + (int64_t)g * CPLC) * hw;
+        const float* xq = a.xq + (zz * a.groups + g) * hw;
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        int pc, y, x;
-        if constexpr (WF) {
-            const int i = col * (32 * NB) + nb * 32 + pl;
-            valid[nb] = i < a.wf_n;
-            y = a.wf_y0 + (valid[nb] ? i : 0);
-            x = a.wf_t - a.wf_slope * y;
-            pc = y * a.w + x;
-        } else {
-            const int64_t p = (int64_t)col * (32 * NB) + nb * 32 + pl;
-            valid[nb] = p < hw;
-            pc = (int)(valid[nb] ? p : hw - 1);
-            y = pc / a.w;
-            x = pc - y * a.w;
-        }
-        pix[nb] = pc;
+        for (int nb = 0; nb < NB; ++nb) {
+            int pc, y, x;
+            if constexpr (WF) {
+                const int i = cc * (32 * NB) + nb * 32 + pl;
+                valid_o[nb] = i < a.wf_n;
+                y = a.wf_y0 + (valid_o[nb] ? i : 0);
+                x = a.wf_t - a.wf_slope * y;
+                pc = y * a.w + x;
+            } else {
+                const int64_t p = (int64_t)cc * (32 * NB) + nb * 32 + pl;
+                valid_o[nb] = p < hw;
+                pc = (int)(valid_o[nb] ? p : hw - 1);
+                y = pc / a.w;
+                x = pc - y * a.w;
+            }
+            pix_o[nb] = pc;
 #pragma unroll
-        for (int k = 0; k < NK0; ++k) {
+            for (int k = 0; k < NK0; ++k) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                // channel of this element: 16k + j for the lanes of half 0, 16k + 8 + j for half 1.  Both are compile-time
-                // constants per branch, so the tap tables are read with constant indexes (scalar loads, no scratch).
-                constexpr int dummy_ = 0;
-                (void)dummy_;
-                const int c_lo = 16 * k + j, c_hi = 16 * k + 8 + j;
-                float v = 0.f;
-                auto fetch = [&](int c) -> float {          // c is a constant at every call site after unrolling
-                    if (c < CPLC) return plc[(int64_t)c * hw + pc];
-                    if (c < C0) {
-                        const int yy = y + a.tap_dy[c - CPLC] - R, xx = x + a.tap_dx[c - CPLC] - R;
-                        return (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) ? xq[(int64_t)yy * a.w + xx] : 0.f;
+                for (int j = 0; j < 8; ++j) {
+                    // channel of this element: 16k + j for the lanes of half 0, 16k + 8 + j for half 1.  Both are compile-time
+                    // constants per branch, so the tap tables are read with constant indexes (scalar loads, no scratch).
+                    const int c_lo = 16 * k + j, c_hi = 16 * k + 8 + j;
+                    float v = 0.f;
+                    // PERS: scalar base (channel c of this image) + a 32-bit lane offset -- 81 h w < 2^31 elements (checked on the
+                    // host) keeps 9 h w * 4 bytes under 2^32 -- instead of a 64-bit address pair per load: 48 loads are in flight
+                    auto fetch = [&](int c) -> float {          // c is a constant at every call site after unrolling
+                        if (c < CPLC) {
+                            if constexpr (PERS) return ld_off32(plc + (int64_t)c * hw, (uint32_t)pc);
+                            else return plc[(int64_t)c * hw + pc];
+                        }
+                        if (c < C0) {
+                            const int yy = y + a.tap_dy[c - CPLC] - R, xx = x + a.tap_dx[c - CPLC] - R;
+                            const bool in = yy >= 0 && yy < a.h && xx >= 0 && xx < a.w;
+                            if constexpr (PERS) return in ? ld_off32(xq, (uint32_t)(yy * a.w + xx)) : 0.f;
+                            else return in ? xq[(int64_t)yy * a.w + xx] : 0.f;
+                        }
+                        return 0.f;
+                    };
+                    if constexpr (DIAG == 2) {                  // no loads: a constant of the inputs' size
+                        v = 0.25f * (float)((c_lo & 7) - 4);
+                    } else if (c_hi < CPLC) {                   // both halves: tree-context features (one load, runtime channel)
+                        if constexpr (PERS) v = ld_off32(plc + (int64_t)c_lo * hw, (uint32_t)(8 * h5) * (uint32_t)hw + (uint32_t)pc);
+                        else v = plc[(int64_t)(c_lo + 8 * h5) * hw + pc];
+                    } else if (h5 == 0) {
+                        v = fetch(c_lo);
+                    } else {
+                        v = fetch(c_hi);
                     }
-                    return 0.f;
-                };
-                if (c_hi < CPLC) {                          // both halves: tree-context features (one load, runtime channel)
-                    v = plc[(int64_t)(c_lo + 8 * h5) * hw + pc];
-                } else if (h5 == 0) {
-                    v = fetch(c_lo);
-                } else {
-                    v = fetch(c_hi);
+                    xin[nb][k][j] = v;
+                    amax = fmaxf(amax, fabsf(v));
                 }
-                xin[nb][k][j] = v;
-                amax = fmaxf(amax, fabsf(v));
             }
         }
+    };
+    if constexpr (PERS) {
+        z = (int64_t)plane * a.batch + blk / a.cols;
+        col = blk % a.cols;
     }
+  for (;;) {                                                     // PERS: over this wave's blocks; the streaming form runs it once
+    amax = 0.f;
+    load_inputs(z, col, pix, valid);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
     // ---- scales: input from its maximum, hidden layers from bounds |h_l| <= |h_{l-1}|max * L1max_l + |b_l|max
     CGP_STAMP(1)
     const float s_in = pow2_scale(amax);
-    const float bound0 = amax * hdr[4] + hdr[8];
-    const float bound1 = bound0 * hdr[5] + hdr[9];
-    const float bound2 = bound1 * hdr[6] + hdr[10];
+    const float bound0 = amax * CGP_H(4) + CGP_H(8);
+    const float bound1 = bound0 * CGP_H(5) + CGP_H(9);
+    const float bound2 = bound1 * CGP_H(6) + CGP_H(10);
     const float s1 = pow2_scale(bound0), s2 = pow2_scale(bound1), s3 = pow2_scale(bound2);
-    const float inv0 = (1.f / s_in) * (1.f / hdr[0]), inv1 = (1.f / s1) * (1.f / hdr[1]);
-    const float inv2 = (1.f / s2) * (1.f / hdr[2]), inv3 = (1.f / s3) * (1.f / hdr[3]);
+    const float inv0 = (1.f / s_in) * (1.f / CGP_H(0)), inv1 = (1.f / s1) * (1.f / CGP_H(1));
+    const float inv2 = (1.f / s2) * (1.f / CGP_H(2)), inv3 = (1.f / s3) * (1.f / CGP_H(3));
     half8 b0h[NB][NK0], b0l[NB][NK0];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
@@ -306,28 +406,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 :
             if constexpr (PREC == 0) split8v(v, b0h[nb][k], b0l[nb][k]);
             else b0h[nb][k] = cvt8<PREC>(v);
         }
-
-    // ---- weight stream: ring of 4 steps
-    half8 ah[4], al[4];
+    CGP_PSTAMP(t_in)
+    // ---- weight stream (PERS: from LDS): ring of 4 steps
+    constexpr int WS = DIAG == 1 ? 0 : SB;                       // DIAG 1: step 0's fragments at every step
+    // ring depth, RD - 1 steps ahead.  LDS latency needs less than L2's: two steps, and one where the three products of a step
+    // (96 matrix cycles) and the 168 registers of three waves per SIMD meet -- with 3 the loop spills
+    constexpr int RD = !PERS ? 4 : PREC == 0 ? 2 : 3;
+    half8 ah[RD], al[RD];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        ah[i] = *reinterpret_cast<const half8*>(wst + i * SB);
-        if constexpr (PREC == 0) al[i] = *reinterpret_cast<const half8*>(wst + i * SB + 1024);
+    for (int i = 0; i < RD - 1; ++i) {
+        ah[i] = *reinterpret_cast<const half8*>(wst + i * WS);
+        if constexpr (PREC == 0) al[i] = *reinterpret_cast<const half8*>(wst + i * WS + 1024);
     }
     int step = 0;
 #define CGP16_NEXT()                                                                                  \
     {                                                                                                 \
-        ah[(step + 3) & 3] = *reinterpret_cast<const half8*>(wst + (step + 3) * SB);                  \
-        if constexpr (PREC == 0) al[(step + 3) & 3] = *reinterpret_cast<const half8*>(wst + (step + 3) * SB + 1024); \
+        ah[(step + RD - 1) % RD] = *reinterpret_cast<const half8*>(wst + (step + RD - 1) * WS);       \
+        if constexpr (PREC == 0) al[(step + RD - 1) % RD] = *reinterpret_cast<const half8*>(wst + (step + RD - 1) * WS + 1024); \
         __builtin_amdgcn_sched_barrier(0);   /* the scheduler otherwise sinks these loads down to their use (3 steps later) */ \
     }
 #define CGP16_MMA(ACC, BH, BL)                                                                        \
     {                                                                                                 \
         if constexpr (PREC == 0) {                                                                    \
-            ACC = mma32<0>(al[step & 3], BH, ACC);                                                    \
-            ACC = mma32<0>(ah[step & 3], BL, ACC);                                                    \
+            ACC = mma32<0>(al[step % RD], BH, ACC);                                                   \
+            ACC = mma32<0>(ah[step % RD], BL, ACC);                                                   \
         }                                                                                             \
-        ACC = mma32<PREC>(ah[step & 3], BH, ACC);                                                     \
+        ACC = mma32<PREC>(ah[step % RD], BH, ACC);                                                    \
     }
 
     floatx16 acc1[NB][NM1];
@@ -376,6 +480,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 :
             }
     }
     CGP_STAMP(2)
+    CGP_PSTAMP(t_l01)
     // ---- layer 2 (54 -> 18)
     floatx16 acc2[NB];
 #pragma unroll
@@ -470,8 +575,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 :
     }
     CGP_STAMP(5)
     CGP_STAMP(7)
+    CGP_PSTAMP(t_rest)
+    if constexpr (!PERS) {
+        break;
+    } else {
+        ++blocks_done;
+        blk += bstride;
+        if (blk >= nblk) break;
+        z = (int64_t)plane * a.batch + blk / a.cols;
+        col = blk % a.cols;
+    }
+  }
+    if constexpr (PERS)
+        if (a.stamps && lane == 0) {
+            unsigned long long* st = a.stamps + ((int64_t)blockIdx.x * NW + wave) * 8;
+            st[0] = t_start; st[1] = t_pro; st[2] = t_in; st[3] = t_l01; st[4] = t_rest; st[5] = (unsigned long long)blocks_done;
+            st[6] = rt_start; st[7] = __builtin_amdgcn_s_memrealtime();
+        }
 }
 #undef CGP_STAMP
+#undef CGP_PSTAMP
+#undef CGP_H
 
 
 // ================================================================================================================
@@ -726,6 +850,16 @@ static unsigned long long* g_cgp_stamps = nullptr;
 static int64_t g_cgp_stamps_bytes = 0;
 namespace lldwt { void cgp16_set_stamps(void* p, int64_t nbytes) { g_cgp_stamps = reinterpret_cast<unsigned long long*>(p); g_cgp_stamps_bytes = p ? nbytes : 0; } }
 
+// Form of the whole-image eval chain (lldwt_cgp16_params): the persistent kernel, or the streaming one with LLDWT_CGP16=stream
+// (read when the library loads; kept for A/B timing and as the reference of the bit-equality test).  The wavefront step and the
+// training forward always stream: their pixel lists are short, or they store activations.
+static const int g_cgp16_stream = [] { const char* e = getenv("LLDWT_CGP16"); return (e && !strcmp(e, "stream")) ? 1 : 0; }();
+// diagnostics (lldwt_set_diagnostics kind 2 flags; tools and tests only): bits 0-1 = bound-only variant of the streaming form
+// (k_cgp16 DIAG: 1 = step 0's weights at every step, 2 = constant inputs; WRONG results), bits 2-3 = force a form
+// (1 = streaming, 2 = persistent) whatever the size
+static int g_cgp16_dbg = 0;
+namespace lldwt { void cgp16_set_debug(int flags) { g_cgp16_dbg = flags; } }
+
 extern "C" int64_t lldwt_cgp16_packed_bytes(int c0, int c1, int c2, int c3, int groups) {
     if (c0 != C0 || c1 != C1 || c2 != C2 || c3 != C3 || groups <= 0) return -1;     // the reference's dimensions only
     return (int64_t)groups * GROUP_BYTES;
@@ -743,6 +877,11 @@ extern "C" int lldwt_cgp16_pack(const float* w0, const float* b0, const float* w
 
 static int cgp16_params_impl(const float* plc, const float* xq, const void* packed, float* params, float* h1, float* h2, float* h3,
                              int64_t planes, int64_t batch, int64_t h, int64_t w_, int groups, int K, uint32_t tap_mask, void* stream);
+// The least number of 32-pixel blocks (all pairs together) for which the persistent form is chosen over the streaming one.  Measured
+// on MI355X (tools/bench_cgp.py, 3 planes x 8 images x 3 groups, us per launch, streaming / persistent): 256^2 = 147 456 blocks
+// 1099 / 883, 128^2 = 36 864 blocks 284 / 233, 64^2 = 9 216 blocks 69.7 / 73.5 -- at 36 blocks per CU the 141 KB prologue
+// (every workgroup of the chip fetching its pair's weights at once) is no longer paid back.
+constexpr int64_t CGP16_PERS_MIN_BLOCKS = 20000;
 
 extern "C" int lldwt_cgp16_params(const float* plc, const float* xq, const void* packed, float* params, int64_t planes,
                                   int64_t batch, int64_t h, int64_t w_, int groups, int K, uint32_t tap_mask, void* stream) {
@@ -780,13 +919,39 @@ static int cgp16_params_impl(const float* plc, const float* xq, const void* pack
     LLDWT_REQUIRE(n == C0 - CPLC, "cgp16_params: %d live taps, the folded first layer expects %d", n, C0 - CPLC);
     a.ntaps = n;
     a.cols = (int)cdiv(h * w_, 32 * NB);
+    const int prec = split_precision();
+    const int64_t pairs = planes * groups, nblk = batch * a.cols;        // blocks of one (plane, group)
+    const int diag = g_cgp16_dbg & 3, force = (g_cgp16_dbg >> 2) & 3;
+    bool pers = false;                                                   // k_cgp16's PERS
+    if (!h1 && !diag && pairs <= 4096 && nblk < ((int64_t)1 << 30)) {    // (the kernel's 32-bit block and workgroup arithmetic)
+        if (force) pers = force == 2;
+        else pers = !g_cgp16_stream && pairs * nblk >= CGP16_PERS_MIN_BLOCKS;
+    }
+    if (pers) {
+        // one workgroup per CU (LDS: 141 KB), dealt to the pairs in proportion; never more than a pair has blocks for, never
+        // fewer than one per pair (a chip with fewer CUs than pairs runs them in rounds)
+        const int nw = 12;
+        int64_t wgs = lldwt_num_cus();
+        if (wgs > pairs * cdiv(nblk, nw)) wgs = pairs * cdiv(nblk, nw);
+        if (wgs < pairs) wgs = pairs;
+        a.pairs = (int)pairs;
+        const int64_t need = wgs * nw * 8 * 8;
+        a.stamps = (g_cgp_stamps && g_cgp_stamps_bytes >= need) ? g_cgp_stamps : nullptr;
+        dim3 grid((unsigned)wgs);
+        if (prec == 1) hipLaunchKernelGGL((k_cgp16<1, false, false, true>), grid, dim3(768), 0, (hipStream_t)stream, a);
+        else if (prec == 2) hipLaunchKernelGGL((k_cgp16<2, false, false, true>), grid, dim3(768), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((k_cgp16<0, false, false, true>), grid, dim3(768), 0, (hipStream_t)stream, a);
+        return check_launch("cgp16_params");
+    }
+    a.pairs = 0;
     {   // diagnostics (tools/cgp_stamps.py, lldwt_set_diagnostics): only when the registered buffer holds this grid's stamps
         const int64_t need = (int64_t)planes * batch * groups * a.cols * 8 * 8;
         a.stamps = (g_cgp_stamps && g_cgp_stamps_bytes >= need) ? g_cgp_stamps : nullptr;
     }
     dim3 grid((unsigned)cdiv(a.cols, 4), (unsigned)groups, (unsigned)(planes * batch));
-    const int prec = split_precision();
     if (h1) hipLaunchKernelGGL((k_cgp16<0, false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (diag == 1 && prec == 0) hipLaunchKernelGGL((k_cgp16<0, false, false, false, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (diag == 2 && prec == 0) hipLaunchKernelGGL((k_cgp16<0, false, false, false, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else if (prec == 1) hipLaunchKernelGGL((k_cgp16<1, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else if (prec == 2) hipLaunchKernelGGL((k_cgp16<2, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((k_cgp16<0, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -842,6 +1007,7 @@ extern "C" int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const f
     a.wf_y = y; a.wf_yhat = yhat; a.wf_table = table63; a.wf_idx = idx; a.wf_sym = sym; a.wf_mu = mu; a.wf_ntot = ntot; a.wf_off = off;
     a.cols = (int)cdiv(a.wf_n, 32 * NB);
     a.stamps = nullptr;
+    a.pairs = 0;
     dim3 grid((unsigned)cdiv(a.cols, 4), (unsigned)groups, (unsigned)(planes * batch));
     // always the fp32-accurate arithmetic: encoder and decoder must agree bit for bit whatever the precision mode of the process
     hipLaunchKernelGGL((k_cgp16<0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);

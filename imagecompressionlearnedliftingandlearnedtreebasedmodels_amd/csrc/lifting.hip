@@ -1506,6 +1506,8 @@ extern "C" int lldwt_set_precision(int prec) {
 }
 extern "C" int lldwt_get_precision(void) { return split_precision(); }
 
+namespace lldwt { void cgp16_set_debug(int flags); }    // cgp_f16x3.hip: bound-only variants / forced form of the eval chain
+
 extern "C" int lldwt_set_diagnostics(int kind, void* stamps, int64_t nbytes, int flags) {
     LLDWT_REQUIRE(kind >= 0 && kind <= 2, "set_diagnostics: kind %d (0 = fused lifting step, 1 = tree-pair conv, 2 = cgp chain)", kind);
     LLDWT_REQUIRE(nbytes >= 0 && (stamps != nullptr || nbytes == 0), "set_diagnostics: bad buffer");
@@ -1516,6 +1518,7 @@ extern "C" int lldwt_set_diagnostics(int kind, void* stamps, int64_t nbytes, int
         f3_set_stamps(stamps, nbytes);
     } else {
         cgp16_set_stamps(stamps, nbytes);
+        cgp16_set_debug(flags);
     }
     return LLDWT_OK;
 }

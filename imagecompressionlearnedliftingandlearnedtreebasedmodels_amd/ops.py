@@ -54,7 +54,8 @@ _diag_keep = {}
 
 def set_diagnostics(kind, stamps=None, flags=0):
     """Diagnostics hook of the split-fp16 kernels (lldwt_set_diagnostics; tools/*_stamps.py and the composed-vs-sequential
-    tests only): kind 0 = fused lifting step (flags = its debug mask), 1 = tree-pair conv, 2 = cgp chain.  ``stamps``: an
+    tests only): kind 0 = fused lifting step (flags = its debug mask), 1 = tree-pair conv, 2 = cgp chain (flags: bound-only variant /
+    forced form of cgp16_params, include/lldwt.h).  ``stamps``: an
     int64 device tensor the kernels write s_memtime stamps into (kept alive here until it is replaced), None = off."""
     _diag_keep[kind] = stamps
     ptr = C.c_void_p(stamps.data_ptr()) if stamps is not None else C.c_void_p(0)

@@ -123,9 +123,13 @@ int lldwt_get_precision(void);
 /* Diagnostics hook of the three split-fp16 kernel families (tools/lift_stamps.py, plc_stamps.py, cgp_stamps.py; the
  * product never calls it).  kind 0 = fused lifting step, 1 = tree-pair conv, 2 = cgp chain.  stamps / nbytes: a device
  * buffer the kernels of that kind write s_memtime stamps into (null = off); a launch whose stamps would not fit in
- * nbytes ignores the buffer.  flags (kind 0 only): debug mask -- bit 0..3 skip a phase (results are then wrong),
+ * nbytes ignores the buffer.  flags, kind 0: debug mask -- bit 0..3 skip a phase (results are then wrong),
  * 16 = sequential conv3 / conv4 for every tile (the check of the composed 9x9 kernel), 32 = no vertical reuse
- * between the tiles of a column.  The caller keeps the buffer alive until it unregisters it.                      */
+ * between the tiles of a column.  flags, kind 2 (lldwt_cgp16_params only): bits 0-1 = bound-only variant of the streaming
+ * chain, timing only (1 = every step reads step 0's weight fragments, 2 = constant inputs; results are then wrong),
+ * bits 2-3 = force a form whatever the size (1 << 2 = streaming, 2 << 2 = persistent; 0 = the dispatch's choice, which
+ * LLDWT_CGP16=stream, read when the library loads, pins to streaming).
+ * The caller keeps the buffer alive until it unregisters it.                                                       */
 int lldwt_set_diagnostics(int kind, void* stamps, int64_t nbytes, int flags);
 int lldwt_get_lift_mode(void);
 /* 1 when the TRAINING forward of the lifting steps (lldwt_lifting_forward_train / _inverse_train, C = 16, K = 5, tanh blocks)
