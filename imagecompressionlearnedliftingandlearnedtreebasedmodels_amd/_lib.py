@@ -186,6 +186,9 @@ SIGNATURES = {
     "lldwt_cdf97_inverse": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i, _p, _i64, _p]),
     "lldwt_cdf97_forward_ex": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i, _i, _p, _i64, _p]),
     "lldwt_cdf97_inverse_ex": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i, _i, _p, _i64, _p]),
+    "lldwt_msssim_ws_floats": (_i64, [_i64, _i64, _i64, _i]),
+    "lldwt_msssim_forward": (_i, [_p, _p, _f, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p]),
+    "lldwt_msssim_backward": (_i, [_p, _p, _f, _i64, _i64, _i64, _i, _p, _p, _p, C.c_double, _p, _p, _p]),
 }
 
 _lib = None

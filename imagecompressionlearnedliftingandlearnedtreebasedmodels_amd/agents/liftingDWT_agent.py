@@ -4,6 +4,7 @@ Same class name, constructor signature and method set as the reference agent (:1
 ``"agent": "LiftingBasedDWTAgent"`` resolves to it (main.py:30).  ``batch_forward`` is the forward half of
 ``train_one_epoch`` (:84-96) / ``validate`` (:171-183): RGB->YCbCr, Y-0.5, model, +0.5, YCbCr->RGB, -0.5, forward3.
 """
+import math
 import os
 
 import torch
@@ -55,8 +56,10 @@ class LiftingBasedDWTAgent(BaseAgent):
         self.lambda_ = config.lambda_
         self.loss_switch_thr = config.loss_switch_thr
         self.training_loss_switch = config.training_loss_switch
-        self.train_loss = TrainDLoss(config.lambda_) if self.training_loss_switch == 0 else TrainRDLoss(config.lambda_)
-        self.valid_loss = TrainRDLoss(config.lambda_)
+        self.distortion = config.get("distortion", "mse")
+        self.report_msssim = bool(config.get("report_msssim", False)) or self.distortion == "ms-ssim"
+        self.train_loss = (TrainDLoss if self.training_loss_switch == 0 else TrainRDLoss)(config.lambda_, self.distortion)
+        self.valid_loss = TrainRDLoss(config.lambda_, self.distortion)
         self.train_logger, self.trnit_logger = RDLogger(), RDLogger()
         self.aux_logger, self.valid_logger, self.test_logger = RDLogger(), RDLogger(), RDLogger()
         self._bucket = None
@@ -66,6 +69,19 @@ class LiftingBasedDWTAgent(BaseAgent):
         elif config.get("resume_training") and "checkpoint_dir" in config:
             self.load_checkpoint(config.checkpoint_file)                         # :68-69
         self.model_size_estimation()                                             # :73
+
+    def _batch_msssim(self, x, xhat, loss_fn=None):
+        """Mean MS-SSIM of one batch: x (B,3,H,W) in [0,1], xhat the reconstruction in [-0.5, 0.5]."""
+        if loss_fn is not None and loss_fn.distortion == "ms-ssim":
+            return float(loss_fn.msssim)                                        # the loss has just computed it
+        return float(ops.ms_ssim((x - 0.5).contiguous(), xhat.contiguous()).mean())
+
+    def _msssim_line(self, vals):
+        """Mean over batches and ranks (like PSNR), printed with its dB form -10 log10(1 - m)."""
+        ms, = parallel.mean_over_ranks([float(torch.tensor(vals).mean()) if vals else 0.0], self.device)
+        db = float("inf") if ms >= 1.0 else -10.0 * math.log10(1.0 - ms)
+        print(" avg_msssim = %.4f, msssim_db = %.2f" % (ms, db))
+        return ms
 
     def batch_forward(self, x, loss_fn, clamp=False):
         """x (B,3,H,W) RGB in [0,1] -> (loss, mse, rate1, rate2, xhat)."""
@@ -131,7 +147,7 @@ class LiftingBasedDWTAgent(BaseAgent):
                 _, trnit_mse, _, _ = self.trnit_logger.display(lr=self.optimizer.param_groups[0]["lr"], typ="it")
                 trnit_mse, = parallel.mean_over_ranks([trnit_mse], self.device)
                 if trnit_mse < self.loss_switch_thr and self.training_loss_switch == 0:     # :104-109
-                    self.train_loss = TrainRDLoss(self.lambda_)
+                    self.train_loss = TrainRDLoss(self.lambda_, self.distortion)
                     print("Switching training loss to Rate+lambda*Distortion (it was only lambda*Distortion up to here)")
                     self.training_loss_switch = 1
         train_rd_loss, _, _, _ = self.train_logger.display(lr=self.optimizer.param_groups[0]["lr"], typ="tr")
@@ -153,6 +169,7 @@ class LiftingBasedDWTAgent(BaseAgent):
         xs = (x - 0.5).contiguous()
         if not train:
             xhat = xhat.clamp(-0.5, 0.5)
+            self._pp_xhat = xhat
             return self.valid_loss.forward3(xs, xhat.contiguous(), si_xe, si_xo)
         return self.train_loss.forward3_train(xs, xhat.contiguous(), si_xe, si_xo)
 
@@ -192,10 +209,12 @@ class LiftingBasedDWTAgent(BaseAgent):
         """agents/liftingDWT_agent.py:203-250."""
         self.model.eval()
         self.postprocess.eval()
-        psnr, r1s, r2s = [], [], []
+        psnr, r1s, r2s, mss = [], [], [], []
         for x in self.data_loader.valid_loader:
             x = x.to(self.device)
             loss, mse, r1, r2 = self._postprocess_batch(x, False)
+            if self.report_msssim:
+                mss.append(self._batch_msssim(x, self._pp_xhat, self.valid_loss))
             self.valid_logger(loss.item(), mse.item(), r1.item(), r2.item())
             psnr.append(10.0 * torch.log10(1.0 / torch.tensor(mse.item())))
             r1s.append(r1.item())
@@ -204,16 +223,20 @@ class LiftingBasedDWTAgent(BaseAgent):
         m = lambda v: float(torch.tensor(v).mean()) if v else 0.0
         valid_rd_loss, ps, a1, a2 = parallel.mean_over_ranks([valid_rd_loss, m(psnr), m(r1s), m(r2s)], self.device)
         print(" avg_psnr = %.2f, rate_1 = %g, rate_2 = %g, total_rate = %g" % (ps, a1, a2, a1 + a2))
+        if self.report_msssim:
+            self._msssim_line(mss)
         return valid_rd_loss
 
     @torch.no_grad()
     def validate(self):
         """agents/liftingDWT_agent.py:155-201."""
         self.model.eval()
-        psnr, r1s, r2s = [], [], []
+        psnr, r1s, r2s, mss = [], [], [], []
         for x in self.data_loader.valid_loader:
             x = x.to(self.device)
-            loss, mse, r1, r2, _ = self.batch_forward(x, self.valid_loss, clamp=True)
+            loss, mse, r1, r2, xhat = self.batch_forward(x, self.valid_loss, clamp=True)
+            if self.report_msssim:
+                mss.append(self._batch_msssim(x, xhat, self.valid_loss))
             self.valid_logger(loss.item(), mse.item(), r1.item(), r2.item())
             psnr.append(10.0 * torch.log10(1.0 / torch.tensor(mse.item())))
             r1s.append(r1.item())
@@ -223,6 +246,8 @@ class LiftingBasedDWTAgent(BaseAgent):
         # mean over ranks: is_best / best_valid_loss (agents/base.py:161-164) must agree on every replica
         valid_rd_loss, ps, a1, a2 = parallel.mean_over_ranks([valid_rd_loss, m(psnr), m(r1s), m(r2s)], self.device)
         print(" avg_psnr = %.2f, rate_1 = %g, rate_2 = %g, total_rate = %g" % (ps, a1, a2, a1 + a2))
+        if self.report_msssim:
+            self._msssim_line(mss)
         return valid_rd_loss
 
     def model_size_estimation(self, print_params=False):
@@ -250,7 +275,7 @@ class LiftingBasedDWTAgent(BaseAgent):
         """agents/liftingDWT_agent.py:262-311: real entropy coding of the test set -- compress (range-ANS streams),
         decompress FROM the streams, PSNR of the reconstruction, bits per pixel from the stream lengths."""
         self.model.eval()
-        psnr, r_hi, r_lo = [], [], []
+        psnr, r_hi, r_lo, mss = [], [], [], []
         for x in self.data_loader.test_loader:
             x = x.to(self.device)
             if self.clrch != 1:
@@ -266,12 +291,16 @@ class LiftingBasedDWTAgent(BaseAgent):
                 xs = (x - 0.5).contiguous()
             mse = float(torch.mean((xs - xhat.clamp(-0.5, 0.5)) ** 2))
             psnr.append(10.0 * torch.log10(1.0 / torch.tensor(mse)))
+            if self.report_msssim:
+                mss.append(self._batch_msssim(x, xhat.clamp(-0.5, 0.5)))
             r_hi.append(byte_xo)
             r_lo.append(byte_xe)
         m = lambda v: float(torch.tensor(v).mean()) if v else 0.0
         ps, hi, lo = parallel.mean_over_ranks([m(psnr), m(r_hi), m(r_lo)], self.device)
         print(" avg_psnr = %.2f, rate_high = %g, rate_low = %g, total_rate = %g" % (ps, hi, lo, hi + lo))
         self.test_result = {"psnr": ps, "rate_high": hi, "rate_low": lo}
+        if self.report_msssim:
+            self.test_result["msssim"] = self._msssim_line(mss)
         return True
 
 

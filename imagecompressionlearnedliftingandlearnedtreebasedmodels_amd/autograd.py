@@ -362,6 +362,30 @@ class SqErrSumFn(torch.autograd.Function):
         return None, ops.axpby(b.contiguous(), a.contiguous(), 2.0, -2.0).mul_(g.to(torch.float32))
 
 
+class MsSsimFn(torch.autograd.Function):
+    """mean over (B,C) of MS-SSIM(x, y) as a 1-element float64 tensor (lldwt_msssim_forward); the gradient goes to y only
+    (x is the target) and is recomputed from x, y and the pooled pyramid by lldwt_msssim_backward."""
+
+    @staticmethod
+    def forward(ctx, x, y, *opts):
+        # opts: (offset=0.5, scales=5); variadic because autograd wants one gradient per argument actually passed to apply()
+        offset = opts[0] if len(opts) > 0 else 0.5
+        scales = opts[1] if len(opts) > 1 else 5
+        x, y = x.contiguous(), y.contiguous()
+        _, m, coef, pyr = ops.ms_ssim_forward(x, y, offset, scales)
+        ctx.save_for_backward(x, y, pyr, coef)
+        ctx.cfg = (offset, scales, len(opts))
+        return m.mean().reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, pyr, coef = ctx.saved_tensors
+        offset, scales, nopts = ctx.cfg
+        g = g.to(torch.float64).contiguous()          # stays on the device: no host synchronisation
+        grad = ops.ms_ssim_backward(x, y, pyr, coef, g, 1.0 / (x.shape[0] * x.shape[1]), offset, scales)
+        return (None, grad) + (None,) * nopts
+
+
 # ------------------------------------------------------------------------------------------------ lifting transform
 _BUF_X, _BUF_LROW, _BUF_HROW, _BUF_TMPL, _BUF_TMPH, _BUF_LL0, _BUF_LL1, _BUF_LL, _BUF_YH0 = range(9)
 

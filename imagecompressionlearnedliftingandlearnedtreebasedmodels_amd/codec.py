@@ -406,6 +406,45 @@ def _check_images(images_u8):
     return B, H, W
 
 
+def msssim_db(m):
+    """MS-SSIM in decibels, -10 log10(1 - m); inf for m >= 1, None for None."""
+    import math
+    if m is None:
+        return None
+    return float("inf") if m >= 1.0 else -10.0 * math.log10(1.0 - m)
+
+
+def quality(a_u8, b_u8):
+    """PSNR and MS-SSIM of image pairs: (B,H,W,3) or (H,W,3) uint8 RGB tensors of one shape, on the host or the device.
+    -> {"psnr": ..., "msssim": ...} with one Python float per image (lists for a batch, plain values for a single (H,W,3)
+    pair).  PSNR is 10 log10(1 / mse) on values in [0,1] over the three channels, inf for identical images; MS-SSIM is the
+    mean over the channels (ops.ms_ssim, five scales), None when a side is below its minimum of 161."""
+    import math
+    import torch
+    from . import ops
+    single = isinstance(a_u8, torch.Tensor) and a_u8.dim() == 3
+    if single:
+        a_u8, b_u8 = a_u8[None], (b_u8[None] if isinstance(b_u8, torch.Tensor) and b_u8.dim() == 3 else b_u8)
+    B, H, W = _check_images(a_u8)
+    _check_images(b_u8)
+    if tuple(a_u8.shape) != tuple(b_u8.shape):
+        raise ValueError("quality: the images differ in shape: %s and %s" % (tuple(a_u8.shape), tuple(b_u8.shape)))
+    dev = a_u8.device if a_u8.is_cuda else (b_u8.device if b_u8.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    a = ops.u8hwc_to_f32chw(a_u8.to(dev).contiguous())                                # (B,3,H,W) in [0,1]
+    b = ops.u8hwc_to_f32chw(b_u8.to(dev).contiguous())
+    sq = torch.zeros(B, dtype=torch.float64, device=dev)
+    for i in range(B):
+        ops.sq_err_sum(a[i], b[i], sq[i:i + 1])
+    ms = None
+    if min(H, W) >= ops.ms_ssim_min_side(5):
+        ms = ops.ms_ssim(a, b, offset=0.0).mean(1).tolist()
+    psnr = [float("inf") if e == 0.0 else 10.0 * math.log10(3.0 * H * W / e) for e in sq.tolist()]
+    msssim = ms if ms is not None else [None] * B
+    if single:
+        return {"psnr": psnr[0], "msssim": msssim[0]}
+    return {"psnr": psnr, "msssim": msssim}
+
+
 def encode_images(net, images_u8, coder="host"):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string)."""

@@ -988,6 +988,74 @@ def factorized_rate(x, eb, noise=None, bit_sum=None):
     return bits, q
 
 
+# ------------------------------------------------------------------------------------------------ MS-SSIM
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def ms_ssim_min_side(scales=5):
+    """Smallest legal side: the coarsest scale must still hold one 11 x 11 window."""
+    return 10 * 2 ** (scales - 1) + 1
+
+
+def _ms_ssim_check(x, y, scales):
+    """Shape rules of MS-SSIM, raised as ValueError on the host before the library is touched."""
+    if not (isinstance(scales, int) and 1 <= scales <= len(MS_SSIM_WEIGHTS)):
+        raise ValueError("ms_ssim: scales must be an integer in 1..%d (got %r)" % (len(MS_SSIM_WEIGHTS), scales))
+    if x.dim() != 4 or tuple(x.shape) != tuple(y.shape):
+        raise ValueError("ms_ssim: x and y must be (B,C,H,W) of one shape (got %s and %s)" % (tuple(x.shape), tuple(y.shape)))
+    need = ms_ssim_min_side(scales)
+    for name, side in (("height", x.shape[2]), ("width", x.shape[3])):
+        if side < need:
+            raise ValueError("ms_ssim: %s %d is below the minimum side %d for %d scale(s)" % (name, side, need, scales))
+    if x.shape[0] * x.shape[1] < 1 or x.shape[0] * x.shape[1] > 65535:
+        raise ValueError("ms_ssim: B*C must be in 1..65535 (got %d)" % (x.shape[0] * x.shape[1]))
+
+
+def ms_ssim_forward(x, y, offset=0.5, scales=5):
+    """One fused launch per scale (lldwt_msssim_forward).  x: target, y: reconstruction, (B,C,H,W) fp32; ``offset`` is added
+    to both on load.  Returns (v (S,B,C), m (B,C), coef (S,B,C), pyr): float64 terms and values, and what the backward needs."""
+    _ms_ssim_check(x, y, scales)
+    lib = _lib.load()
+    B, Cn, H, W = x.shape
+    planes = B * Cn
+    dev = x.device
+    pyr = torch.empty(max(1, lib.lldwt_msssim_ws_floats(planes, H, W, scales)), dtype=torch.float32, device=dev)
+    sums = torch.empty(scales, planes, 2, dtype=torch.float64, device=dev)
+    v = torch.empty(scales, B, Cn, dtype=torch.float64, device=dev)
+    m = torch.empty(B, Cn, dtype=torch.float64, device=dev)
+    coef = torch.empty(scales, B, Cn, dtype=torch.float64, device=dev)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+    check(lib.lldwt_msssim_forward(_chk(x, "x"), _chk(y, "y"), float(offset), planes, H, W, scales, dp(pyr), dp(sums), dp(v), dp(m),
+                                   dp(coef), _stream()), "msssim_forward")
+    return v, m, coef, pyr
+
+
+def ms_ssim_terms(x, y, offset=0.5, scales=5):
+    """v (S,B,C) float64: the clamped spatial mean of cs per scale, of l*cs for the last one."""
+    return ms_ssim_forward(x, y, offset, scales)[0]
+
+
+def ms_ssim(x, y, offset=0.5, scales=5):
+    """MS-SSIM per image and channel, (B,C) float64 on the device (pytorch-msssim 0.2.1 with data_range 1)."""
+    return ms_ssim_forward(x, y, offset, scales)[1]
+
+
+def ms_ssim_backward(x, y, pyr, coef, g, gscale, offset=0.5, scales=5):
+    """grad_y of gscale * g[0] * sum(m) (lldwt_msssim_backward); g: 1-element float64 DEVICE tensor or None."""
+    lib = _lib.load()
+    B, Cn, H, W = x.shape
+    planes = B * Cn
+    grad = torch.empty_like(y)
+    gpyr = torch.empty(max(1, lib.lldwt_msssim_ws_floats(planes, H, W, scales) // 2), dtype=torch.float32, device=x.device)
+    if g is not None and not (g.is_cuda and g.dtype == torch.float64 and g.numel() == 1):
+        raise _lib.LLDWTError("ms_ssim_backward: g must be a 1-element float64 device tensor")
+    dp = lambda t: C.c_void_p(t.data_ptr())
+    check(lib.lldwt_msssim_backward(_chk(x, "x"), _chk(y, "y"), float(offset), planes, H, W, scales, dp(pyr), dp(coef),
+                                    dp(g) if g is not None else C.c_void_p(0), float(gscale), dp(gpyr), _chk(grad), _stream()),
+          "msssim_backward")
+    return grad
+
+
 def sq_err_sum(a, b, out):
     check(_lib.load().lldwt_sq_err_sum(_chk(a), _chk(b), a.numel(), C.c_void_p(out.data_ptr()), _stream()), "sq_err_sum")
 

@@ -22,7 +22,10 @@ DEFAULTS = dict(  # hot-path keys of liftingDWT.json:5-44
     autoencoder="SubbandAutoEncoder", dwtlevels=4, num_lifting_perlayer=2, filtersize=5, block_property="same", scale=0,
     linearity_flag=1, depth_scale=2, res_connection_weight=0.1, batch_size=4, patch_size=256, grad_acc_iters=1,
     loss_prnt_iters=3600, learning_rate=1e-4, lambda_=11700, loss_switch_thr=0.0015, training_loss_switch=1,
-    max_epoch=1, postprocess="none", checkpoint_file="checkpoint.pth.tar")
+    max_epoch=1, postprocess="none", checkpoint_file="checkpoint.pth.tar",
+    # distortion term of the training loss: "mse" or "ms-ssim" (lambda * (1 - MS-SSIM)); report_msssim adds an MS-SSIM line to
+    # validate / validate_postprocess / test ("ms-ssim" implies it)
+    distortion="mse", report_msssim=False)
 
 
 def make_config(**over):

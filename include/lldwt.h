@@ -704,6 +704,27 @@ int lldwt_cdf97_forward_ex(const float* x, float* ll, float* const* yh, int64_t 
 int lldwt_cdf97_inverse_ex(const float* ll, const float* const* yh, float* x, int64_t Z, int64_t H, int64_t W,
                            int levels, int adj, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * MS-SSIM (pytorch-msssim 0.2.1: data_range 1, 11-tap Gaussian window sigma 1.5 applied "valid", K = (0.01, 0.03), weights
+ * (0.0448, 0.2856, 0.3001, 0.2363, 0.1333); the first `scales` weights as they are for scales < 5).  x is the target and y the
+ * reconstruction, both (planes, H, W) fp32 with planes = B*C; `offset` is added to both on load (0.5 for RGB kept in [-0.5, 0.5]).
+ * Between scales: 2x2 average, stride 2, an odd side padded by one zero on both ends, divisor 4 always.  Every side must be at
+ * least 10 * 2^(scales-1) + 1.  One fused launch per scale: no statistic map is written to memory; nothing synchronises.
+ *   pyr   lldwt_msssim_ws_floats() floats: the pooled (x, y) pairs of scales 1.. (x then y, each (planes, Hs, Ws)); written by
+ *         the forward, read by the backward
+ *   sums  (scales, planes, 2) doubles of scratch (sum of cs, sum of l*cs); zeroed by the call
+ *   v     (scales, planes): max(spatial mean of cs, 0), of l*cs for the last scale;  m (planes) = prod_s v_s^w_s
+ *   coef  (scales, planes): dm/dv_s / N_s for the backward; all zero for a plane in which some v_s is clamped to 0, so that
+ *         the gradient there is exactly zero (w v^(w-1) is never evaluated at 0)
+ * lldwt_msssim_backward writes grad_y (planes, H, W) = d(gscale * g[0] * sum_planes m) / dy; g is a DEVICE double (null = 1),
+ * gpyr is scratch of lldwt_msssim_ws_floats() / 2 floats.  The statistics are recomputed; there is no gradient for x. */
+int64_t lldwt_msssim_ws_floats(int64_t planes, int64_t H, int64_t W, int scales);
+int lldwt_msssim_forward(const float* x, const float* y, float offset, int64_t planes, int64_t H, int64_t W, int scales,
+                         float* pyr, double* sums, double* v, double* m, double* coef, void* stream);
+int lldwt_msssim_backward(const float* x, const float* y, float offset, int64_t planes, int64_t H, int64_t W, int scales,
+                          const float* pyr, const double* coef, const double* g, double gscale, float* gpyr, float* grad_y,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,9 @@
     decode --region y0,x0,h,w              decodes only that region (tiled containers only)
     decode --reduce k                      decodes the image at 1/2^k of each side from the coarse levels only (0 <= k <=
                                            dwtlevels; with --region, the region is in the reduced image's coordinates)
+    python tools/codec.py compare a.png b.png              (prints PSNR, MS-SSIM and MS-SSIM in dB of two image files)
+
+    decode --compare SRC                   after decoding, prints the same three figures for the decoded image against SRC
     encode --coder gpu                     codes the streams with the interleaved device coder (irans32); decode reads the
                                            coder from the header
 
@@ -49,6 +52,24 @@ def build_net(config_path, checkpoint=None, device="cuda:0"):
     return net.to(device).eval()
 
 
+def print_quality(a_u8, b_u8):
+    """PSNR / MS-SSIM lines of two (H,W,3) uint8 tensors (codec.quality)."""
+    q = codec.quality(a_u8, b_u8)
+    print("psnr     %.4f dB" % q["psnr"])
+    if q["msssim"] is None:
+        print("ms-ssim  n/a (a side is below 161)")
+    else:
+        print("ms-ssim  %.6f" % q["msssim"])
+        print("ms-ssim  %.4f dB" % codec.msssim_db(q["msssim"]))
+
+
+def _load_rgb(path):
+    import numpy as np
+    import torch
+    from PIL import Image
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -65,8 +86,13 @@ def main(argv=None):
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
     sub.choices["decode"].add_argument("--reduce", type=int, default=0,
                                        help="decode at 1/2^k of each side from the coarse wavelet levels (default 0: full)")
+    sub.choices["decode"].add_argument("--compare", metavar="SRC",
+                                       help="print PSNR and MS-SSIM of the decoded image against this image file")
     p = sub.add_parser("info")
     p.add_argument("src")
+    p = sub.add_parser("compare")
+    p.add_argument("a")
+    p.add_argument("b")
     a = ap.parse_args(argv)
 
     if a.cmd == "info":
@@ -78,6 +104,15 @@ def main(argv=None):
             print("%-15s %d x %d tiles of %d x %d (rows x columns)" % ("grid", hdr["ny"], hdr["nx"], hdr["th"], hdr["tw"]))
         for k, n in enumerate(codec.reduce_bytes(hdr)):
             print("%-15s %d x %d: %d bytes" % ("reduce %d" % k, -(-hdr["W"] >> k), -(-hdr["H"] >> k), n))
+        return 0
+
+    if a.cmd == "compare":
+        xa, xb = _load_rgb(a.a), _load_rgb(a.b)
+        if xa.shape != xb.shape:
+            print("compare: the images differ in size: %dx%d and %dx%d" % (xa.shape[1], xa.shape[0], xb.shape[1], xb.shape[0]),
+                  file=sys.stderr)
+            return 2
+        print_quality(xa, xb)
         return 0
 
     import numpy as np
@@ -122,6 +157,13 @@ def main(argv=None):
         dt = time.perf_counter() - t0
         Image.fromarray(img.numpy()).save(a.dst)
         print("decoded %dx%d: %.3f s" % (img.shape[1], img.shape[0], dt))
+        if a.compare is not None:
+            src = _load_rgb(a.compare)
+            if src.shape != img.shape:
+                print("--compare: %s is %dx%d, the decoded image %dx%d" % (a.compare, src.shape[1], src.shape[0], img.shape[1],
+                                                                         img.shape[0]), file=sys.stderr)
+                return 2
+            print_quality(src, img.cpu())
     return 0
 
 
