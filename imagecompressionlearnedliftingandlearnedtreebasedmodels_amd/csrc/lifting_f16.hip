@@ -387,6 +387,42 @@ __device__ __forceinline__ floatx4 conv16_tile_stream(const uint8_t* __restrict_
     return acc;
 }
 
+// the strip tiles of a border tile, current form: only the k-steps of the wave-uniform mask `need` are issued.  A strip lies
+// outside the image, so most taps of its conv3 read T2 rows / columns that are outside too, where the image holds zeros: a k-step
+// whose two taps read zeros for all 16 positions adds exact zeros to the accumulator (it never holds -0: it starts at +0 and
+// x + (-x) rounds to +0) and leaves its bits alone -- 6 of 13 k-steps remain for a top strip, 5 for a bottom one, 8 / 7 for a left /
+// right one.  The weight fragments of a group of k-steps are all requested before the group's first MFMA.
+template <int WIN, int NIN, int PREC>
+__device__ __forceinline__ floatx4 conv16_tile_need(const uint8_t* __restrict__ img, int basein, bool hi_tap,
+                                                    const _Float16* __restrict__ frag, int step0, int lane, unsigned need) {
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    // two groups of k-steps (taps 0..13 and 14..25: a top strip needs the second only, a bottom strip the first), so that at most
+    // seven fragment pairs are held at once
+    constexpr int KSPLIT = 7;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int k0 = g == 0 ? 0 : KSPLIT, k1 = g == 0 ? KSPLIT : LF_KS;
+        if (((need >> k0) & ((1u << (k1 - k0)) - 1u)) == 0u) continue;
+        half8 ah[KSPLIT], al[KSPLIT];
+#pragma unroll
+        for (int ks = k0; ks < k1; ++ks)
+            if ((need >> ks) & 1u) ldA<PREC>(frag, step0 + ks, lane, ah[ks - k0], al[ks - k0]);
+#pragma unroll
+        for (int ks = k0; ks < k1; ++ks) {
+            if ((need >> ks) & 1u) {
+                const int ta = 2 * ks, tb = (2 * ks + 1) < LF_KK ? 2 * ks + 1 : LF_KK - 1;
+                const int offa = ((ta / LF_K) * WIN + ta % LF_K) * 16, offb = ((tb / LF_K) * WIN + tb % LF_K) * 16;
+                const int off = basein + (hi_tap ? offb : offa);
+                const half8 bh = *reinterpret_cast<const half8*>(img + off);
+                half8 bl = half8{};
+                if constexpr (PREC == 0) bl = *reinterpret_cast<const half8*>(img + 2 * NIN * 16 + off);
+                acc = mma3<PREC>(ah[ks - k0], al[ks - k0], bh, bl, acc);
+            }
+        }
+    }
+    return acc;
+}
+
 // two tiles at once: the A fragments are shared, the two MFMA chains are independent.  The B fragments of k-step ks+1 are
 // read from LDS into a second register set BEFORE the 6 MFMAs of k-step ks (the sched_group_barrier sequence pins that
 // order and leaves room for 2 vector instructions of a neighbouring epilogue after every MFMA), so the matrix pipe never
@@ -1084,6 +1120,9 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // t3 region), kept in fp32, and  sum_{taps outside} w4 . t3v  is subtracted per output pixel.  LLDWT_LF_DBG bit 16
     // selects the sequential evaluation (t3 on 20 x 36, conv4, below) for every tile instead: the check of this algebra.
     const bool interior = y0 >= 2 && y0 + TH + 2 <= h && x0 >= 2 && x0 + TW + 2 <= w;
+    // diagnostics flag 64: the border correction as it was before the k-step mask of the strips and the quarter-wave form of the
+    // correction sums (same output bits; kept for A/B timing and as the reference of tests/test_gpu_lift_border.py)
+    const bool legacy_border = (a.dbg & 64) != 0;
     // strips in t3-region coordinates (20 x 36, origin (y0 - 2, x0 - 2)): rows / columns whose image coordinate is
     // -2, -1 or h, h + 1 (w, w + 1)
     int nR = 0, nC = 0, Rl0 = 0, Rl1 = 0, Rl2 = 0, Rl3 = 0, Cl0 = 0, Cl1 = 0, Cl2 = 0, Cl3 = 0;   // scalars, not arrays: no stack
@@ -1135,8 +1174,34 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     r = q - ic * (TH + 4);
                     c = ic == 0 ? Cl0 : ic == 1 ? Cl1 : ic == 2 ? Cl2 : Cl3;
                 }
-                const floatx4 acc = conv16_tile_stream<R2W, N2, PREC>(lds + LDS_T2, (r * R2W + c) * 16 + halfsel * (N2 * 16), hi_tap,
-                                                                      frag, LF_H_C3 / LF_FRAG, lane);
+                floatx4 acc;
+                if (legacy_border) {
+                    acc = conv16_tile_stream<R2W, N2, PREC>(lds + LDS_T2, (r * R2W + c) * 16 + halfsel * (N2 * 16), hi_tap,
+                                                            frag, LF_H_C3 / LF_FRAG, lane);
+                } else {
+                    // conv3 tap (dy, dx) of this position reads T2 at image (gy - 2 + dy, gx - 2 + dx): the rows and columns of the
+                    // 5 x 5 window that lie inside the image, united over the wave's 16 positions (a superset is harmless)
+                    const int gy = y0 - 2 + r, gx = x0 - 2 + c;
+                    unsigned rc = 0;
+#pragma unroll
+                    for (int d = 0; d < LF_K; ++d) {
+                        rc |= (unsigned)(gy - 2 + d >= 0 && gy - 2 + d < h) << d;
+                        rc |= (unsigned)(gx - 2 + d >= 0 && gx - 2 + d < w) << (LF_K + d);
+                    }
+                    unsigned rcw = 0;
+#pragma unroll
+                    for (int b = 0; b < 2 * LF_K; ++b) rcw |= (unsigned)(__ballot((rc >> b) & 1u) != 0ull) << b;
+                    unsigned need = 0;
+#pragma unroll
+                    for (int ks = 0; ks < LF_KS; ++ks) {
+                        const int ta = 2 * ks, tb = (2 * ks + 1) < LF_KK ? 2 * ks + 1 : LF_KK - 1;
+                        const unsigned ina = (rcw >> (ta / LF_K)) & (rcw >> (LF_K + ta % LF_K)) & 1u;
+                        const unsigned inb = (rcw >> (tb / LF_K)) & (rcw >> (LF_K + tb % LF_K)) & 1u;
+                        need |= (ina | inb) << ks;
+                    }
+                    acc = conv16_tile_need<R2W, N2, PREC>(lds + LDS_T2, (r * R2W + c) * 16 + halfsel * (N2 * 16), hi_tap, frag,
+                                                          LF_H_C3 / LF_FRAG, lane, need);
+                }
                 const floatx4 accr = conv1_tile<PREC>(s16, (r + 4) * SW + c + 4, kgoff0, kgoff1, c1h, c1l);
                 floatx4 v;
 #pragma unroll
@@ -1223,41 +1288,98 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             rlo = 0;
             while (rlo < TH && ((nRA > 0 && rlo == RA0) || (nRA > 1 && rlo == RA1) || (nRA > 2 && rlo == RA2) || (nRA > 3 && rlo == RA3))) ++rlo;
             const int nA = nRA * TW + (TH - nRA) * nCA;
-            const int half = lane >> 5, tap = lane & 31;
-            const int dy = tap / LF_K, dx = tap - dy * LF_K;
-            for (int a0 = wave * 2; a0 < nA; a0 += 2 * NWAVE) {
-                const int ai = a0 + half;
-                float u = 0.f;
-                if (ai < nA && tap < LF_KK) {
-                    int oy, ox;
-                    if (ai < nRA * TW) {
-                        const int ir = ai / TW;
-                        ox = ai - ir * TW;
-                        oy = ir == 0 ? RA0 : ir == 1 ? RA1 : ir == 2 ? RA2 : RA3;
-                    } else {
-                        const int b = ai - nRA * TW, q = b / nCA, ic = b - q * nCA;
-                        oy = rlo + q;
-                        ox = ic == 0 ? CA0 : ic == 1 ? CA1 : ic == 2 ? CA2 : CA3;
-                    }
-                    const int r = oy + dy, c = ox + dx;                  // t3-region coordinates of this tap's position
-                    const int gyy = y0 + oy - 2 + dy, gxx = x0 + ox - 2 + dx;
-                    const bool rowout = gyy < 0 || gyy >= h, colout = gxx < 0 || gxx >= w;
-                    if (rowout || colout) {
-                        const int ir = r == Rl0 ? 0 : r == Rl1 ? 1 : r == Rl2 ? 2 : 3;
-                        const int ic = c == Cl0 ? 0 : c == Cl1 ? 1 : c == Cl2 ? 2 : 3;
-                        const int j = rowout ? ir * R3W + c : nR * R3W + ic * (TH + 4) + r;
-                        const floatx4* tv = reinterpret_cast<const floatx4*>(T3Vp(j));
-                        const floatx4* wv = reinterpret_cast<const floatx4*>(W4L + tap * LF_C);
+            // an opaque copy of the lane number: the per-lane tap constants are formed here, not above the composite loop,
+            // where they would push the next tile's prefetched operands out of the register file
+            int lane_c = lane;
+            asm volatile("" : "+v"(lane_c));
+            if (legacy_border) {                // half a wave per pixel, one lane per tap, five shuffle levels; CORR[ai]
+                const int half = lane_c >> 5, tap = lane_c & 31;
+                const int dy = tap / LF_K, dx = tap - dy * LF_K;
+                for (int a0 = wave * 2; a0 < nA; a0 += 2 * NWAVE) {
+                    const int ai = a0 + half;
+                    float u = 0.f;
+                    if (ai < nA && tap < LF_KK) {
+                        int oy, ox;
+                        if (ai < nRA * TW) {
+                            const int ir = ai / TW;
+                            ox = ai - ir * TW;
+                            oy = ir == 0 ? RA0 : ir == 1 ? RA1 : ir == 2 ? RA2 : RA3;
+                        } else {
+                            const int b = ai - nRA * TW, q = b / nCA, ic = b - q * nCA;
+                            oy = rlo + q;
+                            ox = ic == 0 ? CA0 : ic == 1 ? CA1 : ic == 2 ? CA2 : CA3;
+                        }
+                        const int r = oy + dy, c = ox + dx;                  // t3-region coordinates of this tap's position
+                        const int gyy = y0 + oy - 2 + dy, gxx = x0 + ox - 2 + dx;
+                        const bool rowout = gyy < 0 || gyy >= h, colout = gxx < 0 || gxx >= w;
+                        if (rowout || colout) {
+                            const int ir = r == Rl0 ? 0 : r == Rl1 ? 1 : r == Rl2 ? 2 : 3;
+                            const int ic = c == Cl0 ? 0 : c == Cl1 ? 1 : c == Cl2 ? 2 : 3;
+                            const int j = rowout ? ir * R3W + c : nR * R3W + ic * (TH + 4) + r;
+                            const floatx4* tv = reinterpret_cast<const floatx4*>(T3Vp(j));
+                            const floatx4* wv = reinterpret_cast<const floatx4*>(W4L + tap * LF_C);
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const floatx4 t = tv[q], ww = wv[q];
-                            u += t[0] * ww[0] + t[1] * ww[1] + t[2] * ww[2] + t[3] * ww[3];
+                            for (int q = 0; q < 4; ++q) {
+                                const floatx4 t = tv[q], ww = wv[q];
+                                u += t[0] * ww[0] + t[1] * ww[1] + t[2] * ww[2] + t[3] * ww[3];
+                            }
                         }
                     }
-                }
 #pragma unroll
-                for (int o = 16; o > 0; o >>= 1) u += __shfl_xor(u, o, 64);      // inside each half of the wave
-                if (tap == 0 && ai < nA) CORR[ai] = u;
+                    for (int o = 16; o > 0; o >>= 1) u += __shfl_xor(u, o, 64);      // inside each half of the wave
+                    if (tap == 0 && ai < nA) CORR[ai] = u;
+                }
+            } else {
+                // a QUARTER of a wave per pixel, lane i of it takes taps i and i + 16: their sum is the first level of the same
+                // pairwise tree over 32 tap slots (i with i + 16, then + 8, + 4, + 2, + 1), and the other four levels are rotations
+                // inside a row of 16 lanes on the vector ALU (after the level of distance 2d every partial sum has period 2d over
+                // the lanes, so lane 0 adds the same two operands whichever way the rotation turns).  Twice the pixels per pass
+                // of a wave and no LDS round trip per level; the result lands at the pixel's own slot of the tile, CORR[oy * TW + ox].
+                const int qp = lane_c >> 4, l16 = lane_c & 15;
+                for (int a0 = wave * 4; a0 < nA; a0 += 4 * NWAVE) {
+                    const int ai = a0 + qp;
+                    float u2[2] = {0.f, 0.f};
+                    int slot = 0;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                    const int tap = l16 + 16 * e;
+                    const int dy = tap / LF_K, dx = tap - dy * LF_K;
+                    if (ai < nA && tap < LF_KK) {
+                        int oy, ox;
+                        if (ai < nRA * TW) {
+                            const int ir = ai / TW;
+                            ox = ai - ir * TW;
+                            oy = ir == 0 ? RA0 : ir == 1 ? RA1 : ir == 2 ? RA2 : RA3;
+                        } else {
+                            const int b = ai - nRA * TW, q = b / nCA, ic = b - q * nCA;
+                            oy = rlo + q;
+                            ox = ic == 0 ? CA0 : ic == 1 ? CA1 : ic == 2 ? CA2 : CA3;
+                        }
+                        slot = oy * TW + ox;
+                        const int r = oy + dy, c = ox + dx;                  // t3-region coordinates of this tap's position
+                        const int gyy = y0 + oy - 2 + dy, gxx = x0 + ox - 2 + dx;
+                        const bool rowout = gyy < 0 || gyy >= h, colout = gxx < 0 || gxx >= w;
+                        if (rowout || colout) {
+                            const int ir = r == Rl0 ? 0 : r == Rl1 ? 1 : r == Rl2 ? 2 : 3;
+                            const int ic = c == Cl0 ? 0 : c == Cl1 ? 1 : c == Cl2 ? 2 : 3;
+                            const int j = rowout ? ir * R3W + c : nR * R3W + ic * (TH + 4) + r;
+                            const floatx4* tv = reinterpret_cast<const floatx4*>(T3Vp(j));
+                            const floatx4* wv = reinterpret_cast<const floatx4*>(W4L + tap * LF_C);
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                const floatx4 t = tv[q], ww = wv[q];
+                                u2[e] += t[0] * ww[0] + t[1] * ww[1] + t[2] * ww[2] + t[3] * ww[3];
+                            }
+                        }
+                    }
+                    }
+                    float u = u2[0] + u2[1];
+                    u += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(u), 0x128, 0xF, 0xF, false));   // row_ror:8
+                    u += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(u), 0x124, 0xF, 0xF, false));   // row_ror:4
+                    u += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(u), 0x122, 0xF, 0xF, false));   // row_ror:2
+                    u += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(u), 0x121, 0xF, 0xF, false));   // row_ror:1
+                    if (l16 == 0 && ai < nA) CORR[slot] = u;
+                }
             }
             __syncthreads();
         }
@@ -1273,10 +1395,16 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             net += rs + tail[5];            // b4 + sum_oc (b3 + b1)[oc] * sum_taps w4[oc], summed once per weight update (pack)
             const bool valid = gy < h && gx < w;
             if (!interior) {                   // the conv4 taps of this pixel that land outside the image (CORR, computed above)
-                const int ira = (nRA > 0 && oy == RA0) ? 0 : (nRA > 1 && oy == RA1) ? 1 : (nRA > 2 && oy == RA2) ? 2 : (nRA > 3 && oy == RA3) ? 3 : -1;
-                const int ica = (nCA > 0 && ox == CA0) ? 0 : (nCA > 1 && ox == CA1) ? 1 : (nCA > 2 && ox == CA2) ? 2 : (nCA > 3 && ox == CA3) ? 3 : -1;
-                if (ira >= 0) net -= CORR[ira * TW + ox];
-                else if (ica >= 0) net -= CORR[nRA * TW + (oy - rlo) * nCA + ica];
+                if (legacy_border) {
+                    const int ira = (nRA > 0 && oy == RA0) ? 0 : (nRA > 1 && oy == RA1) ? 1 : (nRA > 2 && oy == RA2) ? 2 : (nRA > 3 && oy == RA3) ? 3 : -1;
+                    const int ica = (nCA > 0 && ox == CA0) ? 0 : (nCA > 1 && ox == CA1) ? 1 : (nCA > 2 && ox == CA2) ? 2 : (nCA > 3 && ox == CA3) ? 3 : -1;
+                    if (ira >= 0) net -= CORR[ira * TW + ox];
+                    else if (ica >= 0) net -= CORR[nRA * TW + (oy - rlo) * nCA + ica];
+                } else if (valid && (gy < 2 || gy >= h - 2 || gx < 2 || gx >= w - 2)) {      // exactly the pixels of RA and CA
+                    int tid_f = tid;                    // opaque, like lane_c: the slot's address is formed here
+                    asm volatile("" : "+v"(tid_f));
+                    net -= CORR[tid_f];
+                }
             }
             const float skip = S[(oy + 8) * SW + ox + 8];
             const float din = din_pre;
