@@ -45,6 +45,17 @@ th x tw (tile_grid), each coded as an independent image -- its streams are byte-
     payload           the streams in the same order
     CRC32             u32       zlib.crc32 of every byte before it
 
+Lapped tiles (``encode_tiled(..., overlap=ov)``): neighbouring tiles share a band of ov pixels, both code
+it, and the decoder cross-fades the two reconstructions with a linear ramp (lap_weights) whose weights sum to exactly 1, so
+a border's step becomes a ramp.  Every tile is still an independent image with the streams of ``encode_images``.  Such a
+frame has its own container, version 1 (overlap == 0 writes LLDT as before):
+
+    magic             4 bytes   b"LLDO"
+    format version    u8        1
+    ... the LLDT fields up to ny, nx (the grid at the stride (th - overlap, tw - overlap), tile_grid_lapped)
+    overlap           u16       a power of two, 2^L <= overlap <= min(th, tw) / 2
+    numerics version .. CRC32   as LLDT
+
 Reduced-resolution decoding (``decode_images(..., reduce=k)``, ``decode_tiled(..., reduce=k)``): for
 0 <= k <= L the output is the image at 1/2^k of each side, ceil(H / 2^k) x ceil(W / 2^k).  Only the xe streams and the xo
 streams of levels k .. L-1 are decoded (the streams of finer levels are never handed to a coder), the inverse transform runs
@@ -71,6 +82,9 @@ _FIXED = struct.Struct("<4sBBBBIIH")          # magic .. numerics version
 TILED_MAGIC = b"LLDT"
 TILED_FORMAT_VERSION = 1
 _TFIXED = struct.Struct("<4sBBBBIIIIHHH")     # magic .. H, W, th, tw, ny, nx, numerics version
+LAPPED_MAGIC = b"LLDO"
+LAPPED_FORMAT_VERSION = 1
+_OFIXED = struct.Struct("<4sBBBBIIIIHHHH")    # magic .. H, W, th, tw, ny, nx, overlap, numerics version
 _PLANES = 3
 # coder name of the API -> value of the arithmetic string's "coder" key (None: the key is absent)
 CODER_KEYS = {"host": None, "gpu": "irans32"}
@@ -262,7 +276,7 @@ def pack_tiled(hdr, tile_streams):
 
 def parse_tiled(blob):
     """LLDT container -> (header dict, list of ny * nx lists of stream bytes).  The structural checks of parse_container plus
-    the grid (ValueError naming the field); host only."""
+    the grid (ValueError naming the field); host only.  The dict carries overlap = 0 (LLDO: parse_lapped)."""
     blob, end = _open(blob, TILED_MAGIC, TILED_FORMAT_VERSION, _TFIXED.size + 1 + 16 + 1)
     _, _, layer, nettype, L, H, W, th, tw, ny, nx, numerics = _TFIXED.unpack_from(blob, 0)
     _check_model_fields(layer, nettype, L, H, W)
@@ -274,23 +288,92 @@ def parse_tiled(blob):
     streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
     tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
     hdr = dict(version=TILED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
-               W=W, th=th, tw=tw, ny=ny, nx=nx, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
+               W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=0, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
                streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
     return hdr, tiles
 
 
+def _check_overlap(L, th, tw, ov):
+    """The overlap of a lapped grid against the level count and the tile size (ValueError naming overlap)."""
+    if ov < 1 or ov & (ov - 1):
+        raise ValueError("overlap: %d is not a power of two (the cross-fade weights must be exact in fp32)" % ov)
+    if ov < 1 << L:
+        raise ValueError("overlap: %d is below 2^dwtlevels = %d (the tile stride must stay a multiple of it)" % (ov, 1 << L))
+    if 2 * ov > min(th, tw):
+        raise ValueError("overlap: %d is more than half of a %d x %d tile (at most two tiles may cover a pixel along an axis)"
+                         % (ov, th, tw))
+
+
+def _check_grid_lapped(nettype, L, H, W, th, tw, ny, nx, ov):
+    """The grid fields of an LLDO header against the image size and the transform (ValueError naming the field): the
+    overlap rule, then along each axis of n tiles of t at the stride s = t - ov: (n - 1) s + t >= size, and for n >= 2 the
+    last tile is needed, (n - 2) s + t < size."""
+    from .graphs.layers.lifting_dwt_nets import padded_dims
+    if th < 1 or tw < 1 or ny < 1 or nx < 1:
+        raise ValueError("tile grid: th, tw, ny, nx must be positive (got %d, %d, %d, %d)" % (th, tw, ny, nx))
+    if padded_dims(L, nettype == "CDF97", th, tw) != (th, tw):
+        raise ValueError("tile size: %d x %d is not a size the %s transform at %d levels accepts" % (th, tw, nettype, L))
+    _check_overlap(L, th, tw, ov)
+    sh, sw = th - ov, tw - ov
+    if (ny - 1) * sh + th < H or (ny >= 2 and (ny - 2) * sh + th >= H):
+        raise ValueError("tile grid rows: %d tiles of %d rows at a stride of %d do not fit an image of %d rows"
+                         % (ny, th, sh, H))
+    if (nx - 1) * sw + tw < W or (nx >= 2 and (nx - 2) * sw + tw >= W):
+        raise ValueError("tile grid columns: %d tiles of %d columns at a stride of %d do not fit an image of %d columns"
+                         % (nx, tw, sw, W))
+
+
+def pack_lapped(hdr, tile_streams):
+    """hdr: as pack_tiled plus overlap (> 0); tile_streams as pack_tiled -> LLDO container."""
+    L, ny, nx, ov = hdr["dwtlevels"], hdr["ny"], hdr["nx"], hdr["overlap"]
+    _check_grid_lapped(hdr["netType"], L, hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx, ov)
+    if ny > 0xFFFF or nx > 0xFFFF:
+        raise ValueError("tile grid: ny, nx must fit 16 bits")
+    if len(tile_streams) != ny * nx or any(len(t) != _PLANES * (L + 1) for t in tile_streams):
+        raise ValueError("stream count: expected %d tiles of %d streams" % (ny * nx, _PLANES * (L + 1)))
+    head = _OFIXED.pack(LAPPED_MAGIC, LAPPED_FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], L,
+                        hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx, ov, hdr["numerics"])
+    return _seal(head + _pack_identity(hdr) + bytes([_PLANES * (L + 1)])
+                 + _pack_streams([s for t in tile_streams for s in t]))
+
+
+def parse_lapped(blob):
+    """LLDO container -> (header dict with overlap, list of ny * nx lists of stream bytes).  The structural checks of
+    parse_tiled with the lapped grid rule (_check_grid_lapped; ValueError naming the field); host only."""
+    blob, end = _open(blob, LAPPED_MAGIC, LAPPED_FORMAT_VERSION, _OFIXED.size + 1 + 16 + 1)
+    _, _, layer, nettype, L, H, W, th, tw, ny, nx, ov, numerics = _OFIXED.unpack_from(blob, 0)
+    _check_model_fields(layer, nettype, L, H, W)
+    _check_grid_lapped(_NETTYPE_NAMES[nettype], L, H, W, th, tw, ny, nx, ov)
+    arith, digest, count, pos = _parse_identity(blob, _OFIXED.size, end)
+    if count != _PLANES * (L + 1):
+        raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
+    coder, _ = _split_coder(arith)
+    streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
+    tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
+    hdr = dict(version=LAPPED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
+               W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
+               streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
+    return hdr, tiles
+
+
+def _magic(blob):
+    return bytes(blob[:4]) if isinstance(blob, (bytes, bytearray, memoryview)) else None
+
+
 def read_header(blob):
-    """The header of a container (LLDW or LLDT) as a dict (CPU only; the library is never loaded).  Raises ValueError as
-    parse_container / parse_tiled."""
-    if isinstance(blob, (bytes, bytearray, memoryview)) and bytes(blob[:4]) == TILED_MAGIC:
+    """The header of a container (LLDW, LLDT or LLDO) as a dict (CPU only; the library is never loaded).  A tiled header
+    carries ``overlap``: 0 for LLDT.  Raises ValueError as parse_container / parse_tiled / parse_lapped."""
+    if _magic(blob) == LAPPED_MAGIC:
+        return parse_lapped(blob)[0]
+    if _magic(blob) == TILED_MAGIC:
         return parse_tiled(blob)[0]
     return parse_container(blob)[0]
 
 
 def reduce_bytes(hdr):
     """-> list of L + 1 ints: entry k is the number of container bytes a decode at reduce=k reads, the header (every byte
-    before the payload) plus the xe streams and the xo streams of levels k .. L-1 of every plane (for LLDT, of every tile).
-    The 4-byte CRC32 trailer is not counted.  hdr: read_header's dict (LLDW or LLDT); CPU only."""
+    before the payload) plus the xe streams and the xo streams of levels k .. L-1 of every plane (for LLDT / LLDO, of every
+    tile).  The 4-byte CRC32 trailer is not counted.  hdr: read_header's dict (LLDW, LLDT or LLDO); CPU only."""
     L, lengths = hdr["dwtlevels"], hdr["stream_lengths"]
     per = L + 1                                       # streams per plane: xe, xo finest -> coarsest
     if len(lengths) % per:
@@ -580,13 +663,56 @@ def tile_grid(nets, H, W, tile=512):
     return th, tw, -(-H // th), -(-W // tw)
 
 
+def lap_weights(t, ov, q, n):
+    """The 1-D cross-fade weights of tile number q of n along an axis: a float32 tensor of t values.  (i + 0.5) / ov on the
+    first ov samples of a tile that has a predecessor (q > 0), (t - i - 0.5) / ov on the last ov of one that has a successor
+    (q < n - 1), 1 elsewhere; ov = 0: all ones.  ov is a power of two, so every weight is exact in fp32 and the falling ramp
+    of a tile and the rising ramp of the next sum to exactly 1.  A pixel's weight is wy * wx (lldwt_ycc_tiles_blend)."""
+    import torch
+    t, ov, q, n = int(t), int(ov), int(q), int(n)
+    if t < 1 or n < 1 or not 0 <= q < n or ov < 0 or ov & (ov - 1) or 2 * ov > t:
+        raise ValueError("lap_weights: need t >= 1, 0 <= q < n and overlap a power of two with 2 * overlap <= t "
+                         "(got t=%d, overlap=%d, q=%d, n=%d)" % (t, ov, q, n))
+    w = torch.ones(t, dtype=torch.float32)
+    if ov:
+        i = torch.arange(ov, dtype=torch.float32)
+        if q > 0:
+            w[:ov] = (i + 0.5) / ov
+        if q < n - 1:
+            w[t - ov:] = (ov - i - 0.5) / ov          # local index t - ov + i: (t - (t - ov + i) - 0.5) / ov
+    return w
+
+
+def tile_grid_lapped(nets, H, W, tile=512, overlap=0):
+    """tile_grid for tiles that share ``overlap`` pixels with each neighbour -> (th, tw, ny, nx).  Along an axis of size S
+    the count n0 = ceil(S / tile) of the plain grid gives the tile side padded_size(ceil((S + (n0 - 1) overlap) / n0)) -- n0
+    tiles at the stride side - overlap then cover S -- and the count is redone with it: 1 if one tile covers the axis, else
+    ceil((S - side) / stride) + 1, the smallest that covers, so the last tile is needed.  ValueError naming overlap unless
+    it is a power of two with 2^L <= overlap <= min(th, tw) / 2; overlap = 0 is tile_grid."""
+    from .graphs.layers.lifting_dwt_nets import _levels, padded_size
+    ov = int(overlap)
+    if ov != overlap or ov < 0:
+        raise ValueError("overlap must be a non-negative integer (got %r)" % (overlap,))
+    if ov == 0:
+        return tile_grid(nets, H, W, tile)
+    if int(tile) < 1 or H < 1 or W < 1:
+        raise ValueError("tile grid: tile, H and W must be positive (got %d, %d, %d)" % (tile, H, W))
+    ny, nx = -(-H // tile), -(-W // tile)
+    th, tw = padded_size(nets, -(-(H + (ny - 1) * ov) // ny), -(-(W + (nx - 1) * ov) // nx))
+    _check_overlap(_levels(nets[0]), th, tw, ov)
+    count = lambda size, t: 1 if t >= size else -(-(size - t) // (t - ov)) + 1
+    return th, tw, count(H, th), count(W, tw)
+
+
 def _tile_streams(s_xe, s_xo, j):
     """The 3 (L + 1) streams of image j of an encode_strings_planes result, in the LLDW order."""
     return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
 
 
-def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host"):
-    """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers.  Every tile is coded as an independent image: its streams
+def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0):
+    """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
+    (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
+    Every tile is coded as an independent image: its streams
     are those of encode_images(net, padded_tile).  The images are uploaded once; groups of tiles_per_call tiles (over all
     images of the batch) are cut out on the device (lldwt_u8hwc_to_ycc_tiles) and coded together, which bounds the device
     memory; one tile per call in the arithmetics that are not batch invariant.  The bytes do not depend on tiles_per_call.
@@ -599,7 +725,13 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host"):
     if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
         raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
     nets = net.nets()
-    th, tw, ny, nx = tile_grid([n.autoencoder for n in nets], H, W, int(tile))
+    ov = int(overlap)
+    if ov != overlap or ov < 0 or ov > 0xFFFF:
+        raise ValueError("overlap must be an integer in [0, 65535] (got %r)" % (overlap,))
+    if ov:
+        th, tw, ny, nx = tile_grid_lapped([n.autoencoder for n in nets], H, W, int(tile), ov)
+    else:
+        th, tw, ny, nx = tile_grid([n.autoencoder for n in nets], H, W, int(tile))
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     arith = arithmetic_string(coder)
@@ -614,10 +746,16 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host"):
     with torch.no_grad():
         for first in range(0, T, g):
             n = min(g, T - first)
-            x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)                 # (3,n,1,th,tw)
+            if ov:
+                x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
+            else:
+                x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
             s_xe, s_xo = encode_strings_planes(nets, x, coder=coder)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
     per = ny * nx
+    if ov:
+        hdr["overlap"] = ov
+        return [pack_lapped(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
     return [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
 
 
@@ -643,8 +781,11 @@ def _region(region, H, W):
 
 
 def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
-    """LLDT container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
+    """LLDT or LLDO container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
+    LLDO (lapped tiles, _decode_lapped): the tiles covering any pixel of the region, overlap included, are decoded in
+    ascending index, each group is blended into a region-sized fp32 buffer (lldwt_ycc_tiles_blend) and the buffer is
+    written once, as the single tile of a 1 x 1 grid, by the same output kernels.
     reduce = k in [0, L]: the image at 1/2^k of each side (decode_images); region is then in the coordinates of the reduced
     image, each tile covers th>>k x tw>>k of its pixels and is written by lldwt_ll_tiles_to_u8hwc.
     Every check (container, region, identity) runs on the host before any GPU work."""
@@ -652,6 +793,8 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
     from . import ops
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
+    if _magic(blob) == LAPPED_MAGIC:
+        return _decode_lapped(net, (layer, nettype, L), blob, region, tiles_per_call, k)
     hdr, tiles = parse_tiled(blob)
     H, W, th, tw, ny, nx = (hdr[key] for key in ("H", "W", "th", "tw", "ny", "nx"))
     H, W, th, tw = _reduced(H, k), _reduced(W, k), th >> k, tw >> k          # tile sides are multiples of 2^L
@@ -682,4 +825,46 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
             else:
                 ops.ll_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), inv_a, b, tiles=grp,
                                       out=out)
+    return out[0].cpu()
+
+
+def _decode_lapped(net, ident, blob, region, tiles_per_call, k):
+    """decode_tiled for an LLDO container at reduce = k (checked by the caller).  At reduce = k the tile side, the stride
+    and the overlap are all shifted by k (they are multiples of 2^L), and the raw LL samples are blended before the
+    per-plane affine map of lldwt_ll_tiles_to_u8hwc."""
+    import torch
+    from . import ops
+    layer, nettype, L = ident
+    hdr, tiles = parse_lapped(blob)
+    ny, nx = hdr["ny"], hdr["nx"]
+    H, W, th, tw, ov = _reduced(hdr["H"], k), _reduced(hdr["W"], k), hdr["th"] >> k, hdr["tw"] >> k, hdr["overlap"] >> k
+    sh, sw = th - ov, tw - ov
+    y0, x0, h, w = _region(region, H, W)
+    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
+        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
+    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
+    _prepare(net)
+    nets = net.nets()
+    dev = next(net.parameters()).device
+    # tile q of an axis covers [q s, q s + t): the tiles with q s + t > first and q s <= last
+    span = lambda first, last, t, s, n: range(max(0, (first - t) // s + 1), min(n - 1, last // s) + 1)
+    want = [ty * nx + tx for ty in span(y0, y0 + h - 1, th, sh, ny) for tx in span(x0, x0 + w - 1, tw, sw, nx)]
+    g = int(tiles_per_call) if _batch_invariant(hdr["arithmetic"]) else 1
+    per = L + 1
+    with torch.no_grad():
+        acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
+        for a in range(0, len(want), g):
+            grp = want[a:a + g]                                                # ascending tile index: the blend's order
+            s_xe = [[tiles[t][p * per] for t in grp] for p in range(_PLANES)]
+            s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(k, L)]
+            kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}
+            if k:
+                kw["first_level"] = k
+            xhat = _decode_tiles(nets, s_xe, s_xo, hdr["th"], hdr["tw"], len(grp), **kw)
+            ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), grp, acc)
+        if k == 0:
+            out = ops.ycc_tiles_to_u8hwc(acc, (h, w, h, w, 1, 1), (0, 0, h, w))
+        else:
+            inv_a, b = ll_norm(net, k)
+            out = ops.ll_tiles_to_u8hwc(acc, (h, w, h, w, 1, 1), (0, 0, h, w), inv_a, b)
     return out[0].cpu()

@@ -161,6 +161,107 @@ __global__ void k_ycc_tiles_to_u8hwc(const float* __restrict__ ycc, const int32_
                          af);
 }
 
+// Lapped tile grid (codec.encode_tiled(..., overlap=ov)): ny x nx tiles of th x tw at the stride
+// (sh, sw) = (th - ov, tw - ov), tile (ty, tx) covering rows [ty*sh, ty*sh + th) and columns [tx*sw, tx*sw + tw); neighbours
+// share a band of ov pixels, and 2 * ov <= min(th, tw) so that at most two tiles cover a pixel along each axis.
+
+// k_u8hwc_to_ycc_tiles<true> at the stride (sh, sw): the same expressions per pixel, so every value is bitwise that of the
+// 1 x 1 grid on the replicate-padded crop at (ty*sh, tx*sw).  Grid (cdiv(tw,256), th, n), one thread per output pixel.
+__global__ void k_u8hwc_to_ycc_tiles_lapped(const uint8_t* __restrict__ src, float* __restrict__ ycc, int64_t H, int64_t W,
+                                            int64_t th, int64_t tw, int64_t sh, int64_t sw, int64_t ny, int64_t nx,
+                                            int64_t first, int64_t n) {
+    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (x >= tw) return;
+    const int64_t y = blockIdx.y, j = blockIdx.z;
+    // block-uniform: 32-bit (the launcher bounds B * ny * nx)
+    const uint32_t t = (uint32_t)(first + j), per = (uint32_t)(ny * nx), b32 = t / per, r = t - b32 * per;
+    const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
+    const int64_t b = b32, gy = y + (int64_t)ty * sh, gx = x + (int64_t)tx * sw;
+    const int64_t sy = gy < H ? gy : H - 1, sx = gx < W ? gx : W - 1;
+    const uint8_t* s = src + ((b * H + sy) * W + sx) * 3;
+    const float rr = (float)s[0] / 255.0f, g = (float)s[1] / 255.0f, bl = (float)s[2] / 255.0f;
+    const float yy = KR * rr + KG * g + KB * bl;
+    const float cb = 0.5f * (bl - yy) / (1.f - KB) + 0.5f;
+    const float cr = 0.5f * (rr - yy) / (1.f - KR) + 0.5f;
+    const int64_t hw = th * tw, p = y * tw + x;
+    ycc[(0 * n + j) * hw + p] = yy - 0.5f;
+    ycc[(1 * n + j) * hw + p] = cb;
+    ycc[(2 * n + j) * hw + p] = cr;
+}
+
+// The tiles of one axis that cover the global position g (n tiles of t at the stride s = t - ov, the grid covering g): the
+// last tile starting at or before g (q1, local index i1) and, when g lies in its leading band, the tile before it
+// (q0 = q1 - 1, i0 = i1 + s; q0 < 0: none).  w0 / w1: codec.lap_weights -- (i + 0.5) / ov on the leading band of a tile
+// that has a predecessor, (t - i - 0.5) / ov on the trailing band of one that has a successor, 1 elsewhere; ov is a power
+// of two (inv_ov exact), so every weight is exact in fp32 and the two of a band sum to exactly 1.
+struct LapAxis {
+    int32_t q0, q1, i0, i1;
+    float w0, w1;
+};
+__device__ __forceinline__ float lap_weight(uint32_t i, uint32_t q, uint32_t t, uint32_t ov, uint32_t n, float inv_ov) {
+    if (q > 0 && i < ov) return __fmul_rn((float)i + 0.5f, inv_ov);
+    if (q + 1 < n && i >= t - ov) return __fmul_rn((float)(t - i) - 0.5f, inv_ov);
+    return 1.0f;
+}
+__device__ __forceinline__ LapAxis lap_axis(uint32_t g, uint32_t t, uint32_t ov, uint32_t n, float inv_ov) {
+    const uint32_t s = t - ov;
+    uint32_t q1 = g / s;
+    if (q1 > n - 1) q1 = n - 1;
+    const uint32_t i1 = g - q1 * s;
+    LapAxis a;
+    a.q1 = (int32_t)q1;
+    a.i1 = (int32_t)i1;
+    a.w1 = lap_weight(i1, q1, t, ov, n, inv_ov);
+    a.q0 = -1;
+    a.i0 = 0;
+    a.w0 = 0.f;
+    if (q1 > 0 && i1 < ov) {                           // i1 + s < t: the previous tile's trailing band
+        a.q0 = (int32_t)q1 - 1;
+        a.i0 = (int32_t)(i1 + s);
+        a.w0 = lap_weight(i1 + s, q1 - 1, t, ov, n, inv_ov);
+    }
+    return a;
+}
+
+// Blend of one decoded group of lapped tiles into the fp32 region buffer acc (3,1,1,h,w) (lldwt_ycc_tiles_blend).  ycc
+// (3,n,1,th,tw): the group's tiles; slots[ty * nx + tx]: the slot of that tile in ycc, or -1 when it is not in this group.
+// Grid (cdiv(w,256), h): one thread per REGION pixel (two tiles of a group can cover one pixel, so a thread per tile pixel
+// would race); it visits the <= 4 covering tiles in ascending tile index and does acc = acc + w * v as a separate rounded
+// product and sum, so a pixel's sequence of fp32 operations is the same whatever the grouping (groups come in ascending
+// index).  The row side (tiles, local rows, wy) is block-uniform; every plane row is read and written coalesced.
+__global__ void k_ycc_tiles_blend(const float* __restrict__ ycc, const int32_t* __restrict__ slots, int64_t n, uint32_t th,
+                                  uint32_t tw, uint32_t ov, uint32_t ny, uint32_t nx, uint32_t y0, uint32_t x0, uint32_t h,
+                                  uint32_t w, float inv_ov, float* __restrict__ acc) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= w) return;
+    const LapAxis ay = lap_axis(y0 + blockIdx.y, th, ov, ny, inv_ov);
+    const LapAxis ax = lap_axis(x0 + x, tw, ov, nx, inv_ov);
+    const int32_t qy[2] = {ay.q0, ay.q1}, iy[2] = {ay.i0, ay.i1}, qx[2] = {ax.q0, ax.q1}, ix[2] = {ax.i0, ax.i1};
+    const float wy[2] = {ay.w0, ay.w1}, wx[2] = {ax.w0, ax.w1};
+    const int64_t hw = (int64_t)th * tw, rhw = (int64_t)h * w, p = (int64_t)blockIdx.y * w + x;
+    float a[3];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] = acc[c * rhw + p];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            if (qy[u] < 0 || qx[v] < 0) continue;
+            const int32_t j = slots[(int64_t)qy[u] * nx + qx[v]];
+            if (j < 0 || j >= n) continue;
+            const float wt = __fmul_rn(wy[u], wx[v]);
+            const int64_t q = (int64_t)iy[u] * tw + ix[v];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a[c] = __fadd_rn(a[c], __fmul_rn(wt, ycc[(c * n + j) * hw + q]));
+            any = true;
+        }
+    }
+    if (!any) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c * rhw + p] = a[c];
+}
+
 // ------------------------------------------------------------------------------------------ subband MLP
 // SubbandAutoEncoder (lifting_dwt_nets.py:99-110): 1 -> 32 -> 32 -> 32 -> 1 per coefficient, tanh between, on the matrix
 // cores: the two 32x32 layers run on v_mfma_f32_16x16x4_f32 with everything in registers.
@@ -1314,6 +1415,49 @@ extern "C" int lldwt_ll_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, i
     }
     return ycc_tiles_to_u8hwc<true>("ll_tiles_to_u8hwc", ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst, af,
                                     stream);
+}
+// the geometry both lapped entry points require: ov a power of two with 2 * ov <= min(th, tw), and the
+// grid at the stride (th - ov, tw - ov) covering the image
+static int lapped_grid_ok(const char* who, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ov, int64_t ny, int64_t nx) {
+    LLDWT_REQUIRE(H > 0 && W > 0 && th > 0 && tw > 0 && ny > 0 && nx > 0, "%s: bad arguments", who);
+    LLDWT_REQUIRE(ov >= 1 && (ov & (ov - 1)) == 0 && 2 * ov <= th && 2 * ov <= tw,
+                  "%s: overlap %lld must be a power of two with 2 * overlap <= min(th, tw) = %lld", who, (long long)ov,
+                  (long long)(th < tw ? th : tw));
+    LLDWT_REQUIRE(H < (1ll << 31) && W < (1ll << 31) && ny < (1ll << 31) && nx < (1ll << 31) && th <= 65535 &&
+                  tw <= (1ll << 30), "%s: grid too large", who);
+    LLDWT_REQUIRE((ny - 1) * (th - ov) + th >= H && (nx - 1) * (tw - ov) + tw >= W, "%s: the grid does not cover the image",
+                  who);
+    return 0;
+}
+extern "C" int lldwt_u8hwc_to_ycc_tiles_lapped(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th,
+                                               int64_t tw, int64_t ov, int64_t ny, int64_t nx, int64_t first, int64_t n,
+                                               void* stream) {
+    LLDWT_REQUIRE(src && ycc && B > 0, "u8hwc_to_ycc_tiles_lapped: bad arguments");
+    if (const int rc = lapped_grid_ok("u8hwc_to_ycc_tiles_lapped", H, W, th, tw, ov, ny, nx)) return rc;
+    LLDWT_REQUIRE(B * ny * nx < (1ll << 31) && n <= 65535, "u8hwc_to_ycc_tiles_lapped: grid too large");
+    LLDWT_REQUIRE(first >= 0 && n > 0 && first + n <= B * ny * nx, "u8hwc_to_ycc_tiles_lapped: tile range [%lld, %lld) "
+                  "outside the %lld tiles", (long long)first, (long long)(first + n), (long long)(B * ny * nx));
+    hipLaunchKernelGGL(k_u8hwc_to_ycc_tiles_lapped, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
+                       (hipStream_t)stream, src, ycc, H, W, th, tw, th - ov, tw - ov, ny, nx, first, n);
+    return check_launch("u8hwc_to_ycc_tiles_lapped");
+}
+extern "C" int lldwt_ycc_tiles_blend(const float* ycc, const int32_t* slots, int64_t nslots, int64_t n, int64_t H, int64_t W,
+                                     int64_t th, int64_t tw, int64_t ov, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
+                                     int64_t h, int64_t w, float* acc, void* stream) {
+    LLDWT_REQUIRE(ycc && slots && acc, "ycc_tiles_blend: null pointer");
+    if (const int rc = lapped_grid_ok("ycc_tiles_blend", H, W, th, tw, ov, ny, nx)) return rc;
+    LLDWT_REQUIRE(ny * nx < (1ll << 31) && nslots == ny * nx, "ycc_tiles_blend: the slot table holds %lld entries, the grid "
+                  "has %lld tiles", (long long)nslots, (long long)(ny * nx));
+    LLDWT_REQUIRE(n > 0 && n <= nslots, "ycc_tiles_blend: %lld tiles in the group, the grid has %lld", (long long)n,
+                  (long long)nslots);
+    LLDWT_REQUIRE(y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && y0 + h <= H && x0 + w <= W,
+                  "ycc_tiles_blend: region (%lld, %lld, %lld, %lld) outside the %lld x %lld image", (long long)y0,
+                  (long long)x0, (long long)h, (long long)w, (long long)H, (long long)W);
+    LLDWT_REQUIRE(h <= 65535, "ycc_tiles_blend: grid too large");
+    hipLaunchKernelGGL(k_ycc_tiles_blend, dim3((unsigned)cdiv(w, 256), (unsigned)h), dim3(256), 0, (hipStream_t)stream, ycc,
+                       slots, n, (uint32_t)th, (uint32_t)tw, (uint32_t)ov, (uint32_t)ny, (uint32_t)nx, (uint32_t)y0,
+                       (uint32_t)x0, (uint32_t)h, (uint32_t)w, 1.0f / (float)ov, acc);
+    return check_launch("ycc_tiles_blend");
 }
 // the untiled codec's I/O: the 1 x 1 grid of one Hp x Wp tile per image
 extern "C" int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,

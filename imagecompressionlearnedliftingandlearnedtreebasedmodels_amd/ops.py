@@ -199,6 +199,47 @@ def ll_tiles_to_u8hwc(y, grid, region, inv_a, b, tiles=None, first=0, B=1, out=N
     return out
 
 
+def u8hwc_to_ycc_tiles_lapped(src, th, tw, ov, ny, nx, first, n):
+    """u8hwc_to_ycc_tiles on a lapped grid: tile (ty, tx) starts at (ty * (th - ov), tx * (tw - ov)), so neighbours share ov
+    pixels (lldwt_u8hwc_to_ycc_tiles_lapped; bitwise u8hwc_to_ycc_pad of the replicate-padded crop)."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+            and src.dim() == 4 and src.shape[3] == 3):
+        raise _lib.LLDWTError("u8hwc_to_ycc_tiles_lapped: expected a contiguous (B,H,W,3) uint8 device tensor")
+    B, H, W, _ = src.shape
+    if n < 1 or th < 1 or tw < 1:
+        raise _lib.LLDWTError("u8hwc_to_ycc_tiles_lapped: n, th, tw must be positive")
+    y = torch.empty(3, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u8hwc_to_ycc_tiles_lapped(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, th, tw, ov, ny, nx,
+                                                      first, n, _stream()), "u8hwc_to_ycc_tiles_lapped")
+    return y
+
+
+def ycc_tiles_blend(y, grid, region, tiles, acc):
+    """Accumulates the decoded lapped tiles y (3,n,1,th,tw), whose tile indexes (ty * nx + tx, one image) are ``tiles``, into
+    the fp32 region buffer acc (3,1,1,h,w) with the cross-fade weights of codec.lap_weights, and returns acc.
+    grid = (H, W, th, tw, ov, ny, nx); region = (y0, x0, h, w) inside the image.  acc must be zero before the first group
+    of a decode and the groups must come in ascending tile index (lldwt_ycc_tiles_blend)."""
+    H, W, th, tw, ov, ny, nx = grid
+    y0, x0, h, w = region
+    if not (isinstance(y, torch.Tensor) and y.dim() == 5 and y.shape[0] == 3 and y.shape[2] == 1):
+        raise _lib.LLDWTError("ycc_tiles_blend: y must be (3,n,1,th,tw)")
+    _, n, _, yh, yw = y.shape
+    if (yh, yw) != (th, tw):
+        raise _lib.LLDWTError("ycc_tiles_blend: tiles are %d x %d, the grid says %d x %d" % (yh, yw, th, tw))
+    tiles = list(tiles)
+    if len(tiles) != n or len(set(tiles)) != n or any(t < 0 or t >= ny * nx for t in tiles):
+        raise _lib.LLDWTError("ycc_tiles_blend: need %d distinct tile indexes in [0, %d)" % (n, ny * nx))
+    if not (isinstance(acc, torch.Tensor) and acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()
+            and tuple(acc.shape) == (3, 1, 1, h, w)):
+        raise _lib.LLDWTError("ycc_tiles_blend: acc must be a contiguous (3,1,1,%d,%d) fp32 device tensor" % (h, w))
+    slots = torch.full((ny * nx,), -1, dtype=torch.int32)
+    slots[torch.tensor(tiles, dtype=torch.int64)] = torch.arange(n, dtype=torch.int32)
+    slots = slots.to(y.device)
+    check(_lib.load().lldwt_ycc_tiles_blend(_chk(y, "y"), C.c_void_p(slots.data_ptr()), ny * nx, n, H, W, th, tw, ov, ny, nx,
+                                            y0, x0, h, w, _chk(acc, "acc"), _stream()), "ycc_tiles_blend")
+    return acc
+
+
 def ycc_to_u8hwc_crop(y, H, W):
     """plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5 -> (B,H,W,3) uint8 RGB of the top-left H x W
     (lldwt_ycc_to_u8hwc_crop: floor((v + 0.5) * 255 + 0.5) of v = ycc_to_rgb(y, clamp=True))."""

@@ -94,6 +94,27 @@ int lldwt_ycc_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t fir
 int lldwt_ll_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
                             int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
                             const float* inv_a, const float* b, uint8_t* dst, void* stream);
+/* Lapped tile grid (codec.py encode_tiled(..., overlap=ov)): ny x nx tiles of th x tw at the stride
+ * (sh, sw) = (th - ov, tw - ov); tile (ty, tx) covers rows [ty*sh, ty*sh + th) and columns [tx*sw, tx*sw + tw), so
+ * neighbours share a band of ov pixels.  Both entry points require ov to be a power of two with 2 * ov <= min(th, tw)
+ * (at most two tiles cover a pixel along an axis) and (ny-1)*sh + th >= H, (nx-1)*sw + tw >= W; H, W < 2^31, th <= 65535.
+ * lldwt_u8hwc_to_ycc_tiles_lapped: lldwt_u8hwc_to_ycc_tiles at that stride: the tiles first .. first+n-1 (index
+ *   (b * ny + ty) * nx + tx) -> ycc (3,n,1,th,tw); every value bitwise lldwt_u8hwc_to_ycc_pad of the replicate-padded crop
+ *   at (ty*sh, tx*sw).  n <= 65535.
+ * lldwt_ycc_tiles_blend: accumulates one group of n decoded tiles of ONE image, ycc (3,n,1,th,tw), into the fp32 region
+ *   buffer acc (3,1,1,h,w) of the region [y0, y0+h) x [x0, x0+w) (inside the image; h <= 65535), which the caller zeroes
+ *   before the first group.  slots: a device int32 array of nslots == ny * nx entries, slots[ty * nx + tx] = the tile's
+ *   slot in ycc, or -1 when it is not in this group.  Per region pixel and plane, for the covering tiles of the group in
+ *   ascending tile index: acc = fadd(acc, fmul(wy * wx, v)), separately rounded (no FMA), with the 1-D weight of local
+ *   index i in tile q of n: (i + 0.5) / ov if q > 0 and i < ov; (t - i - 0.5) / ov if q < n-1 and i >= t - ov; else 1.  Groups
+ *   fed in ascending tile index give the same bits whatever the grouping; a pixel one tile covers gets acc == v.  Samples
+ *   are blended raw (a reduced decode's LL band before the lldwt_ll_tiles_to_u8hwc affine map, with th, tw, ov, H, W the
+ *   reduced sizes); acc is then a 1 x 1 grid for lldwt_ycc_tiles_to_u8hwc / lldwt_ll_tiles_to_u8hwc.                      */
+int lldwt_u8hwc_to_ycc_tiles_lapped(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw,
+                                    int64_t ov, int64_t ny, int64_t nx, int64_t first, int64_t n, void* stream);
+int lldwt_ycc_tiles_blend(const float* ycc, const int32_t* slots, int64_t nslots, int64_t n, int64_t H, int64_t W, int64_t th,
+                          int64_t tw, int64_t ov, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                          float* acc, void* stream);
 int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
                            void* stream);
 int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,

@@ -1,0 +1,444 @@
+"""GPU: lapped tiled coding (codec.encode_tiled(..., overlap=ov) / decode_tiled on LLDO, tools/codec.py --overlap, DESIGN.md
+7.1.4) -- the lapped gather against the untiled pad kernel, the blend kernel against a torch-CPU fp32 reference (two rounded
+operations per tile, ascending tile index) and across groupings, the ramp two constant tiles give, every tile's streams
+against encode_images of its padded crop, decoded bytes against the per-tile decode (outside the bands) and the finalised
+reference blend (everywhere), regions, group sizes, reduced decoding, the device coder, refusals and the command line."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import _lib, codec, ops
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LAYERS = ("conditioned2ZTsepSubbands", "onlyEZWT", "DWTConditioned2EntropyLayerZTBlock")
+H, W, TILE, OV, L = 100, 150, 64, 8, 3          # -> 2 x 3 tiles of 56 x 56 at a stride of 48
+_NETS = {}
+_FRAMES = {}
+
+
+def _net(layer, L=L, **over):
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.graphs.models.LiftingBasedDWT_net import \
+        LiftingBasedDWTNetWrapper
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.utils.config import make_config
+    key = (layer, L, tuple(sorted(over.items())))
+    if key not in _NETS:
+        cfg = make_config(dwtlevels=L, mode="validate", entropy_layer=layer, **over)
+        torch.manual_seed(0)
+        _NETS[key] = LiftingBasedDWTNetWrapper(cfg).to(DEV).eval()
+    return _NETS[key]
+
+
+def _images(B, H, W, seed):
+    """Smooth colour fields plus noise, as uint8 (B,H,W,3) on the host."""
+    g = torch.Generator().manual_seed(seed)
+    low = torch.rand(B, 3, max(2, H // 16), max(2, W // 16), generator=g)
+    x = torch.nn.functional.interpolate(low, size=(H, W), mode="bilinear", align_corners=False)
+    x = x * 200 + torch.rand(B, 3, H, W, generator=g) * 40
+    return x.clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def _frame(layer):
+    """(net, image batch (1,H,W,3), its LLDO container, parsed header, tile streams), encoded once per layer."""
+    if layer not in _FRAMES:
+        net = _net(layer)
+        x = _images(1, H, W, 31)
+        blob = codec.encode_tiled(net, x, tile=TILE, overlap=OV)[0]
+        hdr, tiles = codec.parse_lapped(blob)
+        assert (hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"], hdr["overlap"]) == (56, 56, 2, 3, OV)
+        _FRAMES[layer] = (net, x, blob, hdr, tiles)
+    return _FRAMES[layer]
+
+
+def _padded_crop(img, ty, tx, th, tw, sh, sw):
+    """(H,W,3) -> the (1,th,tw,3) crop at (ty*sh, tx*sw) of the image padded by repeating its last row and column."""
+    Hi, Wi, _ = img.shape
+    ri = torch.arange(ty * sh, ty * sh + th).clamp(max=Hi - 1)
+    ci = torch.arange(tx * sw, tx * sw + tw).clamp(max=Wi - 1)
+    return img[ri][:, ci][None].contiguous()
+
+
+def _covering(grid, region):
+    """The tile indexes that cover a pixel of the region, ascending (by trying every tile)."""
+    Hi, Wi, th, tw, ov, ny, nx = grid
+    y0, x0, h, w = region
+    sh, sw = th - ov, tw - ov
+    return [ty * nx + tx for ty in range(ny) for tx in range(nx)
+            if ty * sh < y0 + h and ty * sh + th > y0 and tx * sw < x0 + w and tx * sw + tw > x0]
+
+
+def _ref_blend(vals, grid, region):
+    """The reference blend on the host in fp32: vals {tile index: (3,th,tw) CPU tensor}; per tile in ascending index
+    acc = acc + w * v as two separately rounded torch operations, w = wy * wx of codec.lap_weights -> (3,h,w)."""
+    Hi, Wi, th, tw, ov, ny, nx = grid
+    y0, x0, h, w = region
+    sh, sw = th - ov, tw - ov
+    acc = torch.zeros(3, h, w, dtype=torch.float32)
+    for t in sorted(vals):
+        ty, tx = divmod(t, nx)
+        wgt = codec.lap_weights(th, ov, ty, ny)[:, None] * codec.lap_weights(tw, ov, tx, nx)[None, :]
+        a0, a1 = max(ty * sh, y0), min(ty * sh + th, y0 + h)
+        c0, c1 = max(tx * sw, x0), min(tx * sw + tw, x0 + w)
+        if a0 >= a1 or c0 >= c1:
+            continue
+        ly, lx = slice(a0 - ty * sh, a1 - ty * sh), slice(c0 - tx * sw, c1 - tx * sw)
+        prod = wgt[ly, lx] * vals[t].float()[:, ly, lx]
+        acc[:, a0 - y0:a1 - y0, c0 - x0:c1 - x0] = acc[:, a0 - y0:a1 - y0, c0 - x0:c1 - x0] + prod
+    return acc
+
+
+def _coverage(grid):
+    """(H,W) int tensor: the number of tiles covering each pixel."""
+    Hi, Wi, th, tw, ov, ny, nx = grid
+    n = torch.zeros(Hi, Wi, dtype=torch.int64)
+    for ty in range(ny):
+        for tx in range(nx):
+            n[ty * (th - ov):ty * (th - ov) + th, tx * (tw - ov):tx * (tw - ov) + tw] += 1
+    return n
+
+
+def _blend_groups(y, grid, region, lst, g):
+    """ops.ycc_tiles_blend of the tiles lst (slots of y in that order) in groups of g -> acc (3,h,w) on the host."""
+    acc = torch.zeros(3, 1, 1, region[2], region[3], device=DEV)
+    for a in range(0, len(lst), g):
+        ops.ycc_tiles_blend(y[:, a:a + g].contiguous(), grid, region, lst[a:a + g], acc)
+    return acc.cpu()[:, 0, 0]
+
+
+def _capture(monkeypatch):
+    """Wraps the codec._decode_tiles hook -> list of (n, result on the host) per call."""
+    seen = []
+    real = codec._decode_tiles
+
+    def wrapped(nets, s_xe, s_xo, th_, tw_, n, **kw):
+        out = real(nets, s_xe, s_xo, th_, tw_, n, **kw)
+        seen.append((n, out.detach().cpu()))
+        return out
+    monkeypatch.setattr(codec, "_decode_tiles", wrapped)
+    return seen
+
+
+# ------------------------------------------------------------------------------------------------ 1. gather
+@pytest.mark.parametrize("B,Hi,Wi,th,tw,ov", [(2, 100, 150, 56, 56, 8), (1, 37, 300, 40, 64, 16), (2, 70, 100, 32, 48, 16)])
+def test_lapped_gather_equals_the_pad_kernel_on_the_padded_crop(B, Hi, Wi, th, tw, ov):
+    sh, sw = th - ov, tw - ov
+    count = lambda size, t, s: 1 if t >= size else -(-(size - t) // s) + 1
+    ny, nx = count(Hi, th, sh), count(Wi, tw, sw)
+    img = torch.randint(0, 256, (B, Hi, Wi, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(Hi))
+    dimg = img.to(DEV)
+    T = B * ny * nx
+    y = ops.u8hwc_to_ycc_tiles_lapped(dimg, th, tw, ov, ny, nx, 0, T)
+    assert y.shape == (3, T, 1, th, tw)
+    for t in range(T):
+        b, r = divmod(t, ny * nx)
+        ty, tx = divmod(r, nx)
+        ref = ops.u8hwc_to_ycc_pad(_padded_crop(img[b], ty, tx, th, tw, sh, sw).to(DEV), th, tw)
+        assert torch.equal(y[:, t:t + 1], ref), t
+    assert T > 2 and torch.equal(ops.u8hwc_to_ycc_tiles_lapped(dimg, th, tw, ov, ny, nx, 1, T - 2), y[:, 1:T - 1])
+    with pytest.raises(_lib.LLDWTError, match="tile range"):
+        ops.u8hwc_to_ycc_tiles_lapped(dimg, th, tw, ov, ny, nx, 1, T)
+    with pytest.raises(_lib.LLDWTError, match="overlap"):
+        ops.u8hwc_to_ycc_tiles_lapped(dimg, th, tw, ov + 1, ny, nx, 0, T)
+    with pytest.raises(_lib.LLDWTError, match="overlap"):
+        ops.u8hwc_to_ycc_tiles_lapped(dimg, th, tw, 2 * ov if 4 * ov > min(th, tw) else 64, ny, nx, 0, T)
+    if nx > 1:
+        with pytest.raises(_lib.LLDWTError, match="cover"):
+            ops.u8hwc_to_ycc_tiles_lapped(dimg, th, tw, ov, ny, nx - 1, 0, 1)
+
+
+# ------------------------------------------------------------------------------------------------ 2. blend
+_BLEND = [
+    # H, W, th, tw, ov, ny, nx, region
+    (100, 150, 56, 56, 8, 2, 3, None),
+    (100, 150, 56, 56, 8, 2, 3, (40, 50, 20, 55)),        # cuts through both bands of the middle column and the row band
+    (100, 150, 56, 56, 8, 2, 3, (50, 100, 3, 2)),         # inside the four-tile corner
+    (70, 100, 32, 48, 16, 4, 3, None),                    # ov = th / 2: every interior row lies in a band
+    (70, 100, 32, 48, 16, 4, 3, (15, 31, 40, 34)),
+    (33, 600, 40, 64, 8, 1, 11, None),                    # one tile high, more than one block along a row
+    (33, 600, 40, 64, 8, 1, 11, (5, 250, 20, 300)),
+]
+
+
+@pytest.mark.parametrize("Hi,Wi,th,tw,ov,ny,nx,region", _BLEND)
+def test_blend_equals_the_host_reference_for_every_grouping(Hi, Wi, th, tw, ov, ny, nx, region):
+    grid = (Hi, Wi, th, tw, ov, ny, nx)
+    region = region or (0, 0, Hi, Wi)
+    g = torch.Generator().manual_seed(Wi + th)
+    vals = torch.randn(3, ny * nx, 1, th, tw, generator=g)
+    lst = _covering(grid, region)
+    if region == (0, 0, Hi, Wi):
+        assert lst == list(range(ny * nx))
+    ref = _ref_blend({t: vals[:, t, 0] for t in lst}, grid, region)
+    y = vals[:, lst].contiguous().to(DEV)
+    got = {k: _blend_groups(y, grid, region, lst, k) for k in (1, 3, len(lst))}
+    for k, acc in got.items():
+        assert torch.equal(acc + 0.0, ref + 0.0), k
+        assert torch.equal(acc, got[1]), k
+    # a pixel one tile covers holds that tile's sample
+    y0, x0, h, w = region
+    one = _coverage(grid)[y0:y0 + h, x0:x0 + w] == 1
+    plain = torch.zeros(3, h, w)
+    for t in lst:
+        ty, tx = divmod(t, nx)
+        a0, a1 = max(ty * (th - ov), y0), min(ty * (th - ov) + th, y0 + h)
+        c0, c1 = max(tx * (tw - ov), x0), min(tx * (tw - ov) + tw, x0 + w)
+        if a0 < a1 and c0 < c1:
+            plain[:, a0 - y0:a1 - y0, c0 - x0:c1 - x0] = vals[:, t, 0, a0 - ty * (th - ov):a1 - ty * (th - ov),
+                                                              c0 - tx * (tw - ov):c1 - tx * (tw - ov)]
+    assert torch.equal((got[1] + 0.0)[:, one], (plain + 0.0)[:, one])
+    assert one.any() or region == (50, 100, 3, 2)
+    # tiles that are not in the group leave the accumulator alone: one tile blended alone touches only its own pixels
+    acc = torch.full((3, 1, 1, h, w), 7.0, device=DEV)
+    ops.ycc_tiles_blend(y[:, :1].contiguous(), grid, region, lst[:1], acc)
+    ty, tx = divmod(lst[0], nx)
+    mine = torch.zeros(Hi, Wi, dtype=torch.bool)
+    mine[ty * (th - ov):ty * (th - ov) + th, tx * (tw - ov):tx * (tw - ov) + tw] = True
+    assert torch.equal(acc.cpu()[:, 0, 0][:, ~mine[y0:y0 + h, x0:x0 + w]],
+                       torch.full((3, int((~mine[y0:y0 + h, x0:x0 + w]).sum())), 7.0))
+
+
+def test_blend_refuses_bad_arguments():
+    grid = (100, 150, 56, 56, 8, 2, 3)
+    y = torch.zeros(3, 2, 1, 56, 56, device=DEV)
+    acc = torch.zeros(3, 1, 1, 100, 150, device=DEV)
+    with pytest.raises(_lib.LLDWTError, match="overlap"):
+        ops.ycc_tiles_blend(y, (100, 150, 56, 56, 12, 2, 3), (0, 0, 100, 150), [0, 1], acc)
+    with pytest.raises(_lib.LLDWTError, match="overlap"):
+        ops.ycc_tiles_blend(y, (100, 150, 56, 56, 32, 2, 5), (0, 0, 100, 150), [0, 1], acc)
+    with pytest.raises(_lib.LLDWTError, match="cover"):
+        ops.ycc_tiles_blend(y, (100, 150, 56, 56, 8, 2, 2), (0, 0, 100, 150), [0, 1], acc)
+    with pytest.raises(_lib.LLDWTError, match="region"):
+        ops.ycc_tiles_blend(y, grid, (1, 0, 100, 150), [0, 1], acc)
+    with pytest.raises(_lib.LLDWTError, match="tile indexes"):
+        ops.ycc_tiles_blend(y, grid, (0, 0, 100, 150), [0, 6], acc)
+    with pytest.raises(_lib.LLDWTError, match="tile indexes"):
+        ops.ycc_tiles_blend(y, grid, (0, 0, 100, 150), [1, 1], acc)
+    with pytest.raises(_lib.LLDWTError, match="acc"):
+        ops.ycc_tiles_blend(y, grid, (0, 0, 50, 150), [0, 1], acc)
+    lib = _lib.load()
+    slots = torch.tensor([0, 1, -1, -1, -1], dtype=torch.int32, device=DEV)         # one entry short of the 2 x 3 grid
+    rc = lib.lldwt_ycc_tiles_blend(y.data_ptr(), slots.data_ptr(), 5, 2, 100, 150, 56, 56, 8, 2, 3, 0, 0, 100, 150,
+                                   acc.data_ptr(), None)
+    assert rc != 0 and b"slot table" in lib.lldwt_last_error()
+    assert float(acc.abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------ 3. ramp
+@pytest.mark.parametrize("a,b", [(0.25, -0.375), (0.3141592, 0.1234567), (-0.2, 0.45)])
+def test_two_constant_tiles_give_a_linear_ramp(a, b):
+    th, tw, ov = 16, 32, 8
+    grid = (th, 2 * tw - ov, th, tw, ov, 1, 2)
+    y = torch.empty(3, 2, 1, th, tw)
+    y[:, 0], y[:, 1] = a, b
+    acc = _blend_groups(y.to(DEV), grid, (0, 0, th, 2 * tw - ov), [0, 1], 2)
+    fa, fb = torch.tensor(a, dtype=torch.float32), torch.tensor(b, dtype=torch.float32)
+    assert torch.equal(acc[:, :, :tw - ov], fa.expand(3, th, tw - ov))                # flat, exactly a
+    assert torch.equal(acc[:, :, tw:], fb.expand(3, th, tw - ov))                     # flat, exactly b
+    row = acc[0, 3, tw - ov - 1:tw + 1].double()                                      # a, the ov ramp samples, b
+    steps = row.diff()
+    assert bool((steps * (b - a) > 0).all())                                          # monotone, towards b
+    want = abs(float(fb.double() - fa.double())) / ov
+    # every ramp sample is fl(fl(w a) + fl((1 - w) b)): three roundings of values no larger than max(|a|, |b|)
+    tol = 2 * 3 * 2.0 ** -24 * max(abs(a), abs(b))
+    assert float((steps[1:-1].abs() - want).abs().max()) <= tol                       # adjacent steps: |a - b| / ov
+    assert abs(abs(float(steps[0])) - want / 2) <= tol and abs(abs(float(steps[-1])) - want / 2) <= tol
+    if (a, b) == (0.25, -0.375):                                                      # dyadic values: no rounding at all
+        assert torch.equal(steps[1:-1], torch.full((ov - 1,), (b - a) / ov, dtype=torch.float64))
+    assert torch.equal(acc[0], acc[1]) and torch.equal(acc[0, 0].expand(th, -1), acc[0])
+
+
+# ------------------------------------------------------------------------------------------------ 4. coded frames
+@pytest.mark.parametrize("layer", LAYERS)
+def test_lapped_frame_streams_and_decoded_bytes(layer, monkeypatch):
+    net, x, blob, hdr, tiles = _frame(layer)
+    assert blob[:4] == b"LLDO" and codec.read_header(blob)["overlap"] == OV
+    th, tw, ny, nx = hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"]
+    sh, sw = th - OV, tw - OV
+    grid = (H, W, th, tw, OV, ny, nx)
+    # every tile's streams are those of encode_images of its padded crop
+    pads = torch.cat([_padded_crop(x[0], t // nx, t % nx, th, tw, sh, sw) for t in range(ny * nx)])
+    ref = codec.encode_images(net, pads)
+    for t in range(ny * nx):
+        assert tiles[t] == codec.parse_container(ref[t])[1], t
+    # outside the overlap bands: the bytes of the per-tile decode
+    per_tile = codec.decode_images(net, ref)
+    seen = _capture(monkeypatch)
+    got = codec.decode_tiled(net, blob)
+    assert got.shape == (H, W, 3) and got.dtype == torch.uint8 and got.device.type == "cpu"
+    assert [n for n, _ in seen] == [ny * nx]
+    one = _coverage(grid) == 1
+    plain = torch.zeros(H, W, 3, dtype=torch.uint8)
+    for t in range(ny * nx):
+        ty, tx = divmod(t, nx)
+        hh, ww = min(th, H - ty * sh), min(tw, W - tx * sw)
+        plain[ty * sh:ty * sh + hh, tx * sw:tx * sw + ww] = per_tile[t][:hh, :ww]
+    assert one.any() and not one.all() and torch.equal(got[one], plain[one])
+    # everywhere: the existing output kernel on the host reference blend of the tiles' float reconstructions
+    xhat = seen[0][1]
+    acc = _ref_blend({t: xhat[:, t, 0] for t in range(ny * nx)}, grid, (0, 0, H, W))
+    want = ops.ycc_tiles_to_u8hwc(acc[:, None, None].contiguous().to(DEV), (H, W, H, W, 1, 1), (0, 0, H, W))[0].cpu()
+    assert torch.equal(got, want)
+
+
+def test_one_tile_high_frame(monkeypatch):
+    net = _net("onlyEZWT")
+    x = _images(1, 56, 150, 32)
+    blob = codec.encode_tiled(net, x, tile=TILE, overlap=OV)[0]
+    hdr, tiles = codec.parse_lapped(blob)
+    assert (hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"]) == (56, 56, 1, 3)
+    grid = (56, 150, 56, 56, OV, 1, 3)
+    seen = _capture(monkeypatch)
+    got = codec.decode_tiled(net, blob)
+    xhat = seen[0][1]
+    acc = _ref_blend({t: xhat[:, t, 0] for t in range(3)}, grid, (0, 0, 56, 150))
+    want = ops.ycc_tiles_to_u8hwc(acc[:, None, None].contiguous().to(DEV), (56, 150, 56, 150, 1, 1), (0, 0, 56, 150))[0].cpu()
+    assert torch.equal(got, want)
+    assert torch.equal(codec.decode_tiled(net, blob, region=(3, 40, 50, 20)), got[3:53, 40:60])
+
+
+# ------------------------------------------------------------------------------------------------ 5. regions
+def test_region_decode_equals_the_crop_and_touches_only_its_tiles(monkeypatch):
+    net, x, blob, hdr, tiles = _frame("conditioned2ZTsepSubbands")
+    grid = (H, W, hdr["th"], hdr["tw"], OV, hdr["ny"], hdr["nx"])
+    full = codec.decode_tiled(net, blob)
+    seen = []
+    real = codec._decode_tiles
+
+    def counting(nets, s_xe, s_xo, th_, tw_, n):
+        seen.append(n)
+        return real(nets, s_xe, s_xo, th_, tw_, n)
+    monkeypatch.setattr(codec, "_decode_tiles", counting)
+    cases = [((10, 20, 30, 20), 1), ((10, 20, 30, 29), 2), ((46, 46, 2, 2), 1), ((47, 47, 2, 2), 4), ((48, 48, 8, 8), 4),
+             ((55, 0, 1, 150), 6), ((56, 56, 44, 40), 1), ((99, 149, 1, 1), 1), ((0, 0, 100, 150), 6)]
+    for region, touched in cases:
+        y0, x0, h, w = region
+        assert len(_covering(grid, region)) == touched
+        seen.clear()
+        got = codec.decode_tiled(net, blob, region=region, tiles_per_call=2)
+        assert torch.equal(got, full[y0:y0 + h, x0:x0 + w]), region
+        assert sum(seen) == touched and max(seen) <= 2, (region, seen)
+    seen.clear()
+    for bad in [(0, 0, 101, 10), (-1, 0, 5, 5), (0, 140, 5, 11), (0, 0, 0, 5), (1, 2, 3)]:
+        with pytest.raises(ValueError, match="region"):
+            codec.decode_tiled(net, blob, region=bad)
+    assert not seen
+
+
+# ------------------------------------------------------------------------------------------------ 6. group size
+def test_tiles_per_call_does_not_change_the_result():
+    net, x, blob, hdr, tiles = _frame("conditioned2ZTsepSubbands")
+    x2 = torch.cat([x, _images(1, H, W, 33)])
+    ref = codec.encode_tiled(net, x2, tile=TILE, tiles_per_call=1, overlap=OV)
+    assert ref[0] == blob                                                   # the batch does not change an image's bytes
+    for g in (3, 12):
+        assert codec.encode_tiled(net, x2, tile=TILE, tiles_per_call=g, overlap=OV) == ref, g
+    img = codec.decode_tiled(net, ref[1], tiles_per_call=1)
+    for g in (3, 6):
+        assert torch.equal(codec.decode_tiled(net, ref[1], tiles_per_call=g), img), g
+
+
+# ------------------------------------------------------------------------------------------------ 7. reduced decoding
+@pytest.mark.parametrize("k", [1, L])
+def test_reduced_decode_blends_the_ll_tiles(k, monkeypatch):
+    net, x, blob, hdr, tiles = _frame("conditioned2ZTsepSubbands")
+    Hr, Wr = -(-H // (1 << k)), -(-W // (1 << k))
+    grid = (Hr, Wr, hdr["th"] >> k, hdr["tw"] >> k, OV >> k, hdr["ny"], hdr["nx"])
+    inv_a, b = codec.ll_norm(net, k)
+    seen = _capture(monkeypatch)
+    for region in [None, (Hr // 3, Wr // 4, Hr // 2, Wr // 2)]:
+        seen.clear()
+        got = codec.decode_tiled(net, blob, region=region, reduce=k)
+        reg = region or (0, 0, Hr, Wr)
+        lst = _covering(grid, reg)
+        assert [n for n, _ in seen] == [len(lst)]
+        ll = seen[0][1]
+        assert ll.shape == (3, len(lst), 1, grid[2], grid[3])
+        acc = _ref_blend({t: ll[:, j, 0] for j, t in enumerate(lst)}, grid, reg)
+        h, w = reg[2], reg[3]
+        want = ops.ll_tiles_to_u8hwc(acc[:, None, None].contiguous().to(DEV), (h, w, h, w, 1, 1), (0, 0, h, w), inv_a, b)
+        assert got.shape == (h, w, 3) and torch.equal(got, want[0].cpu()), region
+    full = codec.decode_tiled(net, blob, reduce=k, tiles_per_call=1)
+    assert torch.equal(full[reg[0]:reg[0] + h, reg[1]:reg[1] + w], got)
+    with pytest.raises(ValueError, match="reduce"):
+        codec.decode_tiled(net, blob, reduce=L + 1)
+
+
+# ------------------------------------------------------------------------------------------------ 8. device coder
+def test_device_coder_round_trip():
+    net, x, blob, hdr, tiles = _frame("conditioned2ZTsepSubbands")
+    gblob = codec.encode_tiled(net, x, tile=TILE, coder="gpu", overlap=OV)[0]
+    gh = codec.read_header(gblob)
+    assert gblob[:4] == b"LLDO" and gh["coder"] == "gpu" and gh["overlap"] == OV and gblob != blob
+    assert torch.equal(codec.decode_tiled(net, gblob), codec.decode_tiled(net, blob))      # the same symbols, another coder
+    assert torch.equal(codec.decode_tiled(net, gblob, region=(10, 40, 30, 30), reduce=1),
+                       codec.decode_tiled(net, blob, region=(10, 40, 30, 30), reduce=1))
+
+
+# ------------------------------------------------------------------------------------------------ 9. overlap = 0
+def test_overlap_zero_is_the_plain_tiled_container():
+    net = _net("onlyEZWT")
+    x = _images(1, 90, 120, 34)
+    plain = codec.encode_tiled(net, x, tile=48)
+    assert codec.encode_tiled(net, x, tile=48, overlap=0) == plain and plain[0][:4] == b"LLDT"
+    for bad in (12, 4, 64, -8):
+        with pytest.raises(ValueError, match="overlap"):
+            codec.encode_tiled(net, x, tile=48, overlap=bad)
+
+
+# ------------------------------------------------------------------------------------------------ 10. refusals
+def test_identity_refusals(monkeypatch):
+    net, x, blob, hdr, tiles = _frame("conditioned2ZTsepSubbands")
+    p = net.model1.entropymodel.plc_list[0][0].weight
+    old = p.data.clone()
+    with torch.no_grad():
+        p.view(-1)[3] = torch.nextafter(p.view(-1)[3], torch.tensor(float("inf"), device=DEV))
+    try:
+        with pytest.raises(ValueError, match="weights"):
+            codec.decode_tiled(net, blob)
+    finally:
+        with torch.no_grad():
+            p.copy_(old)
+    monkeypatch.setenv("LLDWT_PLC_MODE", "f32")
+    with pytest.raises(ValueError, match="plc_mode"):
+        codec.decode_tiled(net, blob)
+    monkeypatch.delenv("LLDWT_PLC_MODE")
+    with pytest.raises(ValueError, match="entropy layer"):
+        codec.decode_tiled(_net("onlyEZWT"), blob)
+    with pytest.raises(ValueError, match="magic"):
+        codec.decode_images(net, [blob])
+
+
+# ------------------------------------------------------------------------------------------------ 11. command line
+def test_command_line_overlap(tmp_path):
+    from PIL import Image
+    import numpy as np
+    cfg = {"dwtlevels": 3, "entropy_layer": "onlyEZWT", "seed": 7}
+    (tmp_path / "cfg.json").write_text(json.dumps(cfg))
+    x = _images(1, 97, 131, 35)
+    Image.fromarray(x[0].numpy()).save(tmp_path / "in.png")
+    tool = os.path.join(REPO, "tools", "codec.py")
+    run = lambda *a: subprocess.run([sys.executable, tool] + list(a), capture_output=True, text=True, timeout=600)
+    c = str(tmp_path / "cfg.json")
+    r = run("encode", "--config", c, "--tile", "64", "--overlap", "8", str(tmp_path / "in.png"), str(tmp_path / "o.lld"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert "tiles: 2 x 3" in r.stdout and "overlap: 8" in r.stdout
+    blob = (tmp_path / "o.lld").read_bytes()
+    assert blob[:4] == b"LLDO"
+    r = run("info", str(tmp_path / "o.lld"))
+    assert r.returncode == 0 and "overlap" in r.stdout and "share 8 pixels" in r.stdout and "2 x 3 tiles" in r.stdout, r.stderr
+    r = run("decode", "--config", c, "--region", "10,20,60,70", str(tmp_path / "o.lld"), str(tmp_path / "r.png"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    reg = np.asarray(Image.open(tmp_path / "r.png").convert("RGB"))
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("codec_cli", tool)
+    cli = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cli)
+    full = codec.decode_tiled(cli.build_net(c), blob).numpy()
+    assert full.shape == (97, 131, 3) and np.array_equal(reg, full[10:70, 20:90])
+    r = run("encode", "--config", c, "--overlap", "8", str(tmp_path / "in.png"), str(tmp_path / "u.lld"))
+    assert r.returncode != 0 and "--tile" in r.stderr

@@ -6,6 +6,8 @@
                                                             at each reduce factor)
 
     encode --tile N [--tiles-per-call K]   writes a tiled (LLDT) container: N x N target tiles, each an independent image
+    encode --tile N --overlap V            writes a lapped (LLDO) container: neighbouring tiles share V pixels (a power of
+                                           two, 2^dwtlevels <= V <= half a tile) and the decoder cross-fades them
     decode --region y0,x0,h,w              decodes only that region (tiled containers only)
     decode --reduce k                      decodes the image at 1/2^k of each side from the coarse levels only (0 <= k <=
                                            dwtlevels; with --region, the region is in the reduced image's coordinates)
@@ -81,6 +83,8 @@ def main(argv=None):
         p.add_argument("src")
         p.add_argument("dst")
     sub.choices["encode"].add_argument("--tile", type=int, help="write a tiled container with this target tile side")
+    sub.choices["encode"].add_argument("--overlap", type=int, default=0,
+                                       help="with --tile: pixels neighbouring tiles share, cross-faded on decode (default 0)")
     sub.choices["encode"].add_argument("--coder", choices=("host", "gpu"), default="host",
                                        help="entropy coder: host (rans64, the default) or gpu (irans32 on the device)")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
@@ -102,6 +106,9 @@ def main(argv=None):
             print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
         if "ny" in hdr:
             print("%-15s %d x %d tiles of %d x %d (rows x columns)" % ("grid", hdr["ny"], hdr["nx"], hdr["th"], hdr["tw"]))
+            if hdr["overlap"]:
+                print("%-15s neighbouring tiles share %d pixels (stride %d x %d)"
+                      % ("lapped", hdr["overlap"], hdr["th"] - hdr["overlap"], hdr["tw"] - hdr["overlap"]))
         for k, n in enumerate(codec.reduce_bytes(hdr)):
             print("%-15s %d x %d: %d bytes" % ("reduce %d" % k, -(-hdr["W"] >> k), -(-hdr["H"] >> k), n))
         return 0
@@ -125,7 +132,13 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tile is None:
+            if a.overlap:
+                print("--overlap needs --tile", file=sys.stderr)
+                return 2
             blob = codec.encode_images(net, x, coder=a.coder)[0]
+        elif a.overlap:
+            blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, coder=a.coder,
+                                      overlap=a.overlap)[0]
         else:
             blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, coder=a.coder)[0]
         torch.cuda.synchronize()
@@ -137,10 +150,12 @@ def main(argv=None):
         if a.tile is not None:
             hdr = codec.read_header(blob)
             print("tiles: %d x %d of %dx%d" % (hdr["ny"], hdr["nx"], hdr["tw"], hdr["th"]))
+            if hdr["overlap"]:
+                print("overlap: %d" % hdr["overlap"])
     else:
         with open(a.src, "rb") as f:
             blob = f.read()
-        tiled = blob[:4] == codec.TILED_MAGIC
+        tiled = blob[:4] in (codec.TILED_MAGIC, codec.LAPPED_MAGIC)
         region = None
         if a.region is not None:
             if not tiled:

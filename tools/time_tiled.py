@@ -4,6 +4,11 @@ spent in the host rANS calls (lldwt_rans_decode_multi) and their count (one host
 
     python tools/time_tiled.py --mode tiled --height 2160 --width 3840 --tile 512
     python tools/time_tiled.py --mode untiled --height 512 --width 512 [--repo DIR]   (DIR: another checkout to time)
+    python tools/time_tiled.py --mode tiled --tile 512 --overlap 16     (lapped tiles; also PSNR / MS-SSIM and the seam figure)
+
+The seam figure (tiled): the mean absolute luma step of the decoded image across the adjacent pixel pairs that straddle a
+nominal tile border (the middle of each overlap band; for overlap 0 the tile edge), divided by the same mean over all other
+adjacent pairs, rows and columns together.  1 means a border is no rougher than the rest of the picture.
 """
 import argparse
 import json
@@ -21,6 +26,7 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--tile", type=int, default=512)
+    ap.add_argument("--overlap", type=int, default=0)
     ap.add_argument("--tiles-per-call", type=int, default=32)
     ap.add_argument("--region", help="y0,x0,h,w: time a region decode too (tiled)")
     ap.add_argument("--reps", type=int, default=3)
@@ -41,7 +47,8 @@ def main():
     x = (x + torch.rand(1, 3, H, W, generator=g) * 40).clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
     if a.mode == "tiled":
-        enc = lambda: codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call)[0]
+        kw = {"overlap": a.overlap} if a.overlap else {}
+        enc = lambda: codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, **kw)[0]
         dec = lambda b, r=None: codec.decode_tiled(net, b, region=r, tiles_per_call=a.tiles_per_call)
     else:
         enc = lambda: codec.encode_images(net, x)[0]
@@ -90,6 +97,12 @@ def main():
     if a.mode == "tiled":
         hdr = codec.read_header(blob)
         res.update(tile=[hdr["th"], hdr["tw"]], grid=[hdr["ny"], hdr["nx"]], tiles_per_call=a.tiles_per_call)
+        if hasattr(codec, "quality"):
+            img = dec(blob)
+            q = codec.quality(x[0], img)
+            ov = hdr.get("overlap", 0)
+            res.update(overlap=ov, psnr=q["psnr"], msssim=q["msssim"],
+                       seam=seam_figure(img, hdr["th"], hdr["tw"], ov, hdr["ny"], hdr["nx"]))
         if a.region:
             reg = tuple(int(v) for v in a.region.split(","))
             for _ in range(a.reps):
@@ -97,6 +110,28 @@ def main():
                 tr.append(t)
             res.update(region=reg, region_decode_s=statistics.median(tr))
     print(json.dumps(res))
+
+
+def seam_figure(img, th, tw, ov, ny, nx):
+    """The module docstring's seam figure of a decoded (H,W,3) uint8 image."""
+    import torch
+    luma = (img.double() * torch.tensor([0.2126, 0.7152, 0.0722], dtype=torch.float64)).sum(-1)
+    num = den = 0.0
+    cnt_b = cnt_o = 0
+    for axis, t, n in ((0, th, ny), (1, tw, nx)):
+        d = luma.diff(dim=axis).abs()
+        border = torch.zeros(d.shape[axis], dtype=torch.bool)
+        for q in range(1, n):
+            i = q * (t - ov) + ov // 2 - 1               # the pair (i, i + 1) straddles the border of tiles q - 1 and q
+            if 0 <= i < d.shape[axis]:
+                border[i] = True
+        sel = d[border] if axis == 0 else d[:, border]
+        rest = d[~border] if axis == 0 else d[:, ~border]
+        num, cnt_b = num + float(sel.sum()), cnt_b + sel.numel()
+        den, cnt_o = den + float(rest.sum()), cnt_o + rest.numel()
+    if not cnt_b or not den:
+        return None
+    return (num / cnt_b) / (den / cnt_o)
 
 
 if __name__ == "__main__":
