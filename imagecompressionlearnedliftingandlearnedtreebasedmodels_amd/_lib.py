@@ -191,6 +191,9 @@ SIGNATURES = {
     "lldwt_msssim_ws_floats": (_i64, [_i64, _i64, _i64, _i]),
     "lldwt_msssim_forward": (_i, [_p, _p, _f, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p]),
     "lldwt_msssim_backward": (_i, [_p, _p, _f, _i64, _i64, _i64, _i, _p, _p, _p, C.c_double, _p, _p, _p]),
+    "lldwt_resid_analyse": (_i, [_p, _p, _p] + [_i64] * 15 + [_i] + [_p] * 6),
+    "lldwt_resid_contexts": (_i, [_p, _p] + [_i64] * 15 + [_p] * 4),
+    "lldwt_resid_apply": (_i, [_p, _p] + [_i64] * 15 + [_i] + [_p] * 4),
 }
 
 _lib = None

@@ -62,6 +62,30 @@ streams of levels k .. L-1 are decoded (the streams of finer levels are never ha
 for the top L-k levels, and the LL band at level k is brought to the image's scale by lifting_dwt_nets.ll_affine before the
 colour conversion.  reduce=0 is the full decode.  ``reduce_bytes`` gives, per factor, the header plus stream bytes such a
 decode reads.  The container format is the same.
+
+Lossless and near-lossless coding (``encode_images(..., near=d)``, ``encode_tiled(..., near=d)``): a residual
+layer over the decoded base image (residual.py, csrc/residual.hip).  near=0 returns the input bit for bit, near=d in 1..32
+bounds the error of every sample by d; near=None writes the containers above, byte for byte.  A unit is the image of an LLDW
+base or the in-image rectangle of one tile of an LLDT base (lapped bases are refused).  Refined container, version 1:
+
+    magic             4 bytes   b"LLDR"
+    format version    u8        1
+    near d            u8        0 lossless, 1..32 the bound
+    classes           u8        8 activity classes per channel (24 contexts per unit)
+    ladder id         u8        1 (64 two-sided geometric tables, b_s = 0.05 * 1600^(s/63))
+    table CRC32       u32       zlib.crc32 of the quantised ladder of d as little-endian int32 (residual.Tables.cdf)
+    base length       LEB128
+    base container    the complete LLDW or LLDT container, as encode_images / encode_tiled write it without ``near``
+    unit count        u32       1 over LLDW, ny * nx over LLDT
+    per unit          cs(xh) u64, cs(x) u64 (0 when d > 0), 24 u8 table indexes (context c * 8 + a), units in tile order
+    stream lengths    LEB128 varints, 3 per unit (R, G, B)
+    payload           the streams in the same order, coded by the base container's coder
+    CRC32             u32       zlib.crc32 of every byte before it
+
+``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
+decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
+touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
+ValueError("reconstruction check: ...") on a mismatch.
 """
 import hashlib
 import struct
@@ -85,6 +109,10 @@ _TFIXED = struct.Struct("<4sBBBBIIIIHHH")     # magic .. H, W, th, tw, ny, nx, n
 LAPPED_MAGIC = b"LLDO"
 LAPPED_FORMAT_VERSION = 1
 _OFIXED = struct.Struct("<4sBBBBIIIIHHHH")    # magic .. H, W, th, tw, ny, nx, overlap, numerics version
+REFINED_MAGIC = b"LLDR"
+REFINED_FORMAT_VERSION = 1
+_RFIXED = struct.Struct("<4sBBBBI")            # magic, version, near, classes, ladder id, table CRC32
+_RUNIT = struct.Struct("<QQ24s")               # cs(xh), cs(x), the 24 table indexes
 _PLANES = 3
 # coder name of the API -> value of the arithmetic string's "coder" key (None: the key is absent)
 CODER_KEYS = {"host": None, "gpu": "irans32"}
@@ -356,13 +384,96 @@ def parse_lapped(blob):
     return hdr, tiles
 
 
+def pack_refined(near, table_crc, base, units):
+    """near: the bound d; table_crc: residual.tables(d).crc; base: a complete LLDW or LLDT container; units: per unit, in
+    tile order, dict(cs_xh, cs_x, scales (24 bytes), streams (3 bytes objects)) -> LLDR container."""
+    from .residual import CLASSES, CONTEXTS, LADDER_ID, LADDER_SIZE, MAX_NEAR
+    if not 0 <= int(near) <= MAX_NEAR:
+        raise ValueError("near: %r is outside [0, %d]" % (near, MAX_NEAR))
+    if _magic(base) not in (MAGIC, TILED_MAGIC):
+        raise ValueError("base container: a residual layer goes over an LLDW or LLDT container")
+    bh = read_header(base)
+    if len(units) != bh.get("ny", 1) * bh.get("nx", 1):
+        raise ValueError("unit count: %d units for a base of %d" % (len(units), bh.get("ny", 1) * bh.get("nx", 1)))
+    body = bytearray(_RFIXED.pack(REFINED_MAGIC, REFINED_FORMAT_VERSION, int(near), CLASSES, LADDER_ID,
+                                  table_crc & 0xFFFFFFFF))
+    body += leb128_encode(len(base)) + bytes(base) + struct.pack("<I", len(units))
+    for u in units:
+        sc = bytes(u["scales"])
+        if len(sc) != CONTEXTS or max(sc) >= LADDER_SIZE:
+            raise ValueError("scale index: a unit needs %d table indexes below %d" % (CONTEXTS, LADDER_SIZE))
+        if len(u["streams"]) != _PLANES:
+            raise ValueError("stream count: a unit has %d streams" % _PLANES)
+        body += _RUNIT.pack(u["cs_xh"], u["cs_x"] if near == 0 else 0, sc)
+    return _seal(bytes(body) + _pack_streams([s for u in units for s in u["streams"]]))
+
+
+def parse_refined(blob, check_tables=True):
+    """LLDR container -> (header dict, base container bytes, units), units being per unit dict(cs_xh, cs_x, scales, streams).
+    The header carries near, classes, ladder, table_crc, base (the nested base header), units (the count), base_bytes,
+    residual_bytes (everything but the base) and stream_lengths.  Every structural check raises ValueError naming the
+    field, on the host: magic, version, CRC, truncation, near, classes, ladder id, the base (parsed by its own parser; a
+    lapped base is refused), the unit count against the base grid, a table index >= 64, the stream lengths and -- with
+    check_tables, which builds the ladder with the library's host code -- the table CRC32."""
+    from .residual import CLASSES, LADDER_ID, LADDER_SIZE, MAX_NEAR
+    blob, end = _open(blob, REFINED_MAGIC, REFINED_FORMAT_VERSION, _RFIXED.size + 1 + 4)
+    _, _, near, classes, ladder, table_crc = _RFIXED.unpack_from(blob, 0)
+    if near > MAX_NEAR:
+        raise ValueError("near: the container holds %d, the largest bound is %d" % (near, MAX_NEAR))
+    if classes != CLASSES:
+        raise ValueError("classes: the container holds %d activity classes, this decoder has %d" % (classes, CLASSES))
+    if ladder != LADDER_ID:
+        raise ValueError("ladder id: the container holds %d, this decoder has %d" % (ladder, LADDER_ID))
+    try:
+        blen, pos = leb128_decode(blob, _RFIXED.size, end)
+    except ValueError:
+        raise ValueError("base length: container truncated or varint too long") from None
+    if pos + blen + 4 > end:
+        raise ValueError("base length: container truncated inside the base container (%d bytes announced, %d left)"
+                         % (blen, max(0, end - pos)))
+    base = blob[pos:pos + blen]
+    if _magic(base) not in (MAGIC, TILED_MAGIC):
+        raise ValueError("base container: a residual layer goes over an LLDW or LLDT container (got magic %r)" % base[:4])
+    bh = read_header(base)
+    pos += blen
+    count = struct.unpack_from("<I", blob, pos)[0]
+    pos += 4
+    if count != bh.get("ny", 1) * bh.get("nx", 1):
+        raise ValueError("unit count: the container holds %d units, the base has %d" % (count, bh.get("ny", 1) * bh.get("nx", 1)))
+    if pos + count * _RUNIT.size > end:
+        raise ValueError("per-unit fields: container truncated inside them (%d units of %d bytes announced, %d bytes left)"
+                         % (count, _RUNIT.size, max(0, end - pos)))
+    units = []
+    for u in range(count):
+        cs_xh, cs_x, sc = _RUNIT.unpack_from(blob, pos)
+        pos += _RUNIT.size
+        if max(sc) >= LADDER_SIZE:
+            raise ValueError("scale index: unit %d holds table index %d, the ladder has %d tables" % (u, max(sc), LADDER_SIZE))
+        units.append(dict(cs_xh=cs_xh, cs_x=cs_x, scales=sc))
+    streams, lengths = _parse_streams(blob, pos, end, _PLANES * count)
+    for u in range(count):
+        units[u]["streams"] = streams[_PLANES * u:_PLANES * (u + 1)]
+    if check_tables:
+        from .residual import tables
+        if tables(near).crc != table_crc:
+            raise ValueError("table CRC32: the container's ladder for near=%d has CRC %08x, this platform builds %08x; the "
+                             "streams cannot be decoded here" % (near, table_crc, tables(near).crc))
+    hdr = dict(version=REFINED_FORMAT_VERSION, near=near, classes=classes, ladder=ladder, table_crc=table_crc, base=bh,
+               units=count, base_bytes=blen, residual_bytes=len(blob) - blen, stream_lengths=lengths)
+    return hdr, base, units
+
+
 def _magic(blob):
     return bytes(blob[:4]) if isinstance(blob, (bytes, bytearray, memoryview)) else None
 
 
 def read_header(blob):
-    """The header of a container (LLDW, LLDT or LLDO) as a dict (CPU only; the library is never loaded).  A tiled header
-    carries ``overlap``: 0 for LLDT.  Raises ValueError as parse_container / parse_tiled / parse_lapped."""
+    """The header of a container (LLDW, LLDT, LLDO or LLDR) as a dict (CPU only; the library is never loaded).  A tiled
+    header carries ``overlap``: 0 for LLDT.  An LLDR header carries ``near``, ``residual_bytes`` and the nested base header
+    under ``base`` (parse_refined; the table CRC is compared by the decoders).  Raises ValueError as parse_container /
+    parse_tiled / parse_lapped / parse_refined."""
+    if _magic(blob) == REFINED_MAGIC:
+        return parse_refined(blob, check_tables=False)[0]
     if _magic(blob) == LAPPED_MAGIC:
         return parse_lapped(blob)[0]
     if _magic(blob) == TILED_MAGIC:
@@ -373,7 +484,10 @@ def read_header(blob):
 def reduce_bytes(hdr):
     """-> list of L + 1 ints: entry k is the number of container bytes a decode at reduce=k reads, the header (every byte
     before the payload) plus the xe streams and the xo streams of levels k .. L-1 of every plane (for LLDT / LLDO, of every
-    tile).  The 4-byte CRC32 trailer is not counted.  hdr: read_header's dict (LLDW, LLDT or LLDO); CPU only."""
+    tile).  The 4-byte CRC32 trailer is not counted.  hdr: read_header's dict (LLDW, LLDT or LLDO; for LLDR the base alone is
+    counted, as a reduced decode never reads the residual layer); CPU only."""
+    if "base" in hdr:
+        hdr = hdr["base"]
     L, lengths = hdr["dwtlevels"], hdr["stream_lengths"]
     per = L + 1                                       # streams per plane: xe, xo finest -> coarsest
     if len(lengths) % per:
@@ -528,10 +642,25 @@ def quality(a_u8, b_u8):
     return {"psnr": psnr, "msssim": msssim}
 
 
-def encode_images(net, images_u8, coder="host"):
+def _refine(base_blobs, img, xh, grid, near, coder):
+    """The residual layer of a batch: base_blobs: the B base containers; img, xh: (B,H,W,3) uint8 device tensors (originals,
+    base reconstructions); grid = (H, W, th, tw, ny, nx) -> B LLDR containers."""
+    from . import residual
+    per = grid[4] * grid[5]
+    units = residual.encode_units(img, xh, grid, list(range(len(base_blobs) * per)), near, coder)
+    crc = residual.tables(near).crc
+    return [pack_refined(near, crc, base_blobs[b], units[b * per:(b + 1) * per]) for b in range(len(base_blobs))]
+
+
+def encode_images(net, images_u8, coder="host", near=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
-    default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string)."""
+    default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
+    near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
+    holding the same LLDW bytes plus the residual layer."""
     import torch
+    if near is not None:
+        from .residual import check_near
+        near = check_near(near)
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
@@ -544,15 +673,23 @@ def encode_images(net, images_u8, coder="host"):
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, numerics=CODING_NUMERICS_VERSION, arithmetic=arith,
                digest=weights_digest(net))
     dev = next(net.parameters()).device
-    x = ops.u8hwc_to_ycc_pad(images_u8.to(dev).contiguous(), Hp, Wp)                  # (3,B,1,Hp,Wp)
+    img = images_u8.to(dev).contiguous()
+    x = ops.u8hwc_to_ycc_pad(img, Hp, Wp)                                             # (3,B,1,Hp,Wp)
     groups = [(0, B)] if _batch_invariant(arith) else [(b, b + 1) for b in range(B)]
-    blobs = []
+    blobs, recon = [], []
     with torch.no_grad():
         for a, e in groups:
-            s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder)
+            if near is None:
+                s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder)
+            else:
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder, recon=True)
+                recon.append(ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W))          # the decoder's call on the same values
             for b in range(e - a):
                 streams = [s for p in range(_PLANES) for s in [s_xe[p][b]] + [lev[p][b] for lev in s_xo]]
                 blobs.append(pack_container(hdr, streams))
+        if near is not None:
+            xh = recon[0] if len(recon) == 1 else torch.cat(recon, 0)
+            blobs = _refine(blobs, img, xh.contiguous(), (H, W, Hp, Wp, 1, 1), near, coder)
     return blobs
 
 
@@ -606,17 +743,30 @@ def ll_norm(net, k):
     return torch.tensor(inv, dtype=torch.float32).tolist(), torch.tensor(b, dtype=torch.float32).tolist()
 
 
-def decode_images(net, blobs, reduce=0):
+def decode_images(net, blobs, reduce=0, refine=True):
     """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
     first; then containers of equal (H, W) and coder are decoded together (the coder comes from each header).
     reduce = k in [0, L]: the image at 1/2^k of each side, (ceil(H / 2^k), ceil(W / 2^k), 3), decoded from the xe streams
-    and the levels k .. L-1 only (the module docstring); reduce=0 is the full decode."""
+    and the levels k .. L-1 only (the module docstring); reduce=0 is the full decode.
+    An LLDR container over LLDW is decoded through its base and then refined on the device (lossless or within its bound,
+    DESIGN.md 7.1.5); refine=False, or reduce > 0 (the residual lives at full resolution), gives exactly the base decode."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
+    refined = {}
+    blobs = list(blobs)
+    for i, b in enumerate(blobs):
+        if _magic(b) == REFINED_MAGIC:
+            rhdr, base, units = parse_refined(b)
+            if _magic(base) != MAGIC:
+                raise ValueError("base container: decode_images takes an LLDR over LLDW; this one is over %s (decode_tiled)"
+                                 % bytes(base[:4]).decode("ascii", "replace"))
+            blobs[i] = base
+            if refine and k == 0:
+                refined[i] = (rhdr["near"], units)
     parsed = [parse_container(b) for b in blobs]
     digest, arith = weights_digest(net), arithmetic_string()
     for hdr, _ in parsed:
@@ -639,7 +789,13 @@ def decode_images(net, blobs, reduce=0):
                 s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(k, L)]
                 if k == 0:
                     xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder)
-                    img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W).cpu()
+                    img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W)
+                    for d in sorted({refined[i][0] for i in g if i in refined}):
+                        from . import residual
+                        js = [j for j, i in enumerate(g) if i in refined and refined[i][0] == d]
+                        residual.decode_units(img, (H, W, Hp, Wp, 1, 1), (0, 0, H, W), js,
+                                              [refined[g[j]][1][0] for j in js], d, coder)
+                    img = img.cpu()
                 else:
                     ll = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, first_level=k)
                     Hr, Wr = _reduced(H, k), _reduced(W, k)
@@ -709,19 +865,26 @@ def _tile_streams(s_xe, s_xo, j):
     return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
 
 
-def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0):
+def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
     are those of encode_images(net, padded_tile).  The images are uploaded once; groups of tiles_per_call tiles (over all
     images of the batch) are cut out on the device (lldwt_u8hwc_to_ycc_tiles) and coded together, which bounds the device
     memory; one tile per call in the arithmetics that are not batch invariant.  The bytes do not depend on tiles_per_call.
-    coder: as encode_images."""
+    coder: as encode_images.  near: as encode_images, every tile's in-image rectangle being a unit of the residual layer
+    (LLDR over LLDT; the bytes do not depend on tiles_per_call either); not with overlap > 0, where the decoded pixels are
+    a blend of two units."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
+    if near is not None:
+        from .residual import check_near
+        near = check_near(near)
+        if overlap:
+            raise ValueError("near: a residual layer over lapped tiles (overlap > 0) is not defined; use overlap=0")
     if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
         raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
     nets = net.nets()
@@ -743,6 +906,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     T = B * ny * nx
     g = int(tiles_per_call) if _batch_invariant(arith) else 1
     tiles = []
+    xh = torch.empty_like(img) if near is not None else None
     with torch.no_grad():
         for first in range(0, T, g):
             n = min(g, T - first)
@@ -750,13 +914,21 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
                 x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
             else:
                 x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
-            s_xe, s_xo = encode_strings_planes(nets, x, coder=coder)
+            if near is None:
+                s_xe, s_xo = encode_strings_planes(nets, x, coder=coder)
+            else:
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True)
+                ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W),
+                                       tiles=list(range(first, first + n)), B=B, out=xh)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
-    per = ny * nx
-    if ov:
-        hdr["overlap"] = ov
-        return [pack_lapped(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
-    return [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
+        per = ny * nx
+        if ov:
+            hdr["overlap"] = ov
+            return [pack_lapped(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
+        blobs = [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
+        if near is not None:
+            blobs = _refine(blobs, img, xh, (H, W, th, tw, ny, nx), near, coder)
+    return blobs
 
 
 def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0):
@@ -780,7 +952,7 @@ def _region(region, H, W):
     return y0, x0, h, w
 
 
-def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
+def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True):
     """LLDT or LLDO container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
     LLDO (lapped tiles, _decode_lapped): the tiles covering any pixel of the region, overlap included, are decoded in
@@ -788,6 +960,8 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
     written once, as the single tile of a 1 x 1 grid, by the same output kernels.
     reduce = k in [0, L]: the image at 1/2^k of each side (decode_images); region is then in the coordinates of the reduced
     image, each tile covers th>>k x tw>>k of its pixels and is written by lldwt_ll_tiles_to_u8hwc.
+    LLDR over LLDT: the base and residual streams of the touched tiles are decoded and the region is cut from their refined
+    rectangles; refine=False, or reduce > 0, gives exactly the base decode.
     Every check (container, region, identity) runs on the host before any GPU work."""
     import torch
     from . import ops
@@ -795,10 +969,25 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
     k = _reduce(reduce, L)
     if _magic(blob) == LAPPED_MAGIC:
         return _decode_lapped(net, (layer, nettype, L), blob, region, tiles_per_call, k)
+    units = None
+    if _magic(blob) == REFINED_MAGIC:
+        rhdr, blob, units = parse_refined(blob)
+        if _magic(blob) != TILED_MAGIC:
+            raise ValueError("base container: decode_tiled takes an LLDR over LLDT; this one is over %s (decode_images)"
+                             % bytes(blob[:4]).decode("ascii", "replace"))
+        if not refine or k:
+            units = None
     hdr, tiles = parse_tiled(blob)
     H, W, th, tw, ny, nx = (hdr[key] for key in ("H", "W", "th", "tw", "ny", "nx"))
     H, W, th, tw = _reduced(H, k), _reduced(W, k), th >> k, tw >> k          # tile sides are multiples of 2^L
     y0, x0, h, w = _region(region, H, W)
+    if units is not None:
+        # the residual's contexts reach every pixel of a unit: decode the rectangles of the touched tiles whole, refine
+        # them, and cut the region out on the device
+        asked = (y0, x0, h, w)
+        y1, x1 = min(H, ((y0 + h - 1) // th + 1) * th), min(W, ((x0 + w - 1) // tw + 1) * tw)
+        y0, x0 = y0 // th * th, x0 // tw * tw
+        h, w = y1 - y0, x1 - x0
     if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
         raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
     check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
@@ -825,6 +1014,12 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0):
             else:
                 ops.ll_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), inv_a, b, tiles=grp,
                                       out=out)
+        if units is not None:
+            from . import residual
+            residual.decode_units(out, (H, W, th, tw, ny, nx), (y0, x0, h, w), want, [units[t] for t in want], rhdr["near"],
+                                  hdr["coder"])
+            ay, ax, ah, aw = asked
+            out = out[:, ay - y0:ay - y0 + ah, ax - x0:ax - x0 + aw]
     return out[0].cpu()
 
 

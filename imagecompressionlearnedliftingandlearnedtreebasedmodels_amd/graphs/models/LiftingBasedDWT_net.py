@@ -1047,15 +1047,20 @@ def compress_planes(nets, x):
     return xhat, s_xe, s_xo
 
 
-def encode_strings_planes(nets, x, coder="host"):
+def encode_strings_planes(nets, x, coder="host", recon=False):
     """The encoder half of compress_planes: encode -> the entropy layer's compress_planes, no decoding.
     x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first).  coder: "host" (rans64 on the host) or "gpu"
-    (irans32 on the device); the symbols are the same, the bytes differ."""
+    (irans32 on the device); the symbols are the same, the bytes differ.
+    recon=True: -> (strings_xe, strings_xo, xhat), xhat (P,B,C,H,W) being decode_planes of the dequantised tensors
+    compress_planes returns -- the tensors decompress_planes returns for these strings, through the call
+    decode_strings_planes makes (the codec's residual layer)."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "compress_planes"):
         raise NotImplementedError(_NOT_CODED)
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
-    s_xe, s_xo, _, _ = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder)
+    s_xe, s_xo, xe_q, xo_q = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder)
+    if recon:
+        return s_xe, s_xo, decode_planes([n.autoencoder for n in nets], xe_q, xo_q)
     return s_xe, s_xo
 
 

@@ -250,6 +250,93 @@ def ycc_to_u8hwc_crop(y, H, W):
     return dst
 
 
+RESID_MAX_NEAR = 32          # LLDWT_RESID_MAX_NEAR
+RESID_CONTEXTS = 24          # 3 channels x 8 activity classes
+
+
+def resid_unit_size(grid, t):
+    """The in-image rectangle size (uh, uw) of tile t of grid = (H, W, th, tw, ny, nx) (any image of the batch)."""
+    H, W, th, tw, ny, nx = grid
+    ty, tx = divmod(int(t) % (ny * nx), nx)
+    return min(th, H - ty * th), min(tw, W - tx * tw)
+
+
+def _resid_args(who, bufs, grid, region, tiles, B):
+    """The shared checks of the residual kernels -> (tile tensor on the device, n, uh, uw, geometry arguments)."""
+    H, W, th, tw, ny, nx = (int(v) for v in grid)
+    y0, x0, h, w = (int(v) for v in region)
+    for t in bufs:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+                and tuple(t.shape) == (B, h, w, 3)):
+            raise _lib.LLDWTError("%s: image buffers must be contiguous (%d,%d,%d,3) uint8 device tensors" % (who, B, h, w))
+    tiles = [int(t) for t in tiles]
+    if not tiles or any(t < 0 or t >= B * ny * nx for t in tiles):
+        raise _lib.LLDWTError("%s: need at least one tile index in [0, %d)" % (who, B * ny * nx))
+    sizes = {resid_unit_size((H, W, th, tw, ny, nx), t) for t in tiles}
+    if len(sizes) != 1:
+        raise _lib.LLDWTError("%s: the units of one call must have one rectangle size (got %s)" % (who, sorted(sizes)))
+    uh, uw = sizes.pop()
+    for t in tiles:
+        ty, tx = divmod(t % (ny * nx), nx)
+        if ty * th < y0 or tx * tw < x0 or ty * th + uh > y0 + h or tx * tw + uw > x0 + w:
+            raise _lib.LLDWTError("%s: tile %d is not inside the region %s" % (who, t, (y0, x0, h, w)))
+    tdev = torch.tensor(tiles, dtype=torch.int32).to(bufs[0].device)
+    return tdev, len(tiles), uh, uw, (0, len(tiles), B, H, W, th, tw, ny, nx, y0, x0, h, w, uh, uw)
+
+
+def resid_analyse(x, xh, grid, region, tiles, d):
+    """Encoder kernel of the residual layer (lldwt_resid_analyse).  x, xh: (B,h,w,3) uint8 device buffers
+    of the region (y0, x0, h, w) of the originals and the base reconstructions; grid = (H, W, th, tw, ny, nx); tiles: the
+    units (tile indexes (b * ny + ty) * nx + tx, one rectangle size, inside the region); d: the bound, 0 = lossless.
+    -> (sym (3n, uh*uw) int32, ctx (3n, uh*uw) int32, hist (n,3,8,2Q+1) int32, cs_xh (n) int64, cs_x (n) int64); the
+    checksums are the uint64 sums reinterpreted as int64."""
+    d = int(d)
+    if not 0 <= d <= RESID_MAX_NEAR:
+        raise _lib.LLDWTError("resid_analyse: near-lossless bound %d outside [0, %d]" % (d, RESID_MAX_NEAR))
+    tdev, n, uh, uw, geo = _resid_args("resid_analyse", (x, xh), grid, region, tiles, int(x.shape[0]))
+    Q = (255 + d) // (2 * d + 1)
+    dev = x.device
+    sym = torch.empty(3 * n, uh * uw, device=dev, dtype=torch.int32)
+    ctx = torch.empty(3 * n, uh * uw, device=dev, dtype=torch.int32)
+    hist = torch.zeros(n, 3, 8, 2 * Q + 1, device=dev, dtype=torch.int32)
+    cs = torch.zeros(2, n, device=dev, dtype=torch.int64)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    check(_lib.load().lldwt_resid_analyse(p(x), p(xh), p(tdev), *geo, d, p(sym), p(ctx), p(hist), p(cs[0]), p(cs[1]),
+                                          _stream()), "resid_analyse")
+    return sym, ctx, hist, cs[0], cs[1]
+
+
+def resid_contexts(xh, grid, region, tiles, scales):
+    """Decoder kernel (lldwt_resid_contexts): xh as resid_analyse; scales: (n, 24) uint8 device tensor, the table index of
+    each context c * 8 + a of each unit -> (idx (3n, uh*uw) int32, cs_xh (n) int64)."""
+    tdev, n, uh, uw, geo = _resid_args("resid_contexts", (xh,), grid, region, tiles, int(xh.shape[0]))
+    if not (isinstance(scales, torch.Tensor) and scales.is_cuda and scales.dtype == torch.uint8 and scales.is_contiguous()
+            and tuple(scales.shape) == (n, RESID_CONTEXTS)):
+        raise _lib.LLDWTError("resid_contexts: scales must be a contiguous (%d,%d) uint8 device tensor" % (n, RESID_CONTEXTS))
+    idx = torch.empty(3 * n, uh * uw, device=xh.device, dtype=torch.int32)
+    cs = torch.zeros(n, device=xh.device, dtype=torch.int64)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    check(_lib.load().lldwt_resid_contexts(p(xh), p(tdev), *geo, p(scales), p(idx), p(cs), _stream()), "resid_contexts")
+    return idx, cs
+
+
+def resid_apply(xh, grid, region, tiles, d, sym, out=None):
+    """Decoder kernel (lldwt_resid_apply): out = clamp(xh + sym * (2d + 1), 0, 255) on the units' pixels, written into out
+    (a buffer like xh; None: xh itself, in place) -> (out, cs_out (n) int64).  sym: (3n, uh*uw) int32 device tensor."""
+    d = int(d)
+    if not 0 <= d <= RESID_MAX_NEAR:
+        raise _lib.LLDWTError("resid_apply: near-lossless bound %d outside [0, %d]" % (d, RESID_MAX_NEAR))
+    out = xh if out is None else out
+    tdev, n, uh, uw, geo = _resid_args("resid_apply", (xh, out), grid, region, tiles, int(xh.shape[0]))
+    if not (isinstance(sym, torch.Tensor) and sym.is_cuda and sym.dtype == torch.int32 and sym.is_contiguous()
+            and tuple(sym.shape) == (3 * n, uh * uw)):
+        raise _lib.LLDWTError("resid_apply: sym must be a contiguous (%d,%d) int32 device tensor" % (3 * n, uh * uw))
+    cs = torch.zeros(n, device=xh.device, dtype=torch.int64)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    check(_lib.load().lldwt_resid_apply(p(xh), p(tdev), *geo, d, p(sym), p(out), p(cs), _stream()), "resid_apply")
+    return out, cs
+
+
 def pblock_packed_floats(Cc, K):
     return int(_lib.load().lldwt_pblock_packed_floats(Cc, K))
 

@@ -748,6 +748,33 @@ int lldwt_msssim_backward(const float* x, const float* y, float offset, int64_t 
                           const float* pyr, const double* coef, const double* g, double gscale, float* gpyr, float* grad_y,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Residual layer of the codec (lossless / near-lossless coding over the decoded base image; DESIGN.md 7.1.5, csrc/residual.hip).
+ * A unit is the in-image rectangle of one tile of the grid of lldwt_ycc_tiles_to_u8hwc: tile t = (b * ny + ty) * nx + tx of
+ * th x tw covers rows [ty*th, min((ty+1)*th, H)) and columns [tx*tw, min((tx+1)*tw, W)).  x, xh and dst are uint8 HWC
+ * (B,h,w,3) buffers holding the region (y0, x0, h, w) of every image.  A call handles the n units tiles[0..n) (device int32;
+ * null: first .. first+n-1), which must all measure uh x uw and lie inside the region; a unit that does not writes nothing.
+ * d: the near-lossless bound in [0, LLDWT_RESID_MAX_NEAR], 0 = lossless; Q = (255 + d) / (2d + 1).  Per pixel and channel c:
+ *   symbol   q = sign(r) * ((|r| + d) / (2d + 1)), r = x - xh;   output  clamp(xh + q * (2d + 1), 0, 255), so |out - x| <= d
+ *   context  c * 8 + a, a = 0 if g == 0 else min(7, 1 + floor(log2 g)),
+ *            g = |xh[y,x+1] - xh[y,x-1]| + |xh[y+1,x] - xh[y-1,x]| with the neighbour coordinates clamped to the unit
+ * sym, ctx, idx: (3 n, uh*uw) int32, row 3 j + c = channel c of unit j in raster order (the range coders' layout).
+ * hist: (n, 3, 8, 2Q+1) int32 counts of q + Q per context.  scales: (n, 24) uint8, the table index of each context.
+ * cs_*: (n) uint64, sum_i (byte_i + 1) * (1 + i mod 65521) mod 2^64 over the unit's bytes in HWC raster order.
+ * hist and every cs_* array must be ZERO on entry (the kernels add with integer atomics: the result is order-independent).
+ * dst may be xh.  Nothing synchronises. */
+#define LLDWT_RESID_MAX_NEAR 32
+int lldwt_resid_analyse(const uint8_t* x, const uint8_t* xh, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H,
+                        int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                        int64_t uh, int64_t uw, int d, int32_t* sym, int32_t* ctx, int32_t* hist, uint64_t* cs_xh, uint64_t* cs_x,
+                        void* stream);
+int lldwt_resid_contexts(const uint8_t* xh, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                         int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w, int64_t uh,
+                         int64_t uw, const uint8_t* scales, int32_t* idx, uint64_t* cs_xh, void* stream);
+int lldwt_resid_apply(const uint8_t* xh, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                      int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w, int64_t uh,
+                      int64_t uw, int d, const int32_t* sym, uint8_t* dst, uint64_t* cs_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

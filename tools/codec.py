@@ -87,6 +87,11 @@ def main(argv=None):
                                        help="with --tile: pixels neighbouring tiles share, cross-faded on decode (default 0)")
     sub.choices["encode"].add_argument("--coder", choices=("host", "gpu"), default="host",
                                        help="entropy coder: host (rans64, the default) or gpu (irans32 on the device)")
+    sub.choices["encode"].add_argument("--near", type=int, metavar="D",
+                                       help="add a residual layer that bounds every sample's error by D in 1..32 (0: lossless)")
+    sub.choices["encode"].add_argument("--lossless", action="store_true", help="the same as --near 0")
+    sub.choices["decode"].add_argument("--base-only", action="store_true",
+                                       help="decode the base layer of a refined (LLDR) container only")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
     sub.choices["decode"].add_argument("--reduce", type=int, default=0,
                                        help="decode at 1/2^k of each side from the coarse wavelet levels (default 0: full)")
@@ -102,6 +107,13 @@ def main(argv=None):
     if a.cmd == "info":
         with open(a.src, "rb") as f:
             hdr = codec.read_header(f.read())
+        if "base" in hdr:                      # LLDR: the layer's own fields and the byte split, then the base container's
+            print("%-15s %s" % ("near", "0 (lossless)" if hdr["near"] == 0 else "%d (every sample within %d)" % (hdr["near"],
+                                                                                                            hdr["near"])))
+            print("%-15s %d" % ("units", hdr["units"]))
+            print("%-15s %d" % ("base_bytes", hdr["base_bytes"]))
+            print("%-15s %d" % ("residual_bytes", hdr["residual_bytes"]))
+            hdr = hdr["base"]
         for k, v in hdr.items():
             print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
         if "ny" in hdr:
@@ -129,33 +141,43 @@ def main(argv=None):
     if a.cmd == "encode":
         img = np.asarray(Image.open(a.src).convert("RGB"), dtype=np.uint8)
         x = torch.from_numpy(np.ascontiguousarray(img))[None]
+        if a.lossless and a.near not in (None, 0):
+            print("--lossless is --near 0; give one of them", file=sys.stderr)
+            return 2
+        kw = {"near": 0 if a.lossless else a.near} if (a.lossless or a.near is not None) else {}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tile is None:
             if a.overlap:
                 print("--overlap needs --tile", file=sys.stderr)
                 return 2
-            blob = codec.encode_images(net, x, coder=a.coder)[0]
+            blob = codec.encode_images(net, x, coder=a.coder, **kw)[0]
         elif a.overlap:
             blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, coder=a.coder,
-                                      overlap=a.overlap)[0]
+                                      overlap=a.overlap, **kw)[0]
         else:
-            blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, coder=a.coder)[0]
+            blob = codec.encode_tiled(net, x, tile=a.tile, tiles_per_call=a.tiles_per_call, coder=a.coder, **kw)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         with open(a.dst, "wb") as f:
             f.write(blob)
         H, W = img.shape[:2]
         print("encoded %dx%d: %d bytes, %.4f bpp, %.3f s" % (W, H, len(blob), len(blob) * 8 / (H * W), dt))
+        hdr = codec.read_header(blob)
+        if "base" in hdr:
+            print("near %d: base %d bytes, residual %d bytes" % (hdr["near"], hdr["base_bytes"], hdr["residual_bytes"]))
+            hdr = hdr["base"]
         if a.tile is not None:
-            hdr = codec.read_header(blob)
             print("tiles: %d x %d of %dx%d" % (hdr["ny"], hdr["nx"], hdr["tw"], hdr["th"]))
             if hdr["overlap"]:
                 print("overlap: %d" % hdr["overlap"])
     else:
         with open(a.src, "rb") as f:
             blob = f.read()
+        kw = {"refine": False} if a.base_only else {}
         tiled = blob[:4] in (codec.TILED_MAGIC, codec.LAPPED_MAGIC)
+        if blob[:4] == codec.REFINED_MAGIC:
+            tiled = "ny" in codec.read_header(blob)["base"]
         region = None
         if a.region is not None:
             if not tiled:
@@ -165,9 +187,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if tiled:
-            img = codec.decode_tiled(net, blob, region=region, tiles_per_call=a.tiles_per_call, reduce=a.reduce)
+            img = codec.decode_tiled(net, blob, region=region, tiles_per_call=a.tiles_per_call, reduce=a.reduce, **kw)
         else:
-            img = codec.decode_images(net, [blob], reduce=a.reduce)[0]
+            img = codec.decode_images(net, [blob], reduce=a.reduce, **kw)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         Image.fromarray(img.numpy()).save(a.dst)
