@@ -82,6 +82,15 @@ base or the in-image rectangle of one tile of an LLDT base (lapped bases are ref
     payload           the streams in the same order, coded by the base container's coder
     CRC32             u32       zlib.crc32 of every byte before it
 
+Variable-rate coding (``encode_images(..., step=q)`` / ``target_bytes=T``, the same on ``encode_tiled``): the
+levels 0 .. L-2 of a coded layer, whose Gaussian parameters are conditioned on an already decoded parent, are quantised with
+a step q = n / 16, n an integer in [4, 1024]: symbol = round((y - mu) / q), value = symbol * q + mu, the table entered with
+sigma / q.  xe and the coarsest level keep the unit step.  The step is one more key of the arithmetic string, ``step=<n>``,
+absent at n = 16: ``step=None`` and ``step=1`` write the containers above byte for byte, no container type changes, and the
+decoders read the step from the header (``hdr["step"]``, a float; on the nested base header of an LLDR).  ``target_bytes=T``
+searches the quarter-octave grid STEP_GRID for the finest step whose container is at most T bytes, one image (or one tiled
+frame) at a time.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -119,7 +128,63 @@ CODER_KEYS = {"host": None, "gpu": "irans32"}
 _CODER_NAMES = {v: k for k, v in CODER_KEYS.items() if v is not None}
 
 
+# quantisation step: q = n / STEP_DENOM, n an integer in [STEP_N_MIN, STEP_N_MAX]; the arithmetic string's
+# "step" key holds n and is absent at n = STEP_DENOM (the unit step)
+STEP_DENOM, STEP_N_MIN, STEP_N_MAX = 16, 4, 1024
+# the candidate steps of a byte target: n_k = round(16 * 2^(k / 4)), k = -8 .. 24 (a quarter octave apart, 0.25 .. 64)
+STEP_GRID_K = (-8, 24)
+STEP_GRID = tuple(int(round(STEP_DENOM * 2.0 ** (k / 4.0))) for k in range(STEP_GRID_K[0], STEP_GRID_K[1] + 1))
+
+
 # ------------------------------------------------------------------------------------------------ byte level (host only)
+def check_step(step):
+    """A quantisation step of the API -> n, the integer with step == n / 16 (None -> 16).  ValueError naming step unless the
+    value is exactly n / 16 with n in [4, 1024]."""
+    if step is None:
+        return STEP_DENOM
+    try:
+        n = float(step) * STEP_DENOM
+    except (TypeError, ValueError):
+        raise ValueError("step must be a number (got %r)" % (step,)) from None
+    if not (n == n and STEP_N_MIN <= n <= STEP_N_MAX and n == int(n)):
+        raise ValueError("step must be n / %d with an integer n in [%d, %d], i.e. a multiple of %g in [%g, %g] (got %r)"
+                         % (STEP_DENOM, STEP_N_MIN, STEP_N_MAX, 1.0 / STEP_DENOM, STEP_N_MIN / STEP_DENOM,
+                            STEP_N_MAX / STEP_DENOM, step))
+    return int(n)
+
+
+def _split_step(arith):
+    """arithmetic string -> (n, the string without the step key); n = 16 when the key is absent.  ValueError naming step if
+    the key occurs twice or its value is not a decimal integer in [4, 1024] other than 16 (the unit step is written by
+    leaving the key out, so that there is one spelling of every arithmetic)."""
+    parts = arith.split(",") if arith else []
+    vals = [p[len("step="):] for p in parts if p.startswith("step=")]
+    if not vals:
+        return STEP_DENOM, arith
+    ok = len(vals) == 1 and vals[0].isascii() and vals[0].isdigit() and vals[0] == str(int(vals[0])) \
+        and STEP_N_MIN <= int(vals[0]) <= STEP_N_MAX and int(vals[0]) != STEP_DENOM
+    if not ok:
+        raise ValueError("step: bad quantisation step %r in the arithmetic string (an integer n in [%d, %d] other than %d, "
+                         "once)" % (",".join(vals), STEP_N_MIN, STEP_N_MAX, STEP_DENOM))
+    return int(vals[0]), ",".join(p for p in parts if not p.startswith("step="))
+
+
+def _with_step(arith, n):
+    """The arithmetic string (without a step key) with the key of step n / 16 merged in at its sorted place."""
+    if n == STEP_DENOM:
+        return arith
+    return ",".join(sorted((arith.split(",") if arith else []) + ["step=%d" % n]))
+
+
+def target_bpp_bytes(bpp, H, W):
+    """A rate target in bits per pixel -> the byte target floor(bpp * H * W / 8) of an H x W image."""
+    import math
+    bpp = float(bpp)
+    if not (bpp == bpp and 0 < bpp < float("inf")):
+        raise ValueError("target_bpp must be a positive number (got %r)" % (bpp,))
+    return int(math.floor(bpp * H * W / 8.0))
+
+
 def leb128_encode(n):
     """Unsigned LEB128: 7 bits per byte, low groups first, high bit = more bytes follow."""
     if n < 0:
@@ -267,10 +332,11 @@ def parse_container(blob):
     if count != _PLANES * (L + 1):
         raise ValueError("stream count %d does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
     coder, _ = _split_coder(arith)
+    step_n, _ = _split_step(arith)
     streams, lengths = _parse_streams(blob, pos, end, count)
     hdr = dict(version=FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
-               numerics=numerics, arithmetic=arith, coder=coder, digest=digest, stream_lengths=lengths,
-               header_bytes=end - sum(lengths))
+               numerics=numerics, arithmetic=arith, coder=coder, step=step_n / STEP_DENOM, digest=digest,
+               stream_lengths=lengths, header_bytes=end - sum(lengths))
     return hdr, streams
 
 
@@ -313,11 +379,12 @@ def parse_tiled(blob):
     if count != _PLANES * (L + 1):
         raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
     coder, _ = _split_coder(arith)
+    step_n, _ = _split_step(arith)
     streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
     tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
     hdr = dict(version=TILED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
                W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=0, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
-               streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
+               step=step_n / STEP_DENOM, streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
     return hdr, tiles
 
 
@@ -376,11 +443,12 @@ def parse_lapped(blob):
     if count != _PLANES * (L + 1):
         raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
     coder, _ = _split_coder(arith)
+    step_n, _ = _split_step(arith)
     streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
     tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
     hdr = dict(version=LAPPED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
                W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
-               streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
+               step=step_n / STEP_DENOM, streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
     return hdr, tiles
 
 
@@ -500,9 +568,10 @@ def reduce_bytes(hdr):
 
 
 # ------------------------------------------------------------------------------------------------ model identity
-def arithmetic_string(coder="host"):
+def arithmetic_string(coder="host", step=None):
     """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path, plus the
-    entropy coder: ``coder=irans32`` for coder="gpu", no key for the host coder (so the host string is unchanged).
+    entropy coder: ``coder=irans32`` for coder="gpu", no key for the host coder (so the host string is unchanged), plus the
+    quantisation step: ``step=<n>`` for step = n / 16 other than 1, no key for None or 1.
     Which reach which layer (the others are carried along, harmlessly):
       plc_mode, plc_fuse, plc_algo, plc_shape, storage -- the tree-context pair: conditioned2ZTsepSubbands, onlyEZWT;
       precision -- the split-fp16 pair and cgp chain (conditioned2ZTsepSubbands, onlyEZWT) and the lifting steps (all);
@@ -516,13 +585,14 @@ def arithmetic_string(coder="host"):
           ("storage", ops.storage_dtype())]
     if CODER_KEYS[coder] is not None:
         kv.append(("coder", CODER_KEYS[coder]))
-    return ",".join("%s=%s" % p for p in sorted(kv))
+    return _with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step))
 
 
 def _batch_invariant(arith):
     """True when the coding path is per image in this arithmetic, so images can be coded together.  Not so when the
     non-fused split-fp16 pair takes its operand scale from an absmax over the whole batch (plc_fuse=0), or with fp16
     storage (a bound over the batch's parents); the one-product precisions are not verified.  Otherwise: one image per call."""
+    arith = _split_step(_split_coder(arith)[1])[1]          # neither the coder nor the step changes what a batch shares
     d = dict(p.split("=") for p in arith.split(","))
     if d["precision"] != "f16x3" or d["storage"] != "fp32":
         return False
@@ -652,23 +722,113 @@ def _refine(base_blobs, img, xh, grid, near, coder):
     return [pack_refined(near, crc, base_blobs[b], units[b * per:(b + 1) * per]) for b in range(len(base_blobs))]
 
 
-def encode_images(net, images_u8, coder="host", near=None):
+def _rate_args(step, target_bytes, near, L):
+    """The rate arguments of encode_images / encode_tiled, checked on the host -> (n of the step, target or None)."""
+    if step is not None and target_bytes is not None:
+        raise ValueError("step and target_bytes: give one of them (a byte target chooses the step)")
+    n = check_step(step)
+    if n != STEP_DENOM and L < 2:
+        raise ValueError("step: a step other than 1 needs dwtlevels >= 2 (it applies to the levels below the coarsest; the "
+                         "net has %d)" % L)
+    if target_bytes is None:
+        return n, None
+    if L < 2:
+        raise ValueError("target_bytes: the search varies the step, which needs dwtlevels >= 2 (the net has %d)" % L)
+    if near is not None:
+        raise ValueError("target_bytes: not with near (the residual layer grows as the base shrinks, so the step does not "
+                         "control the size)")
+    try:
+        T = int(target_bytes)
+    except (TypeError, ValueError):
+        raise ValueError("target_bytes must be a positive integer (got %r)" % (target_bytes,)) from None
+    if T != target_bytes or T < 1:
+        raise ValueError("target_bytes must be a positive integer (got %r)" % (target_bytes,))
+    return n, T
+
+
+SEARCH_STATS = {}          # diagnostics: the last byte-target search's probes (estimates), real encodes and chosen step
+
+
+def _search_step(estimate, encode, T):
+    """The byte target of DESIGN.md 7.1.6 over STEP_GRID.  estimate(n) -> estimated container bytes at step n / 16 (no range
+    coder runs); encode(n) -> the real container.  Bisection on the estimates for the finest grid step that fits T, then
+    the walk on REAL containers that alone decides: while the container exceeds T one grid step coarser, otherwise one
+    grid step finer as long as that still fits.  -> the container of the finest grid step that is <= T bytes; should the
+    sizes not fall monotonically along the grid, the one this walk finds.  ValueError naming target_bytes and the smallest
+    achievable size if the coarsest step does not fit."""
+    lo, hi = 0, len(STEP_GRID) - 1
+    probes = encodes = 0
+    while lo < hi:
+        mid = (lo + hi) // 2
+        probes += 1
+        if estimate(STEP_GRID[mid]) <= T:
+            hi = mid
+        else:
+            lo = mid + 1
+    k = lo
+    blob = encode(STEP_GRID[k])
+    encodes += 1
+    if len(blob) > T:
+        while len(blob) > T:
+            if k == len(STEP_GRID) - 1:
+                raise ValueError("target_bytes: %d bytes cannot be met; at the coarsest step %g the smallest achievable is %d"
+                                 % (T, STEP_GRID[k] / STEP_DENOM, len(blob)))
+            k += 1
+            blob = encode(STEP_GRID[k])
+            encodes += 1
+    else:
+        while k > 0:
+            finer = encode(STEP_GRID[k - 1])
+            encodes += 1
+            if len(finer) > T:
+                break
+            blob, k = finer, k - 1
+    SEARCH_STATS.update(probes=probes, encodes=encodes, step=STEP_GRID[k] / STEP_DENOM, bytes=len(blob))
+    return blob
+
+
+def _estimated_size(empty, estimates):
+    """The size of a container from the estimated stream lengths: ``empty`` is the container packed with empty streams, to
+    which the streams and the bytes of their LEB128 lengths beyond the first are added."""
+    return len(empty) + sum(e + len(leb128_encode(e)) - 1 for e in estimates)
+
+
+def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
-    holding the same LLDW bytes plus the residual layer."""
-    import torch
+    holding the same LLDW bytes plus the residual layer.
+    step: the quantisation step q = n / 16 of the levels 0 .. L-2, recorded in the arithmetic string; None
+    and 1 write the same bytes as ever.  target_bytes = T instead: per image, the finest step of STEP_GRID whose container is
+    at most T bytes (_search_step: estimates first, real containers decide; if the sizes are not monotone along the grid,
+    the step that walk finds); ValueError naming the smallest achievable size if even the coarsest step does not fit.  Not
+    both, and no target with near."""
+    layer, nettype, L = describe(net)
+    B, H, W = _check_images(images_u8)
     if near is not None:
         from .residual import check_near
         near = check_near(near)
+    n, T = _rate_args(step, target_bytes, near, L)
+    if T is None:
+        return _encode_images(net, images_u8, coder, near, n)
+    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode_images(net, i, coder, None, m, estimate=True)[0],
+                         lambda m, i=images_u8[b:b + 1]: _encode_images(net, i, coder, None, m)[0], T) for b in range(B)]
+
+
+def _encode_images(net, images_u8, coder, near, step_n, estimate=False):
+    """encode_images at the step step_n / 16 (arguments checked).  estimate: -> the estimated container sizes (ints) from the
+    code-length kernel instead of the containers; no range coder runs."""
+    import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    from .graphs.models.entropy_coding import ESTIMATE
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
     nets = net.nets()
     Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
-    arith = arithmetic_string(coder)
+    arith = arithmetic_string(coder, step_n / STEP_DENOM)
+    skw = {} if step_n == STEP_DENOM else {"step": step_n / STEP_DENOM}
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, numerics=CODING_NUMERICS_VERSION, arithmetic=arith,
                digest=weights_digest(net))
@@ -679,10 +839,15 @@ def encode_images(net, images_u8, coder="host", near=None):
     blobs, recon = [], []
     with torch.no_grad():
         for a, e in groups:
+            if estimate:
+                s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=ESTIMATE, **skw)
+                empty = pack_container(hdr, [b""] * (_PLANES * (L + 1)))
+                blobs += [_estimated_size(empty, _tile_streams(s_xe, s_xo, b)) for b in range(e - a)]
+                continue
             if near is None:
-                s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder)
+                s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder, **skw)
             else:
-                s_xe, s_xo, xhat = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder, recon=True)
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder, recon=True, **skw)
                 recon.append(ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W))          # the decoder's call on the same values
             for b in range(e - a):
                 streams = [s for p in range(_PLANES) for s in [s_xe[p][b]] + [lev[p][b] for lev in s_xo]]
@@ -695,8 +860,9 @@ def encode_images(net, images_u8, coder="host", near=None):
 
 def check_header(hdr, layer, nettype, L, digest, arith):
     """The identity checks of a parsed header against the decoding net and process (ValueError naming the field).  arith:
-    the process's arithmetic string without a coder key; the header's coder key is checked and set aside first."""
+    the process's arithmetic string without a coder key; the header's coder and step keys are checked and set aside first."""
     _, hdr_arith = _split_coder(hdr["arithmetic"])
+    _, hdr_arith = _split_step(hdr_arith)
     if hdr["layer"] != layer:
         raise ValueError("entropy layer: the container holds %s, the net is %s" % (hdr["layer"], layer))
     if hdr["netType"] != nettype:
@@ -745,7 +911,7 @@ def ll_norm(net, k):
 
 def decode_images(net, blobs, reduce=0, refine=True):
     """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
-    first; then containers of equal (H, W) and coder are decoded together (the coder comes from each header).
+    first; then containers of equal (H, W), coder and quantisation step are decoded together (both come from each header).
     reduce = k in [0, L]: the image at 1/2^k of each side, (ceil(H / 2^k), ceil(W / 2^k), 3), decoded from the xe streams
     and the levels k .. L-1 only (the module docstring); reduce=0 is the full decode.
     An LLDR container over LLDW is decoded through its base and then refined on the device (lossless or within its bound,
@@ -775,20 +941,21 @@ def decode_images(net, blobs, reduce=0, refine=True):
     nets = net.nets()
     by_size = {}
     for i, (hdr, _) in enumerate(parsed):
-        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"]), []).append(i)
+        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"]), []).append(i)
     out = [None] * len(parsed)
     with torch.no_grad():
         if k:
             inv_a, b = ll_norm(net, k)
-        for (H, W, coder), idx in by_size.items():
+        for (H, W, coder, step), idx in by_size.items():
             Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
+            skw = {} if step == 1.0 else {"step": step}        # the unit step: the call as it has always been
             groups = [idx] if _batch_invariant(arith) else [[i] for i in idx]
             for g in groups:
                 per = L + 1                                   # streams per plane: xe, xo finest -> coarsest
                 s_xe = [[parsed[i][1][p * per] for i in g] for p in range(_PLANES)]
                 s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(k, L)]
                 if k == 0:
-                    xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder)
+                    xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, **skw)
                     img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W)
                     for d in sorted({refined[i][0] for i in g if i in refined}):
                         from . import residual
@@ -797,7 +964,7 @@ def decode_images(net, blobs, reduce=0, refine=True):
                                               [refined[g[j]][1][0] for j in js], d, coder)
                     img = img.cpu()
                 else:
-                    ll = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, first_level=k)
+                    ll = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, first_level=k, **skw)
                     Hr, Wr = _reduced(H, k), _reduced(W, k)
                     img = ops.ll_tiles_to_u8hwc(ll.contiguous(), (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr), inv_a,
                                                 b, B=len(g)).cpu()
@@ -865,7 +1032,7 @@ def _tile_streams(s_xe, s_xo, j):
     return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
 
 
-def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None):
+def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -874,10 +1041,9 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     memory; one tile per call in the arithmetics that are not batch invariant.  The bytes do not depend on tiles_per_call.
     coder: as encode_images.  near: as encode_images, every tile's in-image rectangle being a unit of the residual layer
     (LLDR over LLDT; the bytes do not depend on tiles_per_call either); not with overlap > 0, where the decoded pixels are
-    a blend of two units."""
-    import torch
-    from . import ops
-    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    a blend of two units.
+    step, target_bytes: as encode_images, with ONE step for all tiles of a frame; a target is met by each frame's container
+    (the images of a batch are searched one at a time)."""
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
     if near is not None:
@@ -885,6 +1051,22 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
         near = check_near(near)
         if overlap:
             raise ValueError("near: a residual layer over lapped tiles (overlap > 0) is not defined; use overlap=0")
+    n, T = _rate_args(step, target_bytes, near, L)
+    args = (tile, tiles_per_call, coder, overlap)
+    if T is None:
+        return _encode_tiled(net, images_u8, *args, near, n)
+    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode_tiled(net, i, *args, None, m, estimate=True)[0],
+                         lambda m, i=images_u8[b:b + 1]: _encode_tiled(net, i, *args, None, m)[0], T) for b in range(B)]
+
+
+def _encode_tiled(net, images_u8, tile, tiles_per_call, coder, overlap, near, step_n, estimate=False):
+    """encode_tiled at the step step_n / 16 (near and the rate arguments checked); estimate as _encode_images."""
+    import torch
+    from . import ops
+    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    from .graphs.models.entropy_coding import ESTIMATE
+    layer, nettype, L = describe(net)
+    B, H, W = _check_images(images_u8)
     if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
         raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
     nets = net.nets()
@@ -897,7 +1079,8 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
         th, tw, ny, nx = tile_grid([n.autoencoder for n in nets], H, W, int(tile))
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
-    arith = arithmetic_string(coder)
+    arith = arithmetic_string(coder, step_n / STEP_DENOM)
+    skw = {} if step_n == STEP_DENOM else {"step": step_n / STEP_DENOM}
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx,
                numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
@@ -915,15 +1098,19 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
             else:
                 x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
             if near is None:
-                s_xe, s_xo = encode_strings_planes(nets, x, coder=coder)
+                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, **skw)
             else:
-                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True)
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, **skw)
                 ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W),
                                        tiles=list(range(first, first + n)), B=B, out=xh)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
         per = ny * nx
         if ov:
             hdr["overlap"] = ov
+        if estimate:
+            empty = (pack_lapped if ov else pack_tiled)(hdr, [[b""] * (_PLANES * (L + 1))] * per)
+            return [_estimated_size(empty, [e for t in tiles[b * per:(b + 1) * per] for e in t]) for b in range(B)]
+        if ov:
             return [pack_lapped(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
         blobs = [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
         if near is not None:
@@ -931,13 +1118,14 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     return blobs
 
 
-def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0):
+def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step=1.0):
     """One group of n tiles -> xhat (3,n,1,th,tw), or at first_level = k the LL band (3,n,1,th>>k,tw>>k)
     (decode_strings_planes; a module-level hook so the number of tiles a decode touches can be counted)."""
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
+    kw = {} if step == 1.0 else {"step": step}
     if first_level:
-        return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level)
-    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder)
+        return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, **kw)
+    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, **kw)
 
 
 def _region(region, H, W):
@@ -1008,6 +1196,8 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
             kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}     # host: the call as it has always been
             if k:
                 kw["first_level"] = k
+            if hdr["step"] != 1.0:
+                kw["step"] = hdr["step"]
             xhat = _decode_tiles(nets, s_xe, s_xo, hdr["th"], hdr["tw"], len(grp), **kw)
             if k == 0:
                 ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=grp, out=out)
@@ -1055,6 +1245,8 @@ def _decode_lapped(net, ident, blob, region, tiles_per_call, k):
             kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}
             if k:
                 kw["first_level"] = k
+            if hdr["step"] != 1.0:
+                kw["step"] = hdr["step"]
             xhat = _decode_tiles(nets, s_xe, s_xo, hdr["th"], hdr["tw"], len(grp), **kw)
             ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), grp, acc)
         if k == 0:

@@ -166,6 +166,8 @@ struct Cgp16Args {
     int* wf_idx;                          // (Z, ntot, groups) CDF indexes in wavefront order; this step starts at wf_off
     int* wf_sym;                          // encoder: symbols, same layout
     float* wf_mu;                         // decoder: (Z, groups, wf_n) means of this step
+    float* wf_sigma;                      // decoder, optional: the step's sigmas in wf_mu's layout (the quantiser's test); null in the product
+    float wf_q, wf_invq;                  // quantisation step q = n / 16 and fp32(1 / q) (lldwt_cgp16_wavefront_step_q); 1, 1: the unit step
     int64_t wf_ntot, wf_off;
     unsigned long long* stamps;   // diagnostics only (lldwt_set_diagnostics kind 2): [z][group][column][8] s_memtime stamps
     // TRAIN: the hidden activations after LeakyReLU in the layout of the unfused convs, h1 (Z, groups*162, hw), h2 (Z, groups*54,
@@ -548,7 +550,9 @@ __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_e
             for (int nb = 0; nb < NB; ++nb)
                 if (valid[nb]) {
                     const float sigma = acc3[nb][0] * inv3 + bias3[0], mu = acc3[nb][1] * inv3 + bias3[1];
-                    const float sb = fmaxf(sigma, 0.11f);                         // GaussianConditional's scale bound (:32-33)
+                    // the quantiser with a step: the table is entered with sigma / q, symbol = round((y - mu) / q),
+                    // value = symbol * q + mu (|symbol| < 2^12 and q = n / 16: the product is exact); q = 1 leaves every value as it was
+                    const float sb = fmaxf(sigma * a.wf_invq, 0.11f);             // GaussianConditional's scale bound (:32-33)
                     int idx = 0;
                     for (int k = 0; k < 63; ++k) idx += a.wf_table[k] < sb ? 1 : 0;   // build_indexes
                     const int i = col * (32 * NB) + nb * 32 + pl;
@@ -556,11 +560,12 @@ __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_e
                     a.wf_idx[o] = idx;
                     if (a.wf_y) {                                                 // encoder: symbol = round(y - mu), value = symbol + mu
                         const int64_t e = (z * a.groups + g) * hw + pix[nb];
-                        const int sym = (int)rintf(a.wf_y[e] - mu);
+                        const int sym = (int)rintf((a.wf_y[e] - mu) * a.wf_invq);
                         a.wf_sym[o] = sym;
-                        a.wf_yhat[e] = (float)sym + mu;
+                        a.wf_yhat[e] = (float)sym * a.wf_q + mu;
                     } else {
                         a.wf_mu[(z * a.groups + g) * a.wf_n + i] = mu;
+                        if (a.wf_sigma) a.wf_sigma[(z * a.groups + g) * a.wf_n + i] = sigma;
                     }
                 }
         }
@@ -958,14 +963,20 @@ static int cgp16_params_impl(const float* plc, const float* xq, const void* pack
     return check_launch("cgp16_params");
 }
 
-// the decoder's second half of a wavefront step: yhat[pixel] = symbol + mu
+// the decoder's second half of a wavefront step: yhat[pixel] = symbol * q + mu
 __global__ void k_wf_apply(const int* __restrict__ sym, const float* __restrict__ mu, float* __restrict__ yhat, int groups, int h,
-                           int w, int t, int slope, int y0, int n, int64_t ntot, int64_t off) {
+                           int w, int t, int slope, int y0, int n, int64_t ntot, int64_t off, float q) {
     const int64_t z = blockIdx.z;
     const int g = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int y = y0 + i, x = t - slope * y;
-    yhat[(z * groups + g) * (int64_t)h * w + (int64_t)y * w + x] = (float)sym[(z * ntot + off + i) * groups + g] + mu[(z * groups + g) * n + i];
+    yhat[(z * groups + g) * (int64_t)h * w + (int64_t)y * w + x] = (float)sym[(z * ntot + off + i) * groups + g] * q + mu[(z * groups + g) * n + i];
+}
+
+// a quantisation step the coder accepts: q = n / 16, n an integer in [4, 1024], and inv_q = fp32(1 / q)
+static inline bool wf_step_ok(float q, float inv_q) {
+    const float n = q * 16.f;
+    return n >= 4.f && n <= 1024.f && n == (float)(int)n && inv_q == (float)(1.0 / (double)q);
 }
 
 // pixels of wavefront step t: rows y0 .. y0 + n - 1 with x = t - slope * y inside [0, w)
@@ -978,9 +989,14 @@ static inline void wf_range(int t, int slope, int h, int w, int& y0, int& n) {
     n = hi >= lo ? hi - lo + 1 : 0;
 }
 
-extern "C" int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
-                                          int* idx, int* sym, float* mu, int64_t planes, int64_t batch, int64_t h, int64_t w_,
-                                          int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, void* stream) {
+// q = n / 16 with an integer n in [4, 1024], inv_q = fp32(1 / q) from the host (both checked here: encoder and decoder must use the
+// same pair).  sigma_out: decoder only, may be null.
+extern "C" int lldwt_cgp16_wavefront_step_q(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                            int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h,
+                                            int64_t w_, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q,
+                                            float inv_q, void* stream) {
+    LLDWT_REQUIRE(wf_step_ok(q, inv_q), "cgp16_wavefront_step: step %g (1 / step %g) is not n / 16 with n in [4, 1024]", (double)q, (double)inv_q);
+    LLDWT_REQUIRE(!(y && sigma_out), "cgp16_wavefront_step: sigma_out is an output of the decoder mode (y == null)");
     LLDWT_REQUIRE(plc && yhat && packed && table63 && idx && (y ? sym != nullptr : mu != nullptr), "cgp16_wavefront_step: null pointer");
     LLDWT_REQUIRE(planes > 0 && batch > 0 && h > 0 && w_ > 0 && groups > 0 && (K == 3 || K == 5), "cgp16_wavefront_step: bad arguments");
     LLDWT_REQUIRE(planes * batch <= 65535 && groups <= 65535, "cgp16_wavefront_step: grid too large");
@@ -1005,6 +1021,7 @@ extern "C" int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const f
     if (a.wf_n == 0) return LLDWT_OK;
     LLDWT_REQUIRE(off >= 0 && off + a.wf_n <= ntot, "cgp16_wavefront_step: step does not fit the output (off %ld + %d > %ld)", (long)off, a.wf_n, (long)ntot);
     a.wf_y = y; a.wf_yhat = yhat; a.wf_table = table63; a.wf_idx = idx; a.wf_sym = sym; a.wf_mu = mu; a.wf_ntot = ntot; a.wf_off = off;
+    a.wf_sigma = sigma_out; a.wf_q = q; a.wf_invq = inv_q;
     a.cols = (int)cdiv(a.wf_n, 32 * NB);
     a.stamps = nullptr;
     a.pairs = 0;
@@ -1014,8 +1031,17 @@ extern "C" int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const f
     return check_launch("cgp16_wavefront_step");
 }
 
-extern "C" int lldwt_wavefront_apply(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h,
-                                     int64_t w_, int groups, int K, int t, int64_t ntot, int64_t off, void* stream) {
+// the unit step: multiplying by 1.0f changes no bit, so these are the bits this entry point has always produced
+extern "C" int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                          int* idx, int* sym, float* mu, int64_t planes, int64_t batch, int64_t h, int64_t w_,
+                                          int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, void* stream) {
+    return lldwt_cgp16_wavefront_step_q(plc, yhat, y, packed, table63, idx, sym, mu, nullptr, planes, batch, h, w_, groups, K, tap_mask, t,
+                                        ntot, off, 1.f, 1.f, stream);
+}
+
+extern "C" int lldwt_wavefront_apply_q(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h,
+                                       int64_t w_, int groups, int K, int t, int64_t ntot, int64_t off, float q, float inv_q, void* stream) {
+    LLDWT_REQUIRE(wf_step_ok(q, inv_q), "wavefront_apply: step %g (1 / step %g) is not n / 16 with n in [4, 1024]", (double)q, (double)inv_q);
     LLDWT_REQUIRE(sym && mu && yhat && planes > 0 && batch > 0 && h > 0 && w_ > 0 && groups > 0 && (K == 3 || K == 5), "wavefront_apply: bad arguments");
     const int slope = K / 2 + 1;
     int y0, n;
@@ -1023,8 +1049,13 @@ extern "C" int lldwt_wavefront_apply(const int* sym, const float* mu, float* yha
     if (n == 0) return LLDWT_OK;
     LLDWT_REQUIRE(off >= 0 && off + n <= ntot, "wavefront_apply: step does not fit");
     dim3 grid((unsigned)cdiv(n, 64), (unsigned)groups, (unsigned)(planes * batch));
-    hipLaunchKernelGGL(k_wf_apply, grid, dim3(64), 0, (hipStream_t)stream, sym, mu, yhat, groups, (int)h, (int)w_, t, slope, y0, n, ntot, off);
+    hipLaunchKernelGGL(k_wf_apply, grid, dim3(64), 0, (hipStream_t)stream, sym, mu, yhat, groups, (int)h, (int)w_, t, slope, y0, n, ntot, off, q);
     return check_launch("wavefront_apply");
+}
+
+extern "C" int lldwt_wavefront_apply(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h,
+                                     int64_t w_, int groups, int K, int t, int64_t ntot, int64_t off, void* stream) {
+    return lldwt_wavefront_apply_q(sym, mu, yhat, planes, batch, h, w_, groups, K, t, ntot, off, 1.f, 1.f, stream);
 }
 
 extern "C" int64_t lldwt_cgp16_bwd_packed_bytes(int c0, int c1, int c2, int c3, int groups) {

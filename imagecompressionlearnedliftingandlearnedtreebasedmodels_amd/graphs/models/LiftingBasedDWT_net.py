@@ -154,6 +154,16 @@ def _coarse_strings(strings_xo_list, L, first_level):
     return [None] * k + s[len(s) - (L - k):]
 
 
+def _check_step(step, L):
+    """The quantisation step of a coded layer's compress_planes / decompress_planes -> the step as a float.
+    It reaches the levels 0 .. L-2, whose Gaussian parameters are conditioned on a decoded parent; xe and the coarsest level
+    keep the unit step, so with fewer than two levels there is nothing it could apply to."""
+    q, _ = ops.step_pair(step)
+    if q != 1.0 and L < 2:
+        raise ValueError("step: a step other than 1 needs dwtlevels >= 2 (it applies to the levels below the coarsest; got %d)" % L)
+    return q
+
+
 class _EntropyLayerBase(PackedOwnerMixin, nn.Module):
     def _level_channels(self, config):
         self.num_lifting_layers = config.dwtlevels
@@ -256,10 +266,11 @@ class onlyEZWT(_EntropyLayerBase):
         return _conv([s[4] for s in seqs], t)                                       # (P,B,6,h,w): sigma even, mu odd
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host"):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first)."""
         from . import entropy_coding as ec
         L = len(out_xo_list)
+        step = _check_step(step, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
             s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
@@ -270,7 +281,7 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 s, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, out_xo_list[i],
-                                                 out_xo_list[i].shape, tabs, coder=coder)
+                                                 out_xo_list[i].shape, tabs, coder=coder, step=step)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -278,12 +289,13 @@ class onlyEZWT(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
         """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
         xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]); shapes_xo has all L levels, strings_xo_list all L or the
         levels k .. L-1 (_coarse_strings)."""
         from . import entropy_coding as ec
         L = len(shapes_xo)
+        step = _check_step(step, L)
         strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
@@ -297,7 +309,7 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 _, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, None, shapes_xo[i], tabs,
-                                                 strings_xo_list[i], coder=coder)
+                                                 strings_xo_list[i], coder=coder, step=step)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -457,12 +469,13 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return plc, (packed, packed16), dims, cs[0].kernel_size[0], cs[0].tap_bits()
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host"):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0):
         """compress_ar for every tensor (:386-417): -> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q])
         with *_q = round(y - mu) + mu, the values the decoder reconstructs."""
         from . import entropy_coding as ec
         tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
         L = len(out_xo_list)
+        step = _check_step(step, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], out_xe,
                                             out_xe.shape, tabs, coder=coder)
@@ -474,9 +487,10 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, x.shape[2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
                 if packed[1] is not None:       # the reference's cgp widths: one fused launch per wavefront step
-                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder)
+                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder, step=step)
                 else:
-                    s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs, coder=coder)
+                    s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs, coder=coder,
+                                                         step=step)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -484,13 +498,14 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
         """decompress_ar for every tensor (:419-454): strings -> (xe, [xo] finest first), bit-identical to compress_planes'
         dequantised tensors.  first_level = k: decode xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}])
         (_coarse_strings; onlyEZWT.decompress_planes)."""
         from . import entropy_coding as ec
         tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
         L = len(shapes_xo)
+        step = _check_step(step, L)
         strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], None, shape_xe, tabs,
@@ -504,10 +519,11 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, shapes_xo[i][2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
                 if packed[1] is not None:
-                    _, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, None, shapes_xo[i], tabs, strings_xo_list[i], coder=coder)
+                    _, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, None, shapes_xo[i], tabs, strings_xo_list[i], coder=coder,
+                                              step=step)
                 else:
                     _, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, None, shapes_xo[i], tabs,
-                                                      strings_xo_list[i], coder=coder)
+                                                      strings_xo_list[i], coder=coder, step=step)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -633,12 +649,13 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return packs
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host"):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first), *_q the decoder's values."""
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(out_xo_list)
+        step = _check_step(step, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
             s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
@@ -646,7 +663,8 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
             for i in range(L - 1):
                 x = out_xo_list[L - i - 2]
                 ems, tabs = cls._level_models(layers, i, L)
-                s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs, coder=coder)
+                s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs, coder=coder,
+                                             step=step)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -654,13 +672,14 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return s_xe, s_list, xe_q, q_list
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0):
+    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
         """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
         xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]) (_coarse_strings; onlyEZWT.decompress_planes)."""
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(shapes_xo)
+        step = _check_step(step, L)
         strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
@@ -671,7 +690,7 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
             for i in range(L - 1 - first_level):          # i counts from the coarse end: level L - i - 2 >= first_level
                 ems, tabs = cls._level_models(layers, i, L)
                 _, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, None, shapes_xo[L - i - 2], tabs,
-                                             strings_xo_list[L - i - 2], coder=coder)
+                                             strings_xo_list[L - i - 2], coder=coder, step=step)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -1047,24 +1066,26 @@ def compress_planes(nets, x):
     return xhat, s_xe, s_xo
 
 
-def encode_strings_planes(nets, x, coder="host", recon=False):
+def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0):
     """The encoder half of compress_planes: encode -> the entropy layer's compress_planes, no decoding.
     x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first).  coder: "host" (rans64 on the host) or "gpu"
     (irans32 on the device); the symbols are the same, the bytes differ.
     recon=True: -> (strings_xe, strings_xo, xhat), xhat (P,B,C,H,W) being decode_planes of the dequantised tensors
     compress_planes returns -- the tensors decompress_planes returns for these strings, through the call
-    decode_strings_planes makes (the codec's residual layer)."""
+    decode_strings_planes makes (the codec's residual layer).
+    step: the quantisation step of the levels 0 .. L-2 (n / 16, 1 = the trained operating point)."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "compress_planes"):
         raise NotImplementedError(_NOT_CODED)
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
-    s_xe, s_xo, xe_q, xo_q = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder)
+    kw = {} if step == 1.0 else {"step": step}
+    s_xe, s_xo, xe_q, xo_q = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder, **kw)
     if recon:
         return s_xe, s_xo, decode_planes([n.autoencoder for n in nets], xe_q, xo_q)
     return s_xe, s_xo
 
 
-def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0):
+def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0, step=1.0):
     """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them, with the same coder) ->
     xhat (P,B,C,Hp,Wp).
     Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes).
@@ -1076,7 +1097,8 @@ def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host",
     aenc = [n.autoencoder for n in nets]
     k = int(first_level)
     shape_xe, shapes_xo = encode_shapes(aenc, B, Hp, Wp)
-    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder, first_level=k)
+    kw = {} if step == 1.0 else {"step": step}              # the step the strings were coded with (the container's header)
+    xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder, first_level=k, **kw)
     assert [tuple(t.shape) for t in xo] == [tuple(sh) for sh in shapes_xo[k:]]
     return decode_planes(aenc, xe, xo, first_level=k)
 

@@ -969,6 +969,86 @@ def ztblock_phase(parent, level, packed, k, out=None):
     return params
 
 
+STEP_DENOM = 16                      # a quantisation step is n / STEP_DENOM with an integer n in [STEP_N_MIN, STEP_N_MAX]
+STEP_N_MIN, STEP_N_MAX = 4, 1024
+COST_ONE_BIT = 1 << 16               # lldwt_code_cost counts in units of 2^-16 bit
+COST_ESCAPE = 32 * COST_ONE_BIT      # the fixed cost of a symbol outside its table
+
+
+def step_pair(step):
+    """A quantisation step -> (q, inv_q) as Python floats holding fp32 values: q = n / 16 with an integer n
+    in [4, 1024] (exact in fp32) and inv_q = fp32(1 / q), formed here once.  ValueError naming step otherwise."""
+    try:
+        q = float(step)
+    except (TypeError, ValueError):
+        raise ValueError("step must be a number n / 16 with an integer n in [%d, %d] (got %r)"
+                         % (STEP_N_MIN, STEP_N_MAX, step)) from None
+    n = q * STEP_DENOM
+    if not (n == n and STEP_N_MIN <= n <= STEP_N_MAX and n == int(n)):
+        raise ValueError("step must be n / 16 with an integer n in [%d, %d], i.e. a multiple of 0.0625 in [0.25, 64] (got %r)"
+                         % (STEP_N_MIN, STEP_N_MAX, step))
+    return q, float(torch.tensor(1.0 / q, dtype=torch.float32))
+
+
+def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=None):
+    """The Gaussian quantiser with a step on a whole grid in one launch (lldwt_gauss_quantise).  params (P,B,2C,h,w): sigma on
+    the even, mu on the odd channels; level (P,B,C,H,W): the positions (r0 + stride i, c0 + stride j) receive symbol * q + mu,
+    the others are left alone.  Encoder: y (P,B,C,H,W) coefficients read at the same positions (may be level) -> (idx, sym),
+    (P,B,C,h,w) int32.  Decoder: sym (P,B,C,h,w) int32 -> (idx, sym).  Neither (level None too): -> (idx, None), what the
+    decoder needs before it can pop the symbols.  table63: the scale table's first 63 entries."""
+    P, B, C2, h, w = params.shape
+    Cc = C2 // 2
+    q, inv_q = step_pair(step)
+    if (y is not None and sym is not None) or (level is None) != (y is None and sym is None):
+        raise _lib.LLDWTError("gauss_quantise: give y (encoder) or sym (decoder) with level, or none of the three")
+    if C2 != 2 * Cc or (level is not None and (level.dim() != 5 or tuple(level.shape[:3]) != (P, B, Cc))) or \
+            (y is not None and y.shape != level.shape):
+        raise _lib.LLDWTError("gauss_quantise: params %s, level %s, y %s do not belong together" % (
+            tuple(params.shape), None if level is None else tuple(level.shape), None if y is None else tuple(y.shape)))
+    if table63.numel() != 63:
+        raise _lib.LLDWTError("gauss_quantise: the table must hold 63 entries (got %d)" % table63.numel())
+    if sym is not None and not (sym.is_cuda and sym.dtype == torch.int32 and sym.is_contiguous() and sym.numel() == P * B * Cc * h * w):
+        raise _lib.LLDWTError("gauss_quantise: sym must be a contiguous int32 device tensor of %d values" % (P * B * Cc * h * w))
+    H, W = (level.shape[3], level.shape[4]) if level is not None else (r0 + stride * (h - 1) + 1, c0 + stride * (w - 1) + 1)
+    idx = torch.empty(P, B, Cc, h, w, device=params.device, dtype=torch.int32)
+    out = torch.empty_like(idx) if y is not None else None
+    p = lambda t: C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+    check(_lib.load().lldwt_gauss_quantise(_chk(params, "params"), _opt(y, "y"), p(sym), _chk(table63, "table63"), p(idx), p(out),
+                                           _opt(level, "level"), P * B, Cc, h, w, H, W, int(r0), int(c0), int(stride), q, inv_q,
+                                           _stream()), "gauss_quantise")
+    return idx, (out if y is not None else None if sym is None else sym.reshape(P, B, Cc, h, w))
+
+
+def cost_table(cdf, sizes):
+    """Quantised CDF tables (host int32 arrays: cdf (T, width), sizes (T)) -> (T, width) int32 numpy array for code_cost:
+    round(-log2(freq / 65536) * 2^16) for the sizes[t] - 2 symbols of table t, COST_ESCAPE elsewhere."""
+    import numpy as np
+    cdf = np.asarray(cdf, dtype=np.int64)
+    freq = np.diff(cdf, axis=1, append=cdf[:, -1:])
+    col = np.arange(cdf.shape[1])[None, :]
+    ok = (col < np.asarray(sizes)[:, None] - 2) & (freq > 0)
+    bits = -np.log2(np.where(ok, freq, 1) / 65536.0)
+    return np.where(ok, np.rint(bits * COST_ONE_BIT), COST_ESCAPE).astype(np.int32)
+
+
+def code_cost(sym, idx, cost, sizes, offsets):
+    """sym, idx: (Z, n) int32 device tensors; cost (T, width), sizes (T), offsets (T): int32 device tensors (cost_table)
+    -> (sums, escapes): (Z) int64 device tensors, the code length of each stream in units of 2^-16 bit (an escape counts
+    COST_ESCAPE) and its number of escapes (lldwt_code_cost; exact integer sums)."""
+    for t in (sym, idx, cost, sizes, offsets):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise _lib.LLDWTError("code_cost: every argument must be a contiguous int32 device tensor")
+    if sym.dim() != 2 or sym.shape != idx.shape or cost.dim() != 2 or sizes.numel() != cost.shape[0] or offsets.numel() != cost.shape[0]:
+        raise _lib.LLDWTError("code_cost: sym / idx must be (Z, n) and cost (T, width) with T sizes and offsets")
+    Z, n = sym.shape
+    sums = torch.zeros(Z, device=sym.device, dtype=torch.int64)
+    esc = torch.zeros(Z, device=sym.device, dtype=torch.int64)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    check(_lib.load().lldwt_code_cost(p(sym), p(idx), Z, n, p(cost), cost.shape[0], cost.shape[1], p(sizes), p(offsets),
+                                      COST_ESCAPE, p(sums), p(esc), _stream()), "code_cost")
+    return sums, esc
+
+
 def cgp_pack(ws, bs, groups):
     """ws: 4 stacked 1x1 conv weights (P, groups*c_{l+1}, c_l, 1, 1); bs: 4 biases (P, groups*c_{l+1})."""
     lib = _lib.load()

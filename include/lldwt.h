@@ -524,6 +524,33 @@ int lldwt_cgp16_wavefront_step(const float* plc, float* yhat, const float* y, co
                                int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, void* stream);
 int lldwt_wavefront_apply(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h, int64_t w,
                           int groups, int K, int t, int64_t ntot, int64_t off, void* stream);
+/* The same two with a quantisation step (variable-rate coding): q = n / 16 with an integer n in [4, 1024] and
+ * inv_q = fp32(1 / q), both formed on the host and checked here.  All in fp32:
+ *   CDF index = number of table63 entries < max(sigma * inv_q, 0.11);  sym = rint((y - mu) * inv_q);  yhat = sym * q + mu
+ * (sym * q is exact for |sym| < 2^12, so a fused and an unfused multiply-add agree).  q = inv_q = 1 gives the bits of the two
+ * entry points above, which forward here.  sigma_out (decoder mode only, may be null): the step's sigmas in mu's layout. */
+int lldwt_cgp16_wavefront_step_q(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                 int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h,
+                                 int64_t w, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q,
+                                 float inv_q, void* stream);
+int lldwt_wavefront_apply_q(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h, int64_t w,
+                            int groups, int K, int t, int64_t ntot, int64_t off, float q, float inv_q, void* stream);
+/* The same quantiser for a level whose (sigma, mu) are known for a whole grid at once (csrc/quant.hip): a ZTBlock phase or an
+ * onlyEZWT level in one launch.  params (streams, 2 channels, h, w): sigma of channel c on 2c, mu on 2c + 1.  The grid is the
+ * positions (r0 + stride i, c0 + stride j), i < h, j < w, of the (streams, channels, H, W) tensors y and level; level is
+ * written there and nowhere else.  Encoder (y != null, sym_in null): idx and sym_out (streams, channels, h, w) int32 and the
+ * dequantised value into level.  Decoder (sym_in != null, y null): idx again and the value into level.  Neither (level null
+ * too): idx alone, which the decoder needs before it can pop the symbols.  y may be level itself. */
+int lldwt_gauss_quantise(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
+                         int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W,
+                         int r0, int c0, int stride, float q, float inv_q, void* stream);
+/* Code length of `streams` streams of n (sym, idx) pairs under quantised tables, for the byte-target search: sums[z] += sum of
+ * cost[idx][sym - offsets[idx]] with cost (ntab, width) int32 in units of 2^-16 bit, and esc_cost for a symbol outside
+ * [0, sizes[idx] - 2) or an index outside [0, ntab), which escapes[z] counts.  sums and escapes (int64) must be ZERO on entry;
+ * integer additions, so the result is exact and independent of their order. */
+int lldwt_code_cost(const int32_t* sym, const int32_t* idx, int64_t streams, int64_t n, const int32_t* cost, int32_t ntab,
+                    int32_t width, const int32_t* sizes, const int32_t* offsets, int32_t esc_cost, int64_t* sums, int64_t* escapes,
+                    void* stream);
 /* Real entropy coding of DWTConditioned2EntropyLayerZTBlock (csrc/ztblock.hip; nets: LiftingBasedDWT_net.py:618-624,716-744):
  * (sigma, mu) of ONE polyphase phase k (1 ee, 2 eo, 3 oe, 4 oo) of every plane, image and of the 3 subbands, both heads, in
  * one launch.  parent (planes, batch, 3, h2, w2): the decoded coarser level; level (planes, batch, 3, 2*h2, 2*w2): the

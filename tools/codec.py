@@ -17,6 +17,11 @@
     encode --coder gpu                     codes the streams with the interleaved device coder (irans32); decode reads the
                                            coder from the header
 
+    encode --step Q                        quantises the levels below the coarsest with the step Q = n / 16 in [0.25, 64]
+                                           (1: the trained operating point); decode reads the step from the header
+    encode --target-bytes T | --target-bpp R   chooses the finest step of the quarter-octave grid whose container is at most
+                                           T bytes (R bits per pixel: T = floor(R * H * W / 8)); info prints the step
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -90,6 +95,10 @@ def main(argv=None):
     sub.choices["encode"].add_argument("--near", type=int, metavar="D",
                                        help="add a residual layer that bounds every sample's error by D in 1..32 (0: lossless)")
     sub.choices["encode"].add_argument("--lossless", action="store_true", help="the same as --near 0")
+    rate = sub.choices["encode"].add_mutually_exclusive_group()
+    rate.add_argument("--step", type=float, metavar="Q", help="quantisation step n / 16 in [0.25, 64] (default 1)")
+    rate.add_argument("--target-bytes", type=int, metavar="T", help="finest grid step whose container is at most T bytes")
+    rate.add_argument("--target-bpp", type=float, metavar="R", help="the same for R bits per pixel")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
                                        help="decode the base layer of a refined (LLDR) container only")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
@@ -145,6 +154,12 @@ def main(argv=None):
             print("--lossless is --near 0; give one of them", file=sys.stderr)
             return 2
         kw = {"near": 0 if a.lossless else a.near} if (a.lossless or a.near is not None) else {}
+        if a.step is not None:
+            kw["step"] = a.step
+        elif a.target_bytes is not None:
+            kw["target_bytes"] = a.target_bytes
+        elif a.target_bpp is not None:
+            kw["target_bytes"] = codec.target_bpp_bytes(a.target_bpp, img.shape[0], img.shape[1])
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tile is None:
@@ -167,6 +182,8 @@ def main(argv=None):
         if "base" in hdr:
             print("near %d: base %d bytes, residual %d bytes" % (hdr["near"], hdr["base_bytes"], hdr["residual_bytes"]))
             hdr = hdr["base"]
+        if hdr["step"] != 1.0:
+            print("step: %g" % hdr["step"])
         if a.tile is not None:
             print("tiles: %d x %d of %dx%d" % (hdr["ny"], hdr["nx"], hdr["tw"], hdr["th"]))
             if hdr["overlap"]:

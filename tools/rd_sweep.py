@@ -1,0 +1,80 @@
+"""Rate-distortion table of the codec over quantisation steps, for one image and one net:
+
+    python tools/rd_sweep.py --config cfg.json [--checkpoint ckpt.pth.tar] [--image in.png | --size 512]
+                             [--steps 0.25,0.5,1,2,4,8,16,32,64] [--coder host|gpu]
+
+Per step: container bytes, bits per pixel, PSNR and MS-SSIM of the decoded image (codec.quality), and the share of the
+container that the step cannot move -- the header, the xe streams and the streams of the coarsest level, which keep the unit
+step.  Without --image the input is a synthetic --size x --size image: smooth colour fields plus noise, seeded.  The config
+and checkpoint are those of tools/codec.py."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
+
+from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import codec  # noqa: E402
+
+
+def synthetic(size, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    low = torch.rand(1, 3, max(2, size // 16), max(2, size // 16), generator=g)
+    x = torch.nn.functional.interpolate(low, size=(size, size), mode="bilinear", align_corners=False)
+    x = x * 200 + torch.rand(1, 3, size, size, generator=g) * 40
+    return x.clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def fixed_bytes(hdr):
+    """Bytes of a container a step does not reach: everything but the xo streams of the levels 0 .. L-2."""
+    per = hdr["dwtlevels"] + 1
+    moved = sum(n for i, n in enumerate(hdr["stream_lengths"]) if 1 <= i % per < per - 1)
+    return hdr["header_bytes"] + 4 + sum(hdr["stream_lengths"]) - moved
+
+
+def sweep(net, img, steps, coder="host"):
+    """-> list of dicts (step, bytes, bpp, psnr, msssim, fixed_bytes), one per step."""
+    H, W = img.shape[1:3]
+    rows = []
+    for q in steps:
+        blob = codec.encode_images(net, img, coder=coder, step=q)[0]
+        dec = codec.decode_images(net, [blob])[0]
+        qual = codec.quality(img[0], dec)
+        rows.append(dict(step=q, bytes=len(blob), bpp=len(blob) * 8 / (H * W), psnr=qual["psnr"], msssim=qual["msssim"],
+                         fixed_bytes=fixed_bytes(codec.read_header(blob))))
+    return rows
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--checkpoint")
+    ap.add_argument("--image")
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--steps", default="0.25,0.5,1,2,4,8,16,32,64")
+    ap.add_argument("--coder", choices=("host", "gpu"), default="host")
+    ap.add_argument("--json", action="store_true", help="print one JSON line per step instead of the table")
+    a = ap.parse_args(argv)
+    from codec import _load_rgb, build_net            # tools/codec.py
+    net = build_net(a.config, a.checkpoint)
+    img = _load_rgb(a.image)[None] if a.image else synthetic(a.size)
+    rows = sweep(net, img, [float(v) for v in a.steps.split(",")], a.coder)
+    if a.json:
+        for r in rows:
+            print(json.dumps(r))
+        return 0
+    print("%8s %10s %8s %10s %10s %8s" % ("step", "bytes", "bpp", "psnr dB", "ms-ssim", "fixed %"))
+    for r in rows:
+        print("%8g %10d %8.4f %10.4f %10s %8.1f" % (r["step"], r["bytes"], r["bpp"], r["psnr"],
+                                                    "n/a" if r["msssim"] is None else "%.6f" % r["msssim"],
+                                                    100.0 * r["fixed_bytes"] / r["bytes"]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
