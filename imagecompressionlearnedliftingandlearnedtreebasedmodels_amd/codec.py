@@ -122,6 +122,9 @@ REFINED_MAGIC = b"LLDR"
 REFINED_FORMAT_VERSION = 1
 _RFIXED = struct.Struct("<4sBBBBI")            # magic, version, near, classes, ladder id, table CRC32
 _RUNIT = struct.Struct("<QQ24s")               # cs(xh), cs(x), the 24 table indexes
+# the base containers: magic -> (format version, fixed struct)
+_BASE = {MAGIC: (FORMAT_VERSION, _FIXED), TILED_MAGIC: (TILED_FORMAT_VERSION, _TFIXED),
+         LAPPED_MAGIC: (LAPPED_FORMAT_VERSION, _OFIXED)}
 _PLANES = 3
 # coder name of the API -> value of the arithmetic string's "coder" key (None: the key is absent)
 CODER_KEYS = {"host": None, "gpu": "irans32"}
@@ -312,82 +315,6 @@ def _parse_streams(blob, pos, end, count):
     return streams, lengths
 
 
-def pack_container(hdr, streams):
-    """hdr: dict with layer, netType, dwtlevels, H, W, numerics, arithmetic, digest; streams: list of bytes -> container."""
-    ident = _pack_identity(hdr)
-    if len(streams) > 255:
-        raise ValueError("more than 255 streams")
-    head = _FIXED.pack(MAGIC, FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], hdr["dwtlevels"],
-                       hdr["H"], hdr["W"], hdr["numerics"])
-    return _seal(head + ident + bytes([len(streams)]) + _pack_streams(streams))
-
-
-def parse_container(blob):
-    """Container -> (header dict, list of stream bytes).  Every structural check (magic, version, CRC, truncation, stream
-    count, lengths) raises ValueError naming the field; nothing here touches the GPU library."""
-    blob, end = _open(blob, MAGIC, FORMAT_VERSION, _FIXED.size + 1 + 16 + 1)
-    _, _, layer, nettype, L, H, W, numerics = _FIXED.unpack_from(blob, 0)
-    _check_model_fields(layer, nettype, L, H, W)
-    arith, digest, count, pos = _parse_identity(blob, _FIXED.size, end)
-    if count != _PLANES * (L + 1):
-        raise ValueError("stream count %d does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
-    coder, _ = _split_coder(arith)
-    step_n, _ = _split_step(arith)
-    streams, lengths = _parse_streams(blob, pos, end, count)
-    hdr = dict(version=FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
-               numerics=numerics, arithmetic=arith, coder=coder, step=step_n / STEP_DENOM, digest=digest,
-               stream_lengths=lengths, header_bytes=end - sum(lengths))
-    return hdr, streams
-
-
-def _check_grid(nettype, L, H, W, th, tw, ny, nx):
-    """The grid fields of an LLDT header against the image size and the transform (ValueError naming the field)."""
-    from .graphs.layers.lifting_dwt_nets import padded_dims
-    if th < 1 or tw < 1 or ny < 1 or nx < 1:
-        raise ValueError("tile grid: th, tw, ny, nx must be positive (got %d, %d, %d, %d)" % (th, tw, ny, nx))
-    if ny * th < H or (ny - 1) * th >= H:
-        raise ValueError("tile grid rows: %d tiles of %d rows do not fit an image of %d rows" % (ny, th, H))
-    if nx * tw < W or (nx - 1) * tw >= W:
-        raise ValueError("tile grid columns: %d tiles of %d columns do not fit an image of %d columns" % (nx, tw, W))
-    if padded_dims(L, nettype == "CDF97", th, tw) != (th, tw):
-        raise ValueError("tile size: %d x %d is not a size the %s transform at %d levels accepts" % (th, tw, nettype, L))
-
-
-def pack_tiled(hdr, tile_streams):
-    """hdr: as pack_container plus th, tw, ny, nx; tile_streams: ny * nx lists of 3 (L + 1) streams in raster order of
-    (ty, tx) -> LLDT container."""
-    L, ny, nx = hdr["dwtlevels"], hdr["ny"], hdr["nx"]
-    _check_grid(hdr["netType"], L, hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx)
-    if ny > 0xFFFF or nx > 0xFFFF:
-        raise ValueError("tile grid: ny, nx must fit 16 bits")
-    if len(tile_streams) != ny * nx or any(len(t) != _PLANES * (L + 1) for t in tile_streams):
-        raise ValueError("stream count: expected %d tiles of %d streams" % (ny * nx, _PLANES * (L + 1)))
-    head = _TFIXED.pack(TILED_MAGIC, TILED_FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], L,
-                        hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx, hdr["numerics"])
-    return _seal(head + _pack_identity(hdr) + bytes([_PLANES * (L + 1)])
-                 + _pack_streams([s for t in tile_streams for s in t]))
-
-
-def parse_tiled(blob):
-    """LLDT container -> (header dict, list of ny * nx lists of stream bytes).  The structural checks of parse_container plus
-    the grid (ValueError naming the field); host only.  The dict carries overlap = 0 (LLDO: parse_lapped)."""
-    blob, end = _open(blob, TILED_MAGIC, TILED_FORMAT_VERSION, _TFIXED.size + 1 + 16 + 1)
-    _, _, layer, nettype, L, H, W, th, tw, ny, nx, numerics = _TFIXED.unpack_from(blob, 0)
-    _check_model_fields(layer, nettype, L, H, W)
-    _check_grid(_NETTYPE_NAMES[nettype], L, H, W, th, tw, ny, nx)
-    arith, digest, count, pos = _parse_identity(blob, _TFIXED.size, end)
-    if count != _PLANES * (L + 1):
-        raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
-    coder, _ = _split_coder(arith)
-    step_n, _ = _split_step(arith)
-    streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
-    tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
-    hdr = dict(version=TILED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
-               W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=0, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
-               step=step_n / STEP_DENOM, streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
-    return hdr, tiles
-
-
 def _check_overlap(L, th, tw, ov):
     """The overlap of a lapped grid against the level count and the tile size (ValueError naming overlap)."""
     if ov < 1 or ov & (ov - 1):
@@ -399,57 +326,115 @@ def _check_overlap(L, th, tw, ov):
                          % (ov, th, tw))
 
 
-def _check_grid_lapped(nettype, L, H, W, th, tw, ny, nx, ov):
-    """The grid fields of an LLDO header against the image size and the transform (ValueError naming the field): the
-    overlap rule, then along each axis of n tiles of t at the stride s = t - ov: (n - 1) s + t >= size, and for n >= 2 the
-    last tile is needed, (n - 2) s + t < size."""
+def _check_grid(nettype, L, H, W, th, tw, ny, nx, ov=None):
+    """The grid fields of an LLDT (ov = None) or LLDO header against the image size and the transform (ValueError naming
+    the field): the overlap rule of a lapped grid, then along each axis of n tiles of t at the stride s = t - ov (s = t for
+    LLDT): (n - 1) s + t >= size, and for n >= 2 the last tile is needed, (n - 2) s + t < size."""
     from .graphs.layers.lifting_dwt_nets import padded_dims
     if th < 1 or tw < 1 or ny < 1 or nx < 1:
         raise ValueError("tile grid: th, tw, ny, nx must be positive (got %d, %d, %d, %d)" % (th, tw, ny, nx))
     if padded_dims(L, nettype == "CDF97", th, tw) != (th, tw):
         raise ValueError("tile size: %d x %d is not a size the %s transform at %d levels accepts" % (th, tw, nettype, L))
-    _check_overlap(L, th, tw, ov)
-    sh, sw = th - ov, tw - ov
+    if ov is not None:
+        _check_overlap(L, th, tw, ov)
+    sh, sw = th - (ov or 0), tw - (ov or 0)
     if (ny - 1) * sh + th < H or (ny >= 2 and (ny - 2) * sh + th >= H):
-        raise ValueError("tile grid rows: %d tiles of %d rows at a stride of %d do not fit an image of %d rows"
-                         % (ny, th, sh, H))
+        raise ValueError("tile grid rows: %d tiles of %d rows%s do not fit an image of %d rows"
+                         % (ny, th, "" if ov is None else " at a stride of %d" % sh, H))
     if (nx - 1) * sw + tw < W or (nx >= 2 and (nx - 2) * sw + tw >= W):
-        raise ValueError("tile grid columns: %d tiles of %d columns at a stride of %d do not fit an image of %d columns"
-                         % (nx, tw, sw, W))
+        raise ValueError("tile grid columns: %d tiles of %d columns%s do not fit an image of %d columns"
+                         % (nx, tw, "" if ov is None else " at a stride of %d" % sw, W))
+
+
+def _check_grid_lapped(nettype, L, H, W, th, tw, ny, nx, ov):
+    """The grid fields of an LLDO header: _check_grid with the overlap rule (an overlap of 0 is refused)."""
+    _check_grid(nettype, L, H, W, th, tw, ny, nx, int(ov))
+
+
+def _pack_base(magic, hdr, units):
+    """The pack routine of the three base containers.  hdr: dict with layer, netType, dwtlevels, H, W, numerics, arithmetic,
+    digest, for LLDT / LLDO also th, tw, ny, nx and for LLDO overlap; units: the stream lists, one for LLDW (written as it is:
+    the parser refuses a count other than 3 (L + 1)), ny * nx of 3 (L + 1) streams in raster order of (ty, tx) otherwise."""
+    version, fixed = _BASE[magic]
+    L, grid = hdr["dwtlevels"], ()
+    if magic == MAGIC:
+        count = len(units[0])
+    else:
+        count = _PLANES * (L + 1)
+        grid = (hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"]) + ((hdr["overlap"],) if magic == LAPPED_MAGIC else ())
+        _check_grid(hdr["netType"], L, hdr["H"], hdr["W"], *grid)
+        if hdr["ny"] > 0xFFFF or hdr["nx"] > 0xFFFF:
+            raise ValueError("tile grid: ny, nx must fit 16 bits")
+        if len(units) != hdr["ny"] * hdr["nx"] or any(len(u) != count for u in units):
+            raise ValueError("stream count: expected %d tiles of %d streams" % (hdr["ny"] * hdr["nx"], count))
+    ident = _pack_identity(hdr)
+    if count > 255:
+        raise ValueError("more than 255 streams")
+    head = fixed.pack(magic, version, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], L, hdr["H"], hdr["W"], *grid,
+                      hdr["numerics"])
+    return _seal(head + ident + bytes([count]) + _pack_streams([s for u in units for s in u]))
+
+
+def _parse_base(magic, blob):
+    """The parse routine of the three base containers -> (header dict, list of per-unit lists of stream bytes: one unit for
+    LLDW, ny * nx for LLDT / LLDO).  Every structural check (magic, version, CRC, truncation, the grid, stream count,
+    lengths) raises ValueError naming the field; nothing here touches the GPU library.  A tiled header carries th, tw, ny,
+    nx, overlap (0 for LLDT) and streams_per_tile; an LLDW header has none of them."""
+    version, fixed = _BASE[magic]
+    blob, end = _open(blob, magic, version, fixed.size + 1 + 16 + 1)
+    _, _, layer, nettype, L, H, W, *grid, numerics = fixed.unpack_from(blob, 0)
+    _check_model_fields(layer, nettype, L, H, W)
+    if grid:
+        _check_grid(_NETTYPE_NAMES[nettype], L, H, W, *grid)
+    arith, digest, count, pos = _parse_identity(blob, fixed.size, end)
+    if count != _PLANES * (L + 1):
+        raise ValueError("stream count %d%s does not match dwtlevels %d (expected %d)"
+                         % (count, " per tile" if grid else "", L, _PLANES * (L + 1)))
+    coder, _ = _split_coder(arith)
+    step_n, _ = _split_step(arith)
+    n = grid[2] * grid[3] if grid else 1
+    streams, lengths = _parse_streams(blob, pos, end, n * count)
+    hdr = dict(version=version, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
+               numerics=numerics, arithmetic=arith, coder=coder, step=step_n / STEP_DENOM, digest=digest,
+               stream_lengths=lengths, header_bytes=end - sum(lengths))
+    if grid:
+        hdr.update(th=grid[0], tw=grid[1], ny=grid[2], nx=grid[3], overlap=grid[4] if magic == LAPPED_MAGIC else 0,
+                   streams_per_tile=count)
+    return hdr, [streams[u * count:(u + 1) * count] for u in range(n)]
+
+
+def pack_container(hdr, streams):
+    """hdr: dict with layer, netType, dwtlevels, H, W, numerics, arithmetic, digest; streams: list of bytes -> container."""
+    return _pack_base(MAGIC, hdr, [streams])
+
+
+def parse_container(blob):
+    """Container -> (header dict, list of stream bytes); ValueError as _parse_base, host only."""
+    hdr, units = _parse_base(MAGIC, blob)
+    return hdr, units[0]
+
+
+def pack_tiled(hdr, tile_streams):
+    """hdr: as pack_container plus th, tw, ny, nx; tile_streams: ny * nx lists of 3 (L + 1) streams in raster order of
+    (ty, tx) -> LLDT container."""
+    return _pack_base(TILED_MAGIC, hdr, tile_streams)
+
+
+def parse_tiled(blob):
+    """LLDT container -> (header dict, list of ny * nx lists of stream bytes).  The structural checks of parse_container plus
+    the grid (ValueError naming the field); host only.  The dict carries overlap = 0 (LLDO: parse_lapped)."""
+    return _parse_base(TILED_MAGIC, blob)
 
 
 def pack_lapped(hdr, tile_streams):
     """hdr: as pack_tiled plus overlap (> 0); tile_streams as pack_tiled -> LLDO container."""
-    L, ny, nx, ov = hdr["dwtlevels"], hdr["ny"], hdr["nx"], hdr["overlap"]
-    _check_grid_lapped(hdr["netType"], L, hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx, ov)
-    if ny > 0xFFFF or nx > 0xFFFF:
-        raise ValueError("tile grid: ny, nx must fit 16 bits")
-    if len(tile_streams) != ny * nx or any(len(t) != _PLANES * (L + 1) for t in tile_streams):
-        raise ValueError("stream count: expected %d tiles of %d streams" % (ny * nx, _PLANES * (L + 1)))
-    head = _OFIXED.pack(LAPPED_MAGIC, LAPPED_FORMAT_VERSION, LAYER_CODES[hdr["layer"]], NETTYPE_CODES[hdr["netType"]], L,
-                        hdr["H"], hdr["W"], hdr["th"], hdr["tw"], ny, nx, ov, hdr["numerics"])
-    return _seal(head + _pack_identity(hdr) + bytes([_PLANES * (L + 1)])
-                 + _pack_streams([s for t in tile_streams for s in t]))
+    return _pack_base(LAPPED_MAGIC, hdr, tile_streams)
 
 
 def parse_lapped(blob):
     """LLDO container -> (header dict with overlap, list of ny * nx lists of stream bytes).  The structural checks of
-    parse_tiled with the lapped grid rule (_check_grid_lapped; ValueError naming the field); host only."""
-    blob, end = _open(blob, LAPPED_MAGIC, LAPPED_FORMAT_VERSION, _OFIXED.size + 1 + 16 + 1)
-    _, _, layer, nettype, L, H, W, th, tw, ny, nx, ov, numerics = _OFIXED.unpack_from(blob, 0)
-    _check_model_fields(layer, nettype, L, H, W)
-    _check_grid_lapped(_NETTYPE_NAMES[nettype], L, H, W, th, tw, ny, nx, ov)
-    arith, digest, count, pos = _parse_identity(blob, _OFIXED.size, end)
-    if count != _PLANES * (L + 1):
-        raise ValueError("stream count %d per tile does not match dwtlevels %d (expected %d)" % (count, L, _PLANES * (L + 1)))
-    coder, _ = _split_coder(arith)
-    step_n, _ = _split_step(arith)
-    streams, lengths = _parse_streams(blob, pos, end, ny * nx * count)
-    tiles = [streams[t * count:(t + 1) * count] for t in range(ny * nx)]
-    hdr = dict(version=LAPPED_FORMAT_VERSION, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H,
-               W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov, numerics=numerics, arithmetic=arith, coder=coder, digest=digest,
-               step=step_n / STEP_DENOM, streams_per_tile=count, stream_lengths=lengths, header_bytes=end - sum(lengths))
-    return hdr, tiles
+    parse_tiled with the lapped grid rule (ValueError naming the field); host only."""
+    return _parse_base(LAPPED_MAGIC, blob)
 
 
 def pack_refined(near, table_crc, base, units):
@@ -542,11 +527,7 @@ def read_header(blob):
     parse_tiled / parse_lapped / parse_refined."""
     if _magic(blob) == REFINED_MAGIC:
         return parse_refined(blob, check_tables=False)[0]
-    if _magic(blob) == LAPPED_MAGIC:
-        return parse_lapped(blob)[0]
-    if _magic(blob) == TILED_MAGIC:
-        return parse_tiled(blob)[0]
-    return parse_container(blob)[0]
+    return _parse_base(_magic(blob) if _magic(blob) in _BASE else MAGIC, blob)[0]
 
 
 def reduce_bytes(hdr):
@@ -803,58 +784,73 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     at most T bytes (_search_step: estimates first, real containers decide; if the sizes are not monotone along the grid,
     the step that walk finds); ValueError naming the smallest achievable size if even the coarsest step does not fit.  Not
     both, and no target with near."""
+    from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
     if near is not None:
         from .residual import check_near
         near = check_near(near)
     n, T = _rate_args(step, target_bytes, near, L)
+    Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T)
+
+
+def _encode_at_rate(net, images_u8, walk, near, step_n, T):
+    """_encode at the step step_n / 16, or with a byte target T the search of _search_step, one image at a time.  walk: the
+    (magic, grid, group, coder) of _encode."""
     if T is None:
-        return _encode_images(net, images_u8, coder, near, n)
-    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode_images(net, i, coder, None, m, estimate=True)[0],
-                         lambda m, i=images_u8[b:b + 1]: _encode_images(net, i, coder, None, m)[0], T) for b in range(B)]
+        return _encode(net, images_u8, *walk, near, step_n)
+    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True)[0],
+                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m)[0], T)
+            for b in range(images_u8.shape[0])]
 
 
-def _encode_images(net, images_u8, coder, near, step_n, estimate=False):
-    """encode_images at the step step_n / 16 (arguments checked).  estimate: -> the estimated container sizes (ints) from the
-    code-length kernel instead of the containers; no range coder runs."""
+def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False):
+    """The encode walk behind encode_images and encode_tiled (arguments checked there): the batch is cut into the tiles of
+    grid = (th, tw, ny, nx, ov) -- the untiled codec is the 1 x 1 grid of one padded_size tile, which the untiled input and
+    output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
+    arithmetics that are not batch invariant) at the step step_n / 16 -> the B containers of ``magic``, with near the LLDR
+    containers over them.  estimate: -> the estimated container sizes (ints) from the code-length kernel instead; no range
+    coder runs."""
     import torch
     from . import ops
-    from .graphs.layers.lifting_dwt_nets import padded_size
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
     from .graphs.models.entropy_coding import ESTIMATE
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
+    th, tw, ny, nx, ov = grid
     nets = net.nets()
-    Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
-    arith = arithmetic_string(coder, step_n / STEP_DENOM)
-    skw = {} if step_n == STEP_DENOM else {"step": step_n / STEP_DENOM}
+    step = step_n / STEP_DENOM
+    arith = arithmetic_string(coder, step)
     _prepare(net)
-    hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, numerics=CODING_NUMERICS_VERSION, arithmetic=arith,
-               digest=weights_digest(net))
+    hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov,
+               numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
     dev = next(net.parameters()).device
     img = images_u8.to(dev).contiguous()
-    x = ops.u8hwc_to_ycc_pad(img, Hp, Wp)                                             # (3,B,1,Hp,Wp)
-    groups = [(0, B)] if _batch_invariant(arith) else [(b, b + 1) for b in range(B)]
-    blobs, recon = [], []
+    per, count = ny * nx, _PLANES * (L + 1)
+    g = group if _batch_invariant(arith) else 1
+    tiles = []
+    xh = torch.empty_like(img) if near is not None else None
     with torch.no_grad():
-        for a, e in groups:
-            if estimate:
-                s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=ESTIMATE, **skw)
-                empty = pack_container(hdr, [b""] * (_PLANES * (L + 1)))
-                blobs += [_estimated_size(empty, _tile_streams(s_xe, s_xo, b)) for b in range(e - a)]
-                continue
-            if near is None:
-                s_xe, s_xo = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder, **skw)
+        for first in range(0, B * per, g):
+            n = min(g, B * per - first)
+            if ov:
+                x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
             else:
-                s_xe, s_xo, xhat = encode_strings_planes(nets, x[:, a:e].contiguous(), coder=coder, recon=True, **skw)
-                recon.append(ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W))          # the decoder's call on the same values
-            for b in range(e - a):
-                streams = [s for p in range(_PLANES) for s in [s_xe[p][b]] + [lev[p][b] for lev in s_xo]]
-                blobs.append(pack_container(hdr, streams))
+                x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
+            if near is None:
+                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, step=step)
+            else:
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, step=step)
+                # the decoder's call on the same values
+                ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W), first=first, B=B, out=xh)
+            tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
+        if estimate:
+            empty = _pack_base(magic, hdr, [[b""] * count] * per)
+            return [_estimated_size(empty, [e for t in tiles[b * per:(b + 1) * per] for e in t]) for b in range(B)]
+        blobs = [_pack_base(magic, hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
         if near is not None:
-            xh = recon[0] if len(recon) == 1 else torch.cat(recon, 0)
-            blobs = _refine(blobs, img, xh.contiguous(), (H, W, Hp, Wp, 1, 1), near, coder)
+            blobs = _refine(blobs, img, xh, (H, W, th, tw, ny, nx), near, coder)
     return blobs
 
 
@@ -919,7 +915,6 @@ def decode_images(net, blobs, reduce=0, refine=True):
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
-    from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
     refined = {}
@@ -948,14 +943,10 @@ def decode_images(net, blobs, reduce=0, refine=True):
             inv_a, b = ll_norm(net, k)
         for (H, W, coder, step), idx in by_size.items():
             Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
-            skw = {} if step == 1.0 else {"step": step}        # the unit step: the call as it has always been
-            groups = [idx] if _batch_invariant(arith) else [[i] for i in idx]
-            for g in groups:
-                per = L + 1                                   # streams per plane: xe, xo finest -> coarsest
-                s_xe = [[parsed[i][1][p * per] for i in g] for p in range(_PLANES)]
-                s_xo = [[[parsed[i][1][p * per + 1 + lev] for i in g] for p in range(_PLANES)] for lev in range(k, L)]
+            units = [parsed[i][1] for i in idx]
+            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k):
+                g = idx[a:a + n]
                 if k == 0:
-                    xhat = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, **skw)
                     img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W)
                     for d in sorted({refined[i][0] for i in g if i in refined}):
                         from . import residual
@@ -964,9 +955,8 @@ def decode_images(net, blobs, reduce=0, refine=True):
                                               [refined[g[j]][1][0] for j in js], d, coder)
                     img = img.cpu()
                 else:
-                    ll = decode_strings_planes(nets, s_xe, s_xo, Hp, Wp, len(g), coder=coder, first_level=k, **skw)
                     Hr, Wr = _reduced(H, k), _reduced(W, k)
-                    img = ops.ll_tiles_to_u8hwc(ll.contiguous(), (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr), inv_a,
+                    img = ops.ll_tiles_to_u8hwc(xhat.contiguous(), (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr), inv_a,
                                                 b, B=len(g)).cpu()
                 for j, i in enumerate(g):
                     out[i] = img[j]
@@ -1052,80 +1042,50 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
         if overlap:
             raise ValueError("near: a residual layer over lapped tiles (overlap > 0) is not defined; use overlap=0")
     n, T = _rate_args(step, target_bytes, near, L)
-    args = (tile, tiles_per_call, coder, overlap)
-    if T is None:
-        return _encode_tiled(net, images_u8, *args, near, n)
-    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode_tiled(net, i, *args, None, m, estimate=True)[0],
-                         lambda m, i=images_u8[b:b + 1]: _encode_tiled(net, i, *args, None, m)[0], T) for b in range(B)]
-
-
-def _encode_tiled(net, images_u8, tile, tiles_per_call, coder, overlap, near, step_n, estimate=False):
-    """encode_tiled at the step step_n / 16 (near and the rate arguments checked); estimate as _encode_images."""
-    import torch
-    from . import ops
-    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
-    from .graphs.models.entropy_coding import ESTIMATE
-    layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8)
-    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
-        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
-    nets = net.nets()
+    group = _tiles_per_call(tiles_per_call)
     ov = int(overlap)
     if ov != overlap or ov < 0 or ov > 0xFFFF:
         raise ValueError("overlap must be an integer in [0, 65535] (got %r)" % (overlap,))
-    if ov:
-        th, tw, ny, nx = tile_grid_lapped([n.autoencoder for n in nets], H, W, int(tile), ov)
-    else:
-        th, tw, ny, nx = tile_grid([n.autoencoder for n in nets], H, W, int(tile))
+    th, tw, ny, nx = tile_grid_lapped([m.autoencoder for m in net.nets()], H, W, int(tile), ov)
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
-    arith = arithmetic_string(coder, step_n / STEP_DENOM)
-    skw = {} if step_n == STEP_DENOM else {"step": step_n / STEP_DENOM}
-    _prepare(net)
-    hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx,
-               numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
-    dev = next(net.parameters()).device
-    img = images_u8.to(dev).contiguous()
-    T = B * ny * nx
-    g = int(tiles_per_call) if _batch_invariant(arith) else 1
-    tiles = []
-    xh = torch.empty_like(img) if near is not None else None
-    with torch.no_grad():
-        for first in range(0, T, g):
-            n = min(g, T - first)
-            if ov:
-                x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
-            else:
-                x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
-            if near is None:
-                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, **skw)
-            else:
-                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, **skw)
-                ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W),
-                                       tiles=list(range(first, first + n)), B=B, out=xh)
-            tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
-        per = ny * nx
-        if ov:
-            hdr["overlap"] = ov
-        if estimate:
-            empty = (pack_lapped if ov else pack_tiled)(hdr, [[b""] * (_PLANES * (L + 1))] * per)
-            return [_estimated_size(empty, [e for t in tiles[b * per:(b + 1) * per] for e in t]) for b in range(B)]
-        if ov:
-            return [pack_lapped(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
-        blobs = [pack_tiled(hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
-        if near is not None:
-            blobs = _refine(blobs, img, xh, (H, W, th, tw, ny, nx), near, coder)
-    return blobs
+    walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
+    return _encode_at_rate(net, images_u8, walk, near, n, T)
+
+
+def _tiles_per_call(tiles_per_call):
+    """The group size of a tiled walk, checked on the host (ValueError naming tiles_per_call)."""
+    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
+        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
+    return int(tiles_per_call)
 
 
 def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step=1.0):
     """One group of n tiles -> xhat (3,n,1,th,tw), or at first_level = k the LL band (3,n,1,th>>k,tw>>k)
     (decode_strings_planes; a module-level hook so the number of tiles a decode touches can be counted)."""
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
-    kw = {} if step == 1.0 else {"step": step}
-    if first_level:
-        return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, **kw)
-    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, **kw)
+    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, step=step)
+
+
+def _gather(units, k, L):
+    """The stream lists of a group of units (images or tiles, each in the LLDW order) -> (s_xe, s_xo) as
+    decode_strings_planes takes them at first_level = k: the xe streams and the xo streams of the levels k .. L-1."""
+    per = L + 1                                       # streams per plane: xe, xo finest -> coarsest
+    s_xe = [[u[p * per] for u in units] for p in range(_PLANES)]
+    s_xo = [[[u[p * per + 1 + lev] for u in units] for p in range(_PLANES)] for lev in range(k, L)]
+    return s_xe, s_xo
+
+
+def _decode_groups(nets, units, th, tw, group, hdr, k):
+    """The decode walk behind decode_images and decode_tiled: the units (stream lists of images or tiles of th x tw, all of
+    the coder and step of hdr) are decoded ``group`` at a time, one per call in the arithmetics that are not batch invariant,
+    through the _decode_tiles hook -> yields (index of the group's first unit, its size n, the hook's result)."""
+    g = group if _batch_invariant(hdr["arithmetic"]) else 1
+    for a in range(0, len(units), g):
+        grp = units[a:a + g]
+        s_xe, s_xo = _gather(grp, k, hdr["dwtlevels"])
+        yield a, len(grp), _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp), coder=hdr["coder"], first_level=k,
+                                         step=hdr["step"])
 
 
 def _region(region, H, W):
@@ -1143,7 +1103,7 @@ def _region(region, H, W):
 def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True):
     """LLDT or LLDO container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
-    LLDO (lapped tiles, _decode_lapped): the tiles covering any pixel of the region, overlap included, are decoded in
+    LLDO (lapped tiles): the tiles covering any pixel of the region, overlap included, are decoded in
     ascending index, each group is blended into a region-sized fp32 buffer (lldwt_ycc_tiles_blend) and the buffer is
     written once, as the single tile of a 1 x 1 grid, by the same output kernels.
     reduce = k in [0, L]: the image at 1/2^k of each side (decode_images); region is then in the coordinates of the reduced
@@ -1155,8 +1115,6 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     from . import ops
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
-    if _magic(blob) == LAPPED_MAGIC:
-        return _decode_lapped(net, (layer, nettype, L), blob, region, tiles_per_call, k)
     units = None
     if _magic(blob) == REFINED_MAGIC:
         rhdr, blob, units = parse_refined(blob)
@@ -1165,93 +1123,49 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
                              % bytes(blob[:4]).decode("ascii", "replace"))
         if not refine or k:
             units = None
-    hdr, tiles = parse_tiled(blob)
-    H, W, th, tw, ny, nx = (hdr[key] for key in ("H", "W", "th", "tw", "ny", "nx"))
-    H, W, th, tw = _reduced(H, k), _reduced(W, k), th >> k, tw >> k          # tile sides are multiples of 2^L
+    hdr, tiles = _parse_base(LAPPED_MAGIC if _magic(blob) == LAPPED_MAGIC else TILED_MAGIC, blob)
+    ny, nx = hdr["ny"], hdr["nx"]
+    # at reduce = k the tile side, the stride and the overlap are all shifted by k (they are multiples of 2^L)
+    H, W, th, tw, ov = _reduced(hdr["H"], k), _reduced(hdr["W"], k), hdr["th"] >> k, hdr["tw"] >> k, hdr["overlap"] >> k
     y0, x0, h, w = _region(region, H, W)
+    # tile q of an axis covers [q s, q s + t) at the stride s = t - ov: the tiles with q s + t > first and q s <= last
+    span = lambda first, last, t, n: range(max(0, (first - t) // (t - ov) + 1), min(n - 1, last // (t - ov)) + 1)
+    rows, cols = span(y0, y0 + h - 1, th, ny), span(x0, x0 + w - 1, tw, nx)
+    want = [ty * nx + tx for ty in rows for tx in cols]                        # ascending tile index: the blend's order
     if units is not None:
         # the residual's contexts reach every pixel of a unit: decode the rectangles of the touched tiles whole, refine
         # them, and cut the region out on the device
         asked = (y0, x0, h, w)
-        y1, x1 = min(H, ((y0 + h - 1) // th + 1) * th), min(W, ((x0 + w - 1) // tw + 1) * tw)
-        y0, x0 = y0 // th * th, x0 // tw * tw
-        h, w = y1 - y0, x1 - x0
-    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
-        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
+        y0, x0 = rows[0] * th, cols[0] * tw
+        h, w = min(H, (rows[-1] + 1) * th) - y0, min(W, (cols[-1] + 1) * tw) - x0
+    group = _tiles_per_call(tiles_per_call)
     check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
     _prepare(net)
     nets = net.nets()
     dev = next(net.parameters()).device
-    want = [ty * nx + tx for ty in range(y0 // th, (y0 + h - 1) // th + 1) for tx in range(x0 // tw, (x0 + w - 1) // tw + 1)]
-    g = int(tiles_per_call) if _batch_invariant(hdr["arithmetic"]) else 1
-    per = L + 1
-    out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
     with torch.no_grad():
         if k:
             inv_a, b = ll_norm(net, k)
-        for a in range(0, len(want), g):
-            grp = want[a:a + g]
-            s_xe = [[tiles[t][p * per] for t in grp] for p in range(_PLANES)]
-            s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(k, L)]
-            kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}     # host: the call as it has always been
-            if k:
-                kw["first_level"] = k
-            if hdr["step"] != 1.0:
-                kw["step"] = hdr["step"]
-            xhat = _decode_tiles(nets, s_xe, s_xo, hdr["th"], hdr["tw"], len(grp), **kw)
+
+        def write(y, grid, reg, **kw):
             if k == 0:
-                ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=grp, out=out)
+                return ops.ycc_tiles_to_u8hwc(y, grid, reg, **kw)
+            return ops.ll_tiles_to_u8hwc(y, grid, reg, inv_a, b, **kw)
+        if ov:
+            acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
+        else:
+            out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
+        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k):
+            if ov:                   # lapped: the raw samples are blended, then written once as the tile of a 1 x 1 grid
+                ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), want[a:a + n], acc)
             else:
-                ops.ll_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), inv_a, b, tiles=grp,
-                                      out=out)
+                write(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=want[a:a + n], out=out)
+        if ov:
+            out = write(acc, (h, w, h, w, 1, 1), (0, 0, h, w))
         if units is not None:
             from . import residual
             residual.decode_units(out, (H, W, th, tw, ny, nx), (y0, x0, h, w), want, [units[t] for t in want], rhdr["near"],
                                   hdr["coder"])
             ay, ax, ah, aw = asked
             out = out[:, ay - y0:ay - y0 + ah, ax - x0:ax - x0 + aw]
-    return out[0].cpu()
-
-
-def _decode_lapped(net, ident, blob, region, tiles_per_call, k):
-    """decode_tiled for an LLDO container at reduce = k (checked by the caller).  At reduce = k the tile side, the stride
-    and the overlap are all shifted by k (they are multiples of 2^L), and the raw LL samples are blended before the
-    per-plane affine map of lldwt_ll_tiles_to_u8hwc."""
-    import torch
-    from . import ops
-    layer, nettype, L = ident
-    hdr, tiles = parse_lapped(blob)
-    ny, nx = hdr["ny"], hdr["nx"]
-    H, W, th, tw, ov = _reduced(hdr["H"], k), _reduced(hdr["W"], k), hdr["th"] >> k, hdr["tw"] >> k, hdr["overlap"] >> k
-    sh, sw = th - ov, tw - ov
-    y0, x0, h, w = _region(region, H, W)
-    if int(tiles_per_call) < 1 or int(tiles_per_call) > 65535:
-        raise ValueError("tiles_per_call must be in [1, 65535] (got %d)" % tiles_per_call)
-    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
-    _prepare(net)
-    nets = net.nets()
-    dev = next(net.parameters()).device
-    # tile q of an axis covers [q s, q s + t): the tiles with q s + t > first and q s <= last
-    span = lambda first, last, t, s, n: range(max(0, (first - t) // s + 1), min(n - 1, last // s) + 1)
-    want = [ty * nx + tx for ty in span(y0, y0 + h - 1, th, sh, ny) for tx in span(x0, x0 + w - 1, tw, sw, nx)]
-    g = int(tiles_per_call) if _batch_invariant(hdr["arithmetic"]) else 1
-    per = L + 1
-    with torch.no_grad():
-        acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
-        for a in range(0, len(want), g):
-            grp = want[a:a + g]                                                # ascending tile index: the blend's order
-            s_xe = [[tiles[t][p * per] for t in grp] for p in range(_PLANES)]
-            s_xo = [[[tiles[t][p * per + 1 + lev] for t in grp] for p in range(_PLANES)] for lev in range(k, L)]
-            kw = {} if hdr["coder"] == "host" else {"coder": hdr["coder"]}
-            if k:
-                kw["first_level"] = k
-            if hdr["step"] != 1.0:
-                kw["step"] = hdr["step"]
-            xhat = _decode_tiles(nets, s_xe, s_xo, hdr["th"], hdr["tw"], len(grp), **kw)
-            ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), grp, acc)
-        if k == 0:
-            out = ops.ycc_tiles_to_u8hwc(acc, (h, w, h, w, 1, 1), (0, 0, h, w))
-        else:
-            inv_a, b = ll_norm(net, k)
-            out = ops.ll_tiles_to_u8hwc(acc, (h, w, h, w, 1, 1), (0, 0, h, w), inv_a, b)
     return out[0].cpu()

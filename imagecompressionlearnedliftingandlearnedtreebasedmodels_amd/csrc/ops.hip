@@ -72,14 +72,19 @@ __global__ void k_ycc_to_rgb(const float* __restrict__ ycc, float* __restrict__ 
 // tile index t = (b * ny + ty) * nx + tx covering rows [ty*th, (ty+1)*th) and columns [tx*tw, (tx+1)*tw); positions past
 // the last row / column take the clamped source pixel (replicate-edge padding).  The untiled codec is the 1x1 grid
 // (th, tw) = (Hp, Wp).
+// Lapped tile grid (codec.encode_tiled(..., overlap=ov)): the tiles lie at the stride
+// (sh, sw) = (th - ov, tw - ov), tile (ty, tx) covering rows [ty*sh, ty*sh + th) and columns [tx*sw, tx*sw + tw); neighbours
+// share a band of ov pixels, and 2 * ov <= min(th, tw) so that at most two tiles cover a pixel along each axis.
 
-// uint8 HWC RGB -> plane-major (3,n,1,th,tw) YCbCr with Y-0.5 for the tiles first .. first+n-1.  The same expressions as
-// k_u8hwc_to_f32chw then k_rgb_to_ycc, so every value is bitwise equal to that composition on the padded tile.
+// uint8 HWC RGB -> plane-major (3,n,1,th,tw) YCbCr with Y-0.5 for the tiles first .. first+n-1 of the grid at the stride
+// (sh, sw): (th, tw) for the plain grid, (th - ov, tw - ov) for the lapped one.  The same expressions as k_u8hwc_to_f32chw
+// then k_rgb_to_ycc, so every value is bitwise equal to that composition on the replicate-padded crop at (ty*sh, tx*sw).
 // Grid (cdiv(tw,256), th, n): one thread per output pixel, every plane row written coalesced.  GRID = false: the 1 x 1 grid
 // (tile = image), without the tile index arithmetic (the kernel is bandwidth-bound and the untiled codec's path).
 template <bool GRID>
 __global__ void k_u8hwc_to_ycc_tiles(const uint8_t* __restrict__ src, float* __restrict__ ycc, int64_t H, int64_t W,
-                                     int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t first, int64_t n) {
+                                     int64_t th, int64_t tw, int64_t sh, int64_t sw, int64_t ny, int64_t nx, int64_t first,
+                                     int64_t n) {
     const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (x >= tw) return;
     const int64_t y = blockIdx.y, j = blockIdx.z;
@@ -88,8 +93,8 @@ __global__ void k_u8hwc_to_ycc_tiles(const uint8_t* __restrict__ src, float* __r
         const uint32_t t = (uint32_t)(first + j), per = (uint32_t)(ny * nx), b32 = t / per, r = t - b32 * per;
         const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
         b = b32;
-        gy += (int64_t)ty * th;
-        gx += (int64_t)tx * tw;
+        gy += (int64_t)ty * sh;
+        gx += (int64_t)tx * sw;
     }
     const int64_t sy = gy < H ? gy : H - 1, sx = gx < W ? gx : W - 1;
     const uint8_t* s = src + ((b * H + sy) * W + sx) * 3;
@@ -159,34 +164,6 @@ __global__ void k_ycc_tiles_to_u8hwc(const float* __restrict__ ycc, const int32_
     if (gy >= H || gx >= W || gy < y0 || gy >= y0 + h || gx < x0 || gx >= x0 + w) return;
     ycc_px_to_u8<AFFINE>(ycc, n, j, hw, (int64_t)blockIdx.y * tw + x, dst + (((int64_t)b * h + (gy - y0)) * w + (gx - x0)) * 3,
                          af);
-}
-
-// Lapped tile grid (codec.encode_tiled(..., overlap=ov)): ny x nx tiles of th x tw at the stride
-// (sh, sw) = (th - ov, tw - ov), tile (ty, tx) covering rows [ty*sh, ty*sh + th) and columns [tx*sw, tx*sw + tw); neighbours
-// share a band of ov pixels, and 2 * ov <= min(th, tw) so that at most two tiles cover a pixel along each axis.
-
-// k_u8hwc_to_ycc_tiles<true> at the stride (sh, sw): the same expressions per pixel, so every value is bitwise that of the
-// 1 x 1 grid on the replicate-padded crop at (ty*sh, tx*sw).  Grid (cdiv(tw,256), th, n), one thread per output pixel.
-__global__ void k_u8hwc_to_ycc_tiles_lapped(const uint8_t* __restrict__ src, float* __restrict__ ycc, int64_t H, int64_t W,
-                                            int64_t th, int64_t tw, int64_t sh, int64_t sw, int64_t ny, int64_t nx,
-                                            int64_t first, int64_t n) {
-    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (x >= tw) return;
-    const int64_t y = blockIdx.y, j = blockIdx.z;
-    // block-uniform: 32-bit (the launcher bounds B * ny * nx)
-    const uint32_t t = (uint32_t)(first + j), per = (uint32_t)(ny * nx), b32 = t / per, r = t - b32 * per;
-    const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
-    const int64_t b = b32, gy = y + (int64_t)ty * sh, gx = x + (int64_t)tx * sw;
-    const int64_t sy = gy < H ? gy : H - 1, sx = gx < W ? gx : W - 1;
-    const uint8_t* s = src + ((b * H + sy) * W + sx) * 3;
-    const float rr = (float)s[0] / 255.0f, g = (float)s[1] / 255.0f, bl = (float)s[2] / 255.0f;
-    const float yy = KR * rr + KG * g + KB * bl;
-    const float cb = 0.5f * (bl - yy) / (1.f - KB) + 0.5f;
-    const float cr = 0.5f * (rr - yy) / (1.f - KR) + 0.5f;
-    const int64_t hw = th * tw, p = y * tw + x;
-    ycc[(0 * n + j) * hw + p] = yy - 0.5f;
-    ycc[(1 * n + j) * hw + p] = cb;
-    ycc[(2 * n + j) * hw + p] = cr;
 }
 
 // The tiles of one axis that cover the global position g (n tiles of t at the stride s = t - ov, the grid covering g): the
@@ -1367,7 +1344,7 @@ extern "C" int lldwt_u8hwc_to_ycc_tiles(const uint8_t* src, float* ycc, int64_t 
                   "u8hwc_to_ycc_tiles: grid too large");
     const bool grid = ny * nx > 1;
     hipLaunchKernelGGL(grid ? k_u8hwc_to_ycc_tiles<true> : k_u8hwc_to_ycc_tiles<false>, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
-                       (hipStream_t)stream, src, ycc, H, W, th, tw, ny, nx, first, n);
+                       (hipStream_t)stream, src, ycc, H, W, th, tw, th, tw, ny, nx, first, n);
     return check_launch("u8hwc_to_ycc_tiles");
 }
 // the checks and the launch of both tile output entry points (who: the name their messages carry)
@@ -1437,7 +1414,7 @@ extern "C" int lldwt_u8hwc_to_ycc_tiles_lapped(const uint8_t* src, float* ycc, i
     LLDWT_REQUIRE(B * ny * nx < (1ll << 31) && n <= 65535, "u8hwc_to_ycc_tiles_lapped: grid too large");
     LLDWT_REQUIRE(first >= 0 && n > 0 && first + n <= B * ny * nx, "u8hwc_to_ycc_tiles_lapped: tile range [%lld, %lld) "
                   "outside the %lld tiles", (long long)first, (long long)(first + n), (long long)(B * ny * nx));
-    hipLaunchKernelGGL(k_u8hwc_to_ycc_tiles_lapped, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
+    hipLaunchKernelGGL(k_u8hwc_to_ycc_tiles<true>, dim3((unsigned)cdiv(tw, 256), (unsigned)th, (unsigned)n), dim3(256), 0,
                        (hipStream_t)stream, src, ycc, H, W, th, tw, th - ov, tw - ov, ny, nx, first, n);
     return check_launch("u8hwc_to_ycc_tiles_lapped");
 }

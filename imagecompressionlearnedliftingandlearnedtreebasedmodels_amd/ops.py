@@ -98,12 +98,17 @@ def rgb_to_ycc(x):
     return y
 
 
-def u8hwc_to_f32chw(src):
-    """(B,H,W,3) uint8 device tensor -> (B,3,H,W) fp32 in [0,1] (ToTensor semantics, dataloaders/image_dl.py:81)."""
+def _u8hwc(src, who):
+    """The input check of the uint8 image kernels -> (B, H, W)."""
     if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
             and src.dim() == 4 and src.shape[3] == 3):
-        raise _lib.LLDWTError("u8hwc_to_f32chw: expected a contiguous (B,H,W,3) uint8 device tensor")
-    B, H, W, _ = src.shape
+        raise _lib.LLDWTError("%s: expected a contiguous (B,H,W,3) uint8 device tensor" % who)
+    return tuple(src.shape[:3])
+
+
+def u8hwc_to_f32chw(src):
+    """(B,H,W,3) uint8 device tensor -> (B,3,H,W) fp32 in [0,1] (ToTensor semantics, dataloaders/image_dl.py:81)."""
+    B, H, W = _u8hwc(src, "u8hwc_to_f32chw")
     dst = torch.empty(B, 3, H, W, device=src.device, dtype=torch.float32)
     check(_lib.load().lldwt_u8hwc_to_f32chw(C.c_void_p(src.data_ptr()), _chk(dst), B, H, W, _stream()), "u8hwc_to_f32chw")
     return dst
@@ -121,10 +126,7 @@ def ycc_to_rgb(y, clamp=False):
 def u8hwc_to_ycc_pad(src, Hp, Wp):
     """(B,H,W,3) uint8 RGB device tensor -> plane-major (3,B,1,Hp,Wp) YCbCr with Y-0.5, replicate-edge padded
     (lldwt_u8hwc_to_ycc_pad; inside the image bitwise equal to rgb_to_ycc(u8hwc_to_f32chw(src)))."""
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
-            and src.dim() == 4 and src.shape[3] == 3):
-        raise _lib.LLDWTError("u8hwc_to_ycc_pad: expected a contiguous (B,H,W,3) uint8 device tensor")
-    B, H, W, _ = src.shape
+    B, H, W = _u8hwc(src, "u8hwc_to_ycc_pad")
     y = torch.empty(3, B, 1, Hp, Wp, device=src.device, dtype=torch.float32)
     check(_lib.load().lldwt_u8hwc_to_ycc_pad(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, Hp, Wp, _stream()),
           "u8hwc_to_ycc_pad")
@@ -135,14 +137,41 @@ def u8hwc_to_ycc_tiles(src, th, tw, ny, nx, first, n):
     """(B,H,W,3) uint8 RGB device tensor -> plane-major (3,n,1,th,tw) YCbCr with Y-0.5 of the tiles first .. first+n-1 of a
     ny x nx grid of th x tw tiles per image (index (b * ny + ty) * nx + tx), replicate-edge padded past the image
     (lldwt_u8hwc_to_ycc_tiles; bitwise u8hwc_to_ycc_pad of the cropped tile)."""
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
-            and src.dim() == 4 and src.shape[3] == 3):
-        raise _lib.LLDWTError("u8hwc_to_ycc_tiles: expected a contiguous (B,H,W,3) uint8 device tensor")
-    B, H, W, _ = src.shape
+    B, H, W = _u8hwc(src, "u8hwc_to_ycc_tiles")
     y = torch.empty(3, n, 1, th, tw, device=src.device, dtype=torch.float32)
     check(_lib.load().lldwt_u8hwc_to_ycc_tiles(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, th, tw, ny, nx, first, n,
                                                _stream()), "u8hwc_to_ycc_tiles")
     return y
+
+
+def _tiles_to_u8hwc(who, y, grid, region, affine, tiles, first, B, out):
+    """The body of ycc_tiles_to_u8hwc (affine = None) and ll_tiles_to_u8hwc (affine = (inv_a, b)); who: the name in messages."""
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    _, n, _, yh, yw = y.shape
+    if (yh, yw) != (th, tw):
+        raise _lib.LLDWTError("%s: tiles are %d x %d, the grid says %d x %d" % (who, yh, yw, th, tw))
+    if affine is not None and (len(affine[0]) != 3 or len(affine[1]) != 3):
+        raise _lib.LLDWTError("%s: inv_a and b need 3 values each" % who)
+    tptr = C.c_void_p(0)
+    if tiles is not None:
+        if len(tiles) != n or any(t < 0 or t >= B * ny * nx for t in tiles):
+            raise _lib.LLDWTError("%s: need %d tile indexes in [0, %d)" % (who, n, B * ny * nx))
+        tiles = torch.tensor(list(tiles), dtype=torch.int32).to(y.device)
+        tptr = C.c_void_p(tiles.data_ptr())
+    if out is None:
+        out = torch.empty(B, h, w, 3, device=y.device, dtype=torch.uint8)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)):
+        raise _lib.LLDWTError("%s: out must be a contiguous (%d,%d,%d,3) uint8 device tensor" % (who, B, h, w))
+    args = (_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w)
+    if affine is None:
+        check(_lib.load().lldwt_ycc_tiles_to_u8hwc(*args, C.c_void_p(out.data_ptr()), _stream()), who)
+    else:
+        ia = (C.c_float * 3)(*[float(v) for v in affine[0]])
+        bb = (C.c_float * 3)(*[float(v) for v in affine[1]])
+        check(_lib.load().lldwt_ll_tiles_to_u8hwc(*args, C.cast(ia, C.c_void_p), C.cast(bb, C.c_void_p),
+                                                  C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
 
 
 def ycc_tiles_to_u8hwc(y, grid, region, tiles=None, first=0, B=1, out=None):
@@ -150,62 +179,20 @@ def ycc_tiles_to_u8hwc(y, grid, region, tiles=None, first=0, B=1, out=None):
     written into out (B,h,w,3) (allocated when None; pixels no tile covers are left as they are) and returned.
     grid = (H, W, th, tw, ny, nx); region = (y0, x0, h, w) inside the image; tiles: the n tile indexes (list), or None for
     first .. first+n-1 (lldwt_ycc_tiles_to_u8hwc: bytes as ycc_to_u8hwc_crop)."""
-    H, W, th, tw, ny, nx = grid
-    y0, x0, h, w = region
-    _, n, _, yh, yw = y.shape
-    if (yh, yw) != (th, tw):
-        raise _lib.LLDWTError("ycc_tiles_to_u8hwc: tiles are %d x %d, the grid says %d x %d" % (yh, yw, th, tw))
-    tptr = C.c_void_p(0)
-    if tiles is not None:
-        if len(tiles) != n or any(t < 0 or t >= B * ny * nx for t in tiles):
-            raise _lib.LLDWTError("ycc_tiles_to_u8hwc: need %d tile indexes in [0, %d)" % (n, B * ny * nx))
-        tiles = torch.tensor(list(tiles), dtype=torch.int32).to(y.device)
-        tptr = C.c_void_p(tiles.data_ptr())
-    if out is None:
-        out = torch.empty(B, h, w, 3, device=y.device, dtype=torch.uint8)
-    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)):
-        raise _lib.LLDWTError("ycc_tiles_to_u8hwc: out must be a contiguous (%d,%d,%d,3) uint8 device tensor" % (B, h, w))
-    check(_lib.load().lldwt_ycc_tiles_to_u8hwc(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w,
-                                               C.c_void_p(out.data_ptr()), _stream()), "ycc_tiles_to_u8hwc")
-    return out
+    return _tiles_to_u8hwc("ycc_tiles_to_u8hwc", y, grid, region, None, tiles, first, B, out)
 
 
 def ll_tiles_to_u8hwc(y, grid, region, inv_a, b, tiles=None, first=0, B=1, out=None):
     """ycc_tiles_to_u8hwc for a reduced-resolution decode: y (3,n,1,th,tw) holds each tile's decoded LL band at level k, grid
     and region are in reduced coordinates, and plane p's samples become (s - b[p]) * inv_a[p] before the colour and u8 rule
     (lldwt_ll_tiles_to_u8hwc; inv_a, b: 3 floats each, lifting_dwt_nets.ll_affine).  The untiled decode is the 1 x 1 grid."""
-    H, W, th, tw, ny, nx = grid
-    y0, x0, h, w = region
-    _, n, _, yh, yw = y.shape
-    if (yh, yw) != (th, tw):
-        raise _lib.LLDWTError("ll_tiles_to_u8hwc: tiles are %d x %d, the grid says %d x %d" % (yh, yw, th, tw))
-    if len(inv_a) != 3 or len(b) != 3:
-        raise _lib.LLDWTError("ll_tiles_to_u8hwc: inv_a and b need 3 values each")
-    tptr = C.c_void_p(0)
-    if tiles is not None:
-        if len(tiles) != n or any(t < 0 or t >= B * ny * nx for t in tiles):
-            raise _lib.LLDWTError("ll_tiles_to_u8hwc: need %d tile indexes in [0, %d)" % (n, B * ny * nx))
-        tiles = torch.tensor(list(tiles), dtype=torch.int32).to(y.device)
-        tptr = C.c_void_p(tiles.data_ptr())
-    if out is None:
-        out = torch.empty(B, h, w, 3, device=y.device, dtype=torch.uint8)
-    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)):
-        raise _lib.LLDWTError("ll_tiles_to_u8hwc: out must be a contiguous (%d,%d,%d,3) uint8 device tensor" % (B, h, w))
-    ia = (C.c_float * 3)(*[float(v) for v in inv_a])
-    bb = (C.c_float * 3)(*[float(v) for v in b])
-    check(_lib.load().lldwt_ll_tiles_to_u8hwc(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w,
-                                              C.cast(ia, C.c_void_p), C.cast(bb, C.c_void_p), C.c_void_p(out.data_ptr()),
-                                              _stream()), "ll_tiles_to_u8hwc")
-    return out
+    return _tiles_to_u8hwc("ll_tiles_to_u8hwc", y, grid, region, (inv_a, b), tiles, first, B, out)
 
 
 def u8hwc_to_ycc_tiles_lapped(src, th, tw, ov, ny, nx, first, n):
     """u8hwc_to_ycc_tiles on a lapped grid: tile (ty, tx) starts at (ty * (th - ov), tx * (tw - ov)), so neighbours share ov
     pixels (lldwt_u8hwc_to_ycc_tiles_lapped; bitwise u8hwc_to_ycc_pad of the replicate-padded crop)."""
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
-            and src.dim() == 4 and src.shape[3] == 3):
-        raise _lib.LLDWTError("u8hwc_to_ycc_tiles_lapped: expected a contiguous (B,H,W,3) uint8 device tensor")
-    B, H, W, _ = src.shape
+    B, H, W = _u8hwc(src, "u8hwc_to_ycc_tiles_lapped")
     if n < 1 or th < 1 or tw < 1:
         raise _lib.LLDWTError("u8hwc_to_ycc_tiles_lapped: n, th, tw must be positive")
     y = torch.empty(3, n, 1, th, tw, device=src.device, dtype=torch.float32)

@@ -52,10 +52,10 @@ def _tiles(hdr, seed=0):
 
 
 def _raw(hdr, tile_streams, count=None, magic=b"LLDT", version=1):
-    """An LLDT container packed WITHOUT pack_tiled's checks (to build inconsistent ones)."""
-    head = codec._TFIXED.pack(magic, version, codec.LAYER_CODES[hdr["layer"]], codec.NETTYPE_CODES[hdr["netType"]],
-                              hdr["dwtlevels"], hdr["H"], hdr["W"], hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"],
-                              hdr["numerics"])
+    """An LLDT container packed WITHOUT pack_tiled's checks (to build inconsistent ones), from the format's description."""
+    head = struct.pack("<4sBBBBIIIIHHH", magic, version, codec.LAYER_CODES[hdr["layer"]],
+                       codec.NETTYPE_CODES[hdr["netType"]], hdr["dwtlevels"], hdr["H"], hdr["W"], hdr["th"], hdr["tw"],
+                       hdr["ny"], hdr["nx"], hdr["numerics"])
     count = 3 * (hdr["dwtlevels"] + 1) if count is None else count
     body = head + codec._pack_identity(hdr) + bytes([count]) + codec._pack_streams([s for t in tile_streams for s in t])
     return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)

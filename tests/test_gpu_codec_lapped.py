@@ -309,9 +309,9 @@ def test_region_decode_equals_the_crop_and_touches_only_its_tiles(monkeypatch):
     seen = []
     real = codec._decode_tiles
 
-    def counting(nets, s_xe, s_xo, th_, tw_, n):
+    def counting(nets, s_xe, s_xo, th_, tw_, n, **kw):
         seen.append(n)
-        return real(nets, s_xe, s_xo, th_, tw_, n)
+        return real(nets, s_xe, s_xo, th_, tw_, n, **kw)
     monkeypatch.setattr(codec, "_decode_tiles", counting)
     cases = [((10, 20, 30, 20), 1), ((10, 20, 30, 29), 2), ((46, 46, 2, 2), 1), ((47, 47, 2, 2), 4), ((48, 48, 8, 8), 4),
              ((55, 0, 1, 150), 6), ((56, 56, 44, 40), 1), ((99, 149, 1, 1), 1), ((0, 0, 100, 150), 6)]

@@ -242,9 +242,9 @@ def test_lossless_tiled(layer, monkeypatch):
     seen = []
     real = codec._decode_tiles
 
-    def counting(nets, s_xe, s_xo, th_, tw_, n):
+    def counting(nets, s_xe, s_xo, th_, tw_, n, **kw):
         seen.append(n)
-        return real(nets, s_xe, s_xo, th_, tw_, n)
+        return real(nets, s_xe, s_xo, th_, tw_, n, **kw)
     monkeypatch.setattr(codec, "_decode_tiles", counting)
     for region, touched in [((50, 40, 20, 30), 4), ((60, 60, 30, 40), 1), ((99, 149, 1, 1), 1), ((55, 0, 2, 150), 6)]:
         y0, x0, h, w = region

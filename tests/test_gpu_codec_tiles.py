@@ -165,9 +165,9 @@ def test_region_decode_touches_only_its_tiles(monkeypatch):
     seen = []
     real = codec._decode_tiles
 
-    def counting(nets, s_xe, s_xo, th_, tw_, n):
+    def counting(nets, s_xe, s_xo, th_, tw_, n, **kw):
         seen.append(n)
-        return real(nets, s_xe, s_xo, th_, tw_, n)
+        return real(nets, s_xe, s_xo, th_, tw_, n, **kw)
     monkeypatch.setattr(codec, "_decode_tiles", counting)
     for region in [(10, 20, 60, 70), (0, 0, 150, 200), (149, 199, 1, 1), (th - 1, tw - 1, 2, 2), (30, 0, 5, 200)]:
         y0, x0, h, w = region
