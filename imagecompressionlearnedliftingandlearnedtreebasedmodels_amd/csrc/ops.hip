@@ -1208,17 +1208,20 @@ __global__ __launch_bounds__(256) void k_factorized_rate_bwd(const float* __rest
         else { is_m = i < 57; is_f = false; }
         if (is_m) { f = 1.f / (1.f + expf(-v)); v = softplusf(v); }
         else if (is_f) { v = tanhf(v); f = 1.f - v * v; }
-        if (i == 58) f = 0.f;      // the median does not enter the training-mode forward
+        if (i == 58) f = 0.f;      // the median does not enter the training-mode forward and is detached in the eval one
         e[i] = v;
         dfac[i] = f;
     }
     __syncthreads();
     const int64_t base = (z * C + c) * hw;
+    const float med = e[58];
     float ge[LLDWT_EB_FLOATS];
 #pragma unroll
     for (int i = 0; i < LLDWT_EB_FLOATS; ++i) ge[i] = 0.f;
     for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < hw; p += (int64_t)gridDim.x * blockDim.x) {
-        const float v = x[base + p] + (noise ? noise[base + p] : 0.f);
+        // eval: the parameters' gradients are taken where the eval forward evaluates, at round(x - median) + median (the
+        // median is detached there, as in EntropyBottleneck.forward; k_gauss_rate_bwd rounds in the same way)
+        const float v = noise ? x[base + p] + noise[base + p] : rintf(x[base + p] - med) + med;
         EbTrace tl, tu;
         const float lower = eb_logits_trace(e, v - 0.5f, tl);
         const float upper = eb_logits_trace(e, v + 0.5f, tu);

@@ -718,7 +718,8 @@ int lldwt_factorized_rate_tab(const float* x, const float* eb, const float* tabl
                               int64_t planes, int64_t batch, int C, int64_t hw, void* stream);
 
 /* Backward of lldwt_factorized_rate (training, v = x + noise): dx (Z,C,hw) and deb (planes,C,59) += gradient wrt the RAW
- * packed parameters (softplus' / tanh' applied; median slot stays 0).  deb is accumulated with atomics: zero it first. */
+ * packed parameters (softplus' / tanh' applied; median slot stays 0).  deb is accumulated with atomics: zero it first.
+ * noise == NULL (eval): the parameters' gradients at v = round(x - median) + median, where the eval forward evaluates; dx = 0. */
 int lldwt_factorized_rate_bwd(const float* x, const float* eb, const float* noise, const float* gbits, float* dx,
                               float* deb, int64_t planes, int64_t batch, int C, int64_t hw, void* stream);
 
