@@ -286,8 +286,9 @@ def _lift_stacks(sds, nblocks, gu):
 @pytest.mark.parametrize("K,different,linear,scale,geom", [
     (5, False, False, False, (2, 2, 16, 32)), (3, True, False, False, (2, 2, 16, 32)), (3, False, True, False, (2, 2, 16, 32)),
     (5, False, False, True, (2, 2, 16, 32)), (3, False, True, True, (2, 2, 16, 32)),
-    # sizes where the 16x32 lifting tiles have INTERIOR tiles and a persistent workgroup walks several
-    # tiles (level-0 half arrays 128x96 / 64x96 ..., level 1 64x48): the fast paths the training leg of bench.py runs
+    # sizes where the 16x32 lifting tiles have INTERIOR tiles (level-0 half arrays 64x192 / 64x96, level 1
+    # 32x96 / 32x48): the fast paths the training leg of bench.py runs.  At most 4 x 6 tiles per launch, fewer than CUs: every run
+    # of the fused kernel is one tile, no hand-down between tiles (tests/test_gpu_lift_domain.py covers runs of 2 and 3)
     (5, False, False, False, (1, 1, 128, 192)), (3, True, False, True, (1, 2, 96, 160))])
 def test_lifting_forward_backward(K, different, linear, scale, geom):
     """LiftingFn / LiftingInvFn gradients (input, skip-filter taps, every P/U-block parameter, and with config.scale == 1 the

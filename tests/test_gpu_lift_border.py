@@ -8,8 +8,10 @@ Shapes are per plane, one lifting level, P = 3 planes, B = 2 (tiles are 16 x 32;
 column pass on H/2 x W/2):
   32 x 64    one tile row in the row pass: every tile is top and bottom edge at once
   64 x 96    every tile is a border tile, corners and edges distinct
-  96 x 160   exactly one run of the row pass holds interior tiles
+  96 x 160   exactly one tile row of the row pass holds interior tiles
   80 x 144   neither dimension is a multiple of the tile
+At every one of these shapes Z * tiles stays below the CU count, so the launch takes runs of ONE tile: nothing here exercises the
+hand-down of T1 / T2 rows between the tiles of a run (tests/test_gpu_lift_domain.py does).
 
 Tolerances: a single step against the oracle step uses the 2e-5 of test_gpu_lifting.test_lift_step_vs_oracle; a whole level
 (four chained steps per pass, paired column launches) uses that file's TOL = 1e-4 for subband coefficients."""

@@ -25,7 +25,8 @@ def test_lift_step_vs_oracle(K, vertical, sign, hw):
     sds = [filled(weights.autoencoder_template(cfg), "m%d." % p) for p in range(2)]
     g = torch.Generator().manual_seed(5)
     # 19x45: every 16x32 tile touches the border, ragged; 70x150: interior tiles (the kernels' fast path), border tiles
-    # and a ragged last row / column of tiles, several tiles per persistent workgroup
+    # and a ragged last row / column of tiles.  5 x 5 tiles on 4 images stay below the CU count, so every run of the fused
+    # kernel is one tile (no hand-down of T1 / T2 rows here: tests/test_gpu_lift_domain.py forces runs of 2 and 3)
     P, B, (h, w) = 2, 2, hw
     src = torch.rand(P, B, 1, h, w, generator=g) - 0.5
     dst = torch.rand(P, B, 1, h, w, generator=g) - 0.5
@@ -143,7 +144,9 @@ def test_composed_path_with_strip_correction_equals_sequential(hw, vertical):
     subtract the conv4 taps that fall outside the image (t3v on the <= 2-pixel frame).  Debug flag 16 (ops.set_diagnostics)
     runs the sequential evaluation (t3 on the halo region, then conv4) for every tile instead, flag 32 the composed path
     without the vertical hand-down of T1 / T2 rows between the tiles of a column: all three must agree to fp32 rounding on
-    single-tile images (all four edges in one tile), ragged multi-tile images, and images smaller than a tile."""
+    single-tile images (all four edges in one tile), ragged multi-tile images, and images smaller than a tile.  Only 100 x 200
+    (7 x 7 tiles on 6 images, more than 256 CUs hold) is launched with runs of two tiles; at the other shapes every run is one tile,
+    flags 0 and 32 are the same computation, and nothing is handed down."""
     ops, gu = _ops()
     cfg = dict(model.DEFAULT_CFG, filtersize=5, dwtlevels=1)
     sds = [filled(weights.autoencoder_template(cfg), "m%d." % p) for p in range(2)]
@@ -171,8 +174,9 @@ def test_composed_path_with_strip_correction_equals_sequential(hw, vertical):
 
 def test_composed_path_equals_sequential_on_random_shapes():
     """The same comparison on 24 seeded random image sizes (2 .. 130 rows, 2 .. 210 columns, both pass directions): every
-    combination of missing / partial edge strips, tiles overhanging the image, images narrower than the conv reach -- and
-    runs of up to 9 vertically consecutive tiles that hand their last T1 / T2 rows down."""
+    combination of missing / partial edge strips, tiles overhanging the image, images narrower than the conv reach.  At most
+    9 x 7 tiles on 3 images: below the CU count, so the launch takes runs of ONE tile at all 24 shapes and no T1 / T2 rows are handed
+    down (the hand-down is held against float64 in tests/test_gpu_lift_domain.py)."""
     import random
     ops, gu = _ops()
     cfg = dict(model.DEFAULT_CFG, filtersize=5, dwtlevels=1)
