@@ -43,7 +43,7 @@ EB_FLOATS = 59
 
 _p, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
-# name -> (restype, argtypes); every symbol declared in include/lldwt.h
+# name -> (restype, argtypes); every symbol declared in include/lldwt.h (tests/test_host_cpu.py holds the two to each other)
 SIGNATURES = {
     "lldwt_last_error": (C.c_char_p, []),
     "lldwt_version": (_i, []),
@@ -88,13 +88,9 @@ SIGNATURES = {
                                    _p, _p, _p, _i64, _p]),
     "lldwt_lifting_program": (_i, [C.POINTER(LiftOp), _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
     "lldwt_lifting_forward_train": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _f,
-                                         _i, _p, _i64, _p, _p]),
+                                         _i, _p, _p, _p, _i64, _p, _p]),
     "lldwt_lifting_inverse_train": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _f, _i,
-                                         _p, _i64, _p, _p]),
-    "lldwt_lifting_forward_train_ex": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _f,
-                                            _i, _p, _p, _p, _i64, _p, _p]),
-    "lldwt_lifting_inverse_train_ex": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _f, _i,
-                                            _p, _p, _p, _i64, _p, _p]),
+                                         _p, _p, _p, _i64, _p, _p]),
     "lldwt_lift_bwd_pre": (_i, [View, View, _p, _i64, _i64, _i64, _p]),
     "lldwt_lift_bwd_fin": (_i, [_p, _p, _p, View, _i64, _i64, _i64, _i64, _p, _p, _i, _f, _f, _p]),
     "lldwt_lift_step_bwd_ws_bytes": (_i64, [_i64, _i64, _i64, _i]),
@@ -110,18 +106,15 @@ SIGNATURES = {
     "lldwt_subband_mlp_bwd": (_i, [_p] * 9 + [_i64, _i64, _i, _i64, _i] + [_p] * 7 + [_p]),
     "lldwt_subband_mlp": (_i, [_p, _p, _i64, _i64, _i, _i64, _i] + [_p] * 8 + [_i, _p]),
     "lldwt_conv_packed_floats": (_i64, [C.POINTER(ConvDesc)]),
-    "lldwt_conv_pack": (_i, [_p, _p, C.POINTER(ConvDesc), _i64, _p]),
-    "lldwt_conv_pack_ex": (_i, [_p, _p, C.POINTER(ConvDesc), _i64, _i, _p]),
+    "lldwt_conv_pack": (_i, [_p, _p, C.POINTER(ConvDesc), _i64, _i, _p]),
     "lldwt_conv2d": (_i, [_p, _p, _p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
     "lldwt_conv_stack_pair": (_i, [_p, _p, _p, _p, C.POINTER(_p), C.POINTER(_p), C.POINTER(ConvDesc), _i, _i, _p, _p, _i64, _i64, _i64,
                                    _i64, _i64, _i64, _p]),
     "lldwt_conv2d_absmax": (_i, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
     "lldwt_conv2d_f16out": (_i, [_p, _p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
     "lldwt_conv3x3_f16in": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _i64, _i64, _i64, _p]),
-    "lldwt_conv2d_wgrad": (_i, [_p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _p]),
-    "lldwt_conv2d_wgrad_ex": (_i, [_p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _f, _i, _p]),
-    "lldwt_conv3x3_wgrad_f16x3": (_i, [_p, _p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _i64, _f, _p]),
-    "lldwt_conv3x3_wgrad_f16x3_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _i64, _f, _p]),
+    "lldwt_conv2d_wgrad": (_i, [_p, _p, _p, _p, C.POINTER(ConvDesc), _i64, _i64, _i64, _i64, _f, _i, _p]),
+    "lldwt_conv3x3_wgrad_f16x3": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _i64, _f, _p]),
     "lldwt_conv_f16x3_packed_bytes": (_i64, [_i, _i]),
     "lldwt_plc_shape16": (_i, []),
     "lldwt_plc_winograd": (_i, []),
@@ -188,10 +181,8 @@ SIGNATURES = {
     "lldwt_sum": (_i, [_p, _i64, _p, _p]),
     "lldwt_tail_legacy": (_i, []),
     "lldwt_cdf97_ws_bytes": (_i64, [_i64, _i64, _i64]),
-    "lldwt_cdf97_forward": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i, _p, _i64, _p]),
-    "lldwt_cdf97_inverse": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i, _p, _i64, _p]),
-    "lldwt_cdf97_forward_ex": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i, _i, _p, _i64, _p]),
-    "lldwt_cdf97_inverse_ex": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i, _i, _p, _i64, _p]),
+    "lldwt_cdf97_forward": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i, _i, _p, _i64, _p]),
+    "lldwt_cdf97_inverse": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i, _i, _p, _i64, _p]),
     "lldwt_msssim_ws_floats": (_i64, [_i64, _i64, _i64, _i]),
     "lldwt_msssim_forward": (_i, [_p, _p, _f, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p]),
     "lldwt_msssim_backward": (_i, [_p, _p, _f, _i64, _i64, _i64, _i, _p, _p, _p, C.c_double, _p, _p, _p]),

@@ -232,7 +232,7 @@ class FactorizedRateFn(torch.autograd.Function):
 
 
 class Cdf97Fn(torch.autograd.Function):
-    """Fixed CDF 9/7 analysis; backward = its adjoint (lldwt_cdf97_inverse_ex adj=1; bior4.4 is not orthogonal)."""
+    """Fixed CDF 9/7 analysis; backward = its adjoint (lldwt_cdf97_inverse adj=1; bior4.4 is not orthogonal)."""
 
     @staticmethod
     def forward(ctx, x, levels):
@@ -562,7 +562,7 @@ def _grad_buffers(P, B, H, W, levels, dev):
 class LiftingFn(torch.autograd.Function):
     """x (P,B,1,H,W) -> (ll, yh_0..yh_{L-1}); parameters: taps (4,P,3), the effective gains nh, nl (P,) of
     config.scale == 1 (None otherwise) and the 8 stacked P/U-block tensors (nblocks,2,P,...).
-    Forward = lldwt_lifting_forward_train_ex; backward = reversed step program."""
+    Forward = lldwt_lifting_forward_train; backward = reversed step program."""
 
     @staticmethod
     def forward(ctx, x, taps, meta, nh, nl, *Wt):

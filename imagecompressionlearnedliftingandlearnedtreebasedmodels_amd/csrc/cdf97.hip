@@ -560,12 +560,7 @@ static int cdf_args(const char* who, int64_t Z, int64_t H, int64_t W, int levels
 }
 
 extern "C" int lldwt_cdf97_forward(const float* x, float* ll, float* const* yh, int64_t Z, int64_t H, int64_t W,
-                                   int levels, void* ws, int64_t ws_bytes, void* stream) {
-    return lldwt_cdf97_forward_ex(x, ll, yh, Z, H, W, levels, 0, ws, ws_bytes, stream);
-}
-
-extern "C" int lldwt_cdf97_forward_ex(const float* x, float* ll, float* const* yh, int64_t Z, int64_t H, int64_t W,
-                                      int levels, int adj, void* ws, int64_t ws_bytes, void* stream) {
+                                   int levels, int adj, void* ws, int64_t ws_bytes, void* stream) {
     int r = cdf_args("cdf97_forward", Z, H, W, levels, ws, ws_bytes);
     if (r) return r;
     LLDWT_REQUIRE(x && ll && yh, "cdf97_forward: null pointer");
@@ -612,12 +607,7 @@ extern "C" int lldwt_cdf97_forward_ex(const float* x, float* ll, float* const* y
 }
 
 extern "C" int lldwt_cdf97_inverse(const float* ll, const float* const* yh, float* x, int64_t Z, int64_t H, int64_t W,
-                                   int levels, void* ws, int64_t ws_bytes, void* stream) {
-    return lldwt_cdf97_inverse_ex(ll, yh, x, Z, H, W, levels, 0, ws, ws_bytes, stream);
-}
-
-extern "C" int lldwt_cdf97_inverse_ex(const float* ll, const float* const* yh, float* x, int64_t Z, int64_t H, int64_t W,
-                                      int levels, int adj, void* ws, int64_t ws_bytes, void* stream) {
+                                   int levels, int adj, void* ws, int64_t ws_bytes, void* stream) {
     int r = cdf_args("cdf97_inverse", Z, H, W, levels, ws, ws_bytes);
     if (r) return r;
     LLDWT_REQUIRE(x && ll && yh, "cdf97_inverse: null pointer");

@@ -818,11 +818,6 @@ static inline unsigned ew_grid2(int64_t n) {
 }  // namespace lldwt
 using namespace lldwt;
 
-extern "C" int lldwt_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const lldwt_conv_desc* d,
-                                  int64_t planes, int64_t batch, int64_t h, int64_t w_, void* stream) {
-    return lldwt_conv2d_wgrad_ex(x, dy, dw, dbias, d, planes, batch, h, w_, 1.0f, 0, stream);
-}
-
 // LLDWT_W1_TALL=0 keeps the 96 x 192 tile for the 162 x 94 weight gradient
 static const int g_w1_tall = [] { const char* e = getenv("LLDWT_W1_TALL"); return e ? atoi(e) : 1; }();
 
@@ -908,9 +903,9 @@ int wgrad_thin_pair(const float* t3, const float* g, float* dw4, float* db4, con
 }
 }  // namespace lldwt
 
-extern "C" int lldwt_conv2d_wgrad_ex(const float* x, const float* dy, float* dw, float* dbias, const lldwt_conv_desc* d,
-                                     int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha, int swap_hw,
-                                     void* stream) {
+extern "C" int lldwt_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const lldwt_conv_desc* d,
+                                  int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha, int swap_hw,
+                                  void* stream) {
     LLDWT_REQUIRE(x && dy && dw && d, "conv2d_wgrad: null pointer");
     LLDWT_REQUIRE(d->K == 1 || d->K == 3 || d->K == 5, "conv2d_wgrad: K=%d unsupported", d->K);
     LLDWT_REQUIRE(d->groups > 0 && d->cin % d->groups == 0 && d->cout % d->groups == 0, "conv2d_wgrad: bad groups");

@@ -438,12 +438,8 @@ extern "C" int64_t lldwt_conv_packed_floats(const lldwt_conv_desc* d) {
     return make_plan(*d).plane_floats;
 }
 
-extern "C" int lldwt_conv_pack(const float* w, float* packed, const lldwt_conv_desc* d, int64_t planes, void* stream) {
-    return lldwt_conv_pack_ex(w, packed, d, planes, 0, stream);
-}
-
-extern "C" int lldwt_conv_pack_ex(const float* w, float* packed, const lldwt_conv_desc* d, int64_t planes, int swap_hw,
-                                  void* stream) {
+extern "C" int lldwt_conv_pack(const float* w, float* packed, const lldwt_conv_desc* d, int64_t planes, int swap_hw,
+                               void* stream) {
     int r = conv_desc_ok("conv_pack", d, planes, 1, 2, 2);
     if (r) return r;
     LLDWT_REQUIRE(w && packed, "conv_pack: null pointer");

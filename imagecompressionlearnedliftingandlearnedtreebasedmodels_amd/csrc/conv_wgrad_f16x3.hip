@@ -1040,21 +1040,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 using namespace lldwt;
 
 extern "C" int lldwt_absmax_slots(const float* x, int64_t planes, int64_t n_per_plane, float* slots, void* stream);
-extern "C" int lldwt_conv3x3_wgrad_f16x3_ex(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws,
-                                            const float* x_slots, const float* dy_slots, int cin, int cout, int64_t planes,
-                                            int64_t batch, int64_t h, int64_t w_, float alpha, void* stream);
 
-extern "C" int lldwt_conv3x3_wgrad_f16x3(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws, int cin,
-                                         int cout, int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha,
-                                         void* stream) {
-    return lldwt_conv3x3_wgrad_f16x3_ex(x, dy, dw, dbias, slots_ws, nullptr, nullptr, cin, cout, planes, batch, h, w_, alpha, stream);
-}
-
-// + the per-plane |max| slots of x and / or dy when the caller holds them already (planes x 64 floats each, as lldwt_absmax_slots or
-// lldwt_conv2d_absmax leave them): the pass over that tensor is skipped.  slots_ws may be null when both are given.
-extern "C" int lldwt_conv3x3_wgrad_f16x3_ex(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws,
-                                            const float* x_slots, const float* dy_slots, int cin, int cout, int64_t planes,
-                                            int64_t batch, int64_t h, int64_t w_, float alpha, void* stream) {
+// x_slots / dy_slots: the per-plane |max| slots of x and / or dy when the caller holds them already (planes x 64 floats each, as
+// lldwt_absmax_slots or lldwt_conv2d_absmax leave them): the pass over that tensor is skipped.  slots_ws may be null when both are given.
+extern "C" int lldwt_conv3x3_wgrad_f16x3(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws,
+                                         const float* x_slots, const float* dy_slots, int cin, int cout, int64_t planes,
+                                         int64_t batch, int64_t h, int64_t w_, float alpha, void* stream) {
     LLDWT_REQUIRE(x && dy && dw && (slots_ws || (x_slots && dy_slots)), "conv3x3_wgrad_f16x3: null pointer");
     LLDWT_REQUIRE(cin > 0 && cout > 0 && planes > 0 && planes <= 65535 && batch > 0 && h > 0 && w_ >= 4, "conv3x3_wgrad_f16x3: bad dims");
     LLDWT_REQUIRE(w_ % 4 == 0, "conv3x3_wgrad_f16x3: the row length must be a multiple of 4 (16-byte row segments)");

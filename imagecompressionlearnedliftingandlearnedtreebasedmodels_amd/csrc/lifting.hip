@@ -15,29 +15,7 @@ namespace lldwt {
 
 static int g_lift_mode = 1;      // 1: fused split-fp16 step kernel where it applies (eval, C=16, K=5, tanh); 0: fp32 MFMA kernels
 
-static inline __host__ __device__ int pad16(int n) { return (n + 15) & ~15; }
-
-struct PackOff {
-    int w1, b1, w2, b2, w3, b3, w4, b4, orient, f16, total;   // f16: start of the split-fp16 section (lifting_f16.h)
-};
-static inline __host__ __device__ PackOff pack_off(int C, int K) {
-    PackOff o;
-    int KK = K * K;
-    o.w1 = 0;
-    o.b1 = o.w1 + pad16(KK * C);
-    o.w2 = o.b1 + pad16(C);
-    o.b2 = o.w2 + pad16(C * KK * C);
-    o.w3 = o.b2 + pad16(C);
-    o.b3 = o.w3 + pad16(C * KK * C);
-    o.w4 = o.b3 + pad16(C);
-    o.b4 = o.w4 + pad16(C * KK);
-    o.orient = o.b4 + 16;
-    o.f16 = 2 * o.orient;
-    o.total = o.f16 + lift_f16_floats(C, K);
-    return o;
-}
-
-// packed layouts (per orientation): W1[tap][oc], W2/W3[ic][tap][oc], W4[ic][tap]; tap = dy*K+dx in the EFFECTIVE
+// packed layouts (pack_off in lifting_f16.h; per orientation): W1[tap][oc], W2/W3[ic][tap][oc], W4[ic][tap]; tap = dy*K+dx in the EFFECTIVE
 // orientation: vertical uses w[..][dy][dx], horizontal uses w[..][dx][dy].
 __global__ void k_pack_pblock(const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
                               const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3,
@@ -1201,22 +1179,21 @@ static int launch_step(lldwt_view src, lldwt_view dst_in, lldwt_view dst_out, in
                        int64_t w, const float* taps, const float* packed, int64_t pstride, int vertical, float sign,
                        float rw, int linear, const StepBufs& b, hipStream_t st) {
     if constexpr (C == LF_C && K == LF_K) {
-        // eval path (no intermediates to save), tanh P-block: ONE fused launch on the fp16 matrix cores (lifting_f16.hip)
-        if (g_lift_mode == 1 && !linear && b.t1 == nullptr) {
-            LiftF16Views v{src.p, src.sz, src.sy, src.sx, dst_in.p, dst_in.sz, dst_in.sy, dst_in.sx,
+        LiftF16Call c{};
+        c.v = LiftF16Views{src.p, src.sz, src.sy, src.sx, dst_in.p, dst_in.sz, dst_in.sy, dst_in.sx,
                            dst_out.p, dst_out.sz, dst_out.sy, dst_out.sx};
-            const PackOff o = pack_off(C, K);
-            return lift_f16_step(v, Z, batch, h, w, taps, packed, pstride, o.orient, o.f16, vertical, sign, rw, st);
-        }
+        c.Z = Z; c.batch = batch; c.h = h; c.w = w;
+        c.taps = taps; c.packed = packed; c.pstride = pstride;
+        c.vertical = vertical; c.sign = sign; c.rw = rw; c.st = st;
+        // eval path (no intermediates to save), tanh P-block: ONE fused launch on the fp16 matrix cores (lifting_f16.hip)
+        if (g_lift_mode == 1 && !linear && b.t1 == nullptr) return lift_f16_launch(c);
         // training forward (intermediates saved), tanh P-block: the same fused kernel on its sequential path, which forms t3
         // explicitly, + stores of (src, skip, t1, t2, t3) -- the fp16 matrix cores instead of three fp32-MFMA launches.  The packed
         // buffer must carry the split-fp16 section (lldwt_pack_pblock, not _train); LLDWT_TRAIN_LIFT=f32 keeps the fp32 launches
         if (g_lift_mode == 1 && g_train_lift_f16 && !linear && b.t1 != nullptr && b.srcv != nullptr) {
-            LiftF16Views v{src.p, src.sz, src.sy, src.sx, dst_in.p, dst_in.sz, dst_in.sy, dst_in.sx,
-                           dst_out.p, dst_out.sz, dst_out.sy, dst_out.sx};
             const LiftF16Saved sv{b.srcv, b.skip, b.t1, b.t2, b.t3};
-            const PackOff o = pack_off(C, K);
-            return lift_f16_step_train(v, sv, Z, batch, h, w, taps, packed, pstride, o.orient, o.f16, vertical, sign, rw, st);
+            c.saved = &sv;
+            return lift_f16_launch(c);
         }
     }
     dim3 grid((unsigned)cdiv(w, TW), (unsigned)cdiv(h, TH), (unsigned)Z), block(NT);
@@ -1456,7 +1433,6 @@ static int run_program(const lldwt_lift_op* ops, int n, float* const* bases, con
         if (fused_eval && o.kind == 0 && column_pass_pair(ops, n, i)) {
             // step k of the L pass and step k of the H pass in one launch (twice the tiles: the deep levels' launches are
             // too small to fill the chip on their own)
-            const PackOff po = pack_off(c.C, c.K);
             for (int k = 0; k < 4; ++k) {
                 const lldwt_lift_op &a = ops[i + k], &b = ops[i + 4 + k];
                 auto views = [&](const lldwt_lift_op& q) {
@@ -1466,9 +1442,13 @@ static int run_program(const lldwt_lift_op* ops, int n, float* const* bases, con
                     return LiftF16Views{s_.p, s_.sz, s_.sy, s_.sx, d_.p, d_.sz, d_.sy, d_.sx, o_.p, o_.sz, o_.sy, o_.sx};
                 };
                 const float* pk = c.packed + ((int64_t)a.block * 2 + a.is_u) * c.total;
-                const LiftF16Views va = views(a), vb = views(b);
-                int r = lift_f16_step2(va, &vb, c.Z, c.batch, a.h, a.w, c.taps + (int64_t)a.tap * c.planes * 3, pk, c.pstride,
-                                       po.orient, po.f16, a.vertical, a.sign, c.rw, c.st);
+                const LiftF16Views vb = views(b);
+                LiftF16Call fc{};
+                fc.v = views(a); fc.v2 = &vb;
+                fc.Z = c.Z; fc.batch = c.batch; fc.h = a.h; fc.w = a.w;
+                fc.taps = c.taps + (int64_t)a.tap * c.planes * 3; fc.packed = pk; fc.pstride = c.pstride;
+                fc.vertical = a.vertical; fc.sign = a.sign; fc.rw = c.rw; fc.st = c.st;
+                int r = lift_f16_launch(fc);
                 if (r) return r;
             }
             i += 7;
@@ -1564,7 +1544,7 @@ static int pack_pblock_impl(const float* w1, const float* b1, const float* w2, c
     hipLaunchKernelGGL(k_pack_pblock, grid, dim3(256), 0, (hipStream_t)stream, w1, b1, w2, b2, w3, b3, w4, b4, packed, C,
                        K);
     if (with_f16 && lift_f16_floats(C, K) > 0) {
-        int r = lift_f16_pack(w1, w2, w3, w4, b1, b3, b4, packed, o.total, o.f16, planes, compose ? 1 : 0, (hipStream_t)stream);
+        int r = lift_f16_pack(w1, w2, w3, w4, b1, b3, b4, packed, o.total, planes, compose ? 1 : 0, (hipStream_t)stream);
         if (r) return r;
     }
     return check_launch("pack_pblock");
@@ -1681,7 +1661,7 @@ extern "C" int lldwt_pack_pblock_bwd(const float* w1, const float* w2, const flo
         set_error("pack_pblock_bwd: memset failed");
         return LLDWT_EHIP;
     }
-    return lift_f16_pack_bwd(w1, w2, w3, w4, (float*)ws, packed, o.total, o.f16, planes, (hipStream_t)stream);
+    return lift_f16_pack_bwd(w1, w2, w3, w4, (float*)ws, packed, o.total, planes, (hipStream_t)stream);
 }
 
 static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_view g_src, const float* saved_step,
@@ -1759,8 +1739,12 @@ static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_v
         }
         slots_ready = wg16;             // the fused launch leaves both maxima in the slots: no pass over dt3 / dpre2 for them
         const LiftF16Bwd bw{g, t1, t2, dt3, dpre2, dr, dsk, slots_ready ? slots : nullptr};
-        const PackOff o = pack_off(C, K);
-        r = lift_f16_step_bwd(bw, Z, batch, h, w, taps_id, packed_bwd, packed_plane_stride, o.orient, o.f16, vertical, st);
+        LiftF16Call c{};
+        c.bwd = &bw;
+        c.Z = Z; c.batch = batch; c.h = h; c.w = w;
+        c.taps = taps_id; c.packed = packed_bwd; c.pstride = packed_plane_stride;
+        c.vertical = vertical; c.st = st;
+        r = lift_f16_launch(c);
     } else
     r = K == 5 ? launch_step_bwd<5>(g_dst_out, g_dst_in, g, dsk, dt3, dpre2, dr, t1, t2, Z, batch, h, w, packed,
                                         packed_plane_stride, vertical, linear, st)
@@ -1780,7 +1764,7 @@ static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_v
         if ((r = wgrad_thin_pair(t3, g, dw4, db4, skip, dr, dw1, db1, planes, batch, h, w, alpha, swap, K, st))) return r;
     } else {
         desc(C, 1);
-        if ((r = lldwt_conv2d_wgrad_ex(t3, g, dw4, db4, &d, planes, batch, h, w, alpha, swap, stream))) return r;
+        if ((r = lldwt_conv2d_wgrad(t3, g, dw4, db4, &d, planes, batch, h, w, alpha, swap, stream))) return r;
     }
     desc(C, C);
     if (wg16) {
@@ -1797,12 +1781,12 @@ static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_v
     } else if (g_w16_pair) {
         if ((r = wgrad16_pair(t2, dt3, dw3, db3, t1, dpre2, dw2, db2, planes, batch, h, w, alpha, swap, K, st))) return r;
     } else {
-        if ((r = lldwt_conv2d_wgrad_ex(t2, dt3, dw3, db3, &d, planes, batch, h, w, alpha, swap, stream))) return r;
-        if ((r = lldwt_conv2d_wgrad_ex(t1, dpre2, dw2, db2, &d, planes, batch, h, w, alpha, swap, stream))) return r;
+        if ((r = lldwt_conv2d_wgrad(t2, dt3, dw3, db3, &d, planes, batch, h, w, alpha, swap, stream))) return r;
+        if ((r = lldwt_conv2d_wgrad(t1, dpre2, dw2, db2, &d, planes, batch, h, w, alpha, swap, stream))) return r;
     }
     if (!g_thin_pair) {
         desc(1, C);
-        if ((r = lldwt_conv2d_wgrad_ex(skip, dr, dw1, db1, &d, planes, batch, h, w, alpha, swap, stream))) return r;
+        if ((r = lldwt_conv2d_wgrad(skip, dr, dw1, db1, &d, planes, batch, h, w, alpha, swap, stream))) return r;
     }
     return lldwt_lift_bwd_fin(g, dsk, srcv, g_src, Z, batch, h, w, taps, dtaps, vertical, sign, res_weight, stream);
 }
@@ -1883,23 +1867,14 @@ extern "C" int lldwt_lifting_inverse(const float* ll, const float* const* yh, fl
                        ws_bytes, nullptr, stream);
 }
 
-// training variants: identical arithmetic, every step keeps (src, skip, t1, t2, t3) in `saved`
-// (lldwt_lifting_program reports the size and the per-step offsets)
+// training variants: identical arithmetic, every step keeps (src, skip, t1, t2, t3) in `saved` (lldwt_lifting_program reports the
+// size and the per-step offsets); with the gains of config.scale == 1 (per plane; both null = no scaling) the scale ops keep their
+// inputs in `saved` too (lldwt_lifting_program with scale = 1 gives the offsets)
 extern "C" int lldwt_lifting_forward_train(const float* x, float* ll, float* const* yh, int64_t planes, int64_t batch,
                                            int64_t H, int64_t W, int levels, const float* taps, const float* packed,
                                            int nblocks, int block_offset, int different, int C, int K, float res_weight,
-                                           int linear, void* ws, int64_t ws_bytes, float* saved, void* stream) {
-    return lldwt_lifting_forward_train_ex(x, ll, yh, planes, batch, H, W, levels, taps, packed, nblocks, block_offset, different,
-                                          C, K, res_weight, linear, nullptr, nullptr, ws, ws_bytes, saved, stream);
-}
-
-// + the gains of config.scale == 1 (per plane; both null = no scaling): the scale ops keep their inputs in `saved` too
-// (lldwt_lifting_program with scale = 1 gives the offsets)
-extern "C" int lldwt_lifting_forward_train_ex(const float* x, float* ll, float* const* yh, int64_t planes, int64_t batch,
-                                              int64_t H, int64_t W, int levels, const float* taps, const float* packed,
-                                              int nblocks, int block_offset, int different, int C, int K, float res_weight,
-                                              int linear, const float* scale_nh, const float* scale_nl, void* ws,
-                                              int64_t ws_bytes, float* saved, void* stream) {
+                                           int linear, const float* scale_nh, const float* scale_nl, void* ws,
+                                           int64_t ws_bytes, float* saved, void* stream) {
     LLDWT_REQUIRE(saved, "lifting_forward_train: null saved buffer");
     return lifting_run("lifting_forward_train", 0, const_cast<float*>(x), ll, yh, planes, batch, H, W, levels, taps, packed,
                        nblocks, block_offset, different, C, K, res_weight, linear, scale_nh, scale_nl, ws, ws_bytes, saved,
@@ -1909,17 +1884,8 @@ extern "C" int lldwt_lifting_forward_train_ex(const float* x, float* ll, float* 
 extern "C" int lldwt_lifting_inverse_train(const float* ll, const float* const* yh, float* x, int64_t planes,
                                            int64_t batch, int64_t H, int64_t W, int levels, const float* taps,
                                            const float* packed, int nblocks, int block_offset, int C, int K,
-                                           float res_weight, int linear, void* ws, int64_t ws_bytes, float* saved,
-                                           void* stream) {
-    return lldwt_lifting_inverse_train_ex(ll, yh, x, planes, batch, H, W, levels, taps, packed, nblocks, block_offset, C, K,
-                                          res_weight, linear, nullptr, nullptr, ws, ws_bytes, saved, stream);
-}
-
-extern "C" int lldwt_lifting_inverse_train_ex(const float* ll, const float* const* yh, float* x, int64_t planes,
-                                              int64_t batch, int64_t H, int64_t W, int levels, const float* taps,
-                                              const float* packed, int nblocks, int block_offset, int C, int K,
-                                              float res_weight, int linear, const float* scale_nh, const float* scale_nl,
-                                              void* ws, int64_t ws_bytes, float* saved, void* stream) {
+                                           float res_weight, int linear, const float* scale_nh, const float* scale_nl,
+                                           void* ws, int64_t ws_bytes, float* saved, void* stream) {
     LLDWT_REQUIRE(saved, "lifting_inverse_train: null saved buffer");
     return lifting_run("lifting_inverse_train", 1, x, const_cast<float*>(ll), const_cast<float* const*>(yh), planes, batch,
                        H, W, levels, taps, packed, nblocks, block_offset, 0, C, K, res_weight, linear, scale_nh, scale_nl, ws,

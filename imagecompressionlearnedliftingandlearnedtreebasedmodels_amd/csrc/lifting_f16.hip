@@ -1607,7 +1607,7 @@ __global__ void k_lift_bwd_prep(const float* __restrict__ w1, const float* __res
 }
 
 int lift_f16_pack_bwd(const float* w1, const float* w2, const float* w3, const float* w4, float* scratch, float* packed,
-                      int64_t plane_stride, int f16_off, int planes, hipStream_t st) {
+                      int64_t plane_stride, int planes, hipStream_t st) {
     hipLaunchKernelGGL(k_lift_bwd_prep, dim3((unsigned)planes), dim3(256), 0, st, w1, w2, w3, w4, scratch);
     float* o1 = scratch;
     float* o2 = o1 + (int64_t)planes * LF_C * LF_KK;
@@ -1615,61 +1615,35 @@ int lift_f16_pack_bwd(const float* w1, const float* w2, const float* w3, const f
     float* o4 = o3 + (int64_t)planes * LF_C * LF_C * LF_KK;
     float* z = o4 + (int64_t)planes * LF_C * LF_KK;     // 64 zeros per plane: b1, b3 (16 per plane) and b4 (1 per plane) all read zeros
     hipLaunchKernelGGL(k_lift_f16_pack, dim3(2, (unsigned)planes), dim3(PACK_NT), 0, st, o1, o2, o3, o4, z, z, z, packed,
-                       plane_stride, f16_off, 0);          // the backward chain runs the sequential path: no composed kernels
+                       plane_stride, pack_off(LF_C, LF_K).f16, 0);          // the backward chain runs the sequential path: no composed kernels
     return check_launch("lift_f16_pack_bwd");
 }
 int64_t lift_f16_bwd_scratch_floats(int planes) { return (int64_t)planes * BWD_SCRATCH; }
 
 int lift_f16_pack(const float* w1, const float* w2, const float* w3, const float* w4, const float* b1, const float* b3,
-                  const float* b4, float* packed, int64_t plane_stride, int f16_off, int planes, int compose, hipStream_t st) {
-    hipLaunchKernelGGL(k_lift_f16_pack, dim3(2, (unsigned)planes), dim3(PACK_NT), 0, st, w1, w2, w3, w4, b1, b3, b4, packed, plane_stride, f16_off,
-                       compose);
+                  const float* b4, float* packed, int64_t plane_stride, int planes, int compose, hipStream_t st) {
+    hipLaunchKernelGGL(k_lift_f16_pack, dim3(2, (unsigned)planes), dim3(PACK_NT), 0, st, w1, w2, w3, w4, b1, b3, b4, packed, plane_stride,
+                       pack_off(LF_C, LF_K).f16, compose);
     return check_launch("lift_f16_pack");
 }
 
-int lift_f16_step(const LiftF16Views& v, int64_t Z, int64_t batch, int64_t h, int64_t w, const float* taps,
-                  const float* packed, int64_t pstride, int fp32_orient_floats, int f16_off, int vertical, float sign, float rw,
-                  hipStream_t st) {
-    return lift_f16_step2(v, nullptr, Z, batch, h, w, taps, packed, pstride, fp32_orient_floats, f16_off, vertical, sign, rw, st);
-}
-
-int lift_f16_step2(const LiftF16Views& v, const LiftF16Views* v2, int64_t Z, int64_t batch, int64_t h, int64_t w,
-                   const float* taps, const float* packed, int64_t pstride, int fp32_orient_floats, int f16_off, int vertical,
-                   float sign, float rw, hipStream_t st) {
-    return lift_f16_step_any(v, v2, nullptr, Z, batch, h, w, taps, packed, pstride, fp32_orient_floats, f16_off, vertical, sign, rw, st);
-}
-
-int lift_f16_step_train(const LiftF16Views& v, const LiftF16Saved& sv, int64_t Z, int64_t batch, int64_t h, int64_t w,
-                        const float* taps, const float* packed, int64_t pstride, int fp32_orient_floats, int f16_off,
-                        int vertical, float sign, float rw, hipStream_t st) {
-    if (!(sv.src && sv.skip && sv.t1 && sv.t2 && sv.t3)) {
-        set_error("lift_f16_step_train: null saved buffer");
+int lift_f16_launch(const LiftF16Call& c) {
+    const LiftF16Bwd* bw = c.bwd;
+    const LiftF16Saved* sv = bw ? nullptr : c.saved;
+    const LiftF16Views* v2 = bw ? nullptr : c.v2;
+    const int64_t Z = c.Z, batch = c.batch, h = c.h, w = c.w;
+    if (sv && !(sv->src && sv->skip && sv->t1 && sv->t2 && sv->t3)) {
+        set_error("lift_f16_launch: null saved buffer");
         return LLDWT_EINVAL;
     }
-    return lift_f16_step_any(v, nullptr, &sv, Z, batch, h, w, taps, packed, pstride, fp32_orient_floats, f16_off, vertical, sign, rw, st);
-}
-
-static const LiftF16Bwd* g_bwd_call = nullptr;      // set by lift_f16_step_bwd around its call of lift_f16_step_any (host, same thread)
-
-int lift_f16_step_bwd(const LiftF16Bwd& b, int64_t Z, int64_t batch, int64_t h, int64_t w, const float* taps_id,
-                      const float* packed_bwd, int64_t pstride, int fp32_orient_floats, int f16_off, int vertical, hipStream_t st) {
-    if (!(b.g && b.t1 && b.t2 && b.dt3 && b.dpre2 && b.dr && b.dsk && taps_id && packed_bwd)) {
-        set_error("lift_f16_step_bwd: null pointer");
+    if (bw && !(bw->g && bw->t1 && bw->t2 && bw->dt3 && bw->dpre2 && bw->dr && bw->dsk && c.taps && c.packed)) {
+        set_error("lift_f16_launch: null pointer in the backward call");
         return LLDWT_EINVAL;
     }
-    float* gm = const_cast<float*>(b.g);
-    const LiftF16Views v{b.g, h * w, w, 1, b.g, h * w, w, 1, gm, h * w, w, 1};       // din / dout are not used by the BWD mode
-    g_bwd_call = &b;
-    const int r = lift_f16_step_any(v, nullptr, nullptr, Z, batch, h, w, taps_id, packed_bwd, pstride, fp32_orient_floats, f16_off,
-                                    vertical, 1.f, 1.f, st);
-    g_bwd_call = nullptr;
-    return r;
-}
-
-int lift_f16_step_any(const LiftF16Views& v, const LiftF16Views* v2, const LiftF16Saved* sv, int64_t Z, int64_t batch, int64_t h,
-                      int64_t w, const float* taps, const float* packed, int64_t pstride, int fp32_orient_floats, int f16_off,
-                      int vertical, float sign, float rw, hipStream_t st) {
-    const LiftF16Bwd* bw = g_bwd_call;
+    // the BWD mode reads g as its source; din / dout are not used
+    const LiftF16Views v = bw ? LiftF16Views{bw->g, h * w, w, 1, bw->g, h * w, w, 1, const_cast<float*>(bw->g), h * w, w, 1} : c.v;
+    const float sign = bw ? 1.f : c.sign, rw = bw ? 1.f : c.rw;
+    hipStream_t st = c.st;
     static bool attr = false;
     if (!attr) {
         if (hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
@@ -1678,7 +1652,7 @@ int lift_f16_step_any(const LiftF16Views& v, const LiftF16Views* v2, const LiftF
             hipFuncSetAttribute((const void*)k_lift_fused_f16<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<true, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess) {
-            set_error("lift_f16_step: cannot reserve %d bytes of LDS", LDS_TOTAL2);
+            set_error("lift_f16_launch: cannot reserve %d bytes of LDS", LDS_TOTAL2);
             return LLDWT_EHIP;
         }
         attr = true;
@@ -1687,38 +1661,37 @@ int lift_f16_step_any(const LiftF16Views& v, const LiftF16Views* v2, const LiftF
     a.v = v;
     if (v2 && (v2->src_sy != v.src_sy || v2->src_sx != v.src_sx || v2->din_sy != v.din_sy || v2->din_sx != v.din_sx ||
                v2->dout_sy != v.dout_sy || v2->dout_sx != v.dout_sx)) {
-        set_error("lift_f16_step2: the two view sets must share their row / column strides");
+        set_error("lift_f16_launch: the two view sets must share their row / column strides");
         return LLDWT_EINVAL;
     }
     a.src2 = v2 ? v2->src : v.src; a.din2 = v2 ? v2->din : v.din; a.dout2 = v2 ? v2->dout : v.dout;
     a.src2_sz = v2 ? v2->src_sz : v.src_sz; a.din2_sz = v2 ? v2->din_sz : v.din_sz; a.dout2_sz = v2 ? v2->dout_sz : v.dout_sz;
     a.zsplit = Z;
     const int64_t Zl = v2 ? 2 * Z : Z;               // images of the launch
-    a.taps = taps;
-    a.packed = packed;
-    a.pstride = pstride;
-    const int orient = vertical ? 0 : 1;
-    a.orient_fp32 = orient * fp32_orient_floats;
-    // bias offsets inside an fp32 orientation section (mirror of pack_off in lifting.hip for C = 16, K = 5)
-    auto pad16 = [](int n) { return (n + 15) & ~15; };
-    const int w1o = 0, b1o = w1o + pad16(LF_KK * LF_C), w2o = b1o + pad16(LF_C), b2o = w2o + pad16(LF_C * LF_KK * LF_C);
-    const int w3o = b2o + pad16(LF_C), b3o = w3o + pad16(LF_C * LF_KK * LF_C), w4o = b3o + pad16(LF_C), b4o = w4o + pad16(LF_C * LF_KK);
-    a.b1 = b1o; a.b2 = b2o; a.b3 = b3o; a.b4 = b4o; a.w4 = w4o;
-    a.f16 = f16_off + orient * LF_ORIENT_FLOATS;
-    a.batch = (int)batch; a.h = (int)h; a.w = (int)w; a.vertical = vertical;
+    a.taps = c.taps;
+    a.packed = c.packed;
+    a.pstride = c.pstride;
+    const int orient = c.vertical ? 0 : 1;
+    constexpr PackOff po = pack_off(LF_C, LF_K);
+    static_assert(po.f16 == 2 * po.orient && po.total - po.f16 == LF_FLOATS,
+                  "a packed block is two fp32 orientation sections, then the split-fp16 section");
+    a.orient_fp32 = orient * po.orient;
+    a.b1 = po.b1; a.b2 = po.b2; a.b3 = po.b3; a.b4 = po.b4; a.w4 = po.w4;       // bias / w4 offsets inside an fp32 orientation section
+    a.f16 = po.f16 + orient * LF_ORIENT_FLOATS;
+    a.batch = (int)batch; a.h = (int)h; a.w = (int)w; a.vertical = c.vertical;
     a.sign = sign; a.rw = rw;
     a.dbg = g_lf_dbg;
     a.stamps = nullptr;
     auto fits = [&](int64_t sy, int64_t sx) { return llabs(sy) * h + llabs(sx) * w < (int64_t)1 << 31; };
     if (!fits(v.src_sy, v.src_sx) || !fits(v.din_sy, v.din_sx) || !fits(v.dout_sy, v.dout_sx) ||
         (v2 && (!fits(v2->src_sy, v2->src_sx) || !fits(v2->din_sy, v2->din_sx) || !fits(v2->dout_sy, v2->dout_sx)))) {
-        set_error("lift_f16_step: per-image strides beyond 32-bit offsets");
+        set_error("lift_f16_launch: per-image strides beyond 32-bit offsets");
         return LLDWT_EINVAL;
     }
     a.tiles_x = (int)cdiv(w, TW);
     a.tiles_y = (int)cdiv(h, TH);
     if ((int64_t)a.tiles_x * a.tiles_y * Zl >= (int64_t)1 << 30) {
-        set_error("lift_f16_step: more than 2^30 tiles in one launch");
+        set_error("lift_f16_launch: more than 2^30 tiles in one launch");
         return LLDWT_EINVAL;
     }
     if (g_lf_stamps) {              // diagnostics (tools/lift_stamps.py): only when the registered buffer holds every tile's stamps
@@ -1730,7 +1703,7 @@ int lift_f16_step_any(const LiftF16Views& v, const LiftF16Views* v2, const LiftF
         int dev = 0;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) {
-            set_error("lift_f16_step: cannot read the device's CU count");
+            set_error("lift_f16_launch: cannot read the device's CU count");
             return LLDWT_EHIP;
         }
         ncu = prop.multiProcessorCount;
@@ -1774,7 +1747,7 @@ int lift_f16_step_any(const LiftF16Views& v, const LiftF16Views* v2, const LiftF
     else if (prec == 1) hipLaunchKernelGGL((k_lift_fused_f16<false, 1>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
     else if (prec == 2) hipLaunchKernelGGL((k_lift_fused_f16<false, 2>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
     else hipLaunchKernelGGL((k_lift_fused_f16<false, 0>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
-    return check_launch("lift_f16_step");
+    return check_launch("lift_f16_launch");
 }
 
 }  // namespace lldwt

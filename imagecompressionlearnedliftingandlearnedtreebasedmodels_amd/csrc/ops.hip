@@ -1308,7 +1308,7 @@ static inline unsigned ew_grid(int64_t n) {
 using namespace lldwt;
 
 extern "C" const char* lldwt_last_error(void) { return g_err; }
-extern "C" int lldwt_version(void) { return 100; }
+extern "C" int lldwt_version(void) { return 101; }
 // LLDWT_TAIL=legacy (read when the library loads) keeps the earlier launches of the small end-of-step work for A/B timing and
 // the tests: the scalar k_sum and one launch per layer and per stack of the coarsest level's context stacks.
 static const int g_tail_legacy = [] { const char* e = getenv("LLDWT_TAIL"); return (e && !strcmp(e, "legacy")) ? 1 : 0; }();

@@ -4,6 +4,7 @@ Tensor convention: "plane-major" (P, B, C, h, w) fp32 contiguous CUDA(HIP) tenso
 (3 for clrch == 1), parameters stacked on a leading P axis.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -14,18 +15,22 @@ from ._lib import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EPI_LRELU_BWD, EPI_N
 _ws = {}
 
 
+def _env_choice(name, default, allowed):
+    """One of the `allowed` strings from the environment variable `name`; read on every call so tests can switch it."""
+    v = os.environ.get(name, default)
+    if v not in allowed:
+        names = " or ".join(a if a.isdigit() else repr(a) for a in allowed)      # 0 or 1; 'f32' or 'f16x3'
+        raise _lib.LLDWTError("%s must be %s (got %r)" % (name, names, v))
+    return v
+
+
 def plc_mode():
     """Arithmetic of the dense 243 -> 243 3x3 tree-context conv (LiftingBasedDWT_net.py:271-272): 'f32' = fp32 MFMA
     (reference arithmetic), 'f16x3' = split-fp16 (power-of-two scaled hi*hi + hi*lo + lo*hi on the fp16 matrix cores, fp32
     accumulate; ~2^-21 relative per product, csrc/conv_f16x3.hip).
     Default 'f16x3' (parity-gated by tests/test_gpu_fullsize_oracle.py at the same bars as 'f32'); the fp32 kernel
-    stays available as the exact-arithmetic fallback.  Environment variable LLDWT_PLC_MODE; read on every call so tests
-    can switch it."""
-    import os
-    m = os.environ.get("LLDWT_PLC_MODE", "f16x3")
-    if m not in ("f32", "f16x3"):
-        raise _lib.LLDWTError("LLDWT_PLC_MODE must be 'f32' or 'f16x3' (got %r)" % m)
-    return m
+    stays available as the exact-arithmetic fallback.  Environment variable LLDWT_PLC_MODE."""
+    return _env_choice("LLDWT_PLC_MODE", "f16x3", ("f32", "f16x3"))
 
 
 def train_lift_f16():
@@ -433,7 +438,7 @@ def cdf97_forward(x, levels, adj=False):
     yh = [torch.empty(P, B, Cc, 3, H >> (i + 1), W >> (i + 1), device=dev, dtype=torch.float32) for i in range(levels)]
     nb = lib.lldwt_cdf97_ws_bytes(Z, H, W)
     ws = workspace(nb, dev)
-    check(lib.lldwt_cdf97_forward_ex(_chk(x, "x"), _chk(ll), _ptr_array(yh), Z, H, W, levels, int(bool(adj)),
+    check(lib.lldwt_cdf97_forward(_chk(x, "x"), _chk(ll), _ptr_array(yh), Z, H, W, levels, int(bool(adj)),
                                      C.c_void_p(ws.data_ptr()), nb, _stream()), "cdf97_forward")
     return ll, yh
 
@@ -449,7 +454,7 @@ def cdf97_inverse(ll, yh, adj=False):
         _chk(t, "yh")
     nb = lib.lldwt_cdf97_ws_bytes(Z, H, W)
     ws = workspace(nb, ll.device)
-    check(lib.lldwt_cdf97_inverse_ex(_chk(ll, "ll"), _ptr_array(yh), _chk(x), Z, H, W, levels, int(bool(adj)),
+    check(lib.lldwt_cdf97_inverse(_chk(ll, "ll"), _ptr_array(yh), _chk(x), Z, H, W, levels, int(bool(adj)),
                                      C.c_void_p(ws.data_ptr()), nb, _stream()), "cdf97_inverse")
     return x
 
@@ -520,7 +525,7 @@ def conv_pack(w, K, groups=1, transposed=False, tap_mask=None, swap_hw=False):
     d = conv_desc(cin, cout, K, groups, transposed=transposed, tap_mask=tap_mask)
     n = lib.lldwt_conv_packed_floats(C.byref(d))
     packed = torch.empty(P, n, device=w.device, dtype=torch.float32)
-    check(lib.lldwt_conv_pack_ex(_chk(w, "w"), _chk(packed), C.byref(d), P, int(bool(swap_hw)), _stream()), "conv_pack")
+    check(lib.lldwt_conv_pack(_chk(w, "w"), _chk(packed), C.byref(d), P, int(bool(swap_hw)), _stream()), "conv_pack")
     return packed
 
 
@@ -598,11 +603,7 @@ def conv_stack_pair(xa, xb, layers, groups_a, groups_b):
 def storage_dtype():
     """Storage type of the tree-context tensor between the two tree convs: 'fp32' (default, the reference's) or 'fp16'
     (BASELINE configs[4]: half the bytes, two MFMA products instead of three, 1e-2 tolerance class).  LLDWT_STORAGE."""
-    import os
-    m = os.environ.get("LLDWT_STORAGE", "fp32")
-    if m not in ("fp32", "fp16"):
-        raise _lib.LLDWTError("LLDWT_STORAGE must be 'fp32' or 'fp16' (got %r)" % m)
-    return m
+    return _env_choice("LLDWT_STORAGE", "fp32", ("fp32", "fp16"))
 
 
 def conv2d_f16out(x, w, bias, K, oscale, act=ACT_NONE, upsample2=False, packed=None):
@@ -635,11 +636,7 @@ def plc_fuse():
     """Whether the eval path computes the tree-context PAIR in one launch (lldwt_plc_fused: the first conv on the fly
     inside the second's staging, no 243-channel tensor in HBM).  Only with plc_mode() == 'f16x3' and fp32 storage.
     Environment variable LLDWT_PLC_FUSE (default 1)."""
-    import os
-    v = os.environ.get("LLDWT_PLC_FUSE", "1")
-    if v not in ("0", "1"):
-        raise _lib.LLDWTError("LLDWT_PLC_FUSE must be 0 or 1 (got %r)" % v)
-    return v == "1"
+    return _env_choice("LLDWT_PLC_FUSE", "1", ("0", "1")) == "1"
 
 
 def plc_fused_pack1(w1, b1):
@@ -672,11 +669,7 @@ def plc_fused(parent, packed1, packed2, bias2, cmid, cout, act=ACT_NONE):
 def cgp_mode():
     """Arithmetic of the fused cgp stack on the eval path: 'f16x3' (default; split-fp16 register chain, csrc/cgp_f16x3.hip)
     or 'f32' (fp32 MFMA kernel k_cgp_rate).  Environment variable LLDWT_CGP_MODE."""
-    import os
-    m = os.environ.get("LLDWT_CGP_MODE", "f16x3")
-    if m not in ("f32", "f16x3"):
-        raise _lib.LLDWTError("LLDWT_CGP_MODE must be 'f32' or 'f16x3' (got %r)" % m)
-    return m
+    return _env_choice("LLDWT_CGP_MODE", "f16x3", ("f32", "f16x3"))
 
 
 def cgp16_supported(ws, groups):
@@ -802,7 +795,7 @@ def conv2d_wgrad(x, dy, wshape, K, groups=1, upsample2=False, tap_mask=None, wan
         db = torch.zeros(P, cout, device=x.device, dtype=torch.float32)
     d = conv_desc(cin, cout, K, groups, 0, upsample2, False, tap_mask, oc_block, oc_stride, oc_off, ytot, ic_block,
                   ic_stride, ic_off, x.shape[2] if ic_block else 0, 0)
-    check(lib.lldwt_conv2d_wgrad_ex(_chk(x, "x"), _chk(dy, "dy"), _chk(dw), _opt(db), C.byref(d), P, B, h, wd,
+    check(lib.lldwt_conv2d_wgrad(_chk(x, "x"), _chk(dy, "dy"), _chk(dw), _opt(db), C.byref(d), P, B, h, wd,
                                     float(alpha), int(bool(swap_hw)), _stream()), "conv2d_wgrad")
     return dw, db
 
@@ -824,7 +817,7 @@ def wgrad16_f16x3(x, dy, dw=None, db=None, alpha=1.0, swap_hw=False):
 
 
 def conv3x3_wgrad_f16x3(x, dy, wshape, want_bias=True, alpha=1.0, x_slots=None, dy_slots=None):
-    """Backward-weights of a dense 3x3 conv on the fp16 matrix cores, split-fp16 operands (lldwt_conv3x3_wgrad_f16x3_ex).
+    """Backward-weights of a dense 3x3 conv on the fp16 matrix cores, split-fp16 operands (lldwt_conv3x3_wgrad_f16x3).
     x (P,B,cin,h,w), dy (P,B,cout,h,w) -> (dw (P,cout,cin,3,3), dbias (P,cout) or None).  x_slots / dy_slots: the (P,64)
     |max| slots of x / dy (absmax_slots) if the caller has them already -- that pass is then skipped."""
     P, B, cin, h, wd = x.shape
@@ -837,7 +830,7 @@ def conv3x3_wgrad_f16x3(x, dy, wshape, want_bias=True, alpha=1.0, x_slots=None, 
     for nm, t in (("x_slots", x_slots), ("dy_slots", dy_slots)):
         if t is not None and (t.numel() != P * 64 or t.dtype != torch.float32):
             raise _lib.LLDWTError("conv3x3_wgrad_f16x3: %s must hold (P, 64) floats" % nm)
-    check(_lib.load().lldwt_conv3x3_wgrad_f16x3_ex(_chk(x, "x"), _chk(dy, "dy"), _chk(dw), _opt(db), _opt(slots), _opt(x_slots, "x_slots"),
+    check(_lib.load().lldwt_conv3x3_wgrad_f16x3(_chk(x, "x"), _chk(dy, "dy"), _chk(dw), _opt(db), _opt(slots), _opt(x_slots, "x_slots"),
                                                   _opt(dy_slots, "dy_slots"), cin, cout, P, B, h, wd, float(alpha), _stream()),
           "conv3x3_wgrad_f16x3")
     return dw, db
@@ -1316,7 +1309,7 @@ def lifting_forward_train(x, taps, packed, levels, Cc, K, res_weight, linear, di
     yh = [torch.empty(P, B, 3, H >> (i + 1), W >> (i + 1), device=dev, dtype=torch.float32) for i in range(levels)]
     nb = lib.lldwt_lifting_ws_bytes(P * B, H, W, Cc)
     ws = workspace(nb, dev)
-    check(lib.lldwt_lifting_forward_train_ex(_chk(x, "x"), _chk(ll), _ptr_array(yh), P, B, H, W, levels, _chk(taps),
+    check(lib.lldwt_lifting_forward_train(_chk(x, "x"), _chk(ll), _ptr_array(yh), P, B, H, W, levels, _chk(taps),
                                              _chk(packed), int(packed.shape[1]), int(block_offset), int(bool(different)), Cc, K,
                                              float(res_weight), int(bool(linear)), _opt(scale_nh), _opt(scale_nl),
                                              C.c_void_p(ws.data_ptr()), nb, _chk(saved), _stream()), "lifting_forward_train")
@@ -1333,7 +1326,7 @@ def lifting_inverse_train(ll, yh, taps, packed, Cc, K, res_weight, linear, block
         _chk(t, "yh")
     nb = lib.lldwt_lifting_ws_bytes(P * B, H, W, Cc)
     ws = workspace(nb, ll.device)
-    check(lib.lldwt_lifting_inverse_train_ex(_chk(ll), _ptr_array(yh), _chk(x), P, B, H, W, levels, _chk(taps), _chk(packed),
+    check(lib.lldwt_lifting_inverse_train(_chk(ll), _ptr_array(yh), _chk(x), P, B, H, W, levels, _chk(taps), _chk(packed),
                                              int(packed.shape[1]), int(block_offset), Cc, K, float(res_weight),
                                              int(bool(linear)), _opt(scale_nh), _opt(scale_nl), C.c_void_p(ws.data_ptr()), nb,
                                              _chk(saved), _stream()), "lifting_inverse_train")

@@ -39,6 +39,7 @@ extern "C" {
 #define LLDWT_ACT_RELU 3    /* ReLU (post-processing networks, post_processing_networks.py:45,60-70) */
 
 const char* lldwt_last_error(void);
+/* ABI version; raised whenever an entry point is removed, renamed or changes its arguments (101: one entry point per operation). */
 int lldwt_version(void);
 /* 1 if the calling process sees a gfx950 device, 0 otherwise (no compute is launched). */
 int lldwt_device_ok(void);
@@ -229,27 +230,20 @@ typedef struct lldwt_lift_op {
 } lldwt_lift_op;
 int lldwt_lifting_program(lldwt_lift_op* ops, int max_ops, int64_t Z, int64_t H, int64_t W, int levels, int different,
                           int block_offset, int inverse, int scale, int C, int64_t* saved_floats);
+/* The *_train variants: lldwt_lifting_forward / _inverse with every step's intermediates kept in `saved`.  scale_nh / scale_nl:
+ * the per-plane gains of config.scale == 1 (wavelet_forward_v2.py:76-80, wavelet_inverse_v2.py:70-74; both null = no scaling).
+ * Build the program with scale = 1 then: every scale op (kind 1..4) owns h*w*Z floats of `saved` at its saved_off and keeps
+ * its INPUT there (dense Z,h,w), which the host-side backward needs for d(gain). */
 int lldwt_lifting_forward_train(const float* x, float* ll, float* const* yh, int64_t planes, int64_t batch, int64_t H,
                                 int64_t W, int levels, const float* taps, const float* packed, int nblocks,
-                                int block_offset, int different, int C, int K, float res_weight, int linear, void* ws,
-                                int64_t ws_bytes, float* saved, void* stream);
+                                int block_offset, int different, int C, int K, float res_weight, int linear,
+                                const float* scale_nh, const float* scale_nl, void* ws, int64_t ws_bytes, float* saved,
+                                void* stream);
 int lldwt_lifting_inverse_train(const float* ll, const float* const* yh, float* x, int64_t planes, int64_t batch,
                                 int64_t H, int64_t W, int levels, const float* taps, const float* packed, int nblocks,
-                                int block_offset, int C, int K, float res_weight, int linear, void* ws, int64_t ws_bytes,
-                                float* saved, void* stream);
-/* the same with the per-plane gains of config.scale == 1 (wavelet_forward_v2.py:76-80, wavelet_inverse_v2.py:70-74; both
- * null = no scaling).  Build the program with scale = 1: every scale op (kind 1..4) then owns h*w*Z floats of `saved` at
- * its saved_off and keeps its INPUT there (dense Z,h,w), which the host-side backward needs for d(gain). */
-int lldwt_lifting_forward_train_ex(const float* x, float* ll, float* const* yh, int64_t planes, int64_t batch, int64_t H,
-                                   int64_t W, int levels, const float* taps, const float* packed, int nblocks,
-                                   int block_offset, int different, int C, int K, float res_weight, int linear,
-                                   const float* scale_nh, const float* scale_nl, void* ws, int64_t ws_bytes, float* saved,
-                                   void* stream);
-int lldwt_lifting_inverse_train_ex(const float* ll, const float* const* yh, float* x, int64_t planes, int64_t batch,
-                                   int64_t H, int64_t W, int levels, const float* taps, const float* packed, int nblocks,
-                                   int block_offset, int C, int K, float res_weight, int linear, const float* scale_nh,
-                                   const float* scale_nl, void* ws, int64_t ws_bytes, float* saved, void* stream);
-/* backward pieces of one step (chained by the host with lldwt_conv2d / lldwt_conv2d_wgrad_ex):
+                                int block_offset, int C, int K, float res_weight, int linear, const float* scale_nh,
+                                const float* scale_nl, void* ws, int64_t ws_bytes, float* saved, void* stream);
+/* backward pieces of one step (chained by the host with lldwt_conv2d / lldwt_conv2d_wgrad):
  *   pre: g (dense Z,h,w) = G[dst_out];  G[dst_in] = g
  *   fin: dskip = sign*(g + res_weight*dsk);  G[src] += taps^T (x) dskip;  dtaps (planes,3) += sum dskip * src shifted */
 int lldwt_lift_bwd_pre(lldwt_view g_dst_out, lldwt_view g_dst_in, float* g, int64_t Z, int64_t h, int64_t w, void* stream);
@@ -344,13 +338,11 @@ typedef struct lldwt_conv_desc {
 #define LLDWT_EPI_LRELU_BWD 2
 /* Weights are pre-packed once per update into the MFMA A-operand lane order (csrc/conv_mfma.hip):
  * packed holds lldwt_conv_packed_floats(d) floats PER PLANE.  residual (optional): tensor laid out like y, added before
- * the activation (P_block_v2.py:53 "tmp + out_res").                                                       */
+ * the activation (P_block_v2.py:53 "tmp + out_res").  swap_hw != 0 packs the (kh,kw)-transposed kernel W^T (the
+ * horizontal lifting pass: conv(x^T, W)^T == conv(x, W^T), replaces the torch.transpose calls of
+ * wavelet_forward_v2.py:32-51).                                                                             */
 int64_t lldwt_conv_packed_floats(const lldwt_conv_desc* d);
-int lldwt_conv_pack(const float* w, float* packed, const lldwt_conv_desc* d, int64_t planes, void* stream);
-/* As lldwt_conv_pack; swap_hw != 0 packs the (kh,kw)-transposed kernel W^T (the horizontal lifting pass:
- * conv(x^T, W)^T == conv(x, W^T), replaces the torch.transpose calls of wavelet_forward_v2.py:32-51).      */
-int lldwt_conv_pack_ex(const float* w, float* packed, const lldwt_conv_desc* d, int64_t planes, int swap_hw,
-                       void* stream);
+int lldwt_conv_pack(const float* w, float* packed, const lldwt_conv_desc* d, int64_t planes, int swap_hw, void* stream);
 /* y = act( (conv(x) + bias) * epi(aux) + residual ).  transposed != 0 builds the operator from a weight in
  * ConvTranspose2d layout (planes, cin, cout/groups, K, K) with the taps flipped: that is ConvTranspose2d (stride 1)
  * itself and, applied to a forward Conv2d weight with cin/cout swapped, the BACKWARD-DATA pass of that conv.      */
@@ -373,31 +365,26 @@ int lldwt_conv_stack_pair(const float* xa, const float* xb, float* ya, float* yb
 int lldwt_conv2d_absmax(const float* x, float* y, const float* packed, const float* bias, const float* residual,
                         const float* aux, float* absmax_slots, const lldwt_conv_desc* d, int64_t planes, int64_t batch,
                         int64_t h, int64_t w_, void* stream);
-/* Backward-weights: dw (planes,cout,cin/groups,K,K) += sum over batch and pixels of dy[.,oc,p] * x[.,ic,p+tap]
- * (dead taps of tap_mask are skipped), dbias (planes,cout) += sum dy (optional).  dy is read through the OUTPUT
- * placement (oc_*), x through upsample2 / the input placement.  Accumulates with float atomics: zero dw/dbias first. */
+/* Backward-weights: dw (planes,cout,cin/groups,K,K) += alpha * sum over batch and pixels of dy[.,oc,p] * x[.,ic,p+tap]
+ * (dead taps of tap_mask are skipped), dbias (planes,cout) += alpha * sum dy (optional).  dy is read through the OUTPUT
+ * placement (oc_*), x through upsample2 / the input placement.  Accumulates with float atomics: zero dw/dbias first.
+ * swap_hw != 0: the conv was applied with the (kh,kw)-transposed kernel, so tap (ky,kx) of the contraction is
+ * accumulated into dw[..][kx][ky].                                                                         */
 int lldwt_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const lldwt_conv_desc* d,
-                       int64_t planes, int64_t batch, int64_t h, int64_t w_, void* stream);
-/* As lldwt_conv2d_wgrad with dw += alpha * (...), dbias += alpha * (...); swap_hw != 0: the conv was applied with the
- * (kh,kw)-transposed kernel, so tap (ky,kx) of the contraction is accumulated into dw[..][kx][ky].        */
-int lldwt_conv2d_wgrad_ex(const float* x, const float* dy, float* dw, float* dbias, const lldwt_conv_desc* d,
-                          int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha, int swap_hw,
-                          void* stream);
+                       int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha, int swap_hw, void* stream);
 /* Backward-weights of a DENSE 3x3 conv (groups 1, no placement, no upsampling, no dead taps) on the fp16 matrix cores with
  * split-fp16 operands (fp32-level accuracy; csrc/conv_wgrad_f16x3.hip): dw (planes,cout,cin,3,3) += alpha * sum over batch
  * and pixels of dy[.,oc,p] * x[.,ic,p+tap], dbias (planes,cout) += alpha * sum dy (optional).  x (planes,batch,cin,h,w),
  * dy (planes,batch,cout,h,w), both 16-byte aligned, w % 4 == 0.  slots_ws: planes * 128 floats of scratch (the per-plane
  * max |x| and max |dy| the power-of-two operand scales come from).  Float atomics: zero dw / dbias first.  The training
- * path of the 243 -> 243 tree-context conv (LiftingBasedDWT_net.py:271-272); lldwt_conv2d_wgrad covers every other shape. */
-int lldwt_conv3x3_wgrad_f16x3(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws, int cin, int cout,
-                              int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha, void* stream);
-/* As lldwt_conv3x3_wgrad_f16x3; x_slots / dy_slots (planes,64), if not null, are the per-plane |max| slots of x / dy the caller
- * holds already (lldwt_absmax_slots, lldwt_conv2d_absmax): the pass over that tensor is skipped -- in a training step the forward
- * conv has measured x and the backward-data conv dy (autograd of LiftingBasedDWT_net.py:271-272).  slots_ws may be null when
- * both are given.                                                                                                           */
-int lldwt_conv3x3_wgrad_f16x3_ex(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws,
-                                 const float* x_slots, const float* dy_slots, int cin, int cout, int64_t planes, int64_t batch,
-                                 int64_t h, int64_t w_, float alpha, void* stream);
+ * path of the 243 -> 243 tree-context conv (LiftingBasedDWT_net.py:271-272); lldwt_conv2d_wgrad covers every other shape.
+ * x_slots / dy_slots (planes,64), if not null, are the per-plane |max| slots of x / dy the caller holds already
+ * (lldwt_absmax_slots, lldwt_conv2d_absmax): the pass over that tensor is skipped -- in a training step the forward conv has
+ * measured x and the backward-data conv dy (autograd of LiftingBasedDWT_net.py:271-272).  slots_ws may be null when both are
+ * given. */
+int lldwt_conv3x3_wgrad_f16x3(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws,
+                              const float* x_slots, const float* dy_slots, int cin, int cout, int64_t planes, int64_t batch,
+                              int64_t h, int64_t w_, float alpha, void* stream);
 /* Backward-weights of the 16 -> 16 5x5 convs of a P/U block (conv2 / conv3 of graphs/layers/P_block_v2.py:40-55; autograd of
  * agents/liftingDWT_agent.py:97) on the fp16 matrix cores, split-fp16 operands (fp32-level accuracy):
  *   dw[p][oc][ic][ty][tx] += alpha * sum_{b,y,x} dy[p][b][oc][y][x] * x[p][b][ic][y+ty-2][x+tx-2],  dbias += alpha * sum dy.
@@ -743,17 +730,14 @@ int lldwt_axpby(const float* a, const float* b, float* out, int64_t n, float alp
  * LLDWT_EINVAL for such a call instead of silently differing from the reference; 1: compute the periodic form.        */
 int lldwt_set_cdf97_short_levels(int periodic);
 int64_t lldwt_cdf97_ws_bytes(int64_t Z, int64_t H, int64_t W);
+/* adj = 0: the transform.  adj = 1: the adjoints for training (bior4.4 is not orthogonal, so the backward pass is NOT the
+ * other transform):
+ * lldwt_cdf97_inverse(adj=1) maps (g_ll, g_yh) -> g_x   = adjoint of lldwt_cdf97_forward (backward of the analysis);
+ * lldwt_cdf97_forward(adj=1) maps g_x -> (g_ll, g_yh)   = adjoint of lldwt_cdf97_inverse (backward of the synthesis). */
 int lldwt_cdf97_forward(const float* x, float* ll, float* const* yh, int64_t Z, int64_t H, int64_t W, int levels,
-                        void* ws, int64_t ws_bytes, void* stream);
+                        int adj, void* ws, int64_t ws_bytes, void* stream);
 int lldwt_cdf97_inverse(const float* ll, const float* const* yh, float* x, int64_t Z, int64_t H, int64_t W,
-                        int levels, void* ws, int64_t ws_bytes, void* stream);
-/* Adjoints for training (bior4.4 is not orthogonal, so the backward pass is NOT the other transform):
- * lldwt_cdf97_inverse_ex(adj=1) maps (g_ll, g_yh) -> g_x   = adjoint of lldwt_cdf97_forward (backward of the analysis);
- * lldwt_cdf97_forward_ex(adj=1) maps g_x -> (g_ll, g_yh)   = adjoint of lldwt_cdf97_inverse (backward of the synthesis). */
-int lldwt_cdf97_forward_ex(const float* x, float* ll, float* const* yh, int64_t Z, int64_t H, int64_t W, int levels,
-                           int adj, void* ws, int64_t ws_bytes, void* stream);
-int lldwt_cdf97_inverse_ex(const float* ll, const float* const* yh, float* x, int64_t Z, int64_t H, int64_t W,
-                           int levels, int adj, void* ws, int64_t ws_bytes, void* stream);
+                        int levels, int adj, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * MS-SSIM (pytorch-msssim 0.2.1: data_range 1, 11-tap Gaussian window sigma 1.5 applied "valid", K = (0.01, 0.03), weights

@@ -184,7 +184,7 @@ def test_wgrad_f16x3_vs_float64_and_fp32_kernel(shape):
     # accumulation semantics: alpha, and += into an existing buffer is the caller's (zeroed here)
     dw2, _ = ops.conv3x3_wgrad_f16x3(x.to(DEV), dy.to(DEV), (P, cout, cin, 3, 3), want_bias=False, alpha=-0.5)
     assert float((dw2 + 0.5 * dw).abs().max()) < 1e-5 * float(dw.abs().max())
-    # the |max| slots handed in by the caller (lldwt_conv3x3_wgrad_f16x3_ex): same scales, same arithmetic -- equal up to the order of
+    # the |max| slots handed in by the caller (lldwt_conv3x3_wgrad_f16x3's x_slots / dy_slots): same scales, same arithmetic -- equal up to the order of
     # the float atomics; either one alone, too
     xs, ds = ops.absmax_slots(x.to(DEV)), ops.absmax_slots(dy.to(DEV))
     for kw in (dict(x_slots=xs, dy_slots=ds), dict(x_slots=xs), dict(dy_slots=ds)):

@@ -9,7 +9,7 @@ per plane and per tensor, no element left out; the yardstick is the fp32 oracle'
 (the larger of torch.tanh and the kernels' declared tanh formula).  Every comparison prints its error, yardstick and bar
 (pytest -s).  P = 3 planes with distinct weights, B = 2; the fused paths need K = 5, C = 16.
 
-Run lengths.  The launch (lift_f16_step) takes a run length above 1 only when Z * tiles_x * tiles_y exceeds the CU count: of the
+Run lengths.  The launch (lift_f16_launch) takes a run length above 1 only when Z * tiles_x * tiles_y exceeds the CU count: of the
 shapes here 200 x 250 (eval) and the 140 x 300 level of the TRAIN forward / step backward do so on 256 CUs by the dispatch's own
 choice.  The run length is otherwise forced: LLDWT_LF_RL (and LLDWT_WGRAD16_MIN for the split-fp16 weight gradients) are read
 once per process, so test_forced_run_lengths starts one fresh child per setting, which runs the step, TRAIN-forward and
@@ -132,7 +132,7 @@ def test_eval_step_three_forms(hw, vertical, sign):
 @pytest.mark.skipif(CHILD, reason="the dispatch's own choice: not part of the forced runs")
 @pytest.mark.parametrize("vertical", [1, 0])
 def test_eval_step_runs_chosen_by_the_dispatch(vertical):
-    """200 x 250, Z = 6: 13 x 8 tiles per image, 624 in all -- on 256 CUs the cost rule of lift_f16_step takes runs of three with a
+    """200 x 250, Z = 6: 13 x 8 tiles per image, 624 in all -- on 256 CUs the cost rule of lift_f16_launch takes runs of three with a
     last run of one tile, so T1 / T2 rows are handed down twice per run without any diagnostics setting."""
     w = _weights()
     src, dst = _inputs((200, 250))

@@ -1,5 +1,5 @@
-"""CPU (no GPU): the C-ABI library loads and exports every symbol include/lldwt.h declares; the host-side mirror has the
-reference's module API and state_dict layout; the product path has no CPU fallback."""
+"""CPU (no GPU): the C-ABI library loads and its ctypes binding agrees with include/lldwt.h, prototype by prototype and struct by
+struct; the host-side mirror has the reference's module API and state_dict layout; the product path has no CPU fallback."""
 import ctypes
 import os
 import re
@@ -13,18 +13,102 @@ PKG = "imagecompressionlearnedliftingandlearnedtreebasedmodels_amd"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
+def _header_prototypes(text):
+    """{name: (return type, [parameter types])} of every lldwt_* prototype of the header, types as normalised strings
+    ("float*", "float*const*", "lldwt_view", ...).  Every statement of the header must be a prototype or a struct."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    text = text.replace('extern "C" {', " ")
+
+    def norm(t):
+        t = " ".join(w for w in re.sub(r"\s+", " ", t.replace("*", " * ")).split() if w != "const" or "*" in t)
+        return t.replace(" *", "*").replace("* ", "*")
+
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = stmt.strip().strip("}").strip()
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.+?)\b(lldwt_\w+)\s*\((.*)\)", stmt, flags=re.S)
+        assert m, "not a prototype: %r" % stmt
+        ret, name, params = m.groups()
+        args = []
+        if params.strip() != "void":
+            for prm in params.split(","):
+                pm = re.fullmatch(r"(.*[\s\*])(\w+)", prm.strip(), flags=re.S)
+                assert pm, "%s: unnamed parameter %r" % (name, prm)
+                args.append(norm(pm.group(1)))
+        assert name not in protos, name
+        protos[name] = (norm(ret), args)
+    return protos
+
+
+def _ctypes_classes(ctype, _lib, is_return=False):
+    """The ctypes classes that may stand for a header type (c_int is c_int32 and c_uint is c_uint32 on every ROCm host)."""
+    scalars = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+               "float": ctypes.c_float, "double": ctypes.c_double}
+    pointees = set(scalars) | {"void", "char", "uint8_t", "uint64_t"}
+    stars, base = ctype.count("*"), ctype.replace("*", "").replace("const", "").strip()
+    if stars == 0:
+        if is_return and base == "void":
+            return {None}
+        if base == "lldwt_view" and not is_return:
+            return {_lib.View}
+        return {scalars[base]}                                  # KeyError: a type this check does not know -- a failure
+    if ctype == "const lldwt_conv_desc*":
+        return {ctypes.POINTER(_lib.ConvDesc)}
+    if ctype == "lldwt_lift_op*":
+        return {ctypes.POINTER(_lib.LiftOp)}
+    assert base in pointees, ctype
+    if stars >= 2:
+        return {ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p}
+    if is_return and base == "char":
+        return {ctypes.c_char_p}
+    # a plain T* is an untyped address; int64_t* may also be bound as the typed pointer (lldwt_lifting_program's out-parameter)
+    return {ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)} if ctype == "int64_t*" else {ctypes.c_void_p}
+
+
+def test_ctypes_mirror_matches_the_header(tmp_path):
+    """_lib.SIGNATURES and the three ctypes structs against include/lldwt.h: the same set of names, per name the same return
+    class, argument count and class per argument, and per struct the size and every field's offset and size as the host C
+    compiler lays the header's struct out.  A dropped argument or an int bound where the header says int64_t fails here, on
+    the CPU, instead of handing a kernel a wild pointer."""
+    import shutil
+    import subprocess
     from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import _lib
+    protos = _header_prototypes(open(os.path.join(REPO, "include", "lldwt.h")).read())
+    assert len(protos) >= 25
+    assert sorted(protos) == sorted(_lib.SIGNATURES)
     lib = _lib.load()
-    hdr = open(os.path.join(REPO, "include", "lldwt.h")).read()
-    declared = set(re.findall(r"\b(lldwt_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {"lldwt_view", "lldwt_conv_desc"}
-    assert len(declared) >= 25
-    for name in sorted(declared):
+    for name, (ret, args) in sorted(protos.items()):
         assert hasattr(lib, name), name                      # exported by the .so
-        assert name in _lib.SIGNATURES, name                 # bound with a prototype
-    assert lib.lldwt_version() >= 100
+        res, argtypes = _lib.SIGNATURES[name]
+        assert res in _ctypes_classes(ret, _lib, is_return=True), (name, ret, res)
+        assert len(argtypes) == len(args), (name, len(args), len(argtypes))
+        for k, (a, t) in enumerate(zip(args, argtypes)):
+            assert t in _ctypes_classes(a, _lib), (name, k, a, t)
+    assert lib.lldwt_version() >= 101
     assert lib.lldwt_pblock_packed_floats(16, 5) > 2 * (16 * 16 * 25) * 2
+
+    structs = (("lldwt_view", _lib.View), ("lldwt_lift_op", _lib.LiftOp), ("lldwt_conv_desc", _lib.ConvDesc))
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "lldwt.h"', "int main(void) {"]
+    for cname, cls in structs:
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        for f, _ in cls._fields_:
+            lines.append('    printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (cname, f, cname, f, cname, f))
+    lines += ["    return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    cc = shutil.which("cc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang")
+    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), "-o", str(tmp_path / "layout"),
+                    str(tmp_path / "layout.c")], check=True)
+    got = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines()
+    want = []
+    for cname, cls in structs:
+        want.append("%s %d" % (cname, ctypes.sizeof(cls)))
+        want += ["%s.%s %d %d" % (cname, f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_]
+    assert got == want
 
 
 def test_no_gpu_calls_fail_loudly():
