@@ -581,12 +581,10 @@ extern "C" int lldwt_cdf97_forward(const float* x, float* ll, float* const* yh, 
             // Tile of a workgroup: 16 x 32 subband samples (8 x 32 for a level of under 200 tiles of 32 x 32), not 32 x 32: twice
             // (four times) the workgroups, each with half (a quarter of) the load -> LDS -> two passes -> store chain that a level's
             // duration consists of when its tiles are one resident round -- 25.7 -> 22.7 us for the four levels at the BASELINE batch,
-            // batch 96 unchanged within 1 % (LLDWT_CDF_TILE=32 / 1632 force the square / the 16 x 32 tile for an A/B; 16 x 16: no better than 32 x 32)
-            static const bool tile32 = getenv("LLDWT_CDF_TILE") && atoi(getenv("LLDWT_CDF_TILE")) == 32;
-            static const bool tile16 = getenv("LLDWT_CDF_TILE") && atoi(getenv("LLDWT_CDF_TILE")) == 1632;
+            // batch 96 unchanged within 1 % (16 x 16: no better than 32 x 32)
             // one conditional wrap per index is enough from 64 samples up (the 72-wide patch of the last tile ends below 2 h)
             if (h >= 2 * CT && w >= 2 * CT && w % 4 == 0 && in.sx == 1) {
-                if (tile32 || (!tile16 && (int64_t)grid.x >= 4096))      // many rounds of tiles: the square tile streams better
+                if ((int64_t)grid.x >= 4096)                                  // many rounds of tiles: the square tile streams better
                     hipLaunchKernelGGL((k_cdf97_fwd_level_v<CT, CT>), grid, dim3(256), 0, st, in, vLL, vLH, vHL, vHH, (int)h, (int)w);
                 else if ((int64_t)grid.x < 200)
                     hipLaunchKernelGGL((k_cdf97_fwd_level_v<8, 32>), dim3((unsigned)(cdiv(wh, 32) * cdiv(hh, 8) * Z)), dim3(256), 0, st,
@@ -629,11 +627,10 @@ extern "C" int lldwt_cdf97_inverse(const float* ll, const float* const* yh, floa
             // the same for the 36-wide subband patches from 32 samples up
             if (hh >= CT && wh >= CT && wh % 2 == 0)
             {
-                static const int inv_tile = getenv("LLDWT_CDF_TILE") ? atoi(getenv("LLDWT_CDF_TILE")) : 0;   // 32 | 1632 (A/B)
                 // as in the forward transform: the 16 x 32 tile while a level is a few resident rounds at most (28.7 -> 26.0 us for
                 // the four levels at the BASELINE batch); from 4 096 square tiles up the square tile streams better (192 vs 201 us
                 // at batch 96)
-                if (inv_tile == 32 || (inv_tile == 0 && (int64_t)grid.x >= 4096))
+                if ((int64_t)grid.x >= 4096)
                     hipLaunchKernelGGL((k_cdf97_inv_level_v<CT, CT>), grid, dim3(256), 0, st, vLL, vLH, vHL, vHH, vo, (int)h, (int)w);
                 else
                     hipLaunchKernelGGL((k_cdf97_inv_level_v<16, 32>), dim3((unsigned)(cdiv(w, 64) * cdiv(h, 32) * Z)), dim3(256), 0, st,

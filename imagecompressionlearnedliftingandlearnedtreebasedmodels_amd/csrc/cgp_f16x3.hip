@@ -30,9 +30,6 @@
 
 namespace lldwt {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 // the reference's dimensions (after the fold): 93 -> 162 -> 54 -> 18 -> 2
@@ -48,15 +45,6 @@ constexpr int GROUP_BYTES = BF_OFF + (NSTEP + 3) * (STEP_BYTES / 2);     // then
 constexpr int NB = 1;                  // pixel blocks of 32 per wave.  One block and two waves per SIMD (232 VGPRs): the other wave
                                        // computes while this one waits for its 48 input loads (two blocks in one wave at one wave
                                        // per SIMD share the weight stream, but nothing hides the input latency: 12 % slower)
-
-__device__ __forceinline__ float pow2_scale(float amax) {      // s = 2^k with amax * s in [2^14, 2^15)
-    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
-    int e;
-    (void)frexpf(amax, &e);
-    int k = 15 - e;
-    k = k > 120 ? 120 : (k < -120 ? -120 : k);
-    return ldexpf(1.f, k);
-}
 
 // base[elem] with the BYTE offset formed in 32 bits (elem < 2^30): scalar base + 32-bit lane offset, one address register per load
 __device__ __forceinline__ float ld_off32(const float* base, uint32_t elem) {
@@ -106,7 +94,7 @@ __global__ void k_cgp16_pack(const float* __restrict__ w0, const float* __restri
     }
     float sw[4];
 #pragma unroll
-    for (int l = 0; l < 4; ++l) sw[l] = pow2_scale(sc[l][0]);
+    for (int l = 0; l < 4; ++l) sw[l] = pow2_scale<15>(sc[l][0]);
     if (tid < 4) {
         hdr[tid] = sw[tid];              // [0..3]  weight scales
         hdr[4 + tid] = sc[tid][1];       // [4..7]  max row L1 norm
@@ -390,11 +378,11 @@ __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_e
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
     // ---- scales: input from its maximum, hidden layers from bounds |h_l| <= |h_{l-1}|max * L1max_l + |b_l|max
     CGP_STAMP(1)
-    const float s_in = pow2_scale(amax);
+    const float s_in = pow2_scale<15>(amax);
     const float bound0 = amax * CGP_H(4) + CGP_H(8);
     const float bound1 = bound0 * CGP_H(5) + CGP_H(9);
     const float bound2 = bound1 * CGP_H(6) + CGP_H(10);
-    const float s1 = pow2_scale(bound0), s2 = pow2_scale(bound1), s3 = pow2_scale(bound2);
+    const float s1 = pow2_scale<15>(bound0), s2 = pow2_scale<15>(bound1), s3 = pow2_scale<15>(bound2);
     const float inv0 = (1.f / s_in) * (1.f / CGP_H(0)), inv1 = (1.f / s1) * (1.f / CGP_H(1));
     const float inv2 = (1.f / s2) * (1.f / CGP_H(2)), inv3 = (1.f / s3) * (1.f / CGP_H(3));
     half8 b0h[NB][NK0], b0l[NB][NK0];
@@ -651,7 +639,7 @@ __global__ void k_cgp16_pack_bwd(const float* __restrict__ w0, const float* __re
     // backward layer b uses forward layer 3 - b
     float sw[4];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) sw[b] = pow2_scale(sc[3 - b][0]);
+    for (int b = 0; b < 4; ++b) sw[b] = pow2_scale<15>(sc[3 - b][0]);
     if (tid < 4) {
         hdr[tid] = sw[tid];                    // [0..3] weight scales of the backward layers
         hdr[4 + tid] = sc[3 - tid][1];         // [4..7] max row L1 norm of the transposed layers
@@ -718,9 +706,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float amax = fmaxf(fabsf(v0), fabsf(v1));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const float s_in = pow2_scale(amax);
+    const float s_in = pow2_scale<15>(amax);
     const float bound3 = amax * hdr[4], bound2 = bound3 * hdr[5], bound1 = bound2 * hdr[6];
-    const float s3 = pow2_scale(bound3), s2 = pow2_scale(bound2), s1 = pow2_scale(bound1);
+    const float s3 = pow2_scale<15>(bound3), s2 = pow2_scale<15>(bound2), s1 = pow2_scale<15>(bound1);
     const float inv0 = (1.f / s_in) * (1.f / hdr[0]), inv1 = (1.f / s3) * (1.f / hdr[1]);
     const float inv2 = (1.f / s2) * (1.f / hdr[2]), inv3 = (1.f / s1) * (1.f / hdr[3]);
 

@@ -818,9 +818,6 @@ static inline unsigned ew_grid2(int64_t n) {
 }  // namespace lldwt
 using namespace lldwt;
 
-// LLDWT_W1_TALL=0 keeps the 96 x 192 tile for the 162 x 94 weight gradient
-static const int g_w1_tall = [] { const char* e = getenv("LLDWT_W1_TALL"); return e ? atoi(e) : 1; }();
-
 // Weight gradient of a grouped 1x1 conv whose input is two tensors side by side per group: rows < ca of group g from xa
 // (planes, batch, groups*ca, hw), the other cb rows from xb (planes, batch, groups*cb, hw) -- layer 0 of the cgp stack with the folded
 // context (LiftingBasedDWT_net.py:282-289,353-359: [tree-context channels | gathered taps]) without the concatenated tensor.
@@ -835,7 +832,7 @@ extern "C" int lldwt_wgrad1x1_split(const float* xa, const float* xb, const floa
     const int cout_g = cout / groups, nb = ca + cb + (dbias ? 1 : 0);
     // 162 x 94 (layer 0 of the cgp stack): ONE 192 x 96 tile of dW per workgroup (72 accumulator registers) -- both operands are read
     // once; the 96 x 192 tile read the input rows twice (two row blocks)
-    if (g_w1_tall && cout_g > 96 && cout_g <= 192 && nb > 64 && nb <= 96) return launch_wgrad1x1<2, 2, 6, 3>(w, (int)planes, (hipStream_t)stream);
+    if (cout_g > 96 && cout_g <= 192 && nb > 64 && nb <= 96) return launch_wgrad1x1<2, 2, 6, 3>(w, (int)planes, (hipStream_t)stream);
     if (cout_g > 64 && nb > 64 && nb <= 192) return launch_wgrad1x1<1, 4, 6, 3>(w, (int)planes, (hipStream_t)stream);
     if (cout_g > 16 && cout_g <= 64 && nb > 64 && nb <= 192) return launch_wgrad1x1<1, 4, 4, 3>(w, (int)planes, (hipStream_t)stream);
     set_error("wgrad1x1_split: built for 64 < ca + cb (+1) <= 192 input rows and more than 16 output channels per group (got %d, %d)", nb, cout_g);
@@ -1012,12 +1009,11 @@ extern "C" int lldwt_conv2d_wgrad(const float* x, const float* dy, float* dw, fl
 extern "C" int lldwt_act_bwd(const float* dy, const float* y, float* dx, int64_t n, int act, void* stream) {
     LLDWT_REQUIRE(dy && y && dx && n >= 0, "act_bwd: bad arguments");
     if (n == 0) return 0;
-    static const bool scalar = getenv("LLDWT_ACT_BWD") && atoi(getenv("LLDWT_ACT_BWD")) == 1;     // A/B: the 4-byte kernel
-    if (!scalar && (n & 3) == 0 && ((((uintptr_t)dy) | ((uintptr_t)y) | ((uintptr_t)dx)) & 15) == 0) {
+    if ((n & 3) == 0 && ((((uintptr_t)dy) | ((uintptr_t)y) | ((uintptr_t)dx)) & 15) == 0) {
         const int64_t n4 = n >> 2, g = cdiv(n4, 256), cap = (int64_t)lldwt_num_cus() * 128;
         hipLaunchKernelGGL(k_act_bwd4, dim3((unsigned)(g > cap ? cap : g)), dim3(256), 0, (hipStream_t)stream,
                            reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(y), reinterpret_cast<float4*>(dx), n4, act);
-    } else {
+    } else {                                      // unaligned or ragged: the 4-byte kernel
         hipLaunchKernelGGL(k_act_bwd, dim3(ew_grid2(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n, act);
     }
     return check_launch("act_bwd");

@@ -29,8 +29,6 @@
 
 namespace lldwt {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 constexpr int F3_CK = 32;                       // input channels per chunk
 constexpr int F3_TH = 8, F3_TW = 32;            // output pixels per workgroup
 constexpr int F3_IH = F3_TH + 2, F3_IW = F3_TW + 2, F3_NPX = F3_IH * F3_IW;   // 10 x 34 = 340 staged pixels
@@ -80,16 +78,6 @@ static inline int64_t f3_plane_bytes(int cin, int cout) {
     return f3_wino_off(cin, cout) + F3_HDR + (int64_t)f3_nocb(cout) * 4 * w3_nch(cin) * W3_NST * F3_STEP_BYTES + 5 * F3_STEP_BYTES;
 }
 
-__device__ __forceinline__ float pow2_scale_for(float amax) {
-    // power of two s with amax * s in [2^14, 2^15); 1 for amax == 0 / non-finite
-    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
-    int e;
-    (void)frexpf(amax, &e);                      // amax = m * 2^e, m in [0.5, 1)
-    int k = 15 - e;
-    k = k > 120 ? 120 : (k < -120 ? -120 : k);
-    return ldexpf(1.f, k);
-}
-
 // ---- |x| maximum per plane into 64 slots (spreads the atomics; the consumer takes the max of the 64)
 __global__ void k_absmax_slots(const float* __restrict__ x, int64_t n_per_plane, float* __restrict__ slots, int vec) {
     const int plane = blockIdx.y;
@@ -131,7 +119,7 @@ __global__ void k_f3_pack(const float* __restrict__ w, uint8_t* __restrict__ pac
     const int plane = blockIdx.y;
     uint8_t* pp = packed + (int64_t)plane * plane_bytes;
     float* hdr = reinterpret_cast<float*>(pp);
-    const float sw = pow2_scale_for(hdr[1]);
+    const float sw = pow2_scale<15>(hdr[1]);
     const int nch = (cin + F3_CK - 1) / F3_CK, nocb = (cout + F3_OCB - 1) / F3_OCB;
     const int64_t nfrag_elems = (int64_t)nocb * 4 * nch * 9 * 2 * 64 * 8;       // (hi, lo) pairs
     const float* wp = w + (int64_t)plane * cout * cin * 9;
@@ -190,7 +178,7 @@ __global__ void k_f1_pack(const float* __restrict__ w1, const float* __restrict_
     if ((tid & 63) == 0) { red[0][tid >> 6] = mw; red[1][tid >> 6] = ml1; red[2][tid >> 6] = mb; }
     __syncthreads();
     const float amw = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-    const float sw1 = pow2_scale_for(amw);
+    const float sw1 = pow2_scale<15>(amw);
     if (tid == 0) {
         hdr[0] = sw1;
         hdr[1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
@@ -285,7 +273,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         float amax = a.slots[plane * 64 + lane];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-        sx = pow2_scale_for(amax);
+        sx = pow2_scale<15>(amax);
     }
     const uint8_t* pp = a.packed + (int64_t)plane * a.plane_bytes;
     const float sw = *reinterpret_cast<const float*>(pp);
@@ -405,8 +393,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (lane == 0) red[wave] = amax;
         __syncthreads();
         amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        const float s_p = pow2_scale_for(amax);
-        sx = pow2_scale_for(amax * h1[1] + h1[2]);                           // bound on |LeakyReLU(conv1)|: max|parent| * L1max + |b|max
+        const float s_p = pow2_scale<15>(amax);
+        sx = pow2_scale<15>(amax * h1[1] + h1[2]);                           // bound on |LeakyReLU(conv1)|: max|parent| * L1max + |b|max
         out_scale = (1.f / sx) * (1.f / sw);
         inv1 = (1.f / s_p) * (1.f / h1[0]);
         inv1sx = inv1 * sx;
@@ -862,7 +850,7 @@ __global__ void k_f3w_pack(const float* __restrict__ w, uint8_t* __restrict__ pa
     const int plane = blockIdx.y;
     uint8_t* pp = packed + (int64_t)plane * plane_bytes + woff;
     float* hdr = reinterpret_cast<float*>(pp);
-    const double su = pow2_scale_for(hdr[1]);
+    const double su = pow2_scale<15>(hdr[1]);
     const int nch = w3_nch(cin), nocb = (cout + F3_OCB - 1) / F3_OCB;
     const int64_t n = (int64_t)nocb * 4 * nch * W3_NST * 64 * 8;
     const float* wp = w + (int64_t)plane * cout * cin * 9;
@@ -949,9 +937,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (lane == 0) red[wave] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float s_p = pow2_scale_for(amax);
+    const float s_p = pow2_scale<15>(amax);
     // V spans twice the activation bound: half the direct kernel's scale keeps max|V * sx| below 2^15
-    const float sx = 0.5f * pow2_scale_for(amax * h1[1] + h1[2]);
+    const float sx = 0.5f * pow2_scale<15>(amax * h1[1] + h1[2]);
     const float out_scale = (1.f / sx) * (1.f / su);
     const float inv1sx = (1.f / s_p) * (1.f / h1[0]) * sx;
     for (int px = tid; px < F3_NPX; px += 256) {

@@ -1586,8 +1586,8 @@ extern "C" int lldwt_lift_bwd_fin(const float* g, const float* dsk, const float*
                   "lift_bwd_fin: bad arguments");
     // every workgroup ends with three float atomics onto its plane's tap gradients: with 64 row slices a level-0 launch sent 1 024
     // atomics to each of nine addresses (they serialise in L2 and took longer than the 63 MB the kernel moves); 16 slices
-    static const int fin_rows = [] { const char* e = getenv("LLDWT_FIN_ROWS"); const int v = e ? atoi(e) : 16; return v > 0 ? v : 16; }();
-    dim3 grid((unsigned)cdiv(w, 256), (unsigned)(h < fin_rows ? h : fin_rows), (unsigned)Z);
+    constexpr int FIN_ROWS = 16;
+    dim3 grid((unsigned)cdiv(w, 256), (unsigned)(h < FIN_ROWS ? h : FIN_ROWS), (unsigned)Z);
     hipLaunchKernelGGL(k_lift_bwd_fin, grid, dim3(256), 0, (hipStream_t)stream, g, dsk, srcv, g_src, (int)batch, (int)h,
                        (int)w, taps, dtaps, vertical, sign, res_weight);
     return check_launch("lift_bwd_fin");
@@ -1631,13 +1631,8 @@ int wgrad_thin_pair(const float* t3, const float* g, float* dw4, float* db4, con
 int wgrad16_pair(const float* x3, const float* dy3, float* dw3, float* db3, const float* x2, const float* dy2, float* dw2, float* db2,
                  int64_t planes, int64_t batch, int64_t h, int64_t w_, float alpha, int swap_hw, int K, hipStream_t st);
 }
-// LLDWT_WGRAD16_PAIR=0 keeps two launches for the fp32 16 -> 16 weight gradients of a step (the small levels)
-static const int g_w16_pair = [] { const char* e = getenv("LLDWT_WGRAD16_PAIR"); return e ? atoi(e) : 1; }();
-// LLDWT_WGRAD_THIN=2 keeps the two separate launches of the thin (1 <-> 16) weight gradients of a step
-static const int g_thin_pair = [] { const char* e = getenv("LLDWT_WGRAD_THIN"); return (e && !strcmp(e, "2")) ? 0 : 1; }();
-// LLDWT_WGRAD16=f32 keeps the fp32-MFMA weight gradient of the 16 -> 16 lifting convs (k_wgrad16<5>); default: split-fp16
-static const int g_wgrad16_f16 = [] { const char* e = getenv("LLDWT_WGRAD16"); return (e && !strcmp(e, "f32")) ? 0 : 1; }();
-// smallest batch * h * w per plane at which the split-fp16 kernel takes the 16 -> 16 weight gradients (LLDWT_WGRAD16_MIN overrides)
+// smallest batch * h * w per plane at which the split-fp16 kernel takes the 16 -> 16 weight gradients (LLDWT_WGRAD16_MIN overrides);
+// below it the fp32-MFMA pair (k_wgrad16<5>, one launch for both convs) does
 static const int64_t g_wgrad16_min = [] { const char* e = getenv("LLDWT_WGRAD16_MIN"); return e ? (int64_t)atoll(e) : (int64_t)250000; }();
 
 // LLDWT_BWD_LIFT=f32 keeps the three fp32-MFMA backward-data launches even when a backward pack is passed
@@ -1728,7 +1723,7 @@ static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_v
     float* dr = dpre2 + n * C;
     int r;
     float* slots = dr + n * C;          // 128 per plane: max |dt3|, max |dpre2| (the split-fp16 weight gradient's dY scales)
-    const bool wg16 = K == 5 && !linear && g_wgrad16_f16 && w % 4 == 0 && batch * h * w >= g_wgrad16_min;
+    const bool wg16 = K == 5 && !linear && w % 4 == 0 && batch * h * w >= g_wgrad16_min;
     bool slots_ready = false;
     if (packed_bwd && K == LF_K && C == LF_C && !linear && g_bwd_lift_f16 && g_lift_mode == 1) {
         {   // g = G[dst_out], G[dst_in] = g; the same launch zeroes the |max| slots the fused launch fills (no memset per step)
@@ -1754,19 +1749,8 @@ static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_v
     // weight gradients (scaled by sign*res_weight: net enters dst as sign*rw*net); row passes store (kh,kw) swapped
     const float alpha = sign * res_weight;
     const int swap = vertical ? 0 : 1;
-    lldwt_conv_desc d;
-    auto desc = [&](int cin, int cout) {
-        d.cin = cin; d.cout = cout; d.K = K; d.groups = 1; d.act = LLDWT_ACT_NONE; d.upsample2 = 0; d.transposed = 0;
-        d.tap_mask = (1u << (K * K)) - 1u; d.oc_block = cout; d.oc_stride = 0; d.oc_off = 0; d.ytot = cout;
-        d.ic_block = 0; d.ic_stride = 0; d.ic_off = 0; d.xtot = 0; d.epi = 0;
-    };
-    if (g_thin_pair) {          // conv4's and conv1's gradients (both read what the backward-data chain left) in one launch
-        if ((r = wgrad_thin_pair(t3, g, dw4, db4, skip, dr, dw1, db1, planes, batch, h, w, alpha, swap, K, st))) return r;
-    } else {
-        desc(C, 1);
-        if ((r = lldwt_conv2d_wgrad(t3, g, dw4, db4, &d, planes, batch, h, w, alpha, swap, stream))) return r;
-    }
-    desc(C, C);
+    // conv4's and conv1's gradients (both read what the backward-data chain left) in one launch
+    if ((r = wgrad_thin_pair(t3, g, dw4, db4, skip, dr, dw1, db1, planes, batch, h, w, alpha, swap, K, st))) return r;
     if (wg16) {
         // conv3 / conv2: their inputs t2 / t1 are tanh outputs (|x| <= 1): split-fp16 on the fp16 matrix cores (conv_wgrad_f16x3.hip).
         // Only where it wins (measured, 3 planes x 8 images, kernel alone: 228 vs 530 us at 256 x 512, 148 vs 272 at 256 x 256,
@@ -1778,15 +1762,8 @@ static int lift_step_bwd_impl(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_v
         if ((r = wgrad16_f16x3(t2, dt3, dw3, db3, slots, ss, slots_ready, planes, batch, h, w, alpha, tap_of, st))) return r;
         if ((r = wgrad16_f16x3(t1, dpre2, dw2, db2, slots + (slots_ready ? 64 : 0), ss, slots_ready, planes, batch, h, w, alpha, tap_of,
                                st))) return r;
-    } else if (g_w16_pair) {
-        if ((r = wgrad16_pair(t2, dt3, dw3, db3, t1, dpre2, dw2, db2, planes, batch, h, w, alpha, swap, K, st))) return r;
     } else {
-        if ((r = lldwt_conv2d_wgrad(t2, dt3, dw3, db3, &d, planes, batch, h, w, alpha, swap, stream))) return r;
-        if ((r = lldwt_conv2d_wgrad(t1, dpre2, dw2, db2, &d, planes, batch, h, w, alpha, swap, stream))) return r;
-    }
-    if (!g_thin_pair) {
-        desc(1, C);
-        if ((r = lldwt_conv2d_wgrad(skip, dr, dw1, db1, &d, planes, batch, h, w, alpha, swap, stream))) return r;
+        if ((r = wgrad16_pair(t2, dt3, dw3, db3, t1, dpre2, dw2, db2, planes, batch, h, w, alpha, swap, K, st))) return r;
     }
     return lldwt_lift_bwd_fin(g, dsk, srcv, g_src, Z, batch, h, w, taps, dtaps, vertical, sign, res_weight, stream);
 }

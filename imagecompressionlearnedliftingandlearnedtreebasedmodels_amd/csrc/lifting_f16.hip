@@ -26,15 +26,11 @@
 // one element), and conv1's k order is (row dy = lane group, three dx PAIRS (0,1) (2,3) (4,5*)) + one pair of row 4 per
 // lane group (* = a real neighbour value against a zero weight): a lane's 8 k values are four aligned 4-byte LDS reads
 // that land as packed fp16 pairs -- no per-tap gather, no scaling, no split in the loop.
+#include <atomic>
 #include "lifting_f16.h"
 #include "split_f16.h"
 
 namespace lldwt {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -122,15 +118,6 @@ constexpr int LDS_TOTAL2 = LDS_W4L + LF_KK * LF_C * 4;                // 160 960
 static_assert(LDS_TOTAL2 <= 160 * 1024, "one workgroup per CU");
 constexpr float ACT_SCALE = 16384.f;                                  // tanh outputs: |t| <= 1 -> |t * 2^14| < fp16 max
 
-__device__ __forceinline__ float pow2_scale(float amax) {             // s = 2^k with amax * s in [2^14, 2^15)
-    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
-    int e;
-    (void)frexpf(amax, &e);
-    int k = 15 - e;
-    k = k > 120 ? 120 : (k < -120 ? -120 : k);
-    return ldexpf(1.f, k);
-}
-
 __device__ __forceinline__ void split4(const float (&v)[4], half4& hi, half4& lo) { split4v(v, hi, lo); }
 
 // tanh(acc * k + b) with the factor 2 log2(e) of exp(2|x|) = 2^(2 log2(e) |x|) already folded into kc = k * 2 log2(e) and
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(PACK_NT) void k_lift_f16_pack(const float* __restri
     for (int q = 0; q < 4; ++q) {
         float mm = 0.f;
         for (int i = 0; i < PACK_NW; ++i) mm = fmaxf(mm, red[q][i]);
-        sw[q] = pow2_scale(mm);
+        sw[q] = pow2_scale<15>(mm);
     }
     float* dst = packed + (int64_t)plane * plane_stride + f16_off + (int64_t)orient * LF_ORIENT_FLOATS;
     _Float16* hp = reinterpret_cast<_Float16*>(dst);
@@ -232,7 +219,7 @@ __global__ __launch_bounds__(PACK_NT) void k_lift_f16_pack(const float* __restri
     __syncthreads();
     float mcc = 0.f;
     for (int i = 0; i < PACK_NW; ++i) mcc = fmaxf(mcc, redc[i]);
-    const float swc = pow2_scale(mcc);
+    const float swc = pow2_scale<15>(mcc);
     for (int i = tid; i < LF_H_END / 2; i += PACK_NT) {          // one (hi, lo) pair per iteration
         int rem = i;
         const int j = rem % 8; rem /= 8;
@@ -814,10 +801,10 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         float m = RED[0];
 #pragma unroll
         for (int i = 1; i < NWAVE; ++i) m = fmaxf(m, RED[i]);
-        s_skip = pow2_scale(m);
+        s_skip = pow2_scale<15>(m);
         if constexpr (BWD) {                                  // |dt3| <= max|g| L1(conv1'), |dpre2| <= that x L1(conv2') (gates <= 1)
-            act1 = pow2_scale(m * scales[13]);
-            act2 = pow2_scale(m * scales[13] * scales[14]);
+            act1 = pow2_scale<15>(m * scales[13]);
+            act2 = pow2_scale<15>(m * scales[13] * scales[14]);
         }
     }
     if constexpr (BWD) {
@@ -1483,7 +1470,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         float m = RED[8];
 #pragma unroll
         for (int i = 1; i < NWAVE; ++i) m = fmaxf(m, RED[8 + i]);
-        s_t3 = pow2_scale(m);
+        s_t3 = pow2_scale<15>(m);
 #pragma unroll
         for (int it = 0; it < IT3; ++it) {
             const int tile = wave + it * NWAVE;
@@ -1737,8 +1724,8 @@ int lift_f16_launch(const LiftF16Call& c) {
     a.nseg = (int)cdiv(a.tiles_y, a.rl);
     a.nitems = (int)(Zl * a.tiles_x * a.nseg);
     a.nborder = (int)(Zl * (a.tiles_x >= 2 ? 2 : 1) * a.nseg);
-    static unsigned launch_seq = 0;
-    a.qslot = (int)(launch_seq++ & 63u);
+    static std::atomic<unsigned> launch_seq{0};                             // two host threads never draw the same slot
+    a.qslot = (int)(launch_seq.fetch_add(1, std::memory_order_relaxed) & 63u);
     const unsigned grid = (unsigned)(a.nitems < ncu ? a.nitems : ncu);      // one resident workgroup per CU
     const int prec = seq ? 0 : g_precision;
     if (bw) hipLaunchKernelGGL((k_lift_fused_f16<true, 0, false, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);

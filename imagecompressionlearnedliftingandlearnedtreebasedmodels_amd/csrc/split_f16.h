@@ -10,6 +10,23 @@ typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 typedef float f2_t __attribute__((ext_vector_type(2)));
+typedef h2_t half2;          // the spellings the kernels use for MFMA fragments and accumulators
+typedef h4_t half4;
+typedef h8_t half8;
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// power of two s = 2^k with amax * s in [2^(TOP-1), 2^TOP); 1 for amax == 0 / non-finite
+template <int TOP>
+__device__ __forceinline__ float pow2_scale(float amax) {
+    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
+    int e;
+    (void)frexpf(amax, &e);                      // amax = m * 2^e, m in [0.5, 1)
+    int k = TOP - e;
+    k = k > 120 ? 120 : (k < -120 ? -120 : k);
+    return ldexpf(1.f, k);
+}
 
 // lo through v_fma_mixlo_f16 / v_fma_mixhi_f16: D.f16 = round(v * 1.0 - hi) with v read as fp32 and hi as the fp16 half it
 // already is (op_sel_hi / op_sel), one instruction per element and no fp16 -> fp32 conversion: 1.5 vector instructions per
@@ -44,8 +61,8 @@ __device__ __forceinline__ void split8v(const float (&v)[8], h8_t& hi, h8_t& lo)
 }
 
 // ---- the one-product modes (lldwt_set_precision 1 = fp16, 2 = bf16): 16-byte fragments travel as h8_t whatever they hold
-typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
-typedef float f16_t __attribute__((ext_vector_type(16)));
+typedef bf16x8 bf8_t;
+typedef floatx16 f16_t;
 
 // one MFMA product of the 32x32x16 shape on fp16 (PREC 0, 1) or bf16 (PREC 2) operands
 template <int PREC>
@@ -56,7 +73,7 @@ __device__ __forceinline__ f16_t mma32(const h8_t& a, const h8_t& b, const f16_t
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
 }
 // the 16x16x32 shape
-typedef float f4_t __attribute__((ext_vector_type(4)));
+typedef floatx4 f4_t;
 template <int PREC>
 __device__ __forceinline__ f4_t mma16(const h8_t& a, const h8_t& b, const f4_t& acc) {
     if constexpr (PREC == 2)

@@ -391,7 +391,7 @@ int lldwt_conv3x3_wgrad_f16x3(const float* x, const float* dy, float* dw, float*
  * x (planes, batch, 16, h, w) must be bounded by 1 in magnitude (the tanh outputs t1 / t2: its split uses the fixed scale
  * 2^14); dy any magnitude (one power-of-two scale per plane from its |max|).  w % 4 == 0, 16-byte aligned tensors.
  * slots_ws: planes * 64 floats of scratch.  swap_hw != 0: the (kh, kw) axes of dw are stored swapped (row passes).
- * lldwt_lift_step_bwd uses it for K == 5 tanh blocks; LLDWT_WGRAD16=f32 keeps the fp32-MFMA kernel of lldwt_conv2d_wgrad. */
+ * lldwt_lift_step_bwd uses it for K == 5 tanh blocks from LLDWT_WGRAD16_MIN pixels per plane up (below: the fp32-MFMA kernel). */
 int lldwt_wgrad16_f16x3(const float* x, const float* dy, float* dw, float* dbias, float* slots_ws, int64_t planes,
                         int64_t batch, int64_t h, int64_t w, float alpha, int swap_hw, void* stream);
 /* dx = dy * act'(y) elementwise (y = forward output); act as in lldwt_conv_desc. */

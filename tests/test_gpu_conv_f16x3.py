@@ -157,11 +157,13 @@ def test_fused_pair_is_what_the_model_runs(monkeypatch):
     assert float((a - b).abs().max()) < 2e-6 * float(b.abs().max())
 
 
-@pytest.mark.parametrize("shape", [(1, 2, 243, 243, 32, 64), (2, 3, 70, 150, 17, 44), (1, 1, 64, 64, 2, 4), (1, 2, 96, 130, 9, 100)])
+@pytest.mark.parametrize("shape", [(1, 2, 243, 243, 32, 64), (2, 3, 70, 150, 17, 44), (1, 1, 64, 64, 2, 4), (1, 2, 96, 130, 9, 100),
+                                   (2, 3, 100, 243, 38, 84)])
 def test_wgrad_f16x3_vs_float64_and_fp32_kernel(shape):
     """lldwt_conv3x3_wgrad_f16x3 (split-fp16 MFMA GEMM over pixels, K split over workgroups, atomics) vs the float64
     gradient of F.conv2d and vs the fp32 MFMA weight-gradient kernel: ragged channel counts (partial oc / ic blocks), images
-    smaller than a chunk, odd row counts, several images (the reduction runs over them), bias gradient."""
+    smaller than a chunk, odd row counts, several images (the reduction runs over them), bias gradient.  The last shape gives
+    several chunks per slice, partial channel blocks and a ragged last chunk column."""
     ops = _ops()
     P, B, cin, cout, h, w = shape
     g = torch.Generator().manual_seed(cin + h)
@@ -177,6 +179,7 @@ def test_wgrad_f16x3_vs_float64_and_fp32_kernel(shape):
         scale = float(wz.grad.abs().max())
         e16 = float((dw[p].cpu().double() - wz.grad).abs().max()) / scale
         e32 = float((dw32[p].cpu().double() - wz.grad).abs().max()) / scale
+        print("\n[wgrad_f16x3] %s plane %d: e16 = %.3g, e32 = %.3g" % (shape, p, e16, e32))
         assert e16 < 5e-6, (e16, e32)
         assert e16 < 4 * e32 + 5e-7, (e16, e32)
         eb = float((db[p].cpu().double() - bz.grad).abs().max()) / float(bz.grad.abs().max())
@@ -193,30 +196,6 @@ def test_wgrad_f16x3_vs_float64_and_fp32_kernel(shape):
         assert float((db3 - db).abs().max()) < 1e-5 * float(db.abs().max())
     with pytest.raises(Exception):
         ops.conv3x3_wgrad_f16x3(x.to(DEV), dy.to(DEV), (P, cout, cin, 3, 3), x_slots=xs[:, :32].contiguous())
-
-
-def test_wgrad_f16x3_both_kernels_agree():
-    """k_wgrad3_f16x3_v2 (one copy of the input rows + register shifts, staging in the MFMA shadow; the default) against the first
-    kernel (LLDWT_WGRAD3=v1, read at the first call: a child process) on a shape with several chunks per slice, partial channel
-    blocks and a ragged last chunk column."""
-    import subprocess, sys, os
-    code = (
-        "import torch, sys; sys.path.insert(0, %r)\n"
-        "from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import ops\n"
-        "g = torch.Generator().manual_seed(5)\n"
-        "x = ((torch.rand(2, 3, 100, 38, 84, generator=g) - 0.3) * 2).cuda(); dy = (torch.randn(2, 3, 243, 38, 84, generator=g) * 1e-3).cuda()\n"
-        "dw, db = ops.conv3x3_wgrad_f16x3(x, dy, (2, 243, 100, 3, 3))\n"
-        "torch.save((dw.cpu(), db.cpu()), sys.argv[1])\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import tempfile
-    out = {}
-    with tempfile.TemporaryDirectory() as td:
-        for mode in ("v1", "v2"):
-            env = dict(os.environ, LLDWT_WGRAD3=mode)
-            f = os.path.join(td, mode + ".pt")
-            subprocess.run([sys.executable, "-c", code, f], check=True, env=env, timeout=300)
-            out[mode] = torch.load(f, weights_only=True)
-    for a, b in zip(out["v1"], out["v2"]):
-        assert float((a - b).abs().max()) < 2e-6 * float(b.abs().max())
 
 
 def test_fused_pair_random_shapes():

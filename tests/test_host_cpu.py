@@ -335,3 +335,25 @@ def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
         assert s1.size > 0 and (s1 == s2).all()
     y = np.load(tmp_path / "s1" / "y.npy")
     assert (np.diff(y) > 0).all()                     # sorted positions of the flattened array
+
+
+def test_documented_switches_are_the_switches_read():
+    """INTEGRATION.md's "Process-wide switches" section names exactly the LLDWT_* environment variables that the sources read:
+    every getenv("LLDWT_...") of csrc/*.hip|*.h, and every such name read from os.environ in the package's *.py and in bench.py
+    (os.environ.get / os.environ[...] / os.getenv / ops._env_choice).  A switch added without a line there, or a line left behind
+    by a deleted switch, fails here."""
+    import glob
+    name = r'"(LLDWT_[A-Z0-9_]+)"'
+    read = set()
+    csrc = os.path.join(REPO, PKG, "csrc")
+    for f in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        read |= set(re.findall(r"getenv\(\s*" + name, open(f).read()))
+    py_read = r"(?:environ\.get\(|getenv\(|_env_choice\()\s*" + name + r"|environ\[\s*" + name + r"\s*\](?!\s*=(?!=))"
+    for f in glob.glob(os.path.join(REPO, PKG, "**", "*.py"), recursive=True) + [os.path.join(REPO, "bench.py")]:
+        read |= {a or b for a, b in re.findall(py_read, open(f).read())}
+    assert len(read) > 10, sorted(read)                   # the patterns still match the sources
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    section = re.search(r"^### Process-wide switches \(environment[^\n]*\n(.*?)^#{1,6} ", doc, re.S | re.M).group(1)
+    documented = set(re.findall(r"LLDWT_[A-Z0-9_]+", section))
+    assert not (read - documented), "read by the sources, missing in INTEGRATION.md's switch list: %s" % sorted(read - documented)
+    assert not (documented - read), "in INTEGRATION.md's switch list, read by no source: %s" % sorted(documented - read)
