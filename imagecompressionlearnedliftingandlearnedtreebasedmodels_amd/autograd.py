@@ -173,7 +173,12 @@ class CgpRateCtxFn(torch.autograd.Function):
     def forward(ctx, plc, xq, x, noise, groups, K, tap_mask, *wb):
         ws, bs = list(wb[0::2]), list(wb[1::2])
         dims = tuple([ws[0].shape[2]] + [w_.shape[1] // groups for w_ in ws[:3]])
-        if _CGP_TRAIN_F16 and dims == (93, 162, 54, 18) and ops.cgp_mode() == "f16x3":
+        # the split chain serves the reference's widths and weights inside its range (ops.cgp16_supported: one small reduction
+        # and a host read per call -- a stream synchronisation, so this forward cannot be captured in a HIP graph; the answer is
+        # taken anew every step and may change between steps near the limit, where both paths hold the fp32 bars); the backward
+        # takes the same answer
+        chain = ops.cgp_mode() == "f16x3" and (_CGP_TRAIN_F16 or _CGP_TRAIN_BWD_F16) and ops.cgp16_supported(ws, groups, bs)
+        if _CGP_TRAIN_F16 and chain:
             # the forward on the eval path's split-fp16 register chain, which also writes the hidden activations (fp32-level accuracy;
             # 1.4 -> ~3 ms per step against 6.0 for the fp32-MFMA kernel); LLDWT_CGP_TRAIN_FWD=f32 keeps the latter
             params, h1, h2, h3 = ops.cgp16_params_train(plc, xq, ops.cgp16_pack(ws, bs, groups), K, tap_mask)
@@ -182,7 +187,7 @@ class CgpRateCtxFn(torch.autograd.Function):
             packed, dims = ops.cgp_pack(ws, bs, groups)
             bits, params, h1, h2, h3 = ops.cgp_rate_train_ctx(plc, xq, x, packed, dims, noise, K, tap_mask)
         ctx.save_for_backward(plc, xq, x, noise, params, h1, h2, h3, *ws)
-        ctx.dims, ctx.groups, ctx.K, ctx.tap_mask = dims, groups, K, tap_mask
+        ctx.dims, ctx.groups, ctx.K, ctx.tap_mask, ctx.chain = dims, groups, K, tap_mask, chain
         return bits
 
     @staticmethod
@@ -192,7 +197,7 @@ class CgpRateCtxFn(torch.autograd.Function):
         live = CgpRateCtxFn._taps(K, ctx.tap_mask)
         nt, R = len(live), K // 2
         dx, dparams = ops.gauss_rate_bwd(x, params, noise, gbits.contiguous())
-        if _CGP_TRAIN_BWD_F16 and dims == (93, 162, 54, 18) and nt == 12 and ops.cgp_mode() == "f16x3":
+        if _CGP_TRAIN_BWD_F16 and ctx.chain and nt == 12:
             # backward-data on the split-fp16 register chain (LLDWT_CGP_TRAIN_BWD=f32 keeps the fp32-MFMA kernel)
             dplc, dtaps, d1, d2, d3 = ops.cgp16_bwd(dparams, h1, h2, h3, ops.cgp16_pack_bwd(ws, G), G)
         else:

@@ -19,8 +19,13 @@
 //     three steps ahead by a sched_barrier after each load: left alone, the scheduler sinks the loads to their uses).
 //   * one 32-pixel block per wave, two waves per SIMD: the partner wave computes while a wave waits for its inputs.
 // Scales: every operand tensor is multiplied by a power of two before the split so that it cannot overflow fp16; the
-// activations' bounds come from the wave's input maximum and the layers' max row L1 norms (fp16's exponent keeps the full
-// 22-bit split precision over 18 binades, so a loose bound costs nothing).
+// activations' bounds come from the wave's input maximum and the layers' max row L1 norms.  fp16's exponent keeps the full
+// 22-bit split precision over 18 binades below the bound, but the bounds compound from layer to layer and a loose one is NOT
+// free: an even network (rows of similar L1 norm) has about 6 of those 18 binades to spare at layer 3 (the rest lies between the
+// bound and the values themselves).  A unit 2^7 louder than its
+// layer's typical row, or 2^3 in each of the three layers, pushes the other units' low halves into fp16's subnormals and
+// (sigma, mu) leave the fp32 bars (measured); ops.cgp16_supported refuses such weights and the callers take the
+// fp32 kernels.
 // Output: params (planes, batch, 2*groups, h, w) = (sigma, mu) interleaved per subband, consumed by lldwt_gauss_rate.
 #include <stdlib.h>
 #include <string.h>

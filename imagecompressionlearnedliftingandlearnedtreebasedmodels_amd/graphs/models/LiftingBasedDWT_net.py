@@ -838,7 +838,8 @@ def _fold_csc_into_cgp(convs, cs, G):
     ws = [torch.stack(w0n, 0).contiguous()] + [_stack(layer, lambda m: m.weight) for layer in convs[1:]]
     bs = [torch.stack(b0n, 0).contiguous()] + [_stack(layer, lambda m: m.bias) for layer in convs[1:]]
     packed, dims = ops.cgp_pack(ws, bs, G)
-    packed16 = ops.cgp16_pack(ws, bs, G) if ops.cgp16_supported(ws, G) else None       # split-fp16 fragments (eval path)
+    # split-fp16 fragments (eval path and coder); None for other widths and for weights outside the chain's range: fp32 kernels
+    packed16 = ops.cgp16_pack(ws, bs, G) if ops.cgp16_supported(ws, G, bs) else None
     return packed, dims, packed16
 
 

@@ -672,9 +672,44 @@ def cgp_mode():
     return _env_choice("LLDWT_CGP_MODE", "f16x3", ("f32", "f16x3"))
 
 
-def cgp16_supported(ws, groups):
+# The split chain takes every hidden layer's operand scale from a bound (bound_l = bound_{l-1} * max row L1 norm + max |bias|) and
+# fp16 keeps the full 22-bit split over 18 binades below it.  The bounds compound from layer to layer, so an even network (rows of
+# similar L1 norm) already sits well below them and has about 6 of the 18 binades to spare at layer 3; a unit (or bias) far louder
+# than its layer's typical row pushes the bound up and every other unit down by as much, and spends them.  Measured on MI355X
+# (DESIGN.md 2.3): every form holds the fp32 bars up to 6.8 binades of this measure and leaves them from 7.6; the limit keeps two
+# binades of margin.
+CGP16_HEADROOM_LIMIT = 4.8
+
+
+def cgp16_headroom(ws, bs, groups):
+    """Binades of the chain's range that the bounds of layers 0 .. 2 spend beyond an even network: the largest over (plane, group)
+    of sum_l log2(max(max row L1 norm, max |bias|) / median row L1 norm).  ws, bs as cgp16_pack takes them.  An fp32 reduction
+    on the tensors' device and one host read (a stream synchronisation: not capturable in a HIP graph)."""
+    tot = None
+    for l in range(3):
+        w = ws[l].detach()
+        P = w.shape[0]
+        rows = w.abs().reshape(P, groups, w.shape[1] // groups, -1).sum(dim=3).double()
+        top = rows.amax(dim=2)
+        top = torch.maximum(top, bs[l].detach().abs().reshape(P, groups, -1).amax(dim=2).double())
+        t = torch.log2(top / rows.median(dim=2).values)
+        t = torch.where(top > 0, t, torch.zeros_like(t)).clamp_min(0.0)          # an all-zero layer spends nothing
+        tot = t if tot is None else tot + t
+    return float(tot.max())
+
+
+def cgp16_supported(ws, groups, bs):
+    """Whether the split-fp16 register chain serves this stack: the reference's widths, and weights AND biases inside what its
+    bound-derived scales represent (cgp16_headroom <= CGP16_HEADROOM_LIMIT).  Otherwise the callers take the fp32 kernels.
+    The two paths give different bits and the coder follows this answer, so the answer is part of what encoder and decoder must
+    share: the measure is an fp32 sum in the device's order, and weights within rounding of the limit (the two binades of margin
+    lie below it, not around it) could be judged differently by another build or device -- as with every other kernel of the coder,
+    a stream is decoded by the build that wrote it.  In training the answer is taken anew at every call and can change from one
+    step to the next while the weights sit near the limit; either path meets the fp32 bars there."""
     c = [ws[0].shape[2]] + [w.shape[1] // groups for w in ws]
-    return _lib.load().lldwt_cgp16_packed_bytes(c[0], c[1], c[2], c[3], groups) > 0 and c[4] == 2
+    if not (_lib.load().lldwt_cgp16_packed_bytes(c[0], c[1], c[2], c[3], groups) > 0 and c[4] == 2):
+        return False
+    return cgp16_headroom(ws, bs, groups) <= CGP16_HEADROOM_LIMIT
 
 
 def cgp16_pack(ws, bs, groups):

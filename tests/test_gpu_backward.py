@@ -178,8 +178,9 @@ def test_cgp_fused_forward_backward(dims, hw, PB):
         assert maxdiff(bits[p].detach().cpu(), ref) < 2e-4
         ref.backward(gb[p])
         for a, b, name in zip(dv, rv, ["cat", "x"] + ["w%d" % (i // 2) if i % 2 == 0 else "b%d" % (i // 2) for i in range(8)]):
-            scale = max(1.0, float(b.grad.abs().max()))
-            assert maxdiff(a.grad[p].cpu(), b.grad) < 5e-4 * scale, name
+            # relative to the tensor's own maximum, also where that is below 1; measured on MI355X: at most 5.6e-6 of it
+            scale = float(b.grad.abs().max())
+            assert maxdiff(a.grad[p].cpu(), b.grad) < 1e-4 * scale, name
 
 
 @pytest.mark.parametrize("fwd,bwd", [("f32", "f32"), ("f16x3", "f32"), ("f32", "f16x3"), ("f16x3", "f16x3")])
