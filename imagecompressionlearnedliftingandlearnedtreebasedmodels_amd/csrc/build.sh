@@ -14,11 +14,14 @@ mkdir -p "$HERE/obj"
 HDRS="$HERE/common.h $HERE/lifting_f16.h $HERE/split_f16.h $HERE/../../include/lldwt.h"
 pids=()
 names=()
-for f in ops lifting lifting_f16 cdf97 conv_mfma conv_f16x3 conv_wgrad_f16x3 cgp_fused cgp_f16x3 conv_bwd rans rans_gpu ztblock msssim residual quant; do
+for f in ops subband_mlp_f16 lifting lifting_f16 cdf97 conv_mfma conv_f16x3 conv_wgrad_f16x3 cgp_fused cgp_f16x3 conv_bwd rans rans_gpu ztblock msssim residual quant; do
   [ -f "$HERE/$f.hip" ] || continue
   EXTRA=""
   # the 36-unit chunk loop of the split-fp16 conv must unroll completely (register rings indexed by the unit number)
   [ "$f" = conv_f16x3 ] && EXTRA="-mllvm -pragma-unroll-threshold=131072"
+  # the subband MLP is bound by vector issue beside MFMAs, where packed fp32 (v_pk_fma_f32 from the SLP vectoriser) costs more
+  # than the two scalar instructions it replaces (measured: 3 % of the kernel)
+  [ "$f" = subband_mlp_f16 ] && EXTRA="-fno-slp-vectorize"
   key="$( (cat "$HERE/$f.hip" $HDRS; echo "$HIPCC $FLAGS $EXTRA") | sha1sum | cut -d' ' -f1)"
   if [ "$FORCE" = 1 ] || [ ! -f "$HERE/obj/$f.o" ] || [ "$(cat "$HERE/obj/$f.key" 2>/dev/null)" != "$key" ]; then
     rm -f "$HERE/obj/$f.key"

@@ -103,9 +103,11 @@ def ae_planes(aes, x, decode):
     if isinstance(aes[0], SubbandAutoEncoder):
         convs = [[s[n] for s in seq] for n in (0, 2, 4, 6)]
         srcs = [p for layer in convs for m in layer for p in (m.weight, m.bias)]
-        ws = cached(own, tag, srcs, lambda: [t for layer in convs for t in (
-            _stack(layer, lambda m: m.weight).flatten(1), _stack(layer, lambda m: m.bias))])
-        return ops.subband_mlp(x, *ws, transposed=decode, hidden=aes[0].H)
+        def build():
+            ws = [t for layer in convs for t in (_stack(layer, lambda m: m.weight).flatten(1), _stack(layer, lambda m: m.bias))]
+            return ws, ops.subband_mlp_pack(*ws, transposed=decode, hidden=aes[0].H)
+        ws, pack = cached(own, tag, srcs, build)
+        return ops.subband_mlp(x, *ws, transposed=decode, hidden=aes[0].H, pack=pack)
     t = x
     for n in (0, 2, 4, 6):
         layer = [s[n] for s in seq]

@@ -459,13 +459,29 @@ def cdf97_inverse(ll, yh, adj=False):
     return x
 
 
-def subband_mlp(x, w0, b0, w1, b1, w2, b2, w3, b3, transposed=False, hidden=32):
-    """SubbandAutoEncoder encode/decode (lifting_dwt_nets.py:99-110); x: (P,B,C,h,w), weights stacked (P,...)."""
+def subband_mlp_pack(w0, b0, w1, b1, w2, b2, w3, b3, transposed=False, hidden=32):
+    """The operand pack of subband_mlp (lldwt_subband_mlp_pack): weights stacked (P,...) in Conv2d layout, or in
+    ConvTranspose2d layout with transposed=True -> uint8 device tensor, valid until a weight changes."""
+    lib = _lib.load()
+    P, Cc = b3.shape
+    nb = lib.lldwt_subband_mlp_packed_bytes(P, Cc)
+    pack = torch.empty(nb, dtype=torch.uint8, device=w0.device)
+    check(lib.lldwt_subband_mlp_pack(_chk(w0), _chk(b0), _chk(w1), _chk(b1), _chk(w2), _chk(b2), _chk(w3), _chk(b3), P, Cc,
+                                     hidden, int(bool(transposed)), C.c_void_p(pack.data_ptr()), nb, _stream()),
+          "subband_mlp_pack")
+    return pack
+
+
+def subband_mlp(x, w0, b0, w1, b1, w2, b2, w3, b3, transposed=False, hidden=32, pack=None):
+    """SubbandAutoEncoder encode/decode (lifting_dwt_nets.py:99-110); x: (P,B,C,h,w), weights stacked (P,...).  ``pack``: the
+    subband_mlp_pack of these weights when the caller keeps one (ae_planes does); built here otherwise."""
     lib = _lib.load()
     P, B, Cc, h, w = x.shape
+    if pack is None:
+        pack = subband_mlp_pack(w0, b0, w1, b1, w2, b2, w3, b3, transposed=transposed, hidden=hidden)
     y = torch.empty_like(x)
-    check(lib.lldwt_subband_mlp(_chk(x, "x"), _chk(y), P, B, Cc, h * w, hidden, _chk(w0), _chk(b0), _chk(w1), _chk(b1),
-                                _chk(w2), _chk(b2), _chk(w3), _chk(b3), int(bool(transposed)), _stream()), "subband_mlp")
+    check(lib.lldwt_subband_mlp(_chk(x, "x"), _chk(y), P, B, Cc, h * w, hidden, C.c_void_p(pack.data_ptr()), pack.numel(),
+                                _stream()), "subband_mlp")
     return y
 
 

@@ -285,10 +285,21 @@ int lldwt_lift_step_bwd_f16(lldwt_view g_dst_out, lldwt_view g_dst_in, lldwt_vie
  * SubbandAutoEncoder (lifting_dwt_nets.py:99-110): per-coefficient scalar MLP 1 -> Hd -> Hd -> Hd -> 1, tanh
  * between, grouped 1x1 convs (groups == channels).  x,y: (Z,C,h,w).  Parameters per plane, PyTorch layouts:
  *   encode: w0 (C*Hd,1) b0 (C*Hd)  w1,w2 (C*Hd,Hd) b1,b2 (C*Hd)  w3 (C,Hd) b3 (C)         [Conv2d]
- *   decode: ConvTranspose2d weights (in, out/groups): w0 (C,Hd) w1,w2 (C*Hd,Hd) w3 (C*Hd,1); transposed != 0. */
-int lldwt_subband_mlp(const float* x, float* y, int64_t planes, int64_t batch, int C, int64_t hw, int Hd,
-                      const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
-                      const float* b2, const float* w3, const float* b3, int transposed, void* stream);
+ *   decode: ConvTranspose2d weights (in, out/groups): w0 (C,Hd) w1,w2 (C*Hd,Hd) w3 (C*Hd,1); transposed != 0.
+ * The forward reads the parameters from a pack that lldwt_subband_mlp_pack builds from either orientation (once per weight
+ * update; lldwt_subband_mlp_packed_bytes sizes it, 16-byte aligned): per (plane, channel) the two Hd x Hd layers as split-fp16
+ * MFMA fragments (hi, lo) in the kernel's lane order, each layer multiplied by s = 2^k with max|W| * s in [2^14, 2^15), then
+ * w0, b0, b1, b2, w3 in the lane's channel order, then s_1, s_2, 1/(s_1 2^14), 1/(s_2 2^14), b3 (csrc/subband_mlp_f16.hip
+ * states the layout word by word).  k is clamped to [-113, 112]: every finite max|W| >= 2^-97 gets its exact scale, a smaller
+ * layer (all-zero included: s = 1) keeps an absolute error below 2^-118 per weight, and a non-finite weight gives a finite
+ * scale and non-finite outputs, as it does in fp32.  The hidden layers run as hi*hi + hi*lo + lo*hi on the fp16 matrix cores
+ * with fp32 accumulation whatever lldwt_set_precision says; layers 0 and 3 are fp32. */
+int64_t lldwt_subband_mlp_packed_bytes(int64_t planes, int C);
+int lldwt_subband_mlp_pack(const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* w3, const float* b3, int64_t planes, int C, int Hd, int transposed,
+                           void* pack, int64_t pack_bytes, void* stream);
+int lldwt_subband_mlp(const float* x, float* y, int64_t planes, int64_t batch, int C, int64_t hw, int Hd, const void* pack,
+                      int64_t pack_bytes, void* stream);
 /* Backward of the encode-layout MLP (training; replaces autograd through lifting_dwt_nets.py:99-104 / :105-110 once the
  * decoder's ConvTranspose2d weights are viewed in Conv2d layout): recomputes the forward, returns gx (Z,C,hw) and, for
  * the four weight-gradient GEMMs (lldwt_conv2d_wgrad, groups == C), the activations h0,h1,h2 and the pre-activation
