@@ -727,6 +727,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int oc = ocw + (q & 3) + 8 * (q >> 2) + och;
             bq[q] = a.bias ? a.bias[plane * a.cout + (oc < a.cout ? oc : a.cout - 1)] : 0.f;
         }
+        // every bias register is used once HERE, in code all lanes run: the wait for the loads lands in front of the first store.
+        // Without it the first use of bq[q] sits in a block only some lanes run (oc < cout), where the wait counters are
+        // conservative: vmcnt(0) per q, which also waits for the eight stores of the q before to be acknowledged
+#pragma unroll
+        for (int q = 0; q < 16; ++q) asm volatile("" ::"v"(bq[q]));
         const bool full = y0 + F3_TH <= h && x0 + F3_TW <= w;                            // uniform
         if (full && a.act != LLDWT_ACT_TANH) {
             const float slope = a.act == LLDWT_ACT_LRELU ? 0.01f : (a.act == LLDWT_ACT_RELU ? 0.f : 1.f);   // none: max(v, v)
@@ -796,7 +801,9 @@ constexpr int W3_DUMP = 2 * W3_BUF;              // 64-byte slot: dead conv1 row
 constexpr int W3_COLP = 144;                     // im2col pitch
 constexpr int W3_COL = W3_DUMP + 64;
 constexpr int W3_PP = W3_COL + 2 * F3_IH * 17 * W3_COLP;   // parent patch (F1_PP floats)
-constexpr int W3_LDS = W3_PP + 1536;             // 132,480 B
+constexpr int W3_BIAS = W3_PP + 1536;            // the workgroup's 128 output biases (zero without bias or beyond cout)
+constexpr int W3_LDS = W3_BIAS + F3_OCB * 4;     // 132,992 B
+constexpr int W3_LDS_EARLIER = W3_BIAS;          // the earlier form has no bias image
 constexpr int W3_RING = 6;                       // weight steps in flight + 1 (12 % W3_RING == 0: the ring slot of a unit is
                                                  // the same in every chunk)
 static_assert(12 % W3_RING == 0 && W3_RING <= 6, "weight ring");
@@ -879,6 +886,11 @@ __global__ void k_f3w_pack(const float* __restrict__ w, uint8_t* __restrict__ pa
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[0] = (float)su;
 }
 
+// EARLIER (lldwt_set_diagnostics kind 1, flags bit 0; tools/plc_stamps.py and tests/test_gpu_plc_wino_sched.py): the kernel as it
+// was before its epilogue stopped waiting between stores and before the first conv's ACT / STORE work was dealt over the units in
+// pieces -- the A/B leg and the bit-equality reference.  Same arithmetic per value and same MFMA order per accumulator in both
+// forms: the outputs are equal bit for bit.
+template <bool EARLIER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_plc_wino(F3Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -915,6 +927,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         b1r = *reinterpret_cast<const f4_t*>(bias1 + (C1) + 4 * (lane >> 4));                                        \
     }
     W3_FUSED_LOAD(0)
+    // the second conv's bias goes through LDS: loaded here, its latency under the prologue; read back before the epilogue's first
+    // store by an LDS read, which no store of the epilogue counts against
+    float bias2 = 0.f;
+    if constexpr (!EARLIER) {
+        const int oc = ocb * F3_OCB + tid;
+        if (tid < F3_OCB && a.bias && oc < a.cout) bias2 = a.bias[plane * a.cout + oc];
+    }
 
     // ---- the parent patch (as in the direct kernel), then its split im2col for every patch pixel, once per tile
     const int hp = h >> 1, wp_ = w >> 1;
@@ -966,6 +985,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int p = lane & 15, g = lane >> 4;
     int colw[3], vw[3];
     unsigned pinm = 0;                 // bit 4*B + s: pixel 2p + s of row B inside the image
+    bool pin[3][4];                    // the same as twelve conditions: they stay in scalar registers as lane masks over the loop
 #pragma unroll
     for (int B = 0; B < 3; ++B) {
         const int r = wave + 4 * B;
@@ -977,7 +997,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int gx = x0 - 1 + 2 * p + s;
-            if (live && gy >= 0 && gy < h && gx >= 0 && gx < w) pinm |= 1u << (4 * B + s);
+            pin[B][s] = live && gy >= 0 && gy < h && gx >= 0 && gx < w;
+            if (pin[B][s]) pinm |= 1u << (4 * B + s);
         }
     }
     // row B of the first conv for channels C1 .. C1+15 on the 4 shifted pixel sets, in four stages that run in consecutive
@@ -1020,6 +1041,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             *reinterpret_cast<h4_t*>(d0_ + xi * xs_ + lo_) = lo4_;                                                    \
         }                                                                                                             \
     }
+    if constexpr (!EARLIER) {
+        if (tid < F3_OCB) reinterpret_cast<float*>(lds + W3_BIAS)[tid] = bias2;
+    }
+    // ACT and STORE in pieces (one shifted pixel set, one xi), which the chunk loop deals over its units: value for value what the
+    // whole-row stages compute.  xi = 0 needs the sets 0, 2; xi = 1, 2 the sets 1, 2; xi = 3 the sets 1, 3
+#define W3_ROW_ACT1(B, S)                                                                                             \
+    {                                                                                                                 \
+        if ((B) == 0 && (S) == 0) b1v = b1r * sx;                                                                     \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                               \
+            const float v_ = __builtin_fmaf(t1[S][q], inv1sx, b1v[q]);                                                \
+            d1[S][q] = pin[B][S] ? fmaxf(v_, 0.01f * v_) : 0.f;                                                       \
+        }                                                                                                             \
+    }
+#define W3_ROW_STORE1(B, DST, XI)                                                                                     \
+    {                                                                                                                 \
+        const bool livev_ = vw[B] >= 0;                                                                               \
+        uint8_t* d0_ = livev_ ? (DST) + vw[B] : lds + W3_DUMP;                                                        \
+        const int xs_ = livev_ ? 16 * 32 : 0, lo_ = livev_ ? W3_PART : 8;                                             \
+        float v4_[4];                                                                                                 \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                                 \
+            v4_[q] = (XI) == 0 ? d1[0][q] - d1[2][q] : (XI) == 1 ? d1[1][q] + d1[2][q]                                \
+                   : (XI) == 2 ? d1[2][q] - d1[1][q] : d1[1][q] - d1[3][q];                                           \
+        h4_t hi_, lo4_;                                                                                               \
+        split4v(v4_, hi_, lo4_);                                                                                      \
+        *reinterpret_cast<h4_t*>(d0_ + (XI) * xs_) = hi_;                                                             \
+        *reinterpret_cast<h4_t*>(d0_ + (XI) * xs_ + lo_) = lo4_;                                                      \
+    }
     __syncthreads();                   // the im2col is read across lanes
 
     floatx16 acc[4][4];                // [xi][N-tile]
@@ -1044,8 +1092,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     F3_STAMP(1)
     // Per chunk: 12 units (dy, xi), 12 MFMAs each (384 matrix cycles); interleaved between them as in the direct kernel: the
     // 8 fragment reads of unit u+1, the weight step u+5 (ring of 6, continuous across chunks, pack padded by 5 steps), the
-    // next chunk's first-conv operands (unit 0) and its three rows into the idle buffer, each row over four units (READ at
-    // 2, 5, 8; MMA at 3, 6, 9; ACT at 4, 7, 10; STORE at 5, 8, 11).  One barrier per chunk.
+    // next chunk's first-conv operands (unit 0) and its three rows into the idle buffer: READ at 2, 3, 6, MMA at 3, 6, 8, the ACT
+    // and STORE pieces over units 4 .. 11 (EARLIER: each row over four units, READ at 2, 5, 8; MMA at 3, 6, 9; ACT at 4, 7, 10;
+    // STORE at 5, 8, 11).  One barrier per chunk.
     for (int chunk = 0; chunk < a.nch; ++chunk) {
         if (chunk < 16 && !(chunk & 1)) F3_STAMP(2 + (chunk >> 1))
         const int buf = chunk & 1;
@@ -1073,10 +1122,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             al[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES + 1024);
             if (u + 1 < W3_NST) W3_BLOAD(u + 1, (u + 1) & 1)
             if (u == 0) W3_FUSED_LOAD(c1)
-            if (u == 2 || u == 5 || u == 8) W3_ROW_READ((u - 2) / 3)
-            if (u == 3 || u == 6 || u == 9) W3_ROW_MMA()
-            if (u == 4 || u == 7 || u == 10) W3_ROW_ACT((u - 4) / 3)
-            if (u == 5 || u == 8 || u == 11) W3_ROW_STORE((u - 5) / 3, sdst)
+            if constexpr (EARLIER) {
+                if (u == 2 || u == 5 || u == 8) W3_ROW_READ((u - 2) / 3)
+                if (u == 3 || u == 6 || u == 9) W3_ROW_MMA()
+                if (u == 4 || u == 7 || u == 10) W3_ROW_ACT((u - 4) / 3)
+                if (u == 5 || u == 8 || u == 11) W3_ROW_STORE((u - 5) / 3, sdst)
+            } else {
+                // The 24 ACT / STORE pieces of the three rows dealt over units 4 .. 11, at most 56 vector instructions a unit; a
+                // row's READ rides in the unit of the row before's MMA (the fragment registers are free from there).  In program
+                // order every piece follows the MMA it reads and precedes the MMA or ACT piece that overwrites what it reads.
+                if (u == 2) W3_ROW_READ(0)
+                if (u == 3) { W3_ROW_MMA() W3_ROW_READ(1) }
+                if (u == 4) { W3_ROW_ACT1(0, 0) W3_ROW_ACT1(0, 2) W3_ROW_STORE1(0, sdst, 0) }
+                if (u == 5) { W3_ROW_ACT1(0, 1) W3_ROW_STORE1(0, sdst, 1) W3_ROW_STORE1(0, sdst, 2) }
+                if (u == 6) { W3_ROW_ACT1(0, 3) W3_ROW_STORE1(0, sdst, 3) W3_ROW_MMA() W3_ROW_READ(2) }
+                if (u == 7) { W3_ROW_ACT1(1, 0) W3_ROW_ACT1(1, 2) W3_ROW_STORE1(1, sdst, 0) }
+                if (u == 8) { W3_ROW_ACT1(1, 1) W3_ROW_ACT1(1, 3) W3_ROW_STORE1(1, sdst, 1) W3_ROW_MMA() }
+                if (u == 9) { W3_ROW_STORE1(1, sdst, 2) W3_ROW_STORE1(1, sdst, 3) W3_ROW_ACT1(2, 0) }
+                if (u == 10) { W3_ROW_ACT1(2, 2) W3_ROW_STORE1(2, sdst, 0) W3_ROW_ACT1(2, 1) }
+                if (u == 11) { W3_ROW_STORE1(2, sdst, 1) W3_ROW_STORE1(2, sdst, 2) W3_ROW_ACT1(2, 3) W3_ROW_STORE1(2, sdst, 3) }
+            }
             const half8 A_h = ah[u % W3_RING], A_l = al[u % W3_RING];
             // product-major: the three MFMAs of one accumulator are 4 apart (no back-to-back dependent pair)
 #pragma unroll
@@ -1090,7 +1155,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // one MFMA
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        // one LDS read
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                        // one global load
-                __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);                        // a few vector ALU instructions
+                // a gap has 24 free issue cycles beside its MFMA: four vector instructions beside an LDS read, six without one
+                // (the eight fragment reads of the next unit take the first eight gaps; unit 11 has none)
+                if constexpr (EARLIER) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+                else if (u == 11 || i >= 8) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                        // one LDS write
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1102,6 +1171,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W3_ROW_MMA
 #undef W3_ROW_ACT
 #undef W3_ROW_STORE
+#undef W3_ROW_ACT1
+#undef W3_ROW_STORE1
 #undef W3_FUSED_LOAD
 
     F3_STAMP(10)
@@ -1113,6 +1184,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float* ybase = a.y + (z * a.cout + ocw) * hw + (int64_t)y0 * w;                  // wave-uniform
     const unsigned loff = (unsigned)och * (unsigned)hw + (unsigned)(orow * w + x0 + 2 * p);
     const bool full = y0 + F3_TH <= h && x0 + F3_TW <= w;                            // uniform
+    if constexpr (EARLIER) {
     // the activation and the bounds resolved outside the store loops (as in the direct kernel's epilogue)
 #define W3_EPI(COND, ACT0, ACT1)                                                                                      \
     _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                                  \
@@ -1135,6 +1207,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         W3_EPI(colin && y0 + 2 * n + orow < h, act_apply(v0, a.act), act_apply(v1, a.act))
     }
 #undef W3_EPI
+    } else {
+    // The 16 bias values of the lane are in registers before the first store, read from the LDS image the prologue wrote.  A bias
+    // load from global memory BETWEEN the stores stays behind them (a.bias may alias a.y for all the compiler knows), and vmcnt
+    // counts loads and stores in issue order: every wait for a bias value was a wait for the stores in front of it to be
+    // acknowledged, 16 store round trips in sequence.  Global loads hoisted in front of the stores do not cure it: a channel
+    // block only some lanes run (oc < cout) makes the wait counters conservative, and the first use of each bias register in
+    // such a block waits for vmcnt(0) again.  An LDS read counts on lgkmcnt, which no store touches.
+    float bq[16];
+    {
+        const f4_t* bl = reinterpret_cast<const f4_t*>(lds + W3_BIAS + (__builtin_amdgcn_readfirstlane(wave) * 32 + och) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f4_t b4 = bl[2 * k];                  // channels 8k + och .. + 3 of the wave's 32: q = 4k .. 4k + 3
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bq[4 * k + j] = b4[j];
+        }
+    }
+    // the activation is resolved outside the store loops, one copy per activation and no branch per value: a block that only
+    // some lanes run (a partial tile's store) makes the wait counters conservative for whatever follows it
+#define W3_EPI(COND, ACT0, ACT1)                                                                                      \
+    _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                                  \
+        const int ocq = (q & 3) + 8 * (q >> 2);                                                                       \
+        if (ocw + ocq + och < a.cout) {                                                                               \
+            float* yq = ybase + (int64_t)ocq * hw + loff;                                                             \
+            _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                                           \
+                const float v0 = (acc[0][n][q] + acc[1][n][q] + acc[2][n][q]) * out_scale + bq[q];                    \
+                const float v1 = (acc[1][n][q] - acc[2][n][q] - acc[3][n][q]) * out_scale + bq[q];                    \
+                if (COND) *reinterpret_cast<f2_t*>(yq + 2 * n * w) = f2_t{ACT0, ACT1};                                \
+            }                                                                                                         \
+        }                                                                                                             \
+    }
+    if (full && a.act != LLDWT_ACT_TANH) {
+        const float slope = a.act == LLDWT_ACT_LRELU ? 0.01f : (a.act == LLDWT_ACT_RELU ? 0.f : 1.f);   // none: max(v, v)
+        W3_EPI(true, fmaxf(v0, v0 * slope), fmaxf(v1, v1 * slope))
+    } else {
+        const bool colin = x0 + 2 * p < w;        // w is even: a pair is either inside the image or wholly outside it
+#define W3_IN (colin && y0 + 2 * n + orow < h)
+        // the four cases of act_apply, value for value
+        if (a.act == LLDWT_ACT_TANH) {
+            W3_EPI(W3_IN, fast_tanh(v0), fast_tanh(v1))
+        } else if (a.act == LLDWT_ACT_LRELU) {
+            W3_EPI(W3_IN, v0 >= 0.f ? v0 : 0.01f * v0, v1 >= 0.f ? v1 : 0.01f * v1)
+        } else if (a.act == LLDWT_ACT_RELU) {
+            W3_EPI(W3_IN, v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f)
+        } else {
+            W3_EPI(W3_IN, v0, v1)
+        }
+#undef W3_IN
+    }
+#undef W3_EPI
+    }
     F3_STAMP(11)
     F3_STAMP(15)
 }
@@ -1285,6 +1408,9 @@ extern "C" int lldwt_plc_fused_pack1(const float* w1, const float* b1, void* pac
 static unsigned long long* g_f3_stamps = nullptr;
 static int64_t g_f3_stamps_bytes = 0;
 namespace lldwt { void f3_set_stamps(void* p, int64_t nbytes) { g_f3_stamps = reinterpret_cast<unsigned long long*>(p); g_f3_stamps_bytes = p ? nbytes : 0; } }
+// diagnostics flags of the pair (lldwt_set_diagnostics kind 1; read per launch): bit 0 = k_plc_wino in its earlier form
+static int g_f3_flags = 0;
+namespace lldwt { void f3_set_debug(int flags) { g_f3_flags = flags; } }
 
 extern "C" int lldwt_plc_fused(const float* parent, float* y, const void* packed1, const void* packed2, const float* bias2,
                                int cmid, int cout, int act, int64_t planes, int64_t batch, int64_t h, int64_t w_, void* stream) {
@@ -1324,14 +1450,16 @@ extern "C" int lldwt_plc_fused(const float* parent, float* y, const void* packed
     if (prec == 0 && plc_wino_active()) {
         static bool wattr_set = false;
         if (!wattr_set) {
-            if (hipFuncSetAttribute((const void*)k_plc_wino, hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS) != hipSuccess) {
+            if (hipFuncSetAttribute((const void*)k_plc_wino<false>, hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS) != hipSuccess ||
+                hipFuncSetAttribute((const void*)k_plc_wino<true>, hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_EARLIER) != hipSuccess) {
                 set_error("plc_fused: cannot reserve %d bytes of LDS", W3_LDS);
                 return LLDWT_EHIP;
             }
             wattr_set = true;
         }
         a.nch = w3_nch(cmid);
-        hipLaunchKernelGGL(k_plc_wino, grid, dim3(256), W3_LDS, (hipStream_t)stream, a);
+        if (g_f3_flags & 1) hipLaunchKernelGGL(k_plc_wino<true>, grid, dim3(256), W3_LDS_EARLIER, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(k_plc_wino<false>, grid, dim3(256), W3_LDS, (hipStream_t)stream, a);
     } else if (g_f3_shape16) {
         if (prec == 1) hipLaunchKernelGGL((k_conv3_f16x3<2, 1, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);
         else if (prec == 2) hipLaunchKernelGGL((k_conv3_f16x3<2, 2, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);

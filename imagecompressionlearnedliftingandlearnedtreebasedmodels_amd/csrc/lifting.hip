@@ -1487,6 +1487,7 @@ extern "C" int lldwt_set_precision(int prec) {
 extern "C" int lldwt_get_precision(void) { return split_precision(); }
 
 namespace lldwt { void cgp16_set_debug(int flags); }    // cgp_f16x3.hip: bound-only variants / forced form of the eval chain
+namespace lldwt { void f3_set_debug(int flags); }       // conv_f16x3.hip: bit 0 = k_plc_wino in its earlier form (same output bits)
 
 extern "C" int lldwt_set_diagnostics(int kind, void* stamps, int64_t nbytes, int flags) {
     LLDWT_REQUIRE(kind >= 0 && kind <= 2, "set_diagnostics: kind %d (0 = fused lifting step, 1 = tree-pair conv, 2 = cgp chain)", kind);
@@ -1496,6 +1497,7 @@ extern "C" int lldwt_set_diagnostics(int kind, void* stamps, int64_t nbytes, int
         lift_f16_set_debug(flags);
     } else if (kind == 1) {
         f3_set_stamps(stamps, nbytes);
+        f3_set_debug(flags);
     } else {
         cgp16_set_stamps(stamps, nbytes);
         cgp16_set_debug(flags);

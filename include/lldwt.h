@@ -149,6 +149,9 @@ int lldwt_get_precision(void);
  * 16 = sequential conv3 / conv4 for every tile (the check of the composed 9x9 kernel), 32 = no vertical reuse
  * between the tiles of a column, 64 = the border tiles' strip correction in its earlier form (every k-step of the strip
  * convolutions, half a wave per corrected pixel): same output bits, kept for A/B timing and as a test reference.
+ * flags, kind 1: bit 0 = the Winograd pair kernel (k_plc_wino) in its earlier form -- the epilogue that loads each bias value
+ * between the stores and waits for them, the first conv's ACT and STORE stages whole inside one unit of the chunk loop, eight
+ * vector instructions offered per MFMA gap: same output bits, kept for A/B timing (tools/plc_stamps.py) and as a test reference.
  * flags, kind 2 (lldwt_cgp16_params only): bits 0-1 = bound-only variant of the streaming
  * chain, timing only (1 = every step reads step 0's weight fragments, 2 = constant inputs; results are then wrong),
  * bits 2-3 = force a form whatever the size (1 << 2 = streaming, 2 << 2 = persistent; 0 = the dispatch's choice, which

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Diagnostic: in-kernel clock stamps (s_memtime) of the fused tree-context pair (k_conv3_f16x3<2>) at the level-0 shape of
 BASELINE configs[2] (3 planes x 8 images, parent 128 x 128 -> 243 channels at 256 x 256).  The kernel writes stamps only
-when a stamp buffer is registered through lldwt_set_diagnostics (this tool).   python tools/plc_stamps.py"""
+when a stamp buffer is registered through lldwt_set_diagnostics (this tool).  Two legs: the kernel as it is, and k_plc_wino in its
+earlier form (diagnostics flag 1); per leg the prologue, the cycles per 32 channels and what of them is not matrix time, the
+epilogue, the in-kernel clock and the workgroup's cycles.   python tools/plc_stamps.py"""
 import json
 import os
 import sys
@@ -27,37 +29,56 @@ def main():
 
     def run():
         return ops.plc_fused(parent, pk1, pk2, b2, C, C)
-    for _ in range(100):
-        run()
-    torch.cuda.synchronize()
     nwg = (S // 32) * (S // 8) * 2 * P * B
-    st = torch.zeros(nwg, 4, 16, dtype=torch.int64, device=dev)
-    ops.set_diagnostics(1, st)
-    run()
-    torch.cuda.synchronize()
-    ops.set_diagnostics(1, None)
-    s = st.cpu().numpy().astype(np.int64)
-    # k_plc_wino (the default, ops.plc_algo() == "winograd") stamps every second of its 16-channel chunks: a "chunk" below is 32
-    # channels either way; ideal_cycles_per_chunk is the direct kernel's
-    res = {"workgroups": nwg, "algo": ops.plc_algo()}
-    d = np.diff(s[..., :12], axis=-1)
-    names = ["prologue (gather, scales, chunk 0 staging, ring fill)"] + ["chunk %d" % i for i in range(8)] + ["epilogue stores"]
-    cols = [0] + list(range(1, 9)) + [10 - 0]
-    res["mean_cycles_per_wave"] = {"prologue": float(d[..., 0].mean()), "chunks": [float(d[..., 1 + i].mean()) for i in range(8)],
-                                   "last chunk -> loop end": float(d[..., 9].mean()), "epilogue": float(d[..., 10].mean())}
-    res["ideal_cycles_per_chunk"] = 36 * 12 * 32 + 18 * 32
-    tot = s[..., 11] - s[..., 0]
-    real = (s[..., 15] - s[..., 14]).astype(np.float64)
-    ok = real > 0
-    res["total_cycles_mean"] = float(tot.mean())
-    res["in_kernel_clock_GHz"] = float(np.median(tot[ok] / real[ok]) * 0.1)
-    res["wg_duration_us_median"] = float(np.median(real[ok]) / 100.0)
-    t0, t1 = s[..., 14].min(), s[..., 15].max()
-    res["launch_span_us"] = float((t1 - t0) / 100.0)
-    res["sum_wg_duration_over_span_per_cu"] = float(((s[:, 0, 15] - s[:, 0, 14]).sum() / 100.0) / ((t1 - t0) / 100.0) / 256)
-    res["wave_skew_at_loop_end_cycles"] = float((s[..., 10].max(axis=-1) - s[..., 10].min(axis=-1)).mean())
-    print(json.dumps(res, indent=1))
+    wino = ops.plc_algo() == "winograd"
+    # matrix cycles of 32 channels: the direct kernel's 36 x 12 MFMAs of 32 cycles + 18 of the first conv; k_plc_wino's two
+    # 16-channel chunks of 144 x 32 + 36 x 16
+    matrix = 2 * (144 * 32 + 36 * 16) if wino else 36 * 12 * 32 + 18 * 32
 
+    def leg(flags):
+        for _ in range(100):
+            run()
+        torch.cuda.synchronize()
+        st = torch.zeros(nwg, 4, 16, dtype=torch.int64, device=dev)
+        ops.set_diagnostics(1, st, flags=flags)
+        try:
+            run()
+            torch.cuda.synchronize()
+        finally:
+            ops.set_diagnostics(1, None)
+        s = st.cpu().numpy().astype(np.int64)
+        # k_plc_wino (the default, ops.plc_algo() == "winograd") stamps every second of its 16-channel chunks: a "chunk" below is
+        # 32 channels either way
+        res = {"workgroups": nwg, "algo": ops.plc_algo(), "flags": flags}
+        d = np.diff(s[..., :12], axis=-1)
+        chunks = [float(d[..., 1 + i].mean()) for i in range(8)]
+        res["mean_cycles_per_wave"] = {"prologue": float(d[..., 0].mean()), "chunks": chunks,
+                                       "last chunk -> loop end": float(d[..., 9].mean()), "epilogue": float(d[..., 10].mean())}
+        res["matrix_cycles_per_32_channels"] = matrix
+        # stamp 1 sits at the loop's entry and stamp 2 right behind it: chunks[0] is empty, chunks[1:] are seven spans of 32 channels
+        res["cycles_per_32_channels"] = float(np.mean(chunks[1:]))
+        res["non_matrix_cycles_per_32_channels"] = float(np.mean(chunks[1:])) - matrix
+        tot = s[..., 11] - s[..., 0]
+        real = (s[..., 15] - s[..., 14]).astype(np.float64)
+        ok = real > 0
+        res["total_cycles_mean"] = float(tot.mean())
+        res["in_kernel_clock_GHz"] = float(np.median(tot[ok] / real[ok]) * 0.1)
+        res["wg_duration_us_median"] = float(np.median(real[ok]) / 100.0)
+        t0, t1 = s[..., 14].min(), s[..., 15].max()
+        res["launch_span_us"] = float((t1 - t0) / 100.0)
+        res["sum_wg_duration_over_span_per_cu"] = float(((s[:, 0, 15] - s[:, 0, 14]).sum() / 100.0) / ((t1 - t0) / 100.0) / 256)
+        res["wave_skew_at_loop_end_cycles"] = float((s[..., 10].max(axis=-1) - s[..., 10].min(axis=-1)).mean())
+        return res
+
+    # the current form, then (diagnostics flag 1) k_plc_wino in its earlier form: the A/B leg.  The direct kernel has one form
+    legs = {"current": leg(0)}
+    if wino:
+        legs["earlier (flag 1)"] = leg(1)
+    for name, r in legs.items():
+        print("%-18s prologue %7.0f  per 32 channels %7.0f (non-matrix %6.0f)  epilogue %7.0f  workgroup %7.0f cycles  %.3f GHz" % (
+            name, r["mean_cycles_per_wave"]["prologue"], r["cycles_per_32_channels"], r["non_matrix_cycles_per_32_channels"],
+            r["mean_cycles_per_wave"]["epilogue"], r["total_cycles_mean"], r["in_kernel_clock_GHz"]), file=sys.stderr)
+    print(json.dumps(legs, indent=1))
 
 if __name__ == "__main__":
     main()
