@@ -788,10 +788,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 //   4 N-tiles x 3 products per chunk.
 //   V image in LDS: [10 patch rows][4 xi][16 pairs][16 ch] fp16, hi and lo, double-buffered (80 KB).  The 16-byte halves of
 //      an entry swap places on bit 3 of the pair index: each 16-lane group of a ds_read_b128 hits 16 distinct slots.
-//   The first conv (3 -> cmid, K = 27 -> 32) is RECOMPUTED on four pixel sets shifted by s = 0..3 (pixel 2p + s of pair p),
-//      so that d0..d3 of a pair land in one lane and V is lane-local arithmetic -- no cross-lane moves.  It runs on
-//      v_mfma_f32_16x16x32_f16 (16 channels x 16 pairs, K = 32 in one step): 4 shifts x 3 products per patch row, 10 patch
-//      rows per chunk (waves 0, 1 take three, waves 2, 3 two and one dead row).  Its B operand is the split im2col of the
+//   The first conv (3 -> cmid, K = 27 -> 32) runs on v_mfma_f32_16x16x32_f16 (16 channels x 16 pairs, K = 32 in one step) on the
+//      pixel sets s = 0, 1 (pixel 2p + s of pair p): 2 sets x 3 products per patch row, 10 patch rows per chunk (waves 0, 1 take three,
+//      waves 2, 3 two and one dead row).  V needs d0..d3 = the sets 0..3 of a pair in one lane: the sets 2, 3 are the neighbouring
+//      pair's sets 0, 1 and come from lane p + 1 by a DPP row shift behind the activation; pair 16, for lane 15, from one extra
+//      16-column tile per chunk and wave.  21 MFMAs per chunk and wave (the earlier form recomputed all four sets in every lane: 36).  Its B operand is the split im2col of the
 //      parent patch, built once per tile in LDS as [pixel parity][row][17 pixels] at a 144-byte pitch (9 slots: the 16
 //      pairs one read touches map to 16 distinct slots).
 constexpr int W3_NE = F3_IH * 4 * 16;            // V entries: 10 rows x 4 xi x 16 pairs = 640
@@ -830,6 +831,75 @@ __device__ __forceinline__ void w3_row_mma(f4_t (&t)[4], const h8_t& wh, const h
         "s_nop 7\n\ts_nop 7\n\ts_nop 4"
         : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
         : "v"(wl), "v"(wh), "v"(ch[0]), "v"(ch[1]), "v"(ch[2]), "v"(ch[3]), "v"(cl[0]), "v"(cl[1]), "v"(cl[2]), "v"(cl[3]));
+}
+
+// The same chains for two pixel sets (the current form computes every first-conv pixel once: sets 0 and 1 of a pair), and for two sets
+// plus the extra tile that holds pair 16 of the wave's rows.  Product order per accumulator as above; a dependent MFMA follows its
+// producer two (three) issues later, and the matrix pipe interlocks on a result taken whole as C.
+__device__ __forceinline__ void w3_row_mma2(f4_t& t0, f4_t& t1, const h8_t& wh, const h8_t& wl, const h8_t& ch0, const h8_t& ch1,
+                                            const h8_t& cl0, const h8_t& cl1) {
+    asm volatile(
+        "v_mfma_f32_16x16x32_f16 %0, %2, %4, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %2, %5, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %0, %3, %6, %0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %3, %7, %1\n\t"
+        "v_mfma_f32_16x16x32_f16 %0, %3, %4, %0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %3, %5, %1\n\t"
+        "s_nop 7\n\ts_nop 7\n\ts_nop 4"
+        : "=&v"(t0), "=&v"(t1)
+        : "v"(wl), "v"(wh), "v"(ch0), "v"(ch1), "v"(cl0), "v"(cl1));
+}
+__device__ __forceinline__ void w3_row_mma3(f4_t& t0, f4_t& t1, f4_t& t2, const h8_t& wh, const h8_t& wl, const h8_t& ch0,
+                                            const h8_t& ch1, const h8_t& ch2, const h8_t& cl0, const h8_t& cl1, const h8_t& cl2) {
+    asm volatile(
+        "v_mfma_f32_16x16x32_f16 %0, %3, %5, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %3, %6, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %2, %3, %7, 0\n\t"
+        "v_mfma_f32_16x16x32_f16 %0, %4, %8, %0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %4, %9, %1\n\t"
+        "v_mfma_f32_16x16x32_f16 %2, %4, %10, %2\n\t"
+        "v_mfma_f32_16x16x32_f16 %0, %4, %5, %0\n\t"
+        "v_mfma_f32_16x16x32_f16 %1, %4, %6, %1\n\t"
+        "v_mfma_f32_16x16x32_f16 %2, %4, %7, %2\n\t"
+        "s_nop 7\n\ts_nop 7\n\ts_nop 4"
+        : "=&v"(t0), "=&v"(t1), "=&v"(t2)
+        : "v"(wl), "v"(wh), "v"(ch0), "v"(ch1), "v"(ch2), "v"(cl0), "v"(cl1), "v"(cl2));
+}
+// a lane's value from another lane of its 16-lane row (v_mov_b32 with a DPP control); a lane whose source lies outside the row
+// keeps OLD (BOUND = false) or takes zero (BOUND = true).  0x101 = row_shl:1 (lane i reads lane i + 1), 0x110 + k = row_shr:k
+// (lane i reads lane i - k)
+template <int CTRL, bool BOUND>
+__device__ __forceinline__ float w3_dpp(float old, float src) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xf, 0xf, BOUND));
+}
+// split4v in plain C: the same bits (v - hi is exact in fp32, see split_f16.h), twelve vector instructions instead of six.  The pieces
+// of the chunk loop are placed between the MFMAs by sched_group_barrier, which sorts instructions by class and has no class for an
+// inline-assembly statement: the v_fma_mix forms and the LDS stores behind them gathered at the end of their unit, where nothing hid
+// them (measured per unit: a unit with three STORE pieces took 590 cycles more than one without, one with a single piece 80).
+__device__ __forceinline__ void w3_split4(const float (&v)[4], h4_t& hi, h4_t& lo) {
+    const f4_t x = {v[0], v[1], v[2], v[3]};
+    hi = __builtin_convertvector(x, h4_t);
+    lo = __builtin_convertvector(x - __builtin_convertvector(hi, f4_t), h4_t);
+}
+// k-group G (k = 8G .. 8G+7 of the first conv's K = 27 -> 32) of the split im2col for the patch pixels lane, lane + 64, ...: one
+// wave per k-group, so that the tap offsets are constants and all four waves stay busy over the 340 pixels
+template <int G>
+__device__ __forceinline__ void w3_im2col_group(uint8_t* lds, const float* PP, float s_p, int lane) {
+    for (int px = lane; px < F3_NPX; px += 64) {
+        const int ly = px / F3_IW, lx = px - ly * F3_IW;
+        uint8_t* dst = lds + W3_COL + ((lx & 1) * (F3_IH * 17) + ly * 17 + (lx >> 1)) * W3_COLP;
+        float v8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 8 * G + j, q = k < 27 ? k : 26;         // k >= 27 meets zero weights
+            const int dy = (q % 9) / 3, dx = q % 3;
+            v8[j] = PP[(q / 9) * 108 + ((ly + dy) >> 1) * 18 + ((lx + dx) >> 1)] * s_p;
+        }
+        half8 ch_, cl_;
+        split8v(v8, ch_, cl_);
+        *reinterpret_cast<half8*>(dst + G * 16) = ch_;
+        *reinterpret_cast<half8*>(dst + 64 + G * 16) = cl_;
+    }
 }
 
 __device__ __forceinline__ void wino_u(const float* g, double (&u)[4]) {
@@ -886,10 +956,11 @@ __global__ void k_f3w_pack(const float* __restrict__ w, uint8_t* __restrict__ pa
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[0] = (float)su;
 }
 
-// EARLIER (lldwt_set_diagnostics kind 1, flags bit 0; tools/plc_stamps.py and tests/test_gpu_plc_wino_sched.py): the kernel as it
-// was before its epilogue stopped waiting between stores and before the first conv's ACT / STORE work was dealt over the units in
-// pieces -- the A/B leg and the bit-equality reference.  Same arithmetic per value and same MFMA order per accumulator in both
-// forms: the outputs are equal bit for bit.
+// EARLIER (lldwt_set_diagnostics kind 1, flags bit 0; tools/plc_stamps.py, tests/test_gpu_plc_wino_sched.py and
+// tests/test_gpu_plc_wino_once.py): the kernel as it was before its epilogue stopped waiting between stores, before the first conv's
+// ACT / STORE work was dealt over the units in pieces and before the first conv ran once per pixel (four shifted pixel sets in every
+// lane, the im2col one pixel per thread, a barrier behind unit 11) -- the A/B leg and the bit-equality reference.  Same arithmetic
+// per value and same MFMA order per accumulator in both forms: the outputs are equal bit for bit.
 template <bool EARLIER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_plc_wino(F3Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -961,6 +1032,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const float sx = 0.5f * pow2_scale<15>(amax * h1[1] + h1[2]);
     const float out_scale = (1.f / sx) * (1.f / su);
     const float inv1sx = (1.f / s_p) * (1.f / h1[0]) * sx;
+    F3_STAMP(12)                       // prologue stamps: 0 .. 12 the parent patch and its |max|, 12 .. 13 the split im2col,
+                                       // 13 .. 2 the wait at its barrier, 2 .. 1 the chunk-0 rows and their barrier
+    if constexpr (EARLIER) {
     for (int px = tid; px < F3_NPX; px += 256) {
         const int ly = px / F3_IW, lx = px - ly * F3_IW;
         uint8_t* dst = lds + W3_COL + ((lx & 1) * (F3_IH * 17) + ly * 17 + (lx >> 1)) * W3_COLP;
@@ -977,6 +1051,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             split8v(v8, ch_, cl_);
             *reinterpret_cast<half8*>(dst + g * 16) = ch_;
             *reinterpret_cast<half8*>(dst + 64 + g * 16) = cl_;
+        }
+    }
+    } else {
+        // the same values over (pixel, k-group) tasks, 1 360 of them: wave w takes k-group w of every pixel, six passes of 64 pixels
+        // with all four waves busy (the pixel loop above: two passes of four groups in sequence, the second a third full)
+        switch (__builtin_amdgcn_readfirstlane(wave)) {
+            case 0: w3_im2col_group<0>(lds, PP, s_p, lane); break;
+            case 1: w3_im2col_group<1>(lds, PP, s_p, lane); break;
+            case 2: w3_im2col_group<2>(lds, PP, s_p, lane); break;
+            default: w3_im2col_group<3>(lds, PP, s_p, lane); break;
         }
     }
 
@@ -1001,6 +1085,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if (pin[B][s]) pinm |= 1u << (4 * B + s);
         }
     }
+    // The current form computes the sets 0 and 1 only: sets 2 and 3 of pair p are sets 0 and 1 of pair p + 1, the same dot products in
+    // the same k order, so lane p takes them from lane p + 1 of its 16-lane row (same g) after ACT.  Pair 16, which lane 15 needs, comes
+    // from one extra 16-column tile per chunk: column n = 2B + s < 6 is pixel 32 + s of the wave's row B (the im2col holds 17 pairs per
+    // row); columns 6 .. 15 repeat column 0 and are masked.  Its B fragments do not depend on the chunk: read once, kept in registers.
+    const int en = p < 6 ? p : 0, er = wave + 4 * (en >> 1);
+    const bool elive = p < 6 && er < F3_IH;
+    const int cole = W3_COL + (((en & 1) * F3_IH + (elive ? er : 0)) * 17 + 16) * W3_COLP + g * 16;
+    // the image mask of the extra tile's column as an AND mask (all ones inside the image): as a condition the compiler turns the
+    // four selects of the tile's ACT into branches, which split the unit's scheduling region
+    const int pine = (elive && y0 - 1 + er >= 0 && y0 - 1 + er < h && x0 + 31 + (en & 1) < w) ? -1 : 0;
     // row B of the first conv for channels C1 .. C1+15 on the 4 shifted pixel sets, in four stages that run in consecutive
     // units of the chunk loop (one wave per SIMD: nothing else hides an LDS read, an MFMA result or a block of vector
     // instructions): READ the im2col fragments, MMA, ACT = bias + LeakyReLU, STORE = V (4 xi) -> split -> the LDS image at DST
@@ -1044,103 +1138,171 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if constexpr (!EARLIER) {
         if (tid < F3_OCB) reinterpret_cast<float*>(lds + W3_BIAS)[tid] = bias2;
     }
-    // ACT and STORE in pieces (one shifted pixel set, one xi), which the chunk loop deals over its units: value for value what the
-    // whole-row stages compute.  xi = 0 needs the sets 0, 2; xi = 1, 2 the sets 1, 2; xi = 3 the sets 1, 3
-#define W3_ROW_ACT1(B, S)                                                                                             \
+    // The current form's pieces, which the chunk loop deals over its units; every row has registers of its own (what is live is what
+    // the order of the pieces makes live).  READ2 the two sets' im2col fragments; MMA2 / MMA3 (row 0 with the extra tile); ACT2 = bias +
+    // LeakyReLU + image mask of one set, once per pixel; SHIFT = sets 2, 3 from lane p + 1 (lane 15: from column 2B + s of the extra
+    // tile, moved there by a row shift of 15 - 2B - s lanes); STORE2 = one xi of V -> split -> the LDS image at DST.  Value for value what
+    // the whole-row stages compute: xi = 0 needs the sets 0, 2; xi = 1, 2 the sets 1, 2; xi = 3 the sets 1, 3
+    half8 c2h[3][2], c2l[3][2], ceh, cel;
+    f4_t t2[3][2], te;
+    float d2[3][4][4], de[4];
+#define W3_ROW_READ2(B)                                                                                               \
     {                                                                                                                 \
-        if ((B) == 0 && (S) == 0) b1v = b1r * sx;                                                                     \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                               \
-            const float v_ = __builtin_fmaf(t1[S][q], inv1sx, b1v[q]);                                                \
-            d1[S][q] = pin[B][S] ? fmaxf(v_, 0.01f * v_) : 0.f;                                                       \
+        _Pragma("unroll") for (int s = 0; s < 2; ++s) {                                                               \
+            const uint8_t* c_ = lds + colw[B] + s * (F3_IH * 17) * W3_COLP;                                           \
+            c2h[B][s] = *reinterpret_cast<const half8*>(c_);                                                          \
+            c2l[B][s] = *reinterpret_cast<const half8*>(c_ + 64);                                                     \
         }                                                                                                             \
     }
-#define W3_ROW_STORE1(B, DST, XI)                                                                                     \
+#define W3_ROW_MMA2(B) w3_row_mma2(t2[B][0], t2[B][1], w1h, w1l, c2h[B][0], c2h[B][1], c2l[B][0], c2l[B][1]);
+#define W3_ROW_MMA3() w3_row_mma3(t2[0][0], t2[0][1], te, w1h, w1l, c2h[0][0], c2h[0][1], ceh, c2l[0][0], c2l[0][1], cel);
+#define W3_ROW_ACT2(B, S)                                                                                             \
+    {                                                                                                                 \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                               \
+            const float v_ = __builtin_fmaf(t2[B][S][q], inv1sx, b1v[q]);                                             \
+            d2[B][S][q] = pin[B][S] ? fmaxf(v_, 0.01f * v_) : 0.f;                                                    \
+        }                                                                                                             \
+    }
+#define W3_EXTRA_ACT()                                                                                                \
+    {                                                                                                                 \
+        b1v = b1r * sx;                                                                                               \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                               \
+            const float v_ = __builtin_fmaf(te[q], inv1sx, b1v[q]);                                                   \
+            de[q] = __int_as_float(__float_as_int(fmaxf(v_, 0.01f * v_)) & pine);                                     \
+        }                                                                                                             \
+    }
+#define W3_ROW_SHIFT(B)                                                                                               \
+    {                                                                                                                 \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                               \
+            d2[B][2][q] = w3_dpp<0x101, false>(w3_dpp<0x110 + 15 - 2 * (B), true>(0.f, de[q]), d2[B][0][q]);          \
+            d2[B][3][q] = w3_dpp<0x101, false>(w3_dpp<0x110 + 14 - 2 * (B), true>(0.f, de[q]), d2[B][1][q]);          \
+        }                                                                                                             \
+    }
+#define W3_ROW_STORE2(B, DST, XI)                                                                                     \
     {                                                                                                                 \
         const bool livev_ = vw[B] >= 0;                                                                               \
         uint8_t* d0_ = livev_ ? (DST) + vw[B] : lds + W3_DUMP;                                                        \
         const int xs_ = livev_ ? 16 * 32 : 0, lo_ = livev_ ? W3_PART : 8;                                             \
         float v4_[4];                                                                                                 \
         _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                                 \
-            v4_[q] = (XI) == 0 ? d1[0][q] - d1[2][q] : (XI) == 1 ? d1[1][q] + d1[2][q]                                \
-                   : (XI) == 2 ? d1[2][q] - d1[1][q] : d1[1][q] - d1[3][q];                                           \
+            v4_[q] = (XI) == 0 ? d2[B][0][q] - d2[B][2][q] : (XI) == 1 ? d2[B][1][q] + d2[B][2][q]                    \
+                   : (XI) == 2 ? d2[B][2][q] - d2[B][1][q] : d2[B][1][q] - d2[B][3][q];                               \
         h4_t hi_, lo4_;                                                                                               \
-        split4v(v4_, hi_, lo4_);                                                                                      \
+        w3_split4(v4_, hi_, lo4_);                                                                                    \
         *reinterpret_cast<h4_t*>(d0_ + (XI) * xs_) = hi_;                                                             \
         *reinterpret_cast<h4_t*>(d0_ + (XI) * xs_ + lo_) = lo4_;                                                      \
     }
+    F3_STAMP(13)
     __syncthreads();                   // the im2col is read across lanes
+    F3_STAMP(2)
 
     floatx16 acc[4][4];                // [xi][N-tile]
+#define W3_ZERO_ACC()                                                                                                 \
+    _Pragma("unroll") for (int xi = 0; xi < 4; ++xi)                                                                  \
+        _Pragma("unroll") for (int n = 0; n < 4; ++n)                                                                 \
+            _Pragma("unroll") for (int q = 0; q < 16; ++q) acc[xi][n][q] = 0.f;
+    if constexpr (EARLIER) {
+        W3_ZERO_ACC()
 #pragma unroll
-    for (int xi = 0; xi < 4; ++xi)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[xi][n][q] = 0.f;
-
-#pragma unroll
-    for (int B = 0; B < 3; ++B) {
-        W3_ROW_READ(B)
-        W3_ROW_MMA()
-        W3_ROW_ACT(B)
-        W3_ROW_STORE(B, lds)
+        for (int B = 0; B < 3; ++B) {
+            W3_ROW_READ(B)
+            W3_ROW_MMA()
+            W3_ROW_ACT(B)
+            W3_ROW_STORE(B, lds)
+        }
+    } else {
+        // chunk 0's rows as a pipeline: every fragment read in flight at once, then the three MMA statements, then the vector work;
+        // the accumulators are zeroed behind it, so that the rows' registers cost nothing
+        ceh = *reinterpret_cast<const half8*>(lds + cole);
+        cel = *reinterpret_cast<const half8*>(lds + cole + 64);
+        W3_ROW_READ2(0) W3_ROW_READ2(1) W3_ROW_READ2(2)
+        W3_ROW_MMA3() W3_ROW_MMA2(1) W3_ROW_MMA2(2)
+        W3_EXTRA_ACT()
+        W3_FUSED_LOAD((a.nch > 1 ? 1 : 0) * W3_CK)       // the operands of the chunk that chunk 0 stages (b1v holds chunk 0's bias)
+        W3_ROW_ACT2(0, 0) W3_ROW_ACT2(0, 1) W3_ROW_SHIFT(0)
+        W3_ROW_STORE2(0, lds, 0) W3_ROW_STORE2(0, lds, 1) W3_ROW_STORE2(0, lds, 2) W3_ROW_STORE2(0, lds, 3)
+        W3_ROW_ACT2(1, 0) W3_ROW_ACT2(1, 1) W3_ROW_SHIFT(1)
+        W3_ROW_STORE2(1, lds, 0) W3_ROW_STORE2(1, lds, 1) W3_ROW_STORE2(1, lds, 2) W3_ROW_STORE2(1, lds, 3)
+        W3_ROW_ACT2(2, 0) W3_ROW_ACT2(2, 1) W3_ROW_SHIFT(2)
+        W3_ROW_STORE2(2, lds, 0) W3_ROW_STORE2(2, lds, 1) W3_ROW_STORE2(2, lds, 2) W3_ROW_STORE2(2, lds, 3)
+        W3_ZERO_ACC()
     }
+#undef W3_ZERO_ACC
     __syncthreads();
 
     // B fragment of N-tile n, filter row dy, xi: pair p of output row 2n + ((lane>>4)&1), channel half lane>>5
     const int boff = (((lane >> 4) & 1) * 64 + p) * 32 + (((lane >> 5) ^ (p >> 3)) * 16);
-    F3_STAMP(1)
     // Per chunk: 12 units (dy, xi), 12 MFMAs each (384 matrix cycles); interleaved between them as in the direct kernel: the
     // 8 fragment reads of unit u+1, the weight step u+5 (ring of 6, continuous across chunks, pack padded by 5 steps), the
-    // next chunk's first-conv operands (unit 0) and its three rows into the idle buffer: READ at 2, 3, 6, MMA at 3, 6, 8, the ACT
-    // and STORE pieces over units 4 .. 11 (EARLIER: each row over four units, READ at 2, 5, 8; MMA at 3, 6, 9; ACT at 4, 7, 10;
-    // STORE at 5, 8, 11).  One barrier per chunk.
+    // first-conv operands of the chunk after the next (unit 8) and the next chunk's three rows into the idle buffer: READ at 0, 1, 2,
+    // MMA at 1, 2, 4, the ACT, SHIFT and STORE pieces over units 2 .. 10 (EARLIER: operands in unit 0, each row over four units, READ
+    // at 2, 5, 8; MMA at 3, 6, 9; ACT at 4, 7, 10; STORE at 5, 8, 11).  One barrier per chunk: at the end of unit 10 (EARLIER: behind unit 11), so that unit 11 can load the
+    // next chunk's unit-0 fragments in its gaps and no chunk starts with an LDS round trip that nothing hides.  The order that keeps
+    // this free of races, with buf the buffer chunk c reads and the other one the buffer it stages chunk c + 1 into:
+    //   - every store of chunk c + 1's V image is issued in units 3 .. 10 of chunk c, in front of the barrier; chunk c's unit 11 and
+    //     chunk c + 1 read that image behind it;
+    //   - unit 11's own fragments (buf) are loaded in unit 10 and waited for in front of the barrier (the barrier's fence drains
+    //     every LDS read of the wave), so no wave reads buf behind the barrier of chunk c;
+    //   - the next stores into buf are chunk c + 1's, from its unit 3 on: behind that barrier in every wave.
+    // The last chunk has no successor: its unit 11 loads fragments of the unused staged image (inside the buffer; a branch around the
+    // eight reads would split the unit's scheduling region) and nothing consumes them.
+    half8 bh[2][4], bl[2][4];
+#define W3_BLOAD_AT(BB, U, SET)                                                                        \
+        {                                                                                              \
+            const int dy_ = (U) >> 2, xi_ = (U) & 3;                                                   \
+            _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                            \
+                const int off = ((2 * n + dy_) * 4 + xi_) * 512;                                       \
+                bh[SET][n] = *reinterpret_cast<const half8*>((BB) + off);                              \
+                bl[SET][n] = *reinterpret_cast<const half8*>((BB) + W3_PART + off);                    \
+            }                                                                                          \
+        }
+    if constexpr (!EARLIER) W3_BLOAD_AT(lds + boff, 0, 0)
+    F3_STAMP(1)
     for (int chunk = 0; chunk < a.nch; ++chunk) {
-        if (chunk < 16 && !(chunk & 1)) F3_STAMP(2 + (chunk >> 1))
+        if (chunk >= 2 && chunk < 16 && !(chunk & 1)) F3_STAMP(2 + (chunk >> 1))   // slot 2 is the prologue's
         const int buf = chunk & 1;
         const uint8_t* wp = wbase + (int64_t)chunk * (W3_NST * F3_STEP_BYTES);
         const uint8_t* bb = lds + buf * W3_BUF + boff;
         uint8_t* sdst = lds + (buf ^ 1) * W3_BUF;
         const int c1 = (chunk + 1 < a.nch ? chunk + 1 : chunk) * W3_CK;     // chunk being staged (last: itself, unused)
-        half8 bh[2][4], bl[2][4];
-#define W3_BLOAD(U, SET)                                                                               \
-        {                                                                                              \
-            const int dy_ = (U) >> 2, xi_ = (U) & 3;                                                   \
-            _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                            \
-                const int off = ((2 * n + dy_) * 4 + xi_) * 512;                                       \
-                bh[SET][n] = *reinterpret_cast<const half8*>(bb + off);                                \
-                bl[SET][n] = *reinterpret_cast<const half8*>(bb + W3_PART + off);                      \
-            }                                                                                          \
+        // the current form loads the first conv's operands a chunk ahead, in unit 8, behind the last MMA and ACT that read the present
+        // ones: the rows of the staged chunk then start in unit 0 and their pieces have units 2 .. 10
+        const int c2 = (chunk + 2 < a.nch ? chunk + 2 : a.nch - 1) * W3_CK;
+#define W3_BLOAD(U, SET) W3_BLOAD_AT(bb, U, SET)
+        if constexpr (EARLIER) {
+            W3_BLOAD(0, 0)
+            // all 8 reads of unit 0 in flight before its first MFMA: interleaved by the unit's schedule, each would wait alone
+            __builtin_amdgcn_sched_barrier(0);
         }
-        W3_BLOAD(0, 0)
-        // all 8 reads of unit 0 in flight before its first MFMA: interleaved by the unit's schedule, each would wait alone
-        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < W3_NST; ++u) {
             const int xi = u & 3;
             ah[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES);
             al[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES + 1024);
             if (u + 1 < W3_NST) W3_BLOAD(u + 1, (u + 1) & 1)
-            if (u == 0) W3_FUSED_LOAD(c1)
             if constexpr (EARLIER) {
+                if (u == 0) W3_FUSED_LOAD(c1)
                 if (u == 2 || u == 5 || u == 8) W3_ROW_READ((u - 2) / 3)
                 if (u == 3 || u == 6 || u == 9) W3_ROW_MMA()
                 if (u == 4 || u == 7 || u == 10) W3_ROW_ACT((u - 4) / 3)
                 if (u == 5 || u == 8 || u == 11) W3_ROW_STORE((u - 5) / 3, sdst)
             } else {
-                // The 24 ACT / STORE pieces of the three rows dealt over units 4 .. 11, at most 56 vector instructions a unit; a
-                // row's READ rides in the unit of the row before's MMA (the fragment registers are free from there).  In program
-                // order every piece follows the MMA it reads and precedes the MMA or ACT piece that overwrites what it reads.
-                if (u == 2) W3_ROW_READ(0)
-                if (u == 3) { W3_ROW_MMA() W3_ROW_READ(1) }
-                if (u == 4) { W3_ROW_ACT1(0, 0) W3_ROW_ACT1(0, 2) W3_ROW_STORE1(0, sdst, 0) }
-                if (u == 5) { W3_ROW_ACT1(0, 1) W3_ROW_STORE1(0, sdst, 1) W3_ROW_STORE1(0, sdst, 2) }
-                if (u == 6) { W3_ROW_ACT1(0, 3) W3_ROW_STORE1(0, sdst, 3) W3_ROW_MMA() W3_ROW_READ(2) }
-                if (u == 7) { W3_ROW_ACT1(1, 0) W3_ROW_ACT1(1, 2) W3_ROW_STORE1(1, sdst, 0) }
-                if (u == 8) { W3_ROW_ACT1(1, 1) W3_ROW_ACT1(1, 3) W3_ROW_STORE1(1, sdst, 1) W3_ROW_MMA() }
-                if (u == 9) { W3_ROW_STORE1(1, sdst, 2) W3_ROW_STORE1(1, sdst, 3) W3_ROW_ACT1(2, 0) }
-                if (u == 10) { W3_ROW_ACT1(2, 2) W3_ROW_STORE1(2, sdst, 0) W3_ROW_ACT1(2, 1) }
-                if (u == 11) { W3_ROW_STORE1(2, sdst, 1) W3_ROW_STORE1(2, sdst, 2) W3_ROW_ACT1(2, 3) W3_ROW_STORE1(2, sdst, 3) }
+                if (u == W3_NST - 1) W3_BLOAD_AT(sdst + boff, 0, 0)
+                // The pieces of the three rows and the extra tile dealt over units 0 .. 10, at most 56 vector instructions a unit (16
+                // an ACT2 piece, 16 a SHIFT, 19 a STORE2 piece) and at most 12 LDS reads (8 fragment reads + 4 of a READ2).  In program
+                // order every piece follows the MMA, ACT2 or SHIFT it reads; the rows have registers of their own, so no piece
+                // overwrites another's input.
+                if (u == 0) W3_ROW_READ2(0)
+                if (u == 1) { W3_ROW_MMA3() W3_ROW_READ2(1) }
+                if (u == 2) { W3_EXTRA_ACT() W3_ROW_ACT2(0, 0) W3_ROW_ACT2(0, 1) W3_ROW_MMA2(1) W3_ROW_READ2(2) }
+                if (u == 3) { W3_ROW_SHIFT(0) W3_ROW_STORE2(0, sdst, 0) W3_ROW_STORE2(0, sdst, 1) }
+                if (u == 4) { W3_ROW_STORE2(0, sdst, 2) W3_ROW_STORE2(0, sdst, 3) W3_ROW_ACT2(1, 0) W3_ROW_MMA2(2) }
+                if (u == 5) { W3_ROW_ACT2(1, 1) W3_ROW_SHIFT(1) W3_ROW_STORE2(1, sdst, 0) }
+                if (u == 6) { W3_ROW_STORE2(1, sdst, 1) W3_ROW_STORE2(1, sdst, 2) W3_ROW_ACT2(2, 0) }
+                if (u == 7) { W3_ROW_STORE2(1, sdst, 3) W3_ROW_ACT2(2, 1) W3_ROW_SHIFT(2) }
+                if (u == 8) { W3_ROW_STORE2(2, sdst, 0) W3_ROW_STORE2(2, sdst, 1) W3_FUSED_LOAD(c2) }
+                if (u == 9) W3_ROW_STORE2(2, sdst, 2)
+                if (u == 10) W3_ROW_STORE2(2, sdst, 3)
             }
             const half8 A_h = ah[u % W3_RING], A_l = al[u % W3_RING];
             // product-major: the three MFMAs of one accumulator are 4 apart (no back-to-back dependent pair)
@@ -1156,23 +1318,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        // one LDS read
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                        // one global load
                 // a gap has 24 free issue cycles beside its MFMA: four vector instructions beside an LDS read, six without one
-                // (the eight fragment reads of the next unit take the first eight gaps; unit 11 has none)
+                // (the eight fragment reads of the next unit take the first eight gaps)
                 if constexpr (EARLIER) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-                else if (u == 11 || i >= 8) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+                else if (i >= 8) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
                 else __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                        // one LDS write
             }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!EARLIER) {
+                if (u == W3_NST - 2) __syncthreads();
+            }
         }
 #undef W3_BLOAD
-        __syncthreads();
+        if constexpr (EARLIER) __syncthreads();
     }
+#undef W3_BLOAD_AT
 #undef W3_ROW_READ
 #undef W3_ROW_MMA
 #undef W3_ROW_ACT
 #undef W3_ROW_STORE
-#undef W3_ROW_ACT1
-#undef W3_ROW_STORE1
+#undef W3_ROW_READ2
+#undef W3_ROW_MMA2
+#undef W3_ROW_MMA3
+#undef W3_ROW_ACT2
+#undef W3_EXTRA_ACT
+#undef W3_ROW_SHIFT
+#undef W3_ROW_STORE2
 #undef W3_FUSED_LOAD
 
     F3_STAMP(10)

@@ -2,8 +2,8 @@
 """Diagnostic: in-kernel clock stamps (s_memtime) of the fused tree-context pair (k_conv3_f16x3<2>) at the level-0 shape of
 BASELINE configs[2] (3 planes x 8 images, parent 128 x 128 -> 243 channels at 256 x 256).  The kernel writes stamps only
 when a stamp buffer is registered through lldwt_set_diagnostics (this tool).  Two legs: the kernel as it is, and k_plc_wino in its
-earlier form (diagnostics flag 1); per leg the prologue, the cycles per 32 channels and what of them is not matrix time, the
-epilogue, the in-kernel clock and the workgroup's cycles.   python tools/plc_stamps.py"""
+earlier form (diagnostics flag 1); per leg the prologue (k_plc_wino: in four parts), the cycles per 32 channels and per chunk and what of
+them is not matrix time, the epilogue, the in-kernel clock and the workgroup's cycles.   python tools/plc_stamps.py"""
 import json
 import os
 import sys
@@ -32,8 +32,9 @@ def main():
     nwg = (S // 32) * (S // 8) * 2 * P * B
     wino = ops.plc_algo() == "winograd"
     # matrix cycles of 32 channels: the direct kernel's 36 x 12 MFMAs of 32 cycles + 18 of the first conv; k_plc_wino's two
-    # 16-channel chunks of 144 x 32 + 36 x 16
-    matrix = 2 * (144 * 32 + 36 * 16) if wino else 36 * 12 * 32 + 18 * 32
+    # 16-channel chunks of 144 x 32 + the first conv's 16x16x32 MFMAs of 16 cycles (21 per chunk, 36 in the earlier form)
+    def matrix_cycles(flags):
+        return 2 * (144 * 32 + (36 if flags & 1 else 21) * 16) if wino else 36 * 12 * 32 + 18 * 32
 
     def leg(flags):
         for _ in range(100):
@@ -47,17 +48,33 @@ def main():
         finally:
             ops.set_diagnostics(1, None)
         s = st.cpu().numpy().astype(np.int64)
-        # k_plc_wino (the default, ops.plc_algo() == "winograd") stamps every second of its 16-channel chunks: a "chunk" below is
-        # 32 channels either way
+        matrix = matrix_cycles(flags)
         res = {"workgroups": nwg, "algo": ops.plc_algo(), "flags": flags}
-        d = np.diff(s[..., :12], axis=-1)
-        chunks = [float(d[..., 1 + i].mean()) for i in range(8)]
-        res["mean_cycles_per_wave"] = {"prologue": float(d[..., 0].mean()), "chunks": chunks,
-                                       "last chunk -> loop end": float(d[..., 9].mean()), "epilogue": float(d[..., 10].mean())}
+        if wino:
+            # k_plc_wino: slot 1 at the loop's entry, slots 3 .. 9 at its chunks 2, 4 .. 14, slot 10 behind the loop: eight spans of
+            # two 16-channel chunks.  Slots 12, 13, 2 split the prologue (0 .. 1) into four parts
+            t = s[..., [1, 3, 4, 5, 6, 7, 8, 9, 10]]
+            chunks = [float(v) for v in np.diff(t, axis=-1).mean(axis=(0, 1))]
+            pro = s[..., [0, 12, 13, 2, 1]]
+            parts = np.diff(pro, axis=-1).mean(axis=(0, 1))
+            res["mean_cycles_per_wave"] = {
+                "prologue": float((s[..., 1] - s[..., 0]).mean()),
+                "prologue_parts": {"parent patch + abs-max": float(parts[0]), "im2col": float(parts[1]),
+                                   "wait at the im2col barrier": float(parts[2]), "chunk-0 rows + barrier": float(parts[3])},
+                "chunks": chunks, "epilogue": float((s[..., 11] - s[..., 10]).mean())}
+            res["cycles_per_16_channel_chunk"] = float(np.mean(chunks)) / 2
+            res["cycles_per_chunk_outside_the_144_main_mfmas"] = float(np.mean(chunks)) / 2 - 144 * 32
+            per32 = float(np.mean(chunks))
+        else:
+            # the direct kernel stamps each of its eight 32-channel chunks at its start (slot 2 right behind slot 1)
+            d = np.diff(s[..., :12], axis=-1)
+            chunks = [float(d[..., 1 + i].mean()) for i in range(8)]
+            res["mean_cycles_per_wave"] = {"prologue": float(d[..., 0].mean()), "chunks": chunks,
+                                           "last chunk -> loop end": float(d[..., 9].mean()), "epilogue": float(d[..., 10].mean())}
+            per32 = float(np.mean(chunks[1:]))
         res["matrix_cycles_per_32_channels"] = matrix
-        # stamp 1 sits at the loop's entry and stamp 2 right behind it: chunks[0] is empty, chunks[1:] are seven spans of 32 channels
-        res["cycles_per_32_channels"] = float(np.mean(chunks[1:]))
-        res["non_matrix_cycles_per_32_channels"] = float(np.mean(chunks[1:])) - matrix
+        res["cycles_per_32_channels"] = per32
+        res["non_matrix_cycles_per_32_channels"] = per32 - matrix
         tot = s[..., 11] - s[..., 0]
         real = (s[..., 15] - s[..., 14]).astype(np.float64)
         ok = real > 0
@@ -75,6 +92,11 @@ def main():
     if wino:
         legs["earlier (flag 1)"] = leg(1)
     for name, r in legs.items():
+        if wino:
+            pp = r["mean_cycles_per_wave"]["prologue_parts"]
+            print("%-18s prologue parts: %s; per 16-channel chunk %.0f (outside the 144 main MFMAs %.0f)" % (
+                name, ", ".join("%s %.0f" % kv for kv in pp.items()), r["cycles_per_16_channel_chunk"],
+                r["cycles_per_chunk_outside_the_144_main_mfmas"]), file=sys.stderr)
         print("%-18s prologue %7.0f  per 32 channels %7.0f (non-matrix %6.0f)  epilogue %7.0f  workgroup %7.0f cycles  %.3f GHz" % (
             name, r["mean_cycles_per_wave"]["prologue"], r["cycles_per_32_channels"], r["non_matrix_cycles_per_32_channels"],
             r["mean_cycles_per_wave"]["epilogue"], r["total_cycles_mean"], r["in_kernel_clock_GHz"]), file=sys.stderr)
