@@ -91,6 +91,13 @@ decoders read the step from the header (``hdr["step"]``, a float; on the nested 
 searches the quarter-octave grid STEP_GRID for the finest step whose container is at most T bytes, one image (or one tiled
 frame) at a time.
 
+Rate-distortion optimised quantisation (``encode_images(..., rdo=rho)``, the same on ``encode_tiled``): where
+a step applies, the encoder moves a coefficient one level toward zero when rho * q^2 * (bits saved) exceeds the squared error
+that adds, judged with the exact integer code lengths of the level's tables.  rho = m / 64, m an integer in [1, 256]
+(ln 2 / 6 = 0.1155 is the high-rate slope; 13 / 64 is a good start).  It is an encoder's choice alone: nothing is recorded, no
+header key, the decoders are untouched and never learn of it; ``rdo=None`` and ``rdo=0`` write the bytes above.  It composes
+with ``step``, ``target_bytes`` (probes and real encodes both run with it), ``near``, tiles and both coders.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -154,6 +161,27 @@ def check_step(step):
                          % (STEP_DENOM, STEP_N_MIN, STEP_N_MAX, 1.0 / STEP_DENOM, STEP_N_MIN / STEP_DENOM,
                             STEP_N_MAX / STEP_DENOM, step))
     return int(n)
+
+
+# rate-distortion optimised quantisation: the Lagrangian rho = m / RDO_DENOM in units of q^2 per bit
+RDO_DENOM, RDO_M_MAX = 64, 256
+
+
+def check_rdo(rdo):
+    """The Lagrangian of the API -> m, the integer with rdo == m / 64 (None and 0 -> 0: off).  ValueError naming rdo unless
+    the value is exactly m / 64 with m in [1, 256]."""
+    if rdo is None:
+        return 0
+    try:
+        m = float(rdo) * RDO_DENOM
+    except (TypeError, ValueError):
+        raise ValueError("rdo must be a number (got %r)" % (rdo,)) from None
+    if m == 0:
+        return 0
+    if not (m == m and 1 <= m <= RDO_M_MAX and m == int(m)):
+        raise ValueError("rdo must be m / %d with an integer m in [1, %d], i.e. a multiple of %g in [%g, %g], or 0 / None for "
+                         "off (got %r)" % (RDO_DENOM, RDO_M_MAX, 1.0 / RDO_DENOM, 1.0 / RDO_DENOM, RDO_M_MAX / RDO_DENOM, rdo))
+    return int(m)
 
 
 def _split_step(arith):
@@ -703,6 +731,15 @@ def _refine(base_blobs, img, xh, grid, near, coder):
     return [pack_refined(near, crc, base_blobs[b], units[b * per:(b + 1) * per]) for b in range(len(base_blobs))]
 
 
+def _rdo_arg(rdo, L):
+    """The rdo argument of encode_images / encode_tiled, checked on the host -> rho as a float, or None for off."""
+    m = check_rdo(rdo)
+    if m and L < 2:
+        raise ValueError("rdo: rate-distortion optimised quantisation needs dwtlevels >= 2 (it applies to the levels below the "
+                         "coarsest; the net has %d)" % L)
+    return m / RDO_DENOM if m else None
+
+
 def _rate_args(step, target_bytes, near, L):
     """The rate arguments of encode_images / encode_tiled, checked on the host -> (n of the step, target or None)."""
     if step is not None and target_bytes is not None:
@@ -774,7 +811,7 @@ def _estimated_size(empty, estimates):
     return len(empty) + sum(e + len(leb128_encode(e)) - 1 for e in estimates)
 
 
-def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None):
+def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -783,7 +820,9 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     and 1 write the same bytes as ever.  target_bytes = T instead: per image, the finest step of STEP_GRID whose container is
     at most T bytes (_search_step: estimates first, real containers decide; if the sizes are not monotone along the grid,
     the step that walk finds); ValueError naming the smallest achievable size if even the coarsest step does not fit.  Not
-    both, and no target with near."""
+    both, and no target with near.
+    rdo: the Lagrangian rho = m / 64 of rate-distortion optimised quantisation on the same levels; None and 0
+    write the same bytes as ever.  The encoder's choice only: no header key, and the containers decode as any other."""
     from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
@@ -791,27 +830,28 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
         from .residual import check_near
         near = check_near(near)
     n, T = _rate_args(step, target_bytes, near, L)
+    rdo = _rdo_arg(rdo, L)
     Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T):
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None):
     """_encode at the step step_n / 16, or with a byte target T the search of _search_step, one image at a time.  walk: the
-    (magic, grid, group, coder) of _encode."""
+    (magic, grid, group, coder) of _encode.  rdo: probes and real encodes alike."""
     if T is None:
-        return _encode(net, images_u8, *walk, near, step_n)
-    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True)[0],
-                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m)[0], T)
+        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo)
+    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo)[0],
+                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo)[0], T)
             for b in range(images_u8.shape[0])]
 
 
-def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False):
+def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None):
     """The encode walk behind encode_images and encode_tiled (arguments checked there): the batch is cut into the tiles of
     grid = (th, tw, ny, nx, ov) -- the untiled codec is the 1 x 1 grid of one padded_size tile, which the untiled input and
     output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
     arithmetics that are not batch invariant) at the step step_n / 16 -> the B containers of ``magic``, with near the LLDR
     containers over them.  estimate: -> the estimated container sizes (ints) from the code-length kernel instead; no range
-    coder runs."""
+    coder runs.  rdo: the Lagrangian of DESIGN.md 7.1.7 (None: off), which only the encoder's symbols see."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
@@ -839,9 +879,9 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
             else:
                 x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
             if near is None:
-                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, step=step)
+                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, step=step, rdo=rdo)
             else:
-                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, step=step)
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, step=step, rdo=rdo)
                 # the decoder's call on the same values
                 ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W), first=first, B=B, out=xh)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
@@ -1022,7 +1062,8 @@ def _tile_streams(s_xe, s_xo, j):
     return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
 
 
-def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None):
+def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
+                 rdo=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -1033,7 +1074,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     (LLDR over LLDT; the bytes do not depend on tiles_per_call either); not with overlap > 0, where the decoded pixels are
     a blend of two units.
     step, target_bytes: as encode_images, with ONE step for all tiles of a frame; a target is met by each frame's container
-    (the images of a batch are searched one at a time)."""
+    (the images of a batch are searched one at a time).  rdo: as encode_images, for every tile."""
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
     if near is not None:
@@ -1042,6 +1083,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
         if overlap:
             raise ValueError("near: a residual layer over lapped tiles (overlap > 0) is not defined; use overlap=0")
     n, T = _rate_args(step, target_bytes, near, L)
+    rdo = _rdo_arg(rdo, L)
     group = _tiles_per_call(tiles_per_call)
     ov = int(overlap)
     if ov != overlap or ov < 0 or ov > 0xFFFF:
@@ -1050,7 +1092,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo)
 
 
 def _tiles_per_call(tiles_per_call):

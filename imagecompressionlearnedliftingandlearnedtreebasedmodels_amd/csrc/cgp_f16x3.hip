@@ -162,6 +162,10 @@ struct Cgp16Args {
     float* wf_sigma;                      // decoder, optional: the step's sigmas in wf_mu's layout (the quantiser's test); null in the product
     float wf_q, wf_invq;                  // quantisation step q = n / 16 and fp32(1 / q) (lldwt_cgp16_wavefront_step_q); 1, 1: the unit step
     int64_t wf_ntot, wf_off;
+    // RDO (lldwt_cgp16_wavefront_step_rdo): the tables of lldwt_code_cost and k = rho * 2^-16
+    const int* wf_cost; const int* wf_sizes; const int* wf_offsets;
+    int wf_ntab, wf_width;
+    float wf_k;
     unsigned long long* stamps;   // diagnostics only (lldwt_set_diagnostics kind 2): [z][group][column][8] s_memtime stamps
     // TRAIN: the hidden activations after LeakyReLU in the layout of the unfused convs, h1 (Z, groups*162, hw), h2 (Z, groups*54,
     // hw), h3 (Z, groups*18, hw): what lldwt_cgp_bwd_split gates with and the 1x1 weight-gradient GEMMs read
@@ -231,12 +235,14 @@ __device__ __forceinline__ void next_frags(const floatx16& acc, float k, const f
 // 883 / 233 / 74 us for levels 0 / 1 / 2 of configs[2] -- the third wave hides the input wait as well as the prefetch does.
 // DIAG (streaming form, lldwt_set_diagnostics: timing only, WRONG results): 1 = every step reads the weight fragments of step 0
 // (same instruction stream, L1-resident weights), 2 = the inputs are constants instead of loads.  Addresses: a subset of the real ones.
-template <int PREC, bool WF = false, bool TRAIN = false, bool PERS = false, int DIAG = 0>
+// RDO (WF, encoder only): the epilogue chooses the symbol by the rate-distortion rule of DESIGN.md 7.1.7 (rdo_symbol, common.h)
+template <int PREC, bool WF = false, bool TRAIN = false, bool PERS = false, int DIAG = 0, bool RDO = false>
 __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 : 3, TRAIN ? 2 : 3))) void k_cgp16(Cgp16Args a) {
     // (TRAIN: two waves per SIMD -- the store addresses do not fit the 168 registers of three)
     static_assert(!TRAIN || (PREC == 0 && !WF), "the training forward runs the split-fp16 arithmetic on whole images");
     static_assert(!PERS || (!WF && !TRAIN), "the persistent form is the whole-image eval chain");
     static_assert(DIAG == 0 || (!PERS && PREC == 0 && !WF && !TRAIN), "the bound-only variants are of the streaming eval chain");
+    static_assert(!RDO || WF, "the rate-distortion rule belongs to the wavefront step's encoder epilogue");
     constexpr int SB = PREC == 2 ? STEP_BYTES / 2 : STEP_BYTES;
     constexpr int NW = PERS ? 12 : 4;                       // waves per workgroup
     // (PERS: the wave number as a scalar, so that its block, image and the loads' base addresses are scalars too)
@@ -553,7 +559,11 @@ __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_e
                     a.wf_idx[o] = idx;
                     if (a.wf_y) {                                                 // encoder: symbol = round(y - mu), value = symbol + mu
                         const int64_t e = (z * a.groups + g) * hw + pix[nb];
-                        const int sym = (int)rintf((a.wf_y[e] - mu) * a.wf_invq);
+                        int sym;
+                        if constexpr (RDO)
+                            sym = rdo_symbol(a.wf_y[e] - mu, a.wf_invq, idx,
+                                             RdoTables{a.wf_cost, a.wf_sizes, a.wf_offsets, a.wf_ntab, a.wf_width, a.wf_k});
+                        else sym = (int)rintf((a.wf_y[e] - mu) * a.wf_invq);
                         a.wf_sym[o] = sym;
                         a.wf_yhat[e] = (float)sym * a.wf_q + mu;
                     } else {
@@ -984,10 +994,10 @@ static inline void wf_range(int t, int slope, int h, int w, int& y0, int& n) {
 
 // q = n / 16 with an integer n in [4, 1024], inv_q = fp32(1 / q) from the host (both checked here: encoder and decoder must use the
 // same pair).  sigma_out: decoder only, may be null.
-extern "C" int lldwt_cgp16_wavefront_step_q(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
-                                            int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h,
-                                            int64_t w_, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q,
-                                            float inv_q, void* stream) {
+// rdo: null for the nearest-level quantiser.
+static int wavefront_step(const float* plc, float* yhat, const float* y, const void* packed, const float* table63, int* idx, int* sym,
+                          float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h, int64_t w_, int groups, int K,
+                          uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q, float inv_q, const RdoTables* rdo, void* stream) {
     LLDWT_REQUIRE(wf_step_ok(q, inv_q), "cgp16_wavefront_step: step %g (1 / step %g) is not n / 16 with n in [4, 1024]", (double)q, (double)inv_q);
     LLDWT_REQUIRE(!(y && sigma_out), "cgp16_wavefront_step: sigma_out is an output of the decoder mode (y == null)");
     LLDWT_REQUIRE(plc && yhat && packed && table63 && idx && (y ? sym != nullptr : mu != nullptr), "cgp16_wavefront_step: null pointer");
@@ -1015,13 +1025,39 @@ extern "C" int lldwt_cgp16_wavefront_step_q(const float* plc, float* yhat, const
     LLDWT_REQUIRE(off >= 0 && off + a.wf_n <= ntot, "cgp16_wavefront_step: step does not fit the output (off %ld + %d > %ld)", (long)off, a.wf_n, (long)ntot);
     a.wf_y = y; a.wf_yhat = yhat; a.wf_table = table63; a.wf_idx = idx; a.wf_sym = sym; a.wf_mu = mu; a.wf_ntot = ntot; a.wf_off = off;
     a.wf_sigma = sigma_out; a.wf_q = q; a.wf_invq = inv_q;
+    a.wf_cost = rdo ? rdo->cost : nullptr; a.wf_sizes = rdo ? rdo->sizes : nullptr; a.wf_offsets = rdo ? rdo->offsets : nullptr;
+    a.wf_ntab = rdo ? rdo->ntab : 0; a.wf_width = rdo ? rdo->width : 0; a.wf_k = rdo ? rdo->k : 0.f;
     a.cols = (int)cdiv(a.wf_n, 32 * NB);
     a.stamps = nullptr;
     a.pairs = 0;
     dim3 grid((unsigned)cdiv(a.cols, 4), (unsigned)groups, (unsigned)(planes * batch));
     // always the fp32-accurate arithmetic: encoder and decoder must agree bit for bit whatever the precision mode of the process
-    hipLaunchKernelGGL((k_cgp16<0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    if (rdo) hipLaunchKernelGGL((k_cgp16<0, true, false, false, 0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_cgp16<0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("cgp16_wavefront_step");
+}
+
+extern "C" int lldwt_cgp16_wavefront_step_q(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                            int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h,
+                                            int64_t w_, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q,
+                                            float inv_q, void* stream) {
+    return wavefront_step(plc, yhat, y, packed, table63, idx, sym, mu, sigma_out, planes, batch, h, w_, groups, K, tap_mask, t, ntot, off,
+                          q, inv_q, nullptr, stream);
+}
+
+// the encoder step with rate-distortion optimised quantisation; the decoder is the entry point above
+extern "C" int lldwt_cgp16_wavefront_step_rdo(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                              int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch,
+                                              int64_t h, int64_t w_, int groups, int K, uint32_t tap_mask, int t, int64_t ntot,
+                                              int64_t off, float q, float inv_q, const int32_t* cost, const int32_t* sizes,
+                                              const int32_t* offsets, int32_t ntab, int32_t width, float k, void* stream) {
+    LLDWT_REQUIRE(y, "cgp16_wavefront_step_rdo: encoder mode only (y == null is the decoder, which lldwt_cgp16_wavefront_step_q runs)");
+    LLDWT_REQUIRE(cost && sizes && offsets, "cgp16_wavefront_step_rdo: null cost table pointer");
+    LLDWT_REQUIRE(ntab > 0 && width > 0, "cgp16_wavefront_step_rdo: bad cost table sizes (%d x %d)", ntab, width);
+    LLDWT_REQUIRE(rdo_k_ok(k), "cgp16_wavefront_step_rdo: k %g is not (m / 64) * 2^-16 with an integer m in [1, %d]", (double)k, RDO_M_MAX);
+    const RdoTables rdo{cost, sizes, offsets, ntab, width, k};
+    return wavefront_step(plc, yhat, y, packed, table63, idx, sym, mu, sigma_out, planes, batch, h, w_, groups, K, tap_mask, t, ntot, off,
+                          q, inv_q, &rdo, stream);
 }
 
 // the unit step: multiplying by 1.0f changes no bit, so these are the bits this entry point has always produced

@@ -20,6 +20,7 @@ struct QuantArgs {
     int C, h, w, H, W, r0, c0, s;
     int lvec;                                    // VEC 4: the four level elements of a thread are one aligned float4 (s == 1)
     float q, inv_q;
+    RdoTables rdo;                               // RDO (lldwt_gauss_quantise_rdo): the code-length tables and k of DESIGN.md 7.1.7
 };
 
 // the normative quantiser (the epilogue of k_cgp16's wavefront mode, csrc/cgp_f16x3.hip, is the same three lines)
@@ -31,7 +32,8 @@ __device__ __forceinline__ int cdf_index(float sigma, float inv_q, const float (
     return n;
 }
 
-template <int VEC>
+// RDO: the encoder's symbol is chosen by rdo_symbol (common.h) between the nearest level and the one next to it toward zero
+template <int VEC, bool RDO = false>
 __global__ __launch_bounds__(NT) void k_gauss_quantise(QuantArgs a) {
     const int64_t hw = (int64_t)a.h * a.w;
     const int64_t v = ((int64_t)blockIdx.x * NT + threadIdx.x) * VEC;          // first element of this thread inside the (z, c) grid
@@ -62,8 +64,13 @@ __global__ __launch_bounds__(NT) void k_gauss_quantise(QuantArgs a) {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) val[e] = a.y[lv + e * a.s];
         }
+        if constexpr (RDO) {                                                     // the index does not depend on the choice
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) sym[e] = (int)rintf((val[e] - mu[e]) * a.inv_q);
+            for (int e = 0; e < VEC; ++e) sym[e] = rdo_symbol(val[e] - mu[e], a.inv_q, cdf_index(sigma[e], a.inv_q, tab), a.rdo);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) sym[e] = (int)rintf((val[e] - mu[e]) * a.inv_q);
+        }
     } else if (a.sym_in) {
         if constexpr (VEC == 4) {
             const int4 q4 = *reinterpret_cast<const int4*>(a.sym_in + zc * hw + v);
@@ -136,9 +143,10 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 }  // namespace
 
-extern "C" int lldwt_gauss_quantise(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
-                                    int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H,
-                                    int64_t W, int r0, int c0, int stride, float q, float inv_q, void* stream) {
+// rdo: null for the plain quantiser
+static int gauss_quantise(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
+                          int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W,
+                          int r0, int c0, int stride, float q, float inv_q, const RdoTables* rdo, void* stream) {
     LLDWT_REQUIRE(params && table63 && idx, "gauss_quantise: null pointer");
     LLDWT_REQUIRE(!(y && sym_in), "gauss_quantise: give y (encoder) or sym_in (decoder), not both");
     LLDWT_REQUIRE((level != nullptr) == (y || sym_in), "gauss_quantise: level goes with y or sym_in (neither: the indexes only)");
@@ -159,13 +167,38 @@ extern "C" int lldwt_gauss_quantise(const float* params, const float* y, const i
     a.params = params; a.y = y; a.sym_in = sym_in; a.table = table63; a.idx = idx; a.sym_out = sym_out; a.level = level;
     a.C = channels; a.h = (int)h; a.w = (int)w; a.H = (int)H; a.W = (int)W; a.r0 = r0; a.c0 = c0; a.s = stride;
     a.q = q; a.inv_q = inv_q;
+    a.rdo = rdo ? *rdo : RdoTables{nullptr, nullptr, nullptr, 0, 0, 0.f};
     const bool vec = w % 4 == 0 && aligned16(params) && aligned16(idx) && (!sym_in || aligned16(sym_in)) && (!sym_out || aligned16(sym_out));
     a.lvec = vec && stride == 1 && W % 4 == 0 && c0 % 4 == 0 && (!level || aligned16(level)) && (!y || aligned16(y));
     const int per = vec ? 4 : 1;
     dim3 grid((unsigned)cdiv(cdiv(h * w, per), NT), (unsigned)(streams * channels));
-    if (vec) hipLaunchKernelGGL(k_gauss_quantise<4>, grid, dim3(NT), 0, (hipStream_t)stream, a);
+    if (rdo && vec) hipLaunchKernelGGL((k_gauss_quantise<4, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
+    else if (rdo) hipLaunchKernelGGL((k_gauss_quantise<1, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
+    else if (vec) hipLaunchKernelGGL(k_gauss_quantise<4>, grid, dim3(NT), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(k_gauss_quantise<1>, grid, dim3(NT), 0, (hipStream_t)stream, a);
     return check_launch("gauss_quantise");
+}
+
+extern "C" int lldwt_gauss_quantise(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
+                                    int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H,
+                                    int64_t W, int r0, int c0, int stride, float q, float inv_q, void* stream) {
+    return gauss_quantise(params, y, sym_in, table63, idx, sym_out, level, streams, channels, h, w, H, W, r0, c0, stride, q, inv_q,
+                          nullptr, stream);
+}
+
+// the encoder with rate-distortion optimised quantisation: encoder mode only, the decoder is
+// lldwt_gauss_quantise as ever
+extern "C" int lldwt_gauss_quantise_rdo(const float* params, const float* y, const float* table63, int32_t* idx, int32_t* sym_out,
+                                        float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W,
+                                        int r0, int c0, int stride, float q, float inv_q, const int32_t* cost, const int32_t* sizes,
+                                        const int32_t* offsets, int32_t ntab, int32_t width, float k, void* stream) {
+    LLDWT_REQUIRE(y && level && sym_out, "gauss_quantise_rdo: encoder only (y, level and sym_out must be given)");
+    LLDWT_REQUIRE(cost && sizes && offsets, "gauss_quantise_rdo: null cost table pointer");
+    LLDWT_REQUIRE(ntab > 0 && width > 0, "gauss_quantise_rdo: bad cost table sizes (%d x %d)", ntab, width);
+    LLDWT_REQUIRE(rdo_k_ok(k), "gauss_quantise_rdo: k %g is not (m / 64) * 2^-16 with an integer m in [1, %d]", (double)k, RDO_M_MAX);
+    const RdoTables rdo{cost, sizes, offsets, ntab, width, k};
+    return gauss_quantise(params, y, nullptr, table63, idx, sym_out, level, streams, channels, h, w, H, W, r0, c0, stride, q, inv_q, &rdo,
+                          stream);
 }
 
 extern "C" int lldwt_code_cost(const int32_t* sym, const int32_t* idx, int64_t streams, int64_t n, const int32_t* cost, int32_t ntab,

@@ -164,6 +164,18 @@ def _check_step(step, L):
     return q
 
 
+def _check_rdo(rdo, L):
+    """The Lagrangian of rate-distortion optimised quantisation in a coded layer's compress_planes -> None
+    (None or 0: off) or rho as a float.  It applies exactly where a step applies, the levels 0 .. L-2."""
+    if rdo is None or (isinstance(rdo, (int, float)) and not isinstance(rdo, bool) and rdo == 0):
+        return None
+    ops.rdo_scale(rdo)
+    if L < 2:
+        raise ValueError("rdo: rate-distortion optimised quantisation needs dwtlevels >= 2 (it applies to the levels below the "
+                         "coarsest; got %d)" % L)
+    return float(rdo)
+
+
 class _EntropyLayerBase(PackedOwnerMixin, nn.Module):
     def _level_channels(self, config):
         self.num_lifting_layers = config.dwtlevels
@@ -266,11 +278,12 @@ class onlyEZWT(_EntropyLayerBase):
         return _conv([s[4] for s in seqs], t)                                       # (P,B,6,h,w): sigma even, mu odd
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first)."""
         from . import entropy_coding as ec
         L = len(out_xo_list)
         step = _check_step(step, L)
+        rdo = _check_rdo(rdo, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
             s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
@@ -281,7 +294,7 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 s, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, out_xo_list[i],
-                                                 out_xo_list[i].shape, tabs, coder=coder, step=step)
+                                                 out_xo_list[i].shape, tabs, coder=coder, step=step, rdo=rdo)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -469,13 +482,14 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return plc, (packed, packed16), dims, cs[0].kernel_size[0], cs[0].tap_bits()
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
         """compress_ar for every tensor (:386-417): -> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q])
         with *_q = round(y - mu) + mu, the values the decoder reconstructs."""
         from . import entropy_coding as ec
         tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
         L = len(out_xo_list)
         step = _check_step(step, L)
+        rdo = _check_rdo(rdo, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], out_xe,
                                             out_xe.shape, tabs, coder=coder)
@@ -487,10 +501,11 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, x.shape[2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
                 if packed[1] is not None:       # the reference's cgp widths: one fused launch per wavefront step
-                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder, step=step)
+                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder, step=step,
+                                              rdo=rdo)
                 else:
                     s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs, coder=coder,
-                                                         step=step)
+                                                         step=step, rdo=rdo)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -649,13 +664,14 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         return packs
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0):
+    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first), *_q the decoder's values."""
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(out_xo_list)
         step = _check_step(step, L)
+        rdo = _check_rdo(rdo, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
             s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
@@ -664,7 +680,7 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
                 x = out_xo_list[L - i - 2]
                 ems, tabs = cls._level_models(layers, i, L)
                 s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs, coder=coder,
-                                             step=step)
+                                             step=step, rdo=rdo)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -1067,19 +1083,23 @@ def compress_planes(nets, x):
     return xhat, s_xe, s_xo
 
 
-def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0):
+def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None):
     """The encoder half of compress_planes: encode -> the entropy layer's compress_planes, no decoding.
     x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first).  coder: "host" (rans64 on the host) or "gpu"
     (irans32 on the device); the symbols are the same, the bytes differ.
     recon=True: -> (strings_xe, strings_xo, xhat), xhat (P,B,C,H,W) being decode_planes of the dequantised tensors
     compress_planes returns -- the tensors decompress_planes returns for these strings, through the call
     decode_strings_planes makes (the codec's residual layer).
-    step: the quantisation step of the levels 0 .. L-2 (n / 16, 1 = the trained operating point)."""
+    step: the quantisation step of the levels 0 .. L-2 (n / 16, 1 = the trained operating point).
+    rdo: the Lagrangian of rate-distortion optimised quantisation on the same levels (m / 64, None or 0: off).
+    An encoder's choice: the strings decode with decode_strings_planes as ever."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "compress_planes"):
         raise NotImplementedError(_NOT_CODED)
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
     kw = {} if step == 1.0 else {"step": step}
+    if not (rdo is None or rdo == 0):
+        kw["rdo"] = rdo
     s_xe, s_xo, xe_q, xo_q = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder, **kw)
     if recon:
         return s_xe, s_xo, decode_planes([n.autoencoder for n in nets], xe_q, xo_q)

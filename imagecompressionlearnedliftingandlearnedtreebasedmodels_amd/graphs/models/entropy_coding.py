@@ -163,9 +163,23 @@ def device_cost_tables(tables, dev):
     cache = tables.__dict__.setdefault("_cost_dev", {})
     key = str(dev)
     if key not in cache:
-        arrs = (ops.cost_table(tables.cdf, tables.sizes), tables.sizes, tables.offsets)
-        cache[key] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev) for a in arrs)
+        # the layers build a fresh table object per level and call, from the same scale table: a second cache on the content
+        # keeps the logarithms and the three uploads out of every encode with rdo and every probe
+        import hashlib
+        h = hashlib.sha1()
+        for a in (tables.cdf, tables.sizes, tables.offsets):
+            h.update(np.ascontiguousarray(a, dtype=np.int32).tobytes())
+        ckey = (h.digest(), tuple(tables.cdf.shape), key)
+        if ckey not in _COST_TABLES:
+            if len(_COST_TABLES) >= 16:
+                _COST_TABLES.clear()
+            arrs = (ops.cost_table(tables.cdf, tables.sizes), tables.sizes, tables.offsets)
+            _COST_TABLES[ckey] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev) for a in arrs)
+        cache[key] = _COST_TABLES[ckey]
     return cache[key]
+
+
+_COST_TABLES = {}                # (sha1 of cdf | sizes | offsets, cdf shape, device) -> device_cost_tables' tensors
 
 
 class _CostSink(_DeviceSink):
@@ -200,9 +214,29 @@ def _make_sink(coder, P, B, tables, strings, n, device):
     raise ValueError("coder must be one of %s (got %r)" % (", ".join(CODERS), coder))
 
 
-def _finish_step(emodel, sink, sigma, mu, yv, step=1.0):
+def _rdo_args(rdo, tables, dev):
+    """rdo (the Lagrangian rho of DESIGN.md 7.1.7, None or 0: off) -> None or (k, cost, sizes, offsets) for the encoder half of a
+    level: k = ops.rdo_scale(rdo) and the device cost tables of the level's CDF tables."""
+    if rdo is None or rdo == 0:
+        return None
+    return (ops.rdo_scale(rdo),) + tuple(device_cost_tables(tables, dev))
+
+
+def _finish_step(emodel, sink, sigma, mu, yv, step=1.0, rdo=None):
     """sigma, mu (P,B,g,N); yv (P,B,g,N) or None when decoding -> dequantised values (P,B,g,N).  step != 1: the quantiser
-    of DESIGN.md 7.1.6 restated in fp32 tensor ops (the table entered with sigma / q, round((y - mu) / q), symbol * q + mu)."""
+    of DESIGN.md 7.1.6 restated in fp32 tensor ops (the table entered with sigma / q, round((y - mu) / q), symbol * q + mu).
+    rdo (encoder only): (k, cost, sizes, offsets) of _rdo_args -- the symbol is chosen by the rule of DESIGN.md 7.1.7, restated
+    in tensor ops (ops.rdo_lookup, ops.rdo_choose)."""
+    if rdo is not None and yv is not None:
+        q, inv_q = ops.step_pair(step)
+        idx = emodel.build_indexes(sigma * inv_q)                                       # (P,B,g,N); does not depend on the choice
+        v = (yv - mu) * inv_q                                                           # the rounded fp32 product
+        s0 = torch.round(v)
+        s1 = s0 - torch.sign(s0)
+        k, cost, sizes, offsets = rdo
+        sym = ops.rdo_choose(v, s0, ops.rdo_lookup(cost, sizes, offsets, idx, s0), ops.rdo_lookup(cost, sizes, offsets, idx, s1), k)
+        sym = sink.step(idx.permute(0, 1, 3, 2).contiguous(), sym.int().permute(0, 1, 3, 2).contiguous())
+        return sym.permute(0, 1, 3, 2).float() * q + mu
     if step == 1.0:
         idx = emodel.build_indexes(sigma).permute(0, 1, 3, 2).contiguous()             # (P,B,N,g)
         sym = None
@@ -257,7 +291,7 @@ def _step_offsets(H, W, slope):
     return np.searchsorted(t, np.arange(W + slope * (H - 1) + 1)).tolist()
 
 
-def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strings=None, coder="host", step=1.0):
+def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strings=None, coder="host", step=1.0, rdo=None):
     """A level with tree context + masked KxK context + cgp (:402-417 / :440-454 with kernel size 5).  plc: (P,B,G*81,H,W)
     tree-context features of the (decoded) parent; packed16: the cgp stack with the masked conv folded into its first layer,
     packed for the register-chain kernel (_fold_csc_into_cgp).
@@ -270,7 +304,9 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     small launch that writes symbol + mu.  With coder="gpu" the decoder never waits: per step the step kernel, the irans32 pop
     of every stream and the apply launch are queued back to back, and the streams are checked once at the end of the level.
     step: the quantisation step q of DESIGN.md 7.1.6 (lldwt_cgp16_wavefront_step_q / lldwt_wavefront_apply_q; the unit step
-    goes through them too and gives the bits of the entry points without a step)."""
+    goes through them too and gives the bits of the entry points without a step).
+    rdo: the Lagrangian of DESIGN.md 7.1.7 (None or 0: off); the encoder's steps then go through
+    lldwt_cgp16_wavefront_step_rdo with the level's cost tables, the decoder ignores it."""
     import ctypes as C
     from ... import _lib
     lib = _lib.load()
@@ -289,7 +325,15 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
         yc = y.contiguous()
         idx_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
         sym_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
+        ra = _rdo_args(rdo, tables, dev)
         for t in range(nsteps):
+            if ra is not None:
+                k, cost, csizes, coffs = ra
+                ops.check(lib.lldwt_cgp16_wavefront_step_rdo(ptr(plc), ptr(yhat), ptr(yc), ptr(packed16), ptr(table63), ptr(idx_all),
+                                                             ptr(sym_all), None, None, P, B, H, W, G, K, int(tap_bits), t, ntot,
+                                                             starts[t], q, inv_q, ptr(cost), ptr(csizes), ptr(coffs), cost.shape[0],
+                                                             cost.shape[1], k, st), "cgp16_wavefront_step_rdo")
+                continue
             ops.check(lib.lldwt_cgp16_wavefront_step_q(ptr(plc), ptr(yhat), ptr(yc), ptr(packed16), ptr(table63), ptr(idx_all),
                                                        ptr(sym_all), None, None, P, B, H, W, G, K, int(tap_bits), t, ntot, starts[t],
                                                        q, inv_q, st), "cgp16_wavefront_step")
@@ -335,7 +379,7 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
 
 
 def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, shape, tables, strings=None, coder="host",
-                            step=1.0):
+                            step=1.0, rdo=None):
     """A level with tree context + masked KxK context + cgp (:402-417 / :440-454 with kernel size 5).  plc: (P,B,G*81,H,W)
     tree-context features of the (decoded) parent; cgp_packed/dims: the cgp stack with the masked conv folded into its
     first layer (_fold_csc_into_cgp).  The host-stepped schedule (a handful of tensor ops and launches per step) for cgp widths
@@ -347,6 +391,7 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
     cpl = plc.shape[2] // G
     hs, ws, starts = wavefront(H, W, R + 1, dev)
     sink = _make_sink(coder, P, B, tables, strings, H * W * G, dev)
+    ra = None if sink.decoding else _rdo_args(rdo, tables, dev)
     yhat = torch.zeros(P, B, G, H + 2 * R, W + 2 * R, device=dev, dtype=torch.float32)
     dy = torch.tensor([t[0] for t in taps], device=dev)
     dx = torch.tensor([t[1] for t in taps], device=dev)
@@ -363,7 +408,7 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
         xarg = (yv if yv is not None else torch.zeros(P, B, G, N, device=dev)).reshape(P, B, G, 1, N).contiguous()
         _, params = ops.cgp_rate(cat, xarg, cgp_packed, cgp_dims, want_params=True)   # (P,B,2G,1,N)
         sigma, mu = params[:, :, 0::2, 0, :], params[:, :, 1::2, 0, :]
-        yhat[:, :, :, h + R, w + R] = _finish_step(emodels[0], sink, sigma, mu, yv, step)
+        yhat[:, :, :, h + R, w + R] = _finish_step(emodels[0], sink, sigma, mu, yv, step, ra)
     out = yhat[:, :, :, R:-R, R:-R].contiguous()
     if sink.decoding:
         sink.finish()
@@ -373,7 +418,7 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
 ZT_PHASES = ((0, 0), (0, 1), (1, 0), (1, 1))        # ee, eo, oe, oo: (row, column) offset of phase k in the level
 
 
-def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None, coder="host", step=1.0):
+def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None, coder="host", step=1.0, rdo=None):
     """One finer level of DWTConditioned2EntropyLayerZTBlock (the reference's forward, LiftingBasedDWT_net.py:716-744, coded
     with compressai's GaussianConditional contract).  parent (P,B,3,h,w): the DECODED coarser level; y (P,B,3,2h,2w) the
     coefficients (encoder) or None (decoder); emodels: the GaussianConditional of each subband (build_indexes); packs[k]:
@@ -384,17 +429,19 @@ def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None, c
     coder over every stream.  Symbols inside a stream: phase ascending, then subband, then raster order over the phase grid.
     Index, symbol and the dequantised value written into the phase's positions of the level are one launch of
     lldwt_gauss_quantise per phase (two in the decoder: the indexes before the symbols are popped, the values after), with
-    the quantisation step of DESIGN.md 7.1.6; the three subbands' models carry one scale table.
+    the quantisation step of DESIGN.md 7.1.6; the three subbands' models carry one scale table.  rdo: the Lagrangian of DESIGN.md
+    7.1.7 for the encoder's launches (None or 0: off); the decoder ignores it.
     -> (strings or None, dequantised (P,B,3,2h,2w))."""
     P, B, G, H, W = shape
     h2, w2 = H // 2, W // 2
     lev = torch.zeros(P, B, G, H, W, device=parent.device, dtype=torch.float32)
     sink = _make_sink(coder, P, B, tables, strings, G * H * W, parent.device)
     table63 = emodels[0].scale_table.to(parent.device).float()[:63].contiguous()
+    ra = None if y is None else _rdo_args(rdo, tables, parent.device)
     for k, (r, c) in enumerate(ZT_PHASES):
         params = ops.ztblock_phase(parent, lev, packs[k], k + 1)
         if y is not None:
-            idx, sym = ops.gauss_quantise(params, table63, lev, r, c, 2, step, y=y)
+            idx, sym = ops.gauss_quantise(params, table63, lev, r, c, 2, step, y=y, rdo=ra)
             sink.step(idx.reshape(P, B, G * h2 * w2, 1), sym.reshape(P, B, G * h2 * w2, 1))
         else:
             idx, _ = ops.gauss_quantise(params, table63, None, r, c, 2, step)
@@ -463,16 +510,18 @@ def _code_factorized_device(emodels, y, shape, strings, coder):
     return (strs if strings is None else None), torch.stack(out, 0)
 
 
-def code_gaussian_parallel(emodels, params, y, shape, tables, strings=None, coder="host", step=1.0):
+def code_gaussian_parallel(emodels, params, y, shape, tables, strings=None, coder="host", step=1.0, rdo=None):
     """A level whose (sigma, mu) depend only on already decoded tensors (onlyEZWT: the tree context of the parent level,
     LiftingBasedDWT_net.py:822-835): fully parallel -- indexes and symbols of the whole tensor in one pass, raster order.
-    params (P,B,2C,h,w): sigma on the even, mu on the odd channels.  -> (strings or None, dequantised (P,B,C,h,w))."""
+    params (P,B,2C,h,w): sigma on the even, mu on the odd channels.  rdo: the Lagrangian of DESIGN.md 7.1.7 for the encoder's
+    launch (None or 0: off); the decoder ignores it.  -> (strings or None, dequantised (P,B,C,h,w))."""
     P, B, Cc, H, W = shape
     params = params.contiguous()
     table63 = emodels[0].scale_table.to(params.device).float()[:63].contiguous()
     out = torch.empty(P, B, Cc, H, W, device=params.device, dtype=torch.float32)
     if strings is None:                                 # index, symbol and value of the whole level: one launch
-        idx, sym = ops.gauss_quantise(params, table63, out, 0, 0, 1, step, y=y.contiguous())
+        idx, sym = ops.gauss_quantise(params, table63, out, 0, 0, 1, step, y=y.contiguous(),
+                                      rdo=_rdo_args(rdo, tables, params.device))
     else:
         idx, _ = ops.gauss_quantise(params, table63, None, 0, 0, 1, step)
     if coder != "host":

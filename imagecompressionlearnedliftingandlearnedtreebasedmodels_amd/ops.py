@@ -1021,15 +1021,61 @@ def step_pair(step):
     return q, float(torch.tensor(1.0 / q, dtype=torch.float32))
 
 
-def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=None):
+RDO_DENOM = 64                       # a Lagrangian of rate-distortion optimised quantisation is m / RDO_DENOM, m in [1, RDO_M_MAX]
+RDO_M_MAX = 256
+
+
+def rdo_scale(rdo):
+    """The Lagrangian rho of rate-distortion optimised quantisation, in units of q^2 per bit -> k, the Python
+    float holding fp32(rho) * 2^-16 that the kernels multiply a code-length difference (units of 2^-16 bit) with.  rho = m / 64
+    with an integer m in [1, 256] (exact in fp32, and so is k).  ValueError naming rdo otherwise."""
+    try:
+        rho = float(rdo)
+    except (TypeError, ValueError):
+        raise ValueError("rdo must be a number m / %d with an integer m in [1, %d] (got %r)" % (RDO_DENOM, RDO_M_MAX, rdo)) from None
+    m = rho * RDO_DENOM
+    if not (m == m and 1 <= m <= RDO_M_MAX and m == int(m)):
+        raise ValueError("rdo must be m / %d with an integer m in [1, %d], i.e. a multiple of %g in [%g, %g] (got %r)"
+                         % (RDO_DENOM, RDO_M_MAX, 1 / RDO_DENOM, 1 / RDO_DENOM, RDO_M_MAX / RDO_DENOM, rdo))
+    return rho / COST_ONE_BIT
+
+
+def rdo_choose(v, s0, cost0, cost1, k):
+    """The decision of DESIGN.md 7.1.7 in fp32 tensor ops (any device).  v: the rounded product (y - mu) * inv_q, s0 = round(v)
+    (float), cost0 / cost1: int32 code lengths of s0 and of s1 = s0 - sign(s0) in units of 2^-16 bit -> the chosen symbol
+    (float): s1 where (float)(cost0 - cost1) * k > 1 + 2 sign(s0) (v - s0), s0 elsewhere and wherever s0 == 0."""
+    g = torch.sign(s0)
+    t = 1.0 + 2.0 * g * (v - s0)                                   # v - s0 and 2 g r are exact
+    move = ((cost0 - cost1).float() * torch.tensor(k, dtype=torch.float32, device=v.device) > t) & (s0 != 0)
+    return torch.where(move, s0 - g, s0)
+
+
+def rdo_lookup(cost, sizes, offsets, idx, sym):
+    """cost[idx][sym - offsets[idx]] as lldwt_code_cost looks it up (COST_ESCAPE outside the table); int tensors of one device,
+    cost (T, width), idx / sym of one shape -> int32."""
+    T, width = cost.shape
+    idx = idx.long()
+    ok = (idx >= 0) & (idx < T)
+    ti = torch.where(ok, idx, torch.zeros_like(idx))
+    v = sym.long() - offsets.long()[ti]
+    ok &= (v >= 0) & (v < sizes.long()[ti] - 2) & (v < width)
+    got = cost[ti, torch.where(ok, v, torch.zeros_like(v))]
+    return torch.where(ok, got, torch.full_like(got, COST_ESCAPE)).int()
+
+
+def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=None, rdo=None):
     """The Gaussian quantiser with a step on a whole grid in one launch (lldwt_gauss_quantise).  params (P,B,2C,h,w): sigma on
     the even, mu on the odd channels; level (P,B,C,H,W): the positions (r0 + stride i, c0 + stride j) receive symbol * q + mu,
     the others are left alone.  Encoder: y (P,B,C,H,W) coefficients read at the same positions (may be level) -> (idx, sym),
     (P,B,C,h,w) int32.  Decoder: sym (P,B,C,h,w) int32 -> (idx, sym).  Neither (level None too): -> (idx, None), what the
-    decoder needs before it can pop the symbols.  table63: the scale table's first 63 entries."""
+    decoder needs before it can pop the symbols.  table63: the scale table's first 63 entries.
+    rdo: encoder only, (k, cost, sizes, offsets) -- k of rdo_scale and the int32 device tensors of cost_table /
+    entropy_coding.device_cost_tables: the symbols are chosen by the rule of DESIGN.md 7.1.7 (lldwt_gauss_quantise_rdo)."""
     P, B, C2, h, w = params.shape
     Cc = C2 // 2
     q, inv_q = step_pair(step)
+    if rdo is not None and y is None:
+        raise _lib.LLDWTError("gauss_quantise: rdo is a choice of the encoder (give y)")
     if (y is not None and sym is not None) or (level is None) != (y is None and sym is None):
         raise _lib.LLDWTError("gauss_quantise: give y (encoder) or sym (decoder) with level, or none of the three")
     if C2 != 2 * Cc or (level is not None and (level.dim() != 5 or tuple(level.shape[:3]) != (P, B, Cc))) or \
@@ -1044,6 +1090,18 @@ def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=Non
     idx = torch.empty(P, B, Cc, h, w, device=params.device, dtype=torch.int32)
     out = torch.empty_like(idx) if y is not None else None
     p = lambda t: C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+    if rdo is not None:
+        k, cost, sizes, offsets = rdo
+        for t in (cost, sizes, offsets):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+                raise _lib.LLDWTError("gauss_quantise: the rdo tables must be contiguous int32 device tensors")
+        if cost.dim() != 2 or sizes.numel() != cost.shape[0] or offsets.numel() != cost.shape[0]:
+            raise _lib.LLDWTError("gauss_quantise: rdo needs cost (T, width) with T sizes and offsets")
+        check(_lib.load().lldwt_gauss_quantise_rdo(_chk(params, "params"), _chk(y, "y"), _chk(table63, "table63"), p(idx), p(out),
+                                                   _chk(level, "level"), P * B, Cc, h, w, H, W, int(r0), int(c0), int(stride), q,
+                                                   inv_q, p(cost), p(sizes), p(offsets), cost.shape[0], cost.shape[1], float(k),
+                                                   _stream()), "gauss_quantise_rdo")
+        return idx, out
     check(_lib.load().lldwt_gauss_quantise(_chk(params, "params"), _opt(y, "y"), p(sym), _chk(table63, "table63"), p(idx), p(out),
                                            _opt(level, "level"), P * B, Cc, h, w, H, W, int(r0), int(c0), int(stride), q, inv_q,
                                            _stream()), "gauss_quantise")

@@ -545,6 +545,23 @@ int lldwt_wavefront_apply_q(const int* sym, const float* mu, float* yhat, int64_
 int lldwt_gauss_quantise(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
                          int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W,
                          int r0, int c0, int stride, float q, float inv_q, void* stream);
+/* Rate-distortion optimised quantisation: the ENCODER modes of the two quantisers above with the symbol chosen
+ * between the nearest level s0 = rint(v), v = fp32((y - mu) * inv_q), and s1 = s0 - sign(s0), one level toward zero:
+ *   sym = ((float)(cost[idx][s0] - cost[idx][s1]) * k > 1 + 2 sign(s0) (v - s0)) ? s1 : s0,   s0 == 0 stays
+ * cost (ntab, width), sizes, offsets: the int32 device tables of lldwt_code_cost with its lookup (a symbol outside its table
+ * counts 32 * 2^16); k = rho * 2^-16 with the Lagrangian rho = m / 64, m an integer in [1, 256], in units of q^2 per bit.  idx
+ * does not depend on the choice and yhat / level receive sym * q + mu of the chosen symbol, so the decoders (the entry points
+ * above with y == null, lldwt_wavefront_apply_q) follow without knowing.  y == null is LLDWT_EINVAL; mu and sigma_out of the
+ * wavefront step are outputs of its decoder mode and are not written. */
+int lldwt_cgp16_wavefront_step_rdo(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                   int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h,
+                                   int64_t w, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q,
+                                   float inv_q, const int32_t* cost, const int32_t* sizes, const int32_t* offsets, int32_t ntab,
+                                   int32_t width, float k, void* stream);
+int lldwt_gauss_quantise_rdo(const float* params, const float* y, const float* table63, int32_t* idx, int32_t* sym_out,
+                             float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W, int r0,
+                             int c0, int stride, float q, float inv_q, const int32_t* cost, const int32_t* sizes,
+                             const int32_t* offsets, int32_t ntab, int32_t width, float k, void* stream);
 /* Code length of `streams` streams of n (sym, idx) pairs under quantised tables, for the byte-target search: sums[z] += sum of
  * cost[idx][sym - offsets[idx]] with cost (ntab, width) int32 in units of 2^-16 bit, and esc_cost for a symbol outside
  * [0, sizes[idx] - 2) or an index outside [0, ntab), which escapes[z] counts.  sums and escapes (int64) must be ZERO on entry;

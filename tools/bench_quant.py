@@ -1,13 +1,15 @@
 """Kernel times of variable-rate coding on HIP events: lldwt_gauss_quantise and lldwt_code_cost at the
 level-0 shape of the BASELINE batch (8 x 3 x 512 x 512: 3 planes x 8 images x 3 subbands of 256 x 256).
 
-    python tools/bench_quant.py [--batch 8] [--size 512] [--reps 200]
+    python tools/bench_quant.py [--batch 8] [--size 512] [--reps 200] [--rdo 0.203125]
 
 Per kernel: the median (minimum - maximum) of --reps event-timed launches after a warm-up, and the achieved bytes/s with the
 bytes computed from the shapes: per coefficient the encoder reads sigma, mu and y and writes index, symbol and value
 (24 bytes), the decoder's two launches move 12 (sigma, mu -> index) and 20 (sigma, mu, symbol -> index, value), and the
 cost kernel reads a symbol and an index (8 bytes; its tables stay in cache).  ``pad`` is lldwt_u8hwc_to_ycc_pad on the same
-batch in the same process, the copy kernel the other sections of DESIGN.md use as their yardstick."""
+batch in the same process, the copy kernel the other sections of DESIGN.md use as their yardstick.  The ``rdo`` row is the
+encoder with rate-distortion optimised quantisation (lldwt_gauss_quantise_rdo): the same 24 bytes per
+coefficient plus two table lookups that stay in cache; the line after it gives what the choice does to the ideal code length."""
 import argparse
 import os
 import statistics
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--step", type=float, default=2.5)
+    ap.add_argument("--rdo", type=float, default=13 / 64)
     a = ap.parse_args()
     P, B, G, S = 3, a.batch, 3, a.size // 2
     g = torch.Generator().manual_seed(0)
@@ -77,6 +80,13 @@ def main():
     s2, i2 = sym.reshape(P * B, -1).contiguous(), idx.reshape(P * B, -1).contiguous()
     report("code_cost, %d streams" % (P * B), timed(lambda: ops.code_cost(s2, i2, *ct), a.reps), 8 * n)
     sums, esc = ops.code_cost(s2, i2, *ct)
+    ra = (ops.rdo_scale(a.rdo),) + tuple(ct)
+    report("gauss_quantise rdo encode, full grid", timed(lambda: ops.gauss_quantise(params, table, level, 0, 0, 1, a.step, y=y, rdo=ra), a.reps), 24 * n)
+    _, symr = ops.gauss_quantise(params, table, level, 0, 0, 1, a.step, y=y, rdo=ra)
+    sumr, _ = ops.code_cost(symr.reshape(P * B, -1).contiguous(), i2, *ct)
+    print("rdo %g: %.2f %% of the symbols moved, ideal code length %.0f -> %.0f bytes (%.2f %% saved)"
+          % (a.rdo, 100.0 * float((symr != sym).float().mean()), int(sums.sum()) / ops.COST_ONE_BIT / 8,
+             int(sumr.sum()) / ops.COST_ONE_BIT / 8, 100.0 * (1 - int(sumr.sum()) / int(sums.sum()))))
     bits, e = ec.ideal_bits(s2[0].cpu().numpy(), i2[0].cpu().numpy(), tabs)
     print("stream 0: %.1f bits + %d escapes (numpy: %.1f bits, %d escapes)" % ((int(sums[0]) - int(esc[0]) * ops.COST_ESCAPE)
                                                                                / ops.COST_ONE_BIT, int(esc[0]), bits, e))

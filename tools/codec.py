@@ -21,6 +21,9 @@
                                            (1: the trained operating point); decode reads the step from the header
     encode --target-bytes T | --target-bpp R   chooses the finest step of the quarter-octave grid whose container is at most
                                            T bytes (R bits per pixel: T = floor(R * H * W / 8)); info prints the step
+    encode --rdo R                         rate-distortion optimised quantisation with the Lagrangian R = m / 64 in (0, 4]
+                                           (q^2 per bit; try 0.203125 = 13 / 64): fewer bytes for a little more error.  The
+                                           encoder's choice alone: nothing in the container tells, decode needs no option
 
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
@@ -99,6 +102,8 @@ def main(argv=None):
     rate.add_argument("--step", type=float, metavar="Q", help="quantisation step n / 16 in [0.25, 64] (default 1)")
     rate.add_argument("--target-bytes", type=int, metavar="T", help="finest grid step whose container is at most T bytes")
     rate.add_argument("--target-bpp", type=float, metavar="R", help="the same for R bits per pixel")
+    sub.choices["encode"].add_argument("--rdo", type=float, metavar="R",
+                                       help="rate-distortion optimised quantisation, Lagrangian m / 64 in (0, 4] (default off)")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
                                        help="decode the base layer of a refined (LLDR) container only")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
@@ -160,6 +165,8 @@ def main(argv=None):
             kw["target_bytes"] = a.target_bytes
         elif a.target_bpp is not None:
             kw["target_bytes"] = codec.target_bpp_bytes(a.target_bpp, img.shape[0], img.shape[1])
+        if a.rdo is not None:
+            kw["rdo"] = a.rdo
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tile is None:

@@ -1,12 +1,13 @@
 """Rate-distortion table of the codec over quantisation steps, for one image and one net:
 
     python tools/rd_sweep.py --config cfg.json [--checkpoint ckpt.pth.tar] [--image in.png | --size 512]
-                             [--steps 0.25,0.5,1,2,4,8,16,32,64] [--coder host|gpu]
+                             [--steps 0.25,0.5,1,2,4,8,16,32,64] [--coder host|gpu] [--rdo R]
 
 Per step: container bytes, bits per pixel, PSNR and MS-SSIM of the decoded image (codec.quality), and the share of the
 container that the step cannot move -- the header, the xe streams and the streams of the coarsest level, which keep the unit
 step.  Without --image the input is a synthetic --size x --size image: smooth colour fields plus noise, seeded.  The config
-and checkpoint are those of tools/codec.py."""
+and checkpoint are those of tools/codec.py.  --rdo R: every encode with rate-distortion optimised quantisation at the Lagrangian
+R = m / 64; run the sweep with and without it to see what it buys at each step."""
 import argparse
 import json
 import os
@@ -37,12 +38,12 @@ def fixed_bytes(hdr):
     return hdr["header_bytes"] + 4 + sum(hdr["stream_lengths"]) - moved
 
 
-def sweep(net, img, steps, coder="host"):
-    """-> list of dicts (step, bytes, bpp, psnr, msssim, fixed_bytes), one per step."""
+def sweep(net, img, steps, coder="host", rdo=None):
+    """-> list of dicts (step, bytes, bpp, psnr, msssim, fixed_bytes), one per step.  rdo: the Lagrangian of DESIGN.md 7.1.7."""
     H, W = img.shape[1:3]
     rows = []
     for q in steps:
-        blob = codec.encode_images(net, img, coder=coder, step=q)[0]
+        blob = codec.encode_images(net, img, coder=coder, step=q, **({} if rdo is None else {"rdo": rdo}))[0]
         dec = codec.decode_images(net, [blob])[0]
         qual = codec.quality(img[0], dec)
         rows.append(dict(step=q, bytes=len(blob), bpp=len(blob) * 8 / (H * W), psnr=qual["psnr"], msssim=qual["msssim"],
@@ -58,12 +59,13 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--steps", default="0.25,0.5,1,2,4,8,16,32,64")
     ap.add_argument("--coder", choices=("host", "gpu"), default="host")
+    ap.add_argument("--rdo", type=float, metavar="R", help="rate-distortion optimised quantisation, Lagrangian m / 64 (default off)")
     ap.add_argument("--json", action="store_true", help="print one JSON line per step instead of the table")
     a = ap.parse_args(argv)
     from codec import _load_rgb, build_net            # tools/codec.py
     net = build_net(a.config, a.checkpoint)
     img = _load_rgb(a.image)[None] if a.image else synthetic(a.size)
-    rows = sweep(net, img, [float(v) for v in a.steps.split(",")], a.coder)
+    rows = sweep(net, img, [float(v) for v in a.steps.split(",")], a.coder, a.rdo)
     if a.json:
         for r in rows:
             print(json.dumps(r))

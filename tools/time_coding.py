@@ -1,10 +1,12 @@
 """Wall time of coding one 3x512x512 image with each coded entropy layer: compress + decompress from the strings.
 
-    python tools/time_coding.py [--step q]
+    python tools/time_coding.py [--step q] [--rdo R]
 
 --step q (default 1, the trained operating point): the quantisation step of DESIGN.md 7.1.6.  At 1 the timed call is
 net.compress(x), as this tool has always done; at any other step it is encode_strings_planes(step=q) followed by
-decode_strings_planes(step=q), the same two halves with the step passed down."""
+decode_strings_planes(step=q), the same two halves with the step passed down.
+--rdo R: the encoder half with rate-distortion optimised quantisation at the Lagrangian R = m / 64, through
+the two halves as well; the decoder half is the same call as without it."""
 import argparse
 import os
 import sys
@@ -21,15 +23,16 @@ from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd.utils.config im
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--step", type=float, default=1.0)
+ap.add_argument("--rdo", type=float, default=None)
 a = ap.parse_args()
 
 
 def code(net, x):
-    if a.step == 1.0:
+    if a.step == 1.0 and not a.rdo:
         return net.compress(x)
     B, _, H, W = x.shape
     x_pm = x.permute(1, 0, 2, 3).unsqueeze(2).contiguous()
-    s_xe, s_xo = encode_strings_planes(net.nets(), x_pm, step=a.step)
+    s_xe, s_xo = encode_strings_planes(net.nets(), x_pm, step=a.step, rdo=a.rdo)
     xhat = decode_strings_planes(net.nets(), s_xe, s_xo, H, W, B, step=a.step)
     len_xe = sum(byte_extractor(row) for row in s_xe)
     len_xo = sum(byte_extractor(row) for level in s_xo for row in level)
@@ -48,4 +51,4 @@ for ent in ("conditioned2ZTsepSubbands", "onlyEZWT", "DWTConditioned2EntropyLaye
         xhat, bxe, bxo = code(net, x)
         torch.cuda.synchronize()
         print(ent, "compress+decompress of one 3x512x512 image%s: %.2f s, %.3f bpp"
-              % ("" if a.step == 1.0 else " at step %g" % a.step, time.perf_counter() - t0, float(bxe + bxo)))
+              % (("" if a.step == 1.0 else " at step %g" % a.step) + (" with rdo %g" % a.rdo if a.rdo else ""), time.perf_counter() - t0, float(bxe + bxo)))
