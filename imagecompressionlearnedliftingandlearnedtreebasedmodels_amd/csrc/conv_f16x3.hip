@@ -24,6 +24,7 @@
 #include "common.h"
 #include "split_f16.h"
 #include "lifting_f16.h"      // split_precision(): the one-product fp16 / bf16 modes of the fused pair (lldwt_set_precision)
+#include "plc_fold.h"         // plc_fold_pays(): one workgroup per tile or per (tile, channel block) in k_plc_wino
 #include <string.h>
 #include <type_traits>
 
@@ -803,7 +804,7 @@ constexpr int W3_COLP = 144;                     // im2col pitch
 constexpr int W3_COL = W3_DUMP + 64;
 constexpr int W3_PP = W3_COL + 2 * F3_IH * 17 * W3_COLP;   // parent patch (F1_PP floats)
 constexpr int W3_BIAS = W3_PP + 1536;            // the workgroup's 128 output biases (zero without bias or beyond cout)
-constexpr int W3_LDS = W3_BIAS + F3_OCB * 4;     // 132,992 B
+constexpr int W3_LDS = W3_BIAS + 2 * F3_OCB * 4; // 133,504 B: two bias images, alternating by the pass over the channel blocks
 constexpr int W3_LDS_EARLIER = W3_BIAS;          // the earlier form has no bias image
 constexpr int W3_RING = 6;                       // weight steps in flight + 1 (12 % W3_RING == 0: the ring slot of a unit is
                                                  // the same in every chunk)
@@ -865,6 +866,12 @@ __device__ __forceinline__ void w3_row_mma3(f4_t& t0, f4_t& t1, f4_t& t2, const 
         : "=&v"(t0), "=&v"(t1), "=&v"(t2)
         : "v"(wl), "v"(wh), "v"(ch0), "v"(ch1), "v"(ch2), "v"(cl0), "v"(cl1), "v"(cl2));
 }
+// one accumulator value into a vector register, from the accumulator register it lives in (the caller keeps the MFMA's wait states)
+__device__ __forceinline__ float w3_acc_read(float v) {
+    float r;
+    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(r) : "a"(v));
+    return r;
+}
 // a lane's value from another lane of its 16-lane row (v_mov_b32 with a DPP control); a lane whose source lies outside the row
 // keeps OLD (BOUND = false) or takes zero (BOUND = true).  0x101 = row_shl:1 (lane i reads lane i + 1), 0x110 + k = row_shr:k
 // (lane i reads lane i - k)
@@ -885,18 +892,30 @@ __device__ __forceinline__ void w3_split4(const float (&v)[4], h4_t& hi, h4_t& l
 // wave per k-group, so that the tap offsets are constants and all four waves stay busy over the 340 pixels
 template <int G>
 __device__ __forceinline__ void w3_im2col_group(uint8_t* lds, const float* PP, float s_p, int lane) {
-    for (int px = lane; px < F3_NPX; px += 64) {
+    // six passes of 64 pixels, branch-free and unrolled: the 48 patch reads of a lane are in flight before the first split (as a loop,
+    // every pass was an LDS round trip of its own).  A lane past the last pixel repeats it: the same values to the same place.
+    constexpr int NP = (F3_NPX + 63) / 64;
+    float v8[NP][8];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int px = min(lane + 64 * k, F3_NPX - 1);
         const int ly = px / F3_IW, lx = px - ly * F3_IW;
-        uint8_t* dst = lds + W3_COL + ((lx & 1) * (F3_IH * 17) + ly * 17 + (lx >> 1)) * W3_COLP;
-        float v8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int k = 8 * G + j, q = k < 27 ? k : 26;         // k >= 27 meets zero weights
+            const int kk = 8 * G + j, q = kk < 27 ? kk : 26;      // k >= 27 meets zero weights
             const int dy = (q % 9) / 3, dx = q % 3;
-            v8[j] = PP[(q / 9) * 108 + ((ly + dy) >> 1) * 18 + ((lx + dx) >> 1)] * s_p;
+            v8[k][j] = PP[(q / 9) * 108 + ((ly + dy) >> 1) * 18 + ((lx + dx) >> 1)];
         }
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int px = min(lane + 64 * k, F3_NPX - 1);
+        const int ly = px / F3_IW, lx = px - ly * F3_IW;
+        uint8_t* dst = lds + W3_COL + ((lx & 1) * (F3_IH * 17) + ly * 17 + (lx >> 1)) * W3_COLP;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v8[k][j] *= s_p;
         half8 ch_, cl_;
-        split8v(v8, ch_, cl_);
+        split8v(v8[k], ch_, cl_);
         *reinterpret_cast<half8*>(dst + G * 16) = ch_;
         *reinterpret_cast<half8*>(dst + 64 + G * 16) = cl_;
     }
@@ -967,19 +986,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t z = blockIdx.z;
     const int plane = (int)(z / a.batch);
-    const int ocb = blockIdx.y;
+    // The current form folds the channel blocks of a pixel tile into one workgroup when the grid has one block in y (the host's
+    // choice, lldwt_plc_fused): pass p runs channel block p, and everything that depends on the tile only -- the parent patch, its
+    // |max|, the scales, the split im2col and the chunk-0 rows of the first conv -- is computed once.  With a grid of nocb blocks in
+    // y a workgroup runs one pass, as the earlier form always does.
+    const int nocb = (a.cout + F3_OCB - 1) / F3_OCB;
+    const int npass = (!EARLIER && gridDim.y == 1) ? nocb : 1;
+    int ocb = blockIdx.y;              // the channel block of the current pass
+// stamps are indexed by the logical channel block, so that the buffer has one layout whatever the grid
+#define W3_STAMP(i)                                                                                                     \
+    if (a.stamps && lane == 0)                                                                                          \
+        a.stamps[((((int64_t)blockIdx.z * nocb + ocb) * gridDim.x + blockIdx.x) * 4 + wave) * 16 + (i)] =               \
+            (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
     const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
     const int y0 = ty * F3_TH, x0 = tx * F3_TW;
     const int h = a.h, w = a.w;
     const int64_t hw = (int64_t)h * w;
 
-    F3_STAMP(0)
-    F3_STAMP(14)
+    W3_STAMP(0)
+    W3_STAMP(14)
     const uint8_t* pp = a.packed + (int64_t)plane * a.plane_bytes + f3_wino_off(a.cin, a.cout);
     const float su = *reinterpret_cast<const float*>(pp);
     const uint8_t* pk1 = a.packed1 + (int64_t)plane * a.plane_bytes1;
     const float* h1 = reinterpret_cast<const float*>(pk1);
     const float* bias1 = h1 + 16;
+    // The current form issues the parent patch's loads first.  vmcnt retires in order: behind the ten ring loads and the first conv's
+    // operands, the patch waited for all of them, and the patch is what the prologue needs first.
+    const int hp = h >> 1, wp_ = w >> 1;
+    const float* par = a.parent + z * 3 * (int64_t)hp * wp_;
+    static_assert(F1_PP <= 512, "two patch values per thread");
+    float pv[2] = {0.f, 0.f};
+    if constexpr (!EARLIER) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            // no branch around a load: at the join the compiler waits for it (threads past the patch's end load its last value again)
+            const int i = min(tid + 256 * k, F1_PP - 1);
+            const int ci = i / 108, rem = i - ci * 108, r = rem / 18, c = rem - r * 18;
+            const int Yp = (y0 >> 1) - 1 + r, Xp = (x0 >> 1) - 1 + c;
+            pv[k] = par[(int64_t)ci * hp * wp_ + min(max(Yp, 0), hp - 1) * wp_ + min(max(Xp, 0), wp_ - 1)];
+        }
+    }
     // the weight ring's first steps and the first conv's chunk-0 operands: in flight during the whole prologue
     const uint8_t* wbase = pp + F3_HDR + ((int64_t)(ocb * 4 + wave) * a.nch) * (W3_NST * F3_STEP_BYTES) + lane * 16;
     half8 ah[W3_RING], al[W3_RING];
@@ -1000,15 +1046,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     W3_FUSED_LOAD(0)
     // the second conv's bias goes through LDS: loaded here, its latency under the prologue; read back before the epilogue's first
     // store by an LDS read, which no store of the epilogue counts against
-    float bias2 = 0.f;
+    float bias2 = 0.f, bias2n = 0.f;   // bias2n: the next pass's values, loaded a pass ahead (pass 1's: here), for the other image
+#define W3_BIAS_LOAD(DST, OCB)                                                                                        \
+    {                                                                                                                 \
+        const int oc_ = (OCB) * F3_OCB + tid;                                                                         \
+        if (tid < F3_OCB && a.bias && oc_ < a.cout) DST = a.bias[plane * a.cout + oc_];                               \
+    }
     if constexpr (!EARLIER) {
-        const int oc = ocb * F3_OCB + tid;
-        if (tid < F3_OCB && a.bias && oc < a.cout) bias2 = a.bias[plane * a.cout + oc];
+        W3_BIAS_LOAD(bias2, ocb)
+        if (npass > 1) W3_BIAS_LOAD(bias2n, ocb + 1)
     }
 
     // ---- the parent patch (as in the direct kernel), then its split im2col for every patch pixel, once per tile
-    const int hp = h >> 1, wp_ = w >> 1;
-    const float* par = a.parent + z * 3 * (int64_t)hp * wp_;
     float* PP = reinterpret_cast<float*>(lds + W3_PP);
     float amax = 0.f;
 #pragma unroll
@@ -1016,7 +1065,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int ci = i / 108, rem = i - ci * 108, r = rem / 18, c = rem - r * 18;
         const int Yp = (y0 >> 1) - 1 + r, Xp = (x0 >> 1) - 1 + c;
         const bool in = Yp >= 0 && Yp < hp && Xp >= 0 && Xp < wp_;
-        const float v = par[(int64_t)ci * hp * wp_ + min(max(Yp, 0), hp - 1) * wp_ + min(max(Xp, 0), wp_ - 1)];
+        const float v = EARLIER ? par[(int64_t)ci * hp * wp_ + min(max(Yp, 0), hp - 1) * wp_ + min(max(Xp, 0), wp_ - 1)] : pv[i >> 8];
         const float vz = in ? v : 0.f;
         PP[i] = vz;
         amax = fmaxf(amax, fabsf(vz));
@@ -1032,7 +1081,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const float sx = 0.5f * pow2_scale<15>(amax * h1[1] + h1[2]);
     const float out_scale = (1.f / sx) * (1.f / su);
     const float inv1sx = (1.f / s_p) * (1.f / h1[0]) * sx;
-    F3_STAMP(12)                       // prologue stamps: 0 .. 12 the parent patch and its |max|, 12 .. 13 the split im2col,
+    W3_STAMP(12)                       // prologue stamps: 0 .. 12 the parent patch and its |max|, 12 .. 13 the split im2col,
                                        // 13 .. 2 the wait at its barrier, 2 .. 1 the chunk-0 rows and their barrier
     if constexpr (EARLIER) {
     for (int px = tid; px < F3_NPX; px += 256) {
@@ -1136,7 +1185,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }                                                                                                             \
     }
     if constexpr (!EARLIER) {
+        // pass 0's image, and pass 1's into the other one: both values were loaded at the kernel's start
         if (tid < F3_OCB) reinterpret_cast<float*>(lds + W3_BIAS)[tid] = bias2;
+        if (npass > 1 && tid < F3_OCB) reinterpret_cast<float*>(lds + W3_BIAS)[F3_OCB + tid] = bias2n;
     }
     // The current form's pieces, which the chunk loop deals over its units; every row has registers of its own (what is live is what
     // the order of the pieces makes live).  READ2 the two sets' im2col fragments; MMA2 / MMA3 (row 0 with the extra tile); ACT2 = bias +
@@ -1192,9 +1243,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         *reinterpret_cast<h4_t*>(d0_ + (XI) * xs_) = hi_;                                                             \
         *reinterpret_cast<h4_t*>(d0_ + (XI) * xs_ + lo_) = lo4_;                                                      \
     }
-    F3_STAMP(13)
+    W3_STAMP(13)
     __syncthreads();                   // the im2col is read across lanes
-    F3_STAMP(2)
+    W3_STAMP(2)
 
     floatx16 acc[4][4];                // [xi][N-tile]
 #define W3_ZERO_ACC()                                                                                                 \
@@ -1212,7 +1263,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
     } else {
         // chunk 0's rows as a pipeline: every fragment read in flight at once, then the three MMA statements, then the vector work;
-        // the accumulators are zeroed behind it, so that the rows' registers cost nothing
+        // the accumulators are zeroed behind it (at the head of pass 0), so that the rows' registers cost nothing
         ceh = *reinterpret_cast<const half8*>(lds + cole);
         cel = *reinterpret_cast<const half8*>(lds + cole + 64);
         W3_ROW_READ2(0) W3_ROW_READ2(1) W3_ROW_READ2(2)
@@ -1225,10 +1276,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         W3_ROW_STORE2(1, lds, 0) W3_ROW_STORE2(1, lds, 1) W3_ROW_STORE2(1, lds, 2) W3_ROW_STORE2(1, lds, 3)
         W3_ROW_ACT2(2, 0) W3_ROW_ACT2(2, 1) W3_ROW_SHIFT(2)
         W3_ROW_STORE2(2, lds, 0) W3_ROW_STORE2(2, lds, 1) W3_ROW_STORE2(2, lds, 2) W3_ROW_STORE2(2, lds, 3)
-        W3_ZERO_ACC()
     }
-#undef W3_ZERO_ACC
-    __syncthreads();
+    if constexpr (EARLIER) __syncthreads();      // the current form: at the head of pass 0, behind the zeroing
 
     // B fragment of N-tile n, filter row dy, xi: pair p of output row 2n + ((lane>>4)&1), channel half lane>>5
     const int boff = (((lane >> 4) & 1) * 64 + p) * 32 + (((lane >> 5) ^ (p >> 3)) * 16);
@@ -1244,8 +1293,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     //   - unit 11's own fragments (buf) are loaded in unit 10 and waited for in front of the barrier (the barrier's fence drains
     //     every LDS read of the wave), so no wave reads buf behind the barrier of chunk c;
     //   - the next stores into buf are chunk c + 1's, from its unit 3 on: behind that barrier in every wave.
-    // The last chunk has no successor: its unit 11 loads fragments of the unused staged image (inside the buffer; a branch around the
-    // eight reads would split the unit's scheduling region) and nothing consumes them.
+    // The last chunk of the last pass has no successor: its unit 11 loads fragments of the unused staged image (inside the buffer; a
+    // branch around the eight reads would split the unit's scheduling region) and nothing consumes them.
+    // Passes: the chunks of all passes form one sequence, g = pass * nch + chunk.  Chunk g reads buffer g & 1 and stages chunk g + 1
+    // into the other one, so the last chunk of a pass with a successor stages chunk 0 again (with one chunk: itself, into the other
+    // buffer), its unit 11 loads the next pass's first fragments, the first conv's operands wrap with it (loaded a chunk ahead:
+    // the chunk before the last loads chunk 0's, the last chunk 1's) and its units 7 .. 11 load the weight steps 0 .. 4 of the next
+    // channel block into the ring.  A later pass therefore starts with everything the loop's unit 0 needs in registers or in LDS:
+    // it zeroes its accumulators and moves wbase.
     half8 bh[2][4], bl[2][4];
 #define W3_BLOAD_AT(BB, U, SET)                                                                        \
         {                                                                                              \
@@ -1256,18 +1311,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 bl[SET][n] = *reinterpret_cast<const half8*>((BB) + W3_PART + off);                    \
             }                                                                                          \
         }
-    if constexpr (!EARLIER) W3_BLOAD_AT(lds + boff, 0, 0)
-    F3_STAMP(1)
+#pragma nounroll
+    for (int pass = 0; pass < npass; ++pass) {
+    const bool succ = !EARLIER && pass + 1 < npass;
+    if constexpr (!EARLIER) {
+        if (pass > 0) {
+            // a later pass: no patch, no |max|, no im2col, no chunk-0 rows (slots 12, 13, 2 close its empty prologue parts)
+            W3_STAMP(0)
+            W3_STAMP(14)
+            W3_STAMP(12)
+            W3_STAMP(13)
+            W3_STAMP(2)
+            wbase += (int64_t)4 * a.nch * (W3_NST * F3_STEP_BYTES);
+            bias2n = 0.f;
+            if (succ) W3_BIAS_LOAD(bias2n, ocb + 1)
+            // the pass's first fragments and the extra tile's are read again here, behind the epilogue, so that its registers are
+            // free of them: 40 fewer live across it, two LDS round trips per pass
+            W3_BLOAD_AT(lds + ((pass * a.nch) & 1) * W3_BUF + boff, 0, 0)
+            ceh = *reinterpret_cast<const half8*>(lds + cole);
+            cel = *reinterpret_cast<const half8*>(lds + cole + 64);
+        }
+        // every pass zeroes its accumulators here: defined at the head of the pass and dead behind its epilogue, they are not carried
+        // around the loop over the passes (zeroed in the prologue as well, they were, as copies of sixteen registers each, and spilled)
+        W3_ZERO_ACC()
+        if (pass == 0) {
+            __syncthreads();           // chunk 0's image is read across waves; the zeroing in front of it covers the waves' skew
+            W3_BLOAD_AT(lds + boff, 0, 0)
+        }
+    }
+    W3_STAMP(1)
     for (int chunk = 0; chunk < a.nch; ++chunk) {
-        if (chunk >= 2 && chunk < 16 && !(chunk & 1)) F3_STAMP(2 + (chunk >> 1))   // slot 2 is the prologue's
-        const int buf = chunk & 1;
+        if (chunk >= 2 && chunk < 16 && !(chunk & 1)) W3_STAMP(2 + (chunk >> 1))   // slot 2 is the prologue's
+        const int buf = EARLIER ? chunk & 1 : (pass * a.nch + chunk) & 1;
         const uint8_t* wp = wbase + (int64_t)chunk * (W3_NST * F3_STEP_BYTES);
+        // the ring steps that lie behind this chunk's twelve: the next chunk's, or steps 0 .. 4 of the next pass's channel block,
+        // which starts 4 nch chunks behind this one's; behind the last chunk of the last pass the 5 steps of padding
+        const uint8_t* wpn = wp + (succ && chunk + 1 == a.nch ? (int64_t)3 * a.nch * (W3_NST * F3_STEP_BYTES) : 0);
         const uint8_t* bb = lds + buf * W3_BUF + boff;
         uint8_t* sdst = lds + (buf ^ 1) * W3_BUF;
-        const int c1 = (chunk + 1 < a.nch ? chunk + 1 : chunk) * W3_CK;     // chunk being staged (last: itself, unused)
+        // chunk being staged (the last of a pass: chunk 0 for the next pass; the last of all: itself, unused)
+        const int c1 = (chunk + 1 < a.nch ? chunk + 1 : succ ? 0 : chunk) * W3_CK;
         // the current form loads the first conv's operands a chunk ahead, in unit 8, behind the last MMA and ACT that read the present
         // ones: the rows of the staged chunk then start in unit 0 and their pieces have units 2 .. 10
-        const int c2 = (chunk + 2 < a.nch ? chunk + 2 : a.nch - 1) * W3_CK;
+        int n2 = chunk + 2;
+        if (n2 >= a.nch) {
+            n2 = succ ? n2 - a.nch : a.nch - 1;
+            if (n2 >= a.nch) n2 -= a.nch;              // one chunk per pass
+        }
+        const int c2 = n2 * W3_CK;
 #define W3_BLOAD(U, SET) W3_BLOAD_AT(bb, U, SET)
         if constexpr (EARLIER) {
             W3_BLOAD(0, 0)
@@ -1277,8 +1368,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int u = 0; u < W3_NST; ++u) {
             const int xi = u & 3;
-            ah[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES);
-            al[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wp + (u + W3_RING - 1) * F3_STEP_BYTES + 1024);
+            const uint8_t* wr = u + W3_RING - 1 < W3_NST ? wp : wpn;
+            ah[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wr + (u + W3_RING - 1) * F3_STEP_BYTES);
+            al[(u + W3_RING - 1) % W3_RING] = *reinterpret_cast<const half8*>(wr + (u + W3_RING - 1) * F3_STEP_BYTES + 1024);
             if (u + 1 < W3_NST) W3_BLOAD(u + 1, (u + 1) & 1)
             if constexpr (EARLIER) {
                 if (u == 0) W3_FUSED_LOAD(c1)
@@ -1344,17 +1436,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W3_EXTRA_ACT
 #undef W3_ROW_SHIFT
 #undef W3_ROW_STORE2
-#undef W3_FUSED_LOAD
 
-    F3_STAMP(10)
+    W3_STAMP(10)
+    // the next pass's bias into the image this pass does not read: its last readers were the previous pass's epilogues, in front of
+    // this pass's barriers in every wave, and its next readers stand behind the next pass's.  (Pass 1's image is the prologue's:
+    // with two passes, the usual case, no wave waits here for a load)
+    if constexpr (!EARLIER) {
+        if (succ && pass > 0 && tid < F3_OCB) reinterpret_cast<float*>(lds + W3_BIAS)[((pass + 1) & 1) * F3_OCB + tid] = bias2n;
+    }
     // ---- epilogue: the inverse transform is lane-local (the four M_xi tiles share one layout): D col = lane&31 = pair p of
     // row 2n + ((lane>>4)&1), D row = (q&3) + 8*(q>>2) + 4*(lane>>5) = channel of the wave's 32.  Two adjacent pixels per
     // store (w is even, so a pair is either inside the image or wholly outside it)
+    // What the epilogue derives from the tile and the lane alone is the same in every pass, and the compiler would compute it once, in
+    // front of the loop over the passes: some 85 registers more that live through the chunk loop, which has none to spare (they went
+    // to scratch).  The current form takes these inputs through an empty assembly statement per pass: recomputed behind every chunk
+    // loop, as the single pass of the earlier form computes them.
+    int eh = h, ew = w, ey0 = y0, ex0 = x0, elane = lane;
+    if constexpr (!EARLIER) asm volatile("" : "+s"(eh), "+s"(ew), "+s"(ey0), "+s"(ex0), "+v"(elane));
+    const int64_t ehw = (int64_t)eh * ew;
+    const int ep = elane & 15;
     const int ocw = ocb * F3_OCB + __builtin_amdgcn_readfirstlane(wave) * 32;
-    const int och = 4 * (lane >> 5), orow = (lane >> 4) & 1;
-    float* ybase = a.y + (z * a.cout + ocw) * hw + (int64_t)y0 * w;                  // wave-uniform
-    const unsigned loff = (unsigned)och * (unsigned)hw + (unsigned)(orow * w + x0 + 2 * p);
-    const bool full = y0 + F3_TH <= h && x0 + F3_TW <= w;                            // uniform
+    const int och = 4 * (elane >> 5), orow = (elane >> 4) & 1;
+    float* ybase = a.y + (z * a.cout + ocw) * ehw + (int64_t)ey0 * ew;               // wave-uniform
+    const unsigned loff = (unsigned)och * (unsigned)ehw + (unsigned)(orow * ew + ex0 + 2 * ep);
+    const bool full = ey0 + F3_TH <= eh && ex0 + F3_TW <= ew;                        // uniform
     if constexpr (EARLIER) {
     // the activation and the bounds resolved outside the store loops (as in the direct kernel's epilogue)
 #define W3_EPI(COND, ACT0, ACT1)                                                                                      \
@@ -1362,11 +1467,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int ocq = (q & 3) + 8 * (q >> 2);                                                                       \
         if (ocw + ocq + och < a.cout) {                                                                               \
             const float bq = a.bias ? a.bias[plane * a.cout + ocw + ocq + och] : 0.f;                                 \
-            float* yq = ybase + (int64_t)ocq * hw + loff;                                                             \
+            float* yq = ybase + (int64_t)ocq * ehw + loff;                                                            \
             _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                                           \
                 const float v0 = (acc[0][n][q] + acc[1][n][q] + acc[2][n][q]) * out_scale + bq;                       \
                 const float v1 = (acc[1][n][q] - acc[2][n][q] - acc[3][n][q]) * out_scale + bq;                       \
-                if (COND) *reinterpret_cast<f2_t*>(yq + 2 * n * w) = f2_t{ACT0, ACT1};                                \
+                if (COND) *reinterpret_cast<f2_t*>(yq + 2 * n * ew) = f2_t{ACT0, ACT1};                               \
             }                                                                                                         \
         }                                                                                                             \
     }
@@ -1374,8 +1479,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const float slope = a.act == LLDWT_ACT_LRELU ? 0.01f : (a.act == LLDWT_ACT_RELU ? 0.f : 1.f);   // none: max(v, v)
         W3_EPI(true, fmaxf(v0, v0 * slope), fmaxf(v1, v1 * slope))
     } else {
-        const bool colin = x0 + 2 * p < w;        // w is even: a pair is either inside the image or wholly outside it
-        W3_EPI(colin && y0 + 2 * n + orow < h, act_apply(v0, a.act), act_apply(v1, a.act))
+        const bool colin = ex0 + 2 * ep < ew;     // w is even: a pair is either inside the image or wholly outside it
+        W3_EPI(colin && ey0 + 2 * n + orow < eh, act_apply(v0, a.act), act_apply(v1, a.act))
     }
 #undef W3_EPI
     } else {
@@ -1387,7 +1492,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // such a block waits for vmcnt(0) again.  An LDS read counts on lgkmcnt, which no store touches.
     float bq[16];
     {
-        const f4_t* bl = reinterpret_cast<const f4_t*>(lds + W3_BIAS + (__builtin_amdgcn_readfirstlane(wave) * 32 + och) * 4);
+        const f4_t* bl = reinterpret_cast<const f4_t*>(lds + W3_BIAS +
+                                                       ((pass & 1) * F3_OCB + __builtin_amdgcn_readfirstlane(wave) * 32 + och) * 4);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const f4_t b4 = bl[2 * k];                  // channels 8k + och .. + 3 of the wave's 32: q = 4k .. 4k + 3
@@ -1395,42 +1501,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int j = 0; j < 4; ++j) bq[4 * k + j] = b4[j];
         }
     }
+    // The accumulators stay where the matrix pipe wrote them and every value is read next to its use (w3_acc_read).  Left to the
+    // compiler, the epilogue's vector instructions pull all sixteen tiles into vector registers at the loop's exit, 256 at once, and
+    // with the ring and the first conv's operands live through the epilogue the overflow went to scratch.  The compiler does not
+    // see a read inside an assembly statement: the wait states between the last MFMA and the first read (19 for 16 passes) are here.
+    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 4");
     // the activation is resolved outside the store loops, one copy per activation and no branch per value: a block that only
     // some lanes run (a partial tile's store) makes the wait counters conservative for whatever follows it
+    // The five copies below start with the same 256 values (transform, scale, bias); taken as common code they are computed in front
+    // of the branch that picks a copy, 256 registers at once -- which a single pass had and a pass with a successor has not (the
+    // weight ring and the first conv's operands live through the epilogue).  Each copy takes the output scale through an empty
+    // assembly statement of its own, so that nothing is common and every value is formed next to its store.
 #define W3_EPI(COND, ACT0, ACT1)                                                                                      \
+    float os_ = out_scale;                                                                                            \
+    asm volatile("" : "+v"(os_));                                                                                     \
     _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                                  \
         const int ocq = (q & 3) + 8 * (q >> 2);                                                                       \
         if (ocw + ocq + och < a.cout) {                                                                               \
-            float* yq = ybase + (int64_t)ocq * hw + loff;                                                             \
+            float* yq = ybase + (int64_t)ocq * ehw + loff;                                                            \
             _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                                           \
-                const float v0 = (acc[0][n][q] + acc[1][n][q] + acc[2][n][q]) * out_scale + bq[q];                    \
-                const float v1 = (acc[1][n][q] - acc[2][n][q] - acc[3][n][q]) * out_scale + bq[q];                    \
-                if (COND) *reinterpret_cast<f2_t*>(yq + 2 * n * w) = f2_t{ACT0, ACT1};                                \
+                const float m0 = w3_acc_read(acc[0][n][q]), m1 = w3_acc_read(acc[1][n][q]);                           \
+                const float m2 = w3_acc_read(acc[2][n][q]), m3 = w3_acc_read(acc[3][n][q]);                           \
+                const float v0 = (m0 + m1 + m2) * os_ + bq[q];                                                        \
+                const float v1 = (m1 - m2 - m3) * os_ + bq[q];                                                        \
+                if (COND) *reinterpret_cast<f2_t*>(yq + 2 * n * ew) = f2_t{ACT0, ACT1};                               \
             }                                                                                                         \
         }                                                                                                             \
     }
     if (full && a.act != LLDWT_ACT_TANH) {
         const float slope = a.act == LLDWT_ACT_LRELU ? 0.01f : (a.act == LLDWT_ACT_RELU ? 0.f : 1.f);   // none: max(v, v)
-        W3_EPI(true, fmaxf(v0, v0 * slope), fmaxf(v1, v1 * slope))
+        { W3_EPI(true, fmaxf(v0, v0 * slope), fmaxf(v1, v1 * slope)) }
     } else {
-        const bool colin = x0 + 2 * p < w;        // w is even: a pair is either inside the image or wholly outside it
-#define W3_IN (colin && y0 + 2 * n + orow < h)
+        const bool colin = ex0 + 2 * ep < ew;     // w is even: a pair is either inside the image or wholly outside it
+#define W3_IN (colin && ey0 + 2 * n + orow < eh)
         // the four cases of act_apply, value for value
         if (a.act == LLDWT_ACT_TANH) {
-            W3_EPI(W3_IN, fast_tanh(v0), fast_tanh(v1))
+            { W3_EPI(W3_IN, fast_tanh(v0), fast_tanh(v1)) }
         } else if (a.act == LLDWT_ACT_LRELU) {
-            W3_EPI(W3_IN, v0 >= 0.f ? v0 : 0.01f * v0, v1 >= 0.f ? v1 : 0.01f * v1)
+            { W3_EPI(W3_IN, v0 >= 0.f ? v0 : 0.01f * v0, v1 >= 0.f ? v1 : 0.01f * v1) }
         } else if (a.act == LLDWT_ACT_RELU) {
-            W3_EPI(W3_IN, v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f)
+            { W3_EPI(W3_IN, v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f) }
         } else {
-            W3_EPI(W3_IN, v0, v1)
+            { W3_EPI(W3_IN, v0, v1) }
         }
 #undef W3_IN
     }
 #undef W3_EPI
     }
-    F3_STAMP(11)
-    F3_STAMP(15)
+    W3_STAMP(11)
+    W3_STAMP(15)
+    ++ocb;
+    }   // pass
+#undef W3_FUSED_LOAD
+#undef W3_BIAS_LOAD
+#undef W3_ZERO_ACC
+#undef W3_STAMP
 }
 #undef F3_STAMP
 
@@ -1579,7 +1704,8 @@ extern "C" int lldwt_plc_fused_pack1(const float* w1, const float* b1, void* pac
 static unsigned long long* g_f3_stamps = nullptr;
 static int64_t g_f3_stamps_bytes = 0;
 namespace lldwt { void f3_set_stamps(void* p, int64_t nbytes) { g_f3_stamps = reinterpret_cast<unsigned long long*>(p); g_f3_stamps_bytes = p ? nbytes : 0; } }
-// diagnostics flags of the pair (lldwt_set_diagnostics kind 1; read per launch): bit 0 = k_plc_wino in its earlier form
+// diagnostics flags of the pair (lldwt_set_diagnostics kind 1; read per launch): bit 0 = k_plc_wino in its earlier form; bit 1 =
+// k_plc_wino with one workgroup per (tile, channel block); bit 2 = one workgroup per tile at any size (lldwt_plc_fused)
 static int g_f3_flags = 0;
 namespace lldwt { void f3_set_debug(int flags) { g_f3_flags = flags; } }
 
@@ -1630,7 +1756,20 @@ extern "C" int lldwt_plc_fused(const float* parent, float* y, const void* packed
         }
         a.nch = w3_nch(cmid);
         if (g_f3_flags & 1) hipLaunchKernelGGL(k_plc_wino<true>, grid, dim3(256), W3_LDS_EARLIER, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(k_plc_wino<false>, grid, dim3(256), W3_LDS, (hipStream_t)stream, a);
+        else {
+            // One workgroup per pixel tile that loops over the tile's channel blocks (grid.y = 1), or one per (tile, channel block).
+            // With n = tiles x images, T a single-block workgroup's time and s what a later pass saves, the fold pays when
+            // ceil(n / CUs) (nocb T - (nocb - 1) s) < ceil(nocb n / CUs) T (plc_fold.h; s / T = 0.09 from the stamps of round 11).
+            // Diagnostics flags: bit 1 forces one workgroup per block, bit 2 the fold.
+            static const int cus = [] {
+                int dev = 0, n = 0;
+                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+                return n;
+            }();
+            const bool fold = (g_f3_flags & 2) ? false : (g_f3_flags & 4) ? true : plc_fold_pays((int64_t)grid.x * grid.z, cus, (int)grid.y);
+            if (fold) grid.y = 1;
+            hipLaunchKernelGGL(k_plc_wino<false>, grid, dim3(256), W3_LDS, (hipStream_t)stream, a);
+        }
     } else if (g_f3_shape16) {
         if (prec == 1) hipLaunchKernelGGL((k_conv3_f16x3<2, 1, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);
         else if (prec == 2) hipLaunchKernelGGL((k_conv3_f16x3<2, 2, true>), grid, dim3(256), F1_LDS, (hipStream_t)stream, a);

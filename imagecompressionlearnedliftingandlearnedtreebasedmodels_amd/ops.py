@@ -59,7 +59,8 @@ _diag_keep = {}
 
 def set_diagnostics(kind, stamps=None, flags=0):
     """Diagnostics hook of the split-fp16 kernels (lldwt_set_diagnostics; tools/*_stamps.py and the composed-vs-sequential
-    tests only): kind 0 = fused lifting step (flags = its debug mask), 1 = tree-pair conv, 2 = cgp chain (flags: bound-only variant /
+    tests only): kind 0 = fused lifting step (flags = its debug mask), 1 = tree-pair conv (flags: 1 = k_plc_wino in its
+    earlier form, 2 = one workgroup per (tile, channel block), 4 = one workgroup per tile at any size), 2 = cgp chain (flags: bound-only variant /
     forced form of cgp16_params, include/lldwt.h).  ``stamps``: an
     int64 device tensor the kernels write s_memtime stamps into (kept alive here until it is replaced), None = off."""
     _diag_keep[kind] = stamps

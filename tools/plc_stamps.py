@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """Diagnostic: in-kernel clock stamps (s_memtime) of the fused tree-context pair (k_conv3_f16x3<2>) at the level-0 shape of
 BASELINE configs[2] (3 planes x 8 images, parent 128 x 128 -> 243 channels at 256 x 256).  The kernel writes stamps only
-when a stamp buffer is registered through lldwt_set_diagnostics (this tool).  Two legs: the kernel as it is, and k_plc_wino in its
-earlier form (diagnostics flag 1); per leg the prologue (k_plc_wino: in four parts), the cycles per 32 channels and per chunk and what of
-them is not matrix time, the epilogue, the in-kernel clock and the workgroup's cycles.   python tools/plc_stamps.py"""
+when a stamp buffer is registered through lldwt_set_diagnostics (this tool).  Three legs: the kernel as it is (one workgroup per
+pixel tile that loops over the tile's channel blocks, where the host's rule folds the launch), k_plc_wino with one workgroup per
+(tile, channel block) (diagnostics flag 2) and in its earlier form (flag 1); per leg the prologue (k_plc_wino: in four parts), the
+cycles per 32 channels and per chunk and what of them is not matrix time, the epilogue, the in-kernel clock and the workgroup's
+cycles.  A folded leg reports pass 0 and the later passes apart (a pass stamps into the slots of its channel block, so the buffer
+has one layout in every leg), and their sum per tile.   python tools/plc_stamps.py"""
 import json
 import os
 import sys
@@ -50,6 +53,25 @@ def main():
         s = st.cpu().numpy().astype(np.int64)
         matrix = matrix_cycles(flags)
         res = {"workgroups": nwg, "algo": ops.plc_algo(), "flags": flags}
+        # [image][channel block][tile][wave][slot]; folded: channel block 1 of a tile is a later pass, with next to no prologue (its
+        # start time says nothing: unfolded, a tile's second workgroup is dispatched a round later, as its first one ends)
+        s5 = s.reshape(P * B, 2, nwg // (2 * P * B), 4, 16)
+        folded = bool(wino and (s5[:, 1, ..., 1] - s5[:, 1, ..., 0]).mean() < 0.25 * (s5[:, 0, ..., 1] - s5[:, 0, ..., 0]).mean())
+        res["folded"] = folded
+        if folded:
+            def part(x):
+                pro = np.diff(x[..., [0, 12, 13, 2, 1]], axis=-1).mean(axis=tuple(range(x.ndim - 1)))
+                ch = np.diff(x[..., [1, 3, 4, 5, 6, 7, 8, 9, 10]], axis=-1).mean(axis=tuple(range(x.ndim - 1)))
+                return {"prologue": float((x[..., 1] - x[..., 0]).mean()),
+                        "prologue_parts": {"parent patch + abs-max": float(pro[0]), "im2col": float(pro[1]),
+                                           "wait at the im2col barrier": float(pro[2]), "chunk-0 rows / zeroing + barrier": float(pro[3])},
+                        "per_16_channel_chunk": float(ch.mean()) / 2, "epilogue": float((x[..., 11] - x[..., 10]).mean()),
+                        "pass_total": float((x[..., 11] - x[..., 0]).mean()),
+                        "pass_us_median": float(np.median(x[..., 15] - x[..., 14]) / 100.0)}
+            res["passes"] = {"pass 0": part(s5[:, 0]), "later passes": part(s5[:, 1:])}
+            res["passes"]["between the passes (stamp 11 of a pass to stamp 0 of the next)"] = float((s5[:, 1, ..., 0] - s5[:, 0, ..., 11]).mean())
+            res["passes"]["sum over a tile's passes (stamp 0 of pass 0 to stamp 11 of the last)"] = float((s5[:, 1, ..., 11] - s5[:, 0, ..., 0]).mean())
+            res["tile_us_median"] = float(np.median(s5[:, 1, ..., 15] - s5[:, 0, ..., 14]) / 100.0)
         if wino:
             # k_plc_wino: slot 1 at the loop's entry, slots 3 .. 9 at its chunks 2, 4 .. 14, slot 10 behind the loop: eight spans of
             # two 16-channel chunks.  Slots 12, 13, 2 split the prologue (0 .. 1) into four parts
@@ -84,14 +106,24 @@ def main():
         t0, t1 = s[..., 14].min(), s[..., 15].max()
         res["launch_span_us"] = float((t1 - t0) / 100.0)
         res["sum_wg_duration_over_span_per_cu"] = float(((s[:, 0, 15] - s[:, 0, 14]).sum() / 100.0) / ((t1 - t0) / 100.0) / 256)
+        # the CU time of the launch that no workgroup's stamps 14 .. 15 cover, per workgroup started (per tile when folded): start, end
+        # and the last, partly filled round together -- an upper bound on the gap between two workgroups on a CU
+        started = nwg // 2 if folded else nwg
+        res["uncovered_cu_us_per_workgroup_started"] = float((256 * (t1 - t0) - (s[:, 0, 15] - s[:, 0, 14]).sum()) / 100.0 / started)
         res["wave_skew_at_loop_end_cycles"] = float((s[..., 10].max(axis=-1) - s[..., 10].min(axis=-1)).mean())
         return res
 
     # the current form, then (diagnostics flag 1) k_plc_wino in its earlier form: the A/B leg.  The direct kernel has one form
     legs = {"current": leg(0)}
     if wino:
+        legs["one workgroup per channel block (flag 2)"] = leg(2)
         legs["earlier (flag 1)"] = leg(1)
     for name, r in legs.items():
+        if r.get("folded"):
+            for pn in ("pass 0", "later passes"):
+                q = r["passes"][pn]
+                print("%-18s %-12s prologue %6.0f  per chunk %6.0f  epilogue %6.0f  pass %7.0f cycles" % (
+                    name, pn, q["prologue"], q["per_16_channel_chunk"], q["epilogue"], q["pass_total"]), file=sys.stderr)
         if wino:
             pp = r["mean_cycles_per_wave"]["prologue_parts"]
             print("%-18s prologue parts: %s; per 16-channel chunk %.0f (outside the 144 main MFMAs %.0f)" % (
