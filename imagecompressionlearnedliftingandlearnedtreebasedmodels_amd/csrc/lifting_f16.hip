@@ -114,8 +114,11 @@ static_assert(DPIECE_BYTES + T3V_PER * LF_C * 4 <= (N1 - KEEP1 * R1W) * 16, "D q
 static_assert(10 * NTH * 4 <= 4 * T2HALF && 2 * T2HALF == (N2 - KEEP2 * R2W) * 16, "a staging quarter fits half of the dying rows of a T2 array");
 static_assert(4 * T3V_PER >= 4 * R3W + 4 * (TH + 4), "the strip buffer holds every tile's border strips");
 constexpr int LDS_W4L = LDS_TOTAL;                                    // conv4's fp32 weights [tap][channel] (border tiles)
-constexpr int LDS_TOTAL2 = LDS_W4L + LF_KK * LF_C * 4;                // 160 960 B
+constexpr int LDS_CORR = LDS_W4L + LF_KK * LF_C * 4;                  // the border correction of each tile pixel, at the pixel's own
+constexpr int LDS_TOTAL2 = LDS_CORR + TH * TW * 4;                    // slot: aliases no image, so the sums need not wait.  163 008 B
 static_assert(LDS_TOTAL2 <= 160 * 1024, "one workgroup per CU");
+// ints of the RED scratch block behind the |max| slots: the next run (QN), the waves whose strips are written, the sum passes dealt
+constexpr int RED_QN = 16, RED_RDY = 17, RED_PASS = 18;
 constexpr float ACT_SCALE = 16384.f;                                  // tanh outputs: |t| <= 1 -> |t * 2^14| < fp16 max
 
 __device__ __forceinline__ void split4(const float (&v)[4], half4& hi, half4& lo) { split4v(v, hi, lo); }
@@ -714,8 +717,42 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     (void)st1_lo; (void)st1_hi; (void)st2_lo; (void)st2_hi;
     int next_item = item_i;
     const int next_j = hand_down ? run_j + 1 : 0;
-    int* QN = reinterpret_cast<int*>(lds + LDS_RED) + 16;       // the run this workgroup takes next (broadcast through LDS)
+    int* QN = reinterpret_cast<int*>(lds + LDS_RED) + RED_QN;   // the run this workgroup takes next (broadcast through LDS)
     if (!hand_down && tid == 0) *QN = (int)gridDim.x + atomicAdd(&g_lf_queue[a.qslot][0], 1);
+    // border tiles of the composed path: RDY counts the waves whose strip values are written, PASS deals the passes of the
+    // correction sums (both idle since the barrier that ended the tile before; the barriers of P0 publish the zeros)
+    int* RDY = reinterpret_cast<int*>(lds + LDS_RED) + RED_RDY;
+    int* PASS = reinterpret_cast<int*>(lds + LDS_RED) + RED_PASS;
+    if (!SEQ && tid == 0) { *RDY = 0; *PASS = 0; }
+    // Diagnostics flag 128: the tile as it was before the sums left the critical path -- composite, barrier, sums, barrier, finish,
+    // and every MFMA tile of conv1 / conv2 computed whether or not one of its pixels lies inside the image (same output bits;
+    // the A/B leg of tools/lift_stamps.py and the reference of tests/test_gpu_lift_border_overlap.py).
+    // Composed path without that flag: region rows above the image (tile at y0 == 0: t1 rows 0..5, t2 rows 0..3) and below it (bottom tile of a
+    // column: t1 rows from h - y0 + 6, t2 rows from h - y0 + 4) hold zeros.  The MFMA tiles (16 flattened pixels, they may straddle a
+    // row) whose pixels ALL lie in such rows are not computed: conv1 / conv2 run on tiles [lo, hi) of their region (width RW, NT
+    // tiles, PADR rows of halo above the tile; a continuing tile starts at tile LOC) and the other pixels are zeroed here.  (The
+    // computed value of such a pixel is +-0, the fill is +0: an operand of either sign leaves every accumulator bit alone.)
+    // Formed where they are used, in P1 and again in P2: scalars carried across the phases would cost registers the phases need.
+    auto tile_range = [&](int base, int arr_bytes, int RW, int NT, int PADR, int LOC, int& lo, int& hi) {
+        lo = cont ? LOC : 0;
+        hi = NT;
+        if (SEQ || (a.dbg & 128)) return;
+        const int rb = h - y0 + PADR;                                           // the first region row below the image
+        if (y0 == 0) lo = (PADR * RW) / 16;                                     // a first tile: lo was 0
+        if (rb < TH + 2 * PADR) hi = max((rb * RW + 15) / 16, lo + 1);
+        typedef unsigned uintx4_t __attribute__((ext_vector_type(4)));
+        constexpr int NARR = PREC == 0 ? 4 : 2;                                 // one product: the two hi arrays only
+        const int ntop = y0 == 0 ? lo * 16 : 0, nbot = (NT - hi) * 16;          // pixels to zero in every array
+        if (ntop + nbot == 0) return;                                           // (a scalar branch: most tiles)
+        unsigned zr = 0u;                       // opaque: four zero registers formed here, not kept alive around the tile loop
+        asm volatile("" : "+s"(zr));
+        const uintx4_t zero4 = {zr, zr, zr, zr};
+        for (int px = tid; px < ntop + nbot; px += NTH) {
+            uint8_t* d = lds + base + (px < ntop ? px : hi * 16 + px - ntop) * 16;
+#pragma unroll
+            for (int arr = 0; arr < NARR; ++arr) *reinterpret_cast<uintx4_t*>(d + arr * arr_bytes) = zero4;
+        }
+    };
     const int64_t stamp_tile = (z * a.tiles_y + y0 / TH) * a.tiles_x + x0 / TW;
     int64_t zv;
     const LiftF16Views vout = view_of_z(z, zv);
@@ -896,8 +933,10 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (!(a.dbg & 1)) {
         // a continuing tile computes rows 12..27 only (tiles 33..76)
         // (sequential path: rows 8..27, tiles 22..76 -- T1 itself is not handed down there)
-        const int nt1 = cont ? (SEQ ? NT1S : NT1C) : NT1, tb1 = NT1 - nt1;
-        const int nit1 = (nt1 + 2 * NWAVE - 1) / (2 * NWAVE);           // 5, or 3 (sequential path: 4)
+        int lo1, hi1;
+        tile_range(LDS_T1, T1A, R1W, NT1, 6, NT1 - (SEQ ? NT1S : NT1C), lo1, hi1);
+        const int nt1 = hi1 - lo1, tb1 = lo1;
+        const int nit1 = (nt1 + 2 * NWAVE - 1) / (2 * NWAVE);           // 5, or 3 (sequential path: 4); fewer at the image's top / bottom
 
         float mx1 = 0.f;                        // BWD: max |dt3| x act1 over this wave's values (for the weight gradient's dY scale)
 #pragma unroll 1
@@ -963,6 +1002,8 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // ---------------- P2: t2 = tanh(conv2(t1) + b2) on 24 x 40
     {
+        int lo2, hi2;
+        tile_range(LDS_T2, T2A, R2W, NT2, 4, NT2 - NT2C, lo2, hi2);
         half8 ah[LF_KS], al[LF_KS];
 #pragma unroll
         for (int ks = 0; ks < LF_KS; ++ks) ldA<PREC>(frag, LF_H_C2 / LF_FRAG + ks, lane, ah[ks], al[ks]);
@@ -981,8 +1022,12 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // a continuing tile computes rows 8..23 only (tiles 20..59): 5 tiles per wave = two pairs and a single one; a first
         // tile 60 = four pairs (the last one half empty for waves 4..7)
         static_assert(NT2C == 5 * NWAVE, "a continuing tile: two pairs and one single conv2 tile per wave");
-        const int nt2 = cont ? NT2C : NT2, tb2 = NT2 - nt2;
-        const int nit2 = cont ? 2 : (NT2 + 2 * NWAVE - 1) / (2 * NWAVE);
+        // at the image's top / bottom (see lo2, hi2 above) the same two shapes with fewer pairs: whole pairs, then a single tile
+        // per wave if at most NWAVE tiles are left, a last pair otherwise
+        const int nt2 = hi2 - lo2, tb2 = lo2;
+        const int rem2 = nt2 & (2 * NWAVE - 1);
+        const bool single = nt2 > NWAVE && rem2 > 0 && rem2 <= NWAVE;               // a continuing tile: 40 = 2 pairs + single
+        const int nit2 = nt2 <= NWAVE ? 1 : nt2 / (2 * NWAVE) + (rem2 > NWAVE);     // a first tile: 60 = 4 pairs
         auto tile_base = [&](int tile, int& p_out) {
             const int tcl = tb2 + (tile < nt2 ? tile : nt2 - 1);       // past the end: the last tile again (same bytes stored twice)
             const int p = tcl * 16 + pl;
@@ -1060,10 +1105,10 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 pdup[0] = wave + 16 * it >= nt2;
                 pdup[1] = wave + 16 * it + NWAVE >= nt2;
             }
-            if (cont) {
+            if (single) {
                 floatx4 n0;
                 int q0;
-                const int b0 = tile_base(wave + 4 * NWAVE, q0);
+                const int b0 = tile_base(wave + 16 * nit2, q0);
                 conv16_tile1<R1W, N1, PREC>(lds + LDS_T1, b0, hi_tap, ah, al, n0, slice);
                 if constexpr (SEQ) {            // TRAIN / BWD: the single tile's epilogue is a pair's first half (gates, saved tensors, maxima)
                     pc[0] = n0; pp[0] = q0; pin[0] = in_image(q0); pdup[0] = false;
@@ -1110,6 +1155,12 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // diagnostics flag 64: the border correction as it was before the k-step mask of the strips and the quarter-wave form of the
     // correction sums (same output bits; kept for A/B timing and as the reference of tests/test_gpu_lift_border.py)
     const bool legacy_border = (a.dbg & 64) != 0;
+    // a border tile's correction sums read the strips' t3v and W4L only, both written before the composite loop, and write CORR,
+    // which aliases nothing: every wave turns to them straight after its own composite tiles, as soon as the strips of all waves
+    // are there, instead of behind a barrier that waits for the slowest wave's composite.  The waves that held no strip tile get
+    // there first and take most of the passes (dealt by a counter), while the others are still in the composite loop.
+    // Flags 64 and 128 keep the order composite, barrier, sums.
+    const bool sums_early = !SEQ && !interior && (a.dbg & (64 | 128)) == 0;
     // strips in t3-region coordinates (20 x 36, origin (y0 - 2, x0 - 2)): rows / columns whose image coordinate is
     // -2, -1 or h, h + 1 (w, w + 1)
     int nR = 0, nC = 0, Rl0 = 0, Rl1 = 0, Rl2 = 0, Rl3 = 0, Cl0 = 0, Cl1 = 0, Cl2 = 0, Cl3 = 0;   // scalars, not arrays: no stack
@@ -1195,6 +1246,12 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int q = 0; q < 4; ++q) v[q] = acc[q] * inv3 + accr[q] * inv1 + bv[q];
                 if (j < nF) *reinterpret_cast<floatx4*>(T3Vp(j) + oc0) = v;
             }
+            // this wave's share of W4L and of the strips is written: the correction sums (behind the composite loop) read them as
+            // soon as all eight waves have said so -- no barrier, so a wave without a strip tile is not held up by the others' strips
+            if (sums_early) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                if (lane == 0) __hip_atomic_fetch_add(RDY, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
         }
         float rs = 0.f;
         {
@@ -1253,14 +1310,21 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
         LF_STAMP(7)
-        __syncthreads();
+        if (!sums_early) __syncthreads();       // (sums_early: the one barrier in front of the finish follows the sums)
         LF_STAMP(8)
         // ---- border tiles: CORR[a] = sum over the conv4 taps of affected pixel a that land outside the image of
         // sum_oc w4[oc][tap] * t3v[position][oc].  Affected pixels (within two of an image edge): the tile's affected rows RA in
         // full, then the affected columns CA of the other rows.  Half a wave per pixel, one lane per tap (25 of 32 lanes), the 32
         // partial sums reduced by a fixed shuffle tree: every lane takes part, and the summation order does not depend on scheduling.
         int nRA = 0, nCA = 0, RA0 = 0, RA1 = 0, RA2 = 0, RA3 = 0, CA0 = 0, CA1 = 0, CA2 = 0, CA3 = 0, rlo = 0;
-        float* CORR = reinterpret_cast<float*>(lds + LDS_T2);   // rows 0..7 of T2 array 0 are dead after the composite loop (5 120 B)
+        float* CORR = reinterpret_cast<float*>(lds + LDS_CORR);
+        // a pass = four pixels.  sums_early: the next pass not yet taken by any wave (which wave sums a pixel does not enter its
+        // sum), once every wave's strips are visible; otherwise the fixed deal behind the barrier
+        auto next_pass = [&]() {
+            int v = 0;
+            if (lane == 0) v = __hip_atomic_fetch_add(PASS, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            return 4 * __builtin_amdgcn_readfirstlane(v);
+        };
         if (!interior) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                       // image rows / columns 0, 1, h-2, h-1 (w-2, w-1) that lie in this tile
@@ -1323,7 +1387,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 // the lanes, so lane 0 adds the same two operands whichever way the rotation turns).  Twice the pixels per pass
                 // of a wave and no LDS round trip per level; the result lands at the pixel's own slot of the tile, CORR[oy * TW + ox].
                 const int qp = lane_c >> 4, l16 = lane_c & 15;
-                for (int a0 = wave * 4; a0 < nA; a0 += 4 * NWAVE) {
+                if (sums_early) {
+                    while (__hip_atomic_load(RDY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < NWAVE) __builtin_amdgcn_s_sleep(1);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                }
+                for (int a0 = sums_early ? next_pass() : wave * 4; a0 < nA; a0 = sums_early ? next_pass() : a0 + 4 * NWAVE) {
                     const int ai = a0 + qp;
                     float u2[2] = {0.f, 0.f};
                     int slot = 0;
@@ -1368,8 +1436,8 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     if (l16 == 0 && ai < nA) CORR[slot] = u;
                 }
             }
-            __syncthreads();
         }
+        if (!interior) __syncthreads();
         {
             const int oy = tid / TW, ox = tid - oy * TW;
             const int gy = y0 + oy, gx = x0 + ox;

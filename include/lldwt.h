@@ -148,7 +148,10 @@ int lldwt_get_precision(void);
  * nbytes ignores the buffer.  flags, kind 0: debug mask -- bit 0..3 skip a phase (results are then wrong),
  * 16 = sequential conv3 / conv4 for every tile (the check of the composed 9x9 kernel), 32 = no vertical reuse
  * between the tiles of a column, 64 = the border tiles' strip correction in its earlier form (every k-step of the strip
- * convolutions, half a wave per corrected pixel): same output bits, kept for A/B timing and as a test reference.
+ * convolutions, half a wave per corrected pixel): same output bits, kept for A/B timing and as a test reference;
+ * 128 = the tile as it was before the correction sums left the critical path: the sums behind a barrier that follows the
+ * composite loop (flag 64 implies this order too), and every MFMA tile of conv1 / conv2 computed at the top and bottom of the
+ * image although all its pixels lie outside it: same output bits, the A/B leg of tools/lift_stamps.py and a test reference.
  * flags, kind 1: bit 0 = the Winograd pair kernel (k_plc_wino) in its earlier form -- the epilogue that loads each bias value
  * between the stores and waits for them, the first conv's ACT and STORE stages whole inside one unit of the chunk loop, eight
  * vector instructions offered per MFMA gap: same output bits, kept for A/B timing (tools/plc_stamps.py) and as a test reference.

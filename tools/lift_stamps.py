@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Diagnostic: in-kernel clock stamps (s_memtime) of the fused lifting step at the level-0 row-pass shape of BASELINE
 configs[2]: per-phase cycles of every wave, barrier waits, in-kernel clock.  The kernel writes stamps only when
-a stamp buffer is registered through lldwt_set_diagnostics (this tool); a normal run executes none.   python tools/lift_stamps.py"""
+a stamp buffer is registered through lldwt_set_diagnostics (this tool); a normal run executes none.   python tools/lift_stamps.py
+
+python tools/lift_stamps.py --ab [FILE]: the tile classes (border, top edge, bottom edge, left edge, interior first / continuing)
+at the level-0 row-pass shape (256 x 512) and at level 3's (32 x 64: four corner tiles per image, runs of one tile), once with
+diagnostics flag 128 (correction sums behind the composite loop's barrier, no skipped MFMA tiles at the image's top / bottom) and
+once without, in one process; written to FILE as JSON if given."""
 import json
 import os
 import sys
@@ -11,12 +16,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+NAMES = ["P0 load+filter", "P0 barrier", "P1 conv1+tanh", "P1 barrier", "P2 conv2+tanh", "P2 barrier",
+         "PC composite", "PC barrier", "PC finish+store"]
 
-def main():
+
+def stamp(h, w, dbg, P=3, B=8):
+    """One stamped launch of a vertical step on P * B images of h x w -> stamps as (Z, tiles_y, tiles_x, 8 waves, 16)."""
     from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import _lib, ops
     lib = _lib.load()
     dev = "cuda:0"
-    P, B, h, w = 3, 8, 256, 512
     torch.manual_seed(0)
     x = torch.rand(P * B, 2 * h, w, device=dev) - 0.5
     ws = [(torch.randn(P, *s, device=dev) * sc) for s, sc in (((16, 1, 5, 5), 0.2), ((16,), 0.1), ((16, 16, 5, 5), 0.05), ((16,), 0.1),
@@ -28,31 +36,78 @@ def main():
     out = torch.empty(P * B, h, w, device=dev)
     dout = ops.view_of(out, P * B, h, w)
     lib.lldwt_set_lift_mode(1)
-    nwg = (w // 32) * (h // 16) * P * B
-    st = torch.zeros(nwg, 8, 16, dtype=torch.int64, device=dev)
+    gx, gy = (w + 31) // 32, (h + 15) // 16
+    st = torch.zeros(gx * gy * P * B, 8, 16, dtype=torch.int64, device=dev)
 
     def run():
         ops.lift_step(src, din, dout, P * B, B, h, w, taps, packed, 16, 5, True, 1.0, 0.1)
-    for _ in range(200):                       # warm the clocks under load
+    try:
+        ops.set_diagnostics(0, None, dbg)
+        for _ in range(200):                   # warm the clocks under load
+            run()
+        torch.cuda.synchronize()
+        ops.set_diagnostics(0, st, dbg)
         run()
-    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_diagnostics(0, None, 0)
+    return st.cpu().numpy().astype(np.int64).reshape(P * B, gy, gx, 8, 16)
+
+
+def classes(s, rl):
+    """Mean cycles (stamp 0 to stamp 9, mean over waves and tiles) of each class of tile present; rl = the launch's run length."""
+    gy, gx = s.shape[1:3]
+    ty = np.arange(gy)[:, None] * np.ones((1, gx), int)
+    tx = np.ones((gy, 1), int) * np.arange(gx)[None, :]
+    inner_x = (tx > 0) & (tx < gx - 1)
+    inner = inner_x & (ty > 0) & (ty < gy - 1)
+    sel = {"all_tiles": np.ones((gy, gx), bool), "border": ~inner, "top_edge": (ty == 0) & inner_x,
+           "bottom_edge": (ty == gy - 1) & inner_x, "left_edge": (tx == 0) & (ty > 0) & (ty < gy - 1),
+           "corner": ((ty == 0) | (ty == gy - 1)) & ~inner_x,
+           "interior_first_of_run": inner & (ty % rl == 0), "interior_continuing": inner & (ty % rl != 0)}
+    out = {}
+    for name, m in sel.items():
+        if m.any():
+            t = s[:, m]
+            d = np.diff(t[..., :10], axis=-1)
+            out[name] = {"tiles_per_image": int(m.sum()), "total_cycles_mean": float((t[..., 9] - t[..., 0]).mean()),
+                         "phases": {n: round(float(d[..., i].mean()), 1) for i, n in enumerate(NAMES)}}
+    return out
+
+
+def ab(path):
+    res = {"what": "k_lift_fused_f16<false, 0>, one vertical step on 24 images; cycles from the tile's first stamp to its last, mean "
+                   "over the eight waves and the tiles of a class; 'parent_form' = diagnostics flag 128, 'change' = no flag; one process",
+           "shapes": {}}
+    for key, (h, w, rl) in (("level0_row_pass_256x512", (256, 512, int(os.environ.get("LLDWT_STAMPS_RL", "8")))),
+                            ("level3_row_pass_32x64", (32, 64, 1))):
+        old, new = classes(stamp(h, w, 128), rl), classes(stamp(h, w, 0), rl)
+        old2, new2 = classes(stamp(h, w, 128), rl), classes(stamp(h, w, 0), rl)      # a second pair: what the stamps resolve
+        res["shapes"][key] = {"run_length": rl, "parent_form": old, "change": new,
+                              "total_cycles_mean": {c: {"parent_form": [old[c]["total_cycles_mean"], old2[c]["total_cycles_mean"]],
+                                                        "change": [new[c]["total_cycles_mean"], new2[c]["total_cycles_mean"]]}
+                                                    for c in old}}
+    txt = json.dumps(res, indent=1)
+    print(txt)
+    if path:
+        with open(path, "w") as f:
+            f.write(txt + "\n")
+
+
+def main():
+    from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import ops
+    if len(sys.argv) > 1 and sys.argv[1] == "--ab":
+        return ab(sys.argv[2] if len(sys.argv) > 2 else "")
+    P, B, h, w = 3, 8, 256, 512
     abl = None
     dbg = int(os.environ.get("LLDWT_LF_DBG", "0"))
-    for _ in range(20):
-        run()
-    ops.set_diagnostics(0, st, dbg)
-    run()
-    torch.cuda.synchronize()
-    ops.set_diagnostics(0, None, 0)
-    s = st.cpu().numpy().astype(np.int64)
+    s = stamp(h, w, dbg, P, B)
     gx, gy = w // 32, h // 16
-    s = s.reshape(P * B, gy, gx, 8, 16)
     interior = np.zeros((gy, gx), bool)
     interior[1:-1, 1:-1] = True                # y0 >= 2 and y0 + 18 <= h etc: every tile but the frame
     res = {"ablations_interior_mean_cycles": abl}
     si = s[:, interior]                        # (Z, n_int, 8, 16)
-    names = ["P0 load+filter", "P0 barrier", "P1 conv1+tanh", "P1 barrier", "P2 conv2+tanh", "P2 barrier",
-             "PC composite", "PC barrier", "PC finish+store"]
+    names = NAMES
     d = np.diff(si[..., :10], axis=-1)
     res["interior_mean_cycles_per_wave"] = {n: float(d[..., i].mean()) for i, n in enumerate(names)}
     res["interior_max_over_waves_mean"] = {n: float(d[..., i].max(axis=-1).mean()) for i, n in enumerate(names)}
