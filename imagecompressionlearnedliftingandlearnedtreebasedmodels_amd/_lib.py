@@ -71,6 +71,11 @@ SIGNATURES = {
                                             C.c_int32, C.c_int32, _f, _p]),
     "lldwt_gauss_quantise_rdo": (_i, [_p] * 6 + [_i64, _i, _i64, _i64, _i64, _i64, _i, _i, _i, _f, _f, _p, _p, _p, C.c_int32, C.c_int32,
                                       _f, _p]),
+    "lldwt_cgp16_wavefront_step_map": (_i, [_p] * 9 + [_i64, _i64, _i64, _i64, _i, _i, C.c_uint32, _i, _i64, _i64, _p, _i64, _i64, _i,
+                                            _p, _p, _p, C.c_int32, C.c_int32, _f, _p]),
+    "lldwt_wavefront_apply_map": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _i, _i64, _i64, _p, _i64, _i64, _i, _p]),
+    "lldwt_gauss_quantise_map": (_i, [_p] * 7 + [_i64, _i64, _i, _i64, _i64, _i64, _i64, _i, _i, _i, _p, _i64, _i64, _i, _p, _p, _p,
+                                      C.c_int32, C.c_int32, _f, _p]),
     "lldwt_code_cost": (_i, [_p, _p, _i64, _i64, _p, C.c_int32, C.c_int32, _p, _p, C.c_int32, _p, _p, _p]),
     "lldwt_ztblock_packed_floats": (_i64, []),
     "lldwt_ztblock_phase": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i, _p]),

@@ -98,6 +98,29 @@ that adds, judged with the exact integer code lengths of the level's tables.  rh
 header key, the decoders are untouched and never learn of it; ``rdo=None`` and ``rdo=0`` write the bytes above.  It composes
 with ``step``, ``target_bytes`` (probes and real encodes both run with it), ``near``, tiles and both coders.
 
+Region-of-interest coding (``encode_images(..., step_map=M)``, the same on ``encode_tiled``): a step per block
+of 2^L x 2^L pixels instead of one per image.  M is (hb, wb) = (ceil(H / 2^L), ceil(W / 2^L)) steps, each n / 16 with n in
+[4, 1024] (``check_step_map``; ``step_map_from_regions`` paints one from rectangles).  The coefficient at (y, x) of a subband of
+level l <= L-2 takes the step of block (min(y >> s, hb - 1), min(x >> s, wb - 1)), s = L - 1 - l, with the arithmetic of 7.1.6
+and 7.1.7 per coefficient; xe and the coarsest level keep the unit step.  The map travels in a wrapping container, version 1:
+
+    magic             4 bytes   b"LLDQ"
+    format version    u8        1
+    block log2        u8        L of the inner container
+    hb, wb            u16, u16  ceil(H / 2^L), ceil(W / 2^L) of the inner container's H, W
+    map CRC32         u32       zlib.crc32 of the hb * wb values n as little-endian u16, raster order
+    run count         LEB128
+    runs              (LEB128 length >= 1, u16 n) each, raster order, maximal: adjacent runs differ
+    inner length      LEB128
+    inner container   a complete LLDW, LLDT, LLDO or LLDR container
+    CRC32             u32       zlib.crc32 of every byte before it
+
+The base container (of an LLDR: its nested base) carries one more arithmetic key, ``qmap=<8 hex digits of the map CRC>``, and no
+``step`` key: the map holds every step.  The key binds base and map; a base with the key is refused without its wrapper, and
+an LLDQ whose key and map disagree is refused.  ``step_map`` composes with ``coder``, ``rdo``, ``near``, ``tile`` and ``overlap``
+(a tile codes with the slice of the map at its origin, clamped as above) and excludes ``step`` and ``target_bytes``.  The
+decoders take an LLDQ wherever they take its inner container, with ``region``, ``reduce`` and ``refine``.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -132,6 +155,9 @@ _RUNIT = struct.Struct("<QQ24s")               # cs(xh), cs(x), the 24 table ind
 # the base containers: magic -> (format version, fixed struct)
 _BASE = {MAGIC: (FORMAT_VERSION, _FIXED), TILED_MAGIC: (TILED_FORMAT_VERSION, _TFIXED),
          LAPPED_MAGIC: (LAPPED_FORMAT_VERSION, _OFIXED)}
+MAPPED_MAGIC = b"LLDQ"
+MAPPED_FORMAT_VERSION = 1
+_QFIXED = struct.Struct("<4sBBHHI")            # magic, version, block log2, hb, wb, map CRC32
 _PLANES = 3
 # coder name of the API -> value of the arithmetic string's "coder" key (None: the key is absent)
 CODER_KEYS = {"host": None, "gpu": "irans32"}
@@ -205,6 +231,190 @@ def _with_step(arith, n):
     if n == STEP_DENOM:
         return arith
     return ",".join(sorted((arith.split(",") if arith else []) + ["step=%d" % n]))
+
+
+def _split_qmap(arith):
+    """arithmetic string -> (map CRC or None, the string without the qmap key).  ValueError naming the step map if the key occurs
+    twice or its value is not 8 lowercase hex digits."""
+    parts = arith.split(",") if arith else []
+    vals = [p[len("qmap="):] for p in parts if p.startswith("qmap=")]
+    if not vals:
+        return None, arith
+    if len(vals) != 1 or len(vals[0]) != 8 or any(c not in "0123456789abcdef" for c in vals[0]):
+        raise ValueError("step map: bad qmap key %r in the arithmetic string (8 lowercase hex digits, once)" % ",".join(vals))
+    return int(vals[0], 16), ",".join(p for p in parts if not p.startswith("qmap="))
+
+
+def _with_qmap(arith, crc):
+    """The arithmetic string (without a qmap key) with the key of the map CRC merged in at its sorted place; None: unchanged."""
+    if crc is None:
+        return arith
+    return ",".join(sorted((arith.split(",") if arith else []) + ["qmap=%08x" % (crc & 0xFFFFFFFF)]))
+
+
+def _blocks(v, L):
+    """ceil(v / 2^L): blocks of a step map along a side of v pixels."""
+    return -(-int(v) >> L)
+
+
+def check_step_map(step_map, H, W, L):
+    """A step map of the API for an H x W image at L levels -> the (hb, wb) uint16 numpy array of n, step = n / 16.  step_map:
+    (hb, wb) = (ceil(H / 2^L), ceil(W / 2^L)) steps (a tensor, an array or nested lists), each exactly n / 16 with n in [4, 1024].
+    ValueError naming step_map for a wrong shape or value, or L < 2 (a step reaches the levels below the coarsest only)."""
+    import numpy as np
+    if L < 2:
+        raise ValueError("step_map: a step map needs dwtlevels >= 2 (it applies to the levels below the coarsest; got %d)" % L)
+    try:
+        a = np.asarray(step_map.detach().cpu().numpy() if hasattr(step_map, "detach") else step_map, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("step_map must be a (hb, wb) array of steps") from None
+    hb, wb = _blocks(H, L), _blocks(W, L)
+    if a.shape != (hb, wb):
+        raise ValueError("step_map: shape %s, a %d x %d image at %d levels has %d x %d blocks of %d pixels"
+                         % (tuple(a.shape), H, W, L, hb, wb, 1 << L))
+    if hb > 0xFFFF or wb > 0xFFFF:
+        raise ValueError("step_map: hb, wb must fit 16 bits (got %d x %d)" % (hb, wb))
+    n = a * STEP_DENOM
+    if not (np.isfinite(n).all() and (n >= STEP_N_MIN).all() and (n <= STEP_N_MAX).all() and (n == np.rint(n)).all()):
+        raise ValueError("step_map: every step must be n / %d with an integer n in [%d, %d], i.e. a multiple of %g in [%g, %g]"
+                         % (STEP_DENOM, STEP_N_MIN, STEP_N_MAX, 1.0 / STEP_DENOM, STEP_N_MIN / STEP_DENOM, STEP_N_MAX / STEP_DENOM))
+    return n.astype(np.uint16)
+
+
+def step_map_from_regions(H, W, L, background, regions):
+    """A step map painted from rectangles -> (hb, wb) float64 numpy array of steps for step_map=.  Every block starts at the step
+    ``background``; regions is a list of (y0, x0, h, w, step) in pixels: every block that a rectangle intersects takes that
+    rectangle's step, later rectangles override earlier ones.  ValueError naming step_map for an empty rectangle or one that is
+    not inside the image, and for steps check_step_map refuses."""
+    import numpy as np
+    hb, wb = _blocks(H, L), _blocks(W, L)
+    m = np.full((hb, wb), check_step(background) / STEP_DENOM, dtype=np.float64)
+    for r in regions:
+        try:
+            y0, x0, h, w = (int(v) for v in r[:4])
+            q = check_step(r[4]) / STEP_DENOM
+            ok = len(r) == 5
+        except (TypeError, ValueError, IndexError):
+            ok = False
+        if not ok:
+            raise ValueError("step_map: a region must be (y0, x0, h, w, step) with a step n / 16 (got %r)" % (r,))
+        if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError("step_map: region (%d, %d, %d, %d) is empty or not inside the %d x %d image" % (y0, x0, h, w, H, W))
+        m[y0 >> L:((y0 + h - 1) >> L) + 1, x0 >> L:((x0 + w - 1) >> L) + 1] = q
+    check_step_map(m, H, W, L)
+    return m
+
+
+def map_crc(map_n):
+    """zlib.crc32 of a step map's values n as little-endian u16 in raster order (the LLDQ field and the qmap key)."""
+    import numpy as np
+    return zlib.crc32(np.ascontiguousarray(map_n, dtype="<u2").tobytes()) & 0xFFFFFFFF
+
+
+def _base_header(hdr):
+    """The header that carries the arithmetic string: the nested base header of an LLDR header, the header itself otherwise."""
+    return hdr["base"] if "base" in hdr else hdr
+
+
+def pack_mapped(map_n, inner):
+    """map_n: (hb, wb) integer array of n = 16 * step; inner: a complete LLDW, LLDT, LLDO or LLDR container whose base carries
+    ``qmap=<CRC of the map>`` -> LLDQ container.  The map is written as maximal runs in raster order.  ValueError naming the
+    field when the map does not belong to the inner container; host only."""
+    import numpy as np
+    a = np.asarray(map_n)
+    if a.ndim != 2 or a.dtype.kind not in "iu" or a.size == 0 or int(a.min()) < STEP_N_MIN or int(a.max()) > STEP_N_MAX:
+        raise ValueError("step map: a (hb, wb) integer array of n in [%d, %d]" % (STEP_N_MIN, STEP_N_MAX))
+    if _magic(inner) not in (MAGIC, TILED_MAGIC, LAPPED_MAGIC, REFINED_MAGIC):
+        raise ValueError("inner container: a step map goes over an LLDW, LLDT, LLDO or LLDR container")
+    bh = _base_header(read_header(inner))
+    L, hb, wb = bh["dwtlevels"], a.shape[0], a.shape[1]
+    if (hb, wb) != (_blocks(bh["H"], L), _blocks(bh["W"], L)) or hb > 0xFFFF or wb > 0xFFFF:
+        raise ValueError("hb, wb: a %d x %d map for an inner container of %d x %d pixels at %d levels" % (hb, wb, bh["H"], bh["W"], L))
+    crc = map_crc(a)
+    if _split_qmap(bh["arithmetic"])[0] != crc:
+        raise ValueError("step map: the inner container's qmap key does not hold the CRC of this map (%08x)" % crc)
+    flat = a.reshape(-1).astype(np.int64)
+    cut = np.flatnonzero(np.diff(flat)) + 1
+    starts = np.concatenate(([0], cut))
+    lengths = np.diff(np.concatenate((starts, [flat.size])))
+    body = bytearray(_QFIXED.pack(MAPPED_MAGIC, MAPPED_FORMAT_VERSION, L, hb, wb, crc))
+    body += leb128_encode(len(starts))
+    for st, ln in zip(starts.tolist(), lengths.tolist()):
+        body += leb128_encode(ln) + struct.pack("<H", int(flat[st]))
+    body += leb128_encode(len(inner)) + bytes(inner)
+    return _seal(bytes(body))
+
+
+def parse_mapped(blob):
+    """LLDQ container -> (header dict, the (hb, wb) uint16 numpy array of n, the inner container's bytes).  The header carries
+    version, block, hb, wb, map_crc, step_min, step_max (floats) and inner, the inner container's header.  Every check raises
+    ValueError naming the field, on the host: magic, version, CRC, truncation; the runs (a length of 0, an n outside [4, 1024],
+    adjacent runs of one value, a sum other than hb * wb); the map CRC; the inner container (parsed by its own parser); block
+    log2, hb, wb against the inner header; and the inner base's qmap key against the map CRC."""
+    import numpy as np
+    blob, end = _open(blob, MAPPED_MAGIC, MAPPED_FORMAT_VERSION, _QFIXED.size + 1 + 3 + 1)
+    _, _, block, hb, wb, crc = _QFIXED.unpack_from(blob, 0)
+    try:
+        nruns, pos = leb128_decode(blob, _QFIXED.size, end)
+    except ValueError:
+        raise ValueError("run count: container truncated or varint too long") from None
+    if hb < 1 or wb < 1:
+        raise ValueError("hb, wb: a step map of %d x %d blocks" % (hb, wb))
+    if nruns < 1 or nruns > hb * wb:
+        raise ValueError("run count: %d runs for a map of %d x %d blocks" % (nruns, hb, wb))
+    vals, lens, prev, total = [], [], None, 0
+    for r in range(nruns):
+        try:
+            ln, pos = leb128_decode(blob, pos, end)
+        except ValueError:
+            raise ValueError("runs: container truncated inside run %d" % r) from None
+        if pos + 2 > end:
+            raise ValueError("runs: container truncated inside run %d" % r)
+        n = struct.unpack_from("<H", blob, pos)[0]
+        pos += 2
+        if ln < 1:
+            raise ValueError("runs: run %d has length 0" % r)
+        if not STEP_N_MIN <= n <= STEP_N_MAX:
+            raise ValueError("runs: run %d holds n = %d, outside [%d, %d]" % (r, n, STEP_N_MIN, STEP_N_MAX))
+        if n == prev:
+            raise ValueError("runs: runs %d and %d hold the same n = %d (the runs are not maximal)" % (r - 1, r, n))
+        total += ln
+        if total > hb * wb:
+            break
+        vals.append(n)
+        lens.append(ln)
+        prev = n
+    if total != hb * wb:
+        raise ValueError("runs: the runs add up to %s%d blocks, the map has %d x %d = %d"
+                         % ("more than " if total > hb * wb else "", min(total, hb * wb), hb, wb, hb * wb))
+    m = np.repeat(np.asarray(vals, dtype=np.uint16), lens).reshape(hb, wb)
+    if map_crc(m) != crc:
+        raise ValueError("map CRC32: the runs give %08x, the container holds %08x" % (map_crc(m), crc))
+    try:
+        ilen, pos = leb128_decode(blob, pos, end)
+    except ValueError:
+        raise ValueError("inner length: container truncated or varint too long") from None
+    if pos + ilen != end:
+        raise ValueError("inner length: %d bytes announced, %d left" % (ilen, max(0, end - pos)))
+    inner = blob[pos:end]
+    if _magic(inner) not in (MAGIC, TILED_MAGIC, LAPPED_MAGIC, REFINED_MAGIC):
+        raise ValueError("inner container: a step map goes over an LLDW, LLDT, LLDO or LLDR container (got magic %r)" % inner[:4])
+    ih = parse_refined(inner, check_tables=False)[0] if _magic(inner) == REFINED_MAGIC else _parse_base(_magic(inner), inner)[0]
+    bh = _base_header(ih)
+    if block != bh["dwtlevels"]:
+        raise ValueError("block log2: the container holds %d, the inner container has dwtlevels %d" % (block, bh["dwtlevels"]))
+    if block < 2:
+        raise ValueError("block log2: a step map needs dwtlevels >= 2 (got %d)" % block)
+    if (hb, wb) != (_blocks(bh["H"], block), _blocks(bh["W"], block)):
+        raise ValueError("hb, wb: the container holds %d x %d, the inner container's %d x %d pixels at %d levels give %d x %d"
+                         % (hb, wb, bh["H"], bh["W"], block, _blocks(bh["H"], block), _blocks(bh["W"], block)))
+    key = _split_qmap(bh["arithmetic"])[0]
+    if key != crc:
+        raise ValueError("step map: the inner container's qmap key is %s, the map's CRC is %08x (the map was not the one the "
+                         "streams were coded with)" % ("absent" if key is None else "%08x" % key, crc))
+    hdr = dict(version=MAPPED_FORMAT_VERSION, block=block, hb=hb, wb=wb, map_crc=crc, step_min=int(m.min()) / STEP_DENOM,
+               step_max=int(m.max()) / STEP_DENOM, inner=ih)
+    return hdr, m, inner
 
 
 def target_bpp_bytes(bpp, H, W):
@@ -549,10 +759,14 @@ def _magic(blob):
 
 
 def read_header(blob):
-    """The header of a container (LLDW, LLDT, LLDO or LLDR) as a dict (CPU only; the library is never loaded).  A tiled
+    """The header of a container (LLDW, LLDT, LLDO, LLDR or LLDQ) as a dict (CPU only; the library is never loaded).  An LLDQ
+    header carries version, block, hb, wb, map_crc, step_min, step_max and the inner container's header under ``inner``
+    (parse_mapped).  A tiled
     header carries ``overlap``: 0 for LLDT.  An LLDR header carries ``near``, ``residual_bytes`` and the nested base header
     under ``base`` (parse_refined; the table CRC is compared by the decoders).  Raises ValueError as parse_container /
     parse_tiled / parse_lapped / parse_refined."""
+    if _magic(blob) == MAPPED_MAGIC:
+        return parse_mapped(blob)[0]
     if _magic(blob) == REFINED_MAGIC:
         return parse_refined(blob, check_tables=False)[0]
     return _parse_base(_magic(blob) if _magic(blob) in _BASE else MAGIC, blob)[0]
@@ -563,6 +777,8 @@ def reduce_bytes(hdr):
     before the payload) plus the xe streams and the xo streams of levels k .. L-1 of every plane (for LLDT / LLDO, of every
     tile).  The 4-byte CRC32 trailer is not counted.  hdr: read_header's dict (LLDW, LLDT or LLDO; for LLDR the base alone is
     counted, as a reduced decode never reads the residual layer); CPU only."""
+    if "inner" in hdr:
+        hdr = hdr["inner"]
     if "base" in hdr:
         hdr = hdr["base"]
     L, lengths = hdr["dwtlevels"], hdr["stream_lengths"]
@@ -577,10 +793,11 @@ def reduce_bytes(hdr):
 
 
 # ------------------------------------------------------------------------------------------------ model identity
-def arithmetic_string(coder="host", step=None):
+def arithmetic_string(coder="host", step=None, qmap=None):
     """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path, plus the
     entropy coder: ``coder=irans32`` for coder="gpu", no key for the host coder (so the host string is unchanged), plus the
-    quantisation step: ``step=<n>`` for step = n / 16 other than 1, no key for None or 1.
+    quantisation step: ``step=<n>`` for step = n / 16 other than 1, no key for None or 1; or, for a step map,
+    ``qmap=<8 hex digits>`` of its CRC (qmap: the CRC as an int), which excludes a step.
     Which reach which layer (the others are carried along, harmlessly):
       plc_mode, plc_fuse, plc_algo, plc_shape, storage -- the tree-context pair: conditioned2ZTsepSubbands, onlyEZWT;
       precision -- the split-fp16 pair and cgp chain (conditioned2ZTsepSubbands, onlyEZWT) and the lifting steps (all);
@@ -594,14 +811,16 @@ def arithmetic_string(coder="host", step=None):
           ("storage", ops.storage_dtype())]
     if CODER_KEYS[coder] is not None:
         kv.append(("coder", CODER_KEYS[coder]))
-    return _with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step))
+    if qmap is not None and check_step(step) != STEP_DENOM:
+        raise ValueError("step and step_map: give one of them (the map holds every step)")
+    return _with_qmap(_with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step)), qmap)
 
 
 def _batch_invariant(arith):
     """True when the coding path is per image in this arithmetic, so images can be coded together.  Not so when the
     non-fused split-fp16 pair takes its operand scale from an absmax over the whole batch (plc_fuse=0), or with fp16
     storage (a bound over the batch's parents); the one-product precisions are not verified.  Otherwise: one image per call."""
-    arith = _split_step(_split_coder(arith)[1])[1]          # neither the coder nor the step changes what a batch shares
+    arith = _split_qmap(_split_step(_split_coder(arith)[1])[1])[1]   # neither the coder nor the step(s) change what a batch shares
     d = dict(p.split("=") for p in arith.split(","))
     if d["precision"] != "f16x3" or d["storage"] != "fp32":
         return False
@@ -764,6 +983,44 @@ def _rate_args(step, target_bytes, near, L):
     return n, T
 
 
+def _map_arg(step_map, step, target_bytes, B, H, W, L):
+    """The step_map argument of encode_images / encode_tiled, checked on the host -> None or the (B, hb, wb) uint16 array of n:
+    one (hb, wb) map for the whole batch or (B, hb, wb).  Not with step or target_bytes."""
+    import numpy as np
+    if step_map is None:
+        return None
+    if step is not None:
+        raise ValueError("step_map and step: give one of them (the map holds every step)")
+    if target_bytes is not None:
+        raise ValueError("step_map and target_bytes: a byte target over a step map is not defined (it needs a rule for moving a "
+                         "whole map along the step grid)")
+    dims = step_map.dim() if hasattr(step_map, "dim") else np.ndim(step_map)
+    if dims == 3:
+        if len(step_map) != B:
+            raise ValueError("step_map: %d maps for a batch of %d images" % (len(step_map), B))
+        return np.stack([check_step_map(m, H, W, L) for m in step_map])
+    m = check_step_map(step_map, H, W, L)
+    return np.broadcast_to(m, (B,) + m.shape)
+
+
+def _unit_maps(maps, units, grid, L, dev):
+    """The step maps of a group of units as the coded layers take them: maps[b] is image b's (hb, wb) array of n; units: the
+    unit numbers b * ny * nx + ty * nx + tx; grid = (th, tw, ny, nx, ov) -> (len(units), th >> L, tw >> L) int32 tensor on dev.
+    A unit's map is the slice of its image's map at the tile's origin (a multiple of 2^L), one entry per coefficient of the
+    tile's coarsest level, clamped to the last block where the tile (or the padding) runs past the image."""
+    import numpy as np
+    import torch
+    th, tw, ny, nx, ov = grid
+    out = []
+    for u in units:
+        m = maps[u // (ny * nx)]
+        ty, tx = divmod(u % (ny * nx), nx)
+        ys = np.minimum(((ty * (th - ov)) >> L) + np.arange(_blocks(th, L)), m.shape[0] - 1)
+        xs = np.minimum(((tx * (tw - ov)) >> L) + np.arange(_blocks(tw, L)), m.shape[1] - 1)
+        out.append(np.asarray(m)[ys][:, xs])
+    return torch.from_numpy(np.stack(out).astype(np.int32)).to(dev)
+
+
 SEARCH_STATS = {}          # diagnostics: the last byte-target search's probes (estimates), real encodes and chosen step
 
 
@@ -811,7 +1068,7 @@ def _estimated_size(empty, estimates):
     return len(empty) + sum(e + len(leb128_encode(e)) - 1 for e in estimates)
 
 
-def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None):
+def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -822,36 +1079,42 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     the step that walk finds); ValueError naming the smallest achievable size if even the coarsest step does not fit.  Not
     both, and no target with near.
     rdo: the Lagrangian rho = m / 64 of rate-distortion optimised quantisation on the same levels; None and 0
-    write the same bytes as ever.  The encoder's choice only: no header key, and the containers decode as any other."""
+    write the same bytes as ever.  The encoder's choice only: no header key, and the containers decode as any other.
+    step_map: a step per block of 2^L x 2^L pixels: (hb, wb) steps for the whole batch or (B, hb, wb)
+    (check_step_map, step_map_from_regions) -> LLDQ containers around what the other arguments select.  Not with step or
+    target_bytes."""
     from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
     if near is not None:
         from .residual import check_near
         near = check_near(near)
+    maps = _map_arg(step_map, step, target_bytes, B, H, W, L)
     n, T = _rate_args(step, target_bytes, near, L)
     rdo = _rdo_arg(rdo, L)
     Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None):
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None):
     """_encode at the step step_n / 16, or with a byte target T the search of _search_step, one image at a time.  walk: the
     (magic, grid, group, coder) of _encode.  rdo: probes and real encodes alike."""
     if T is None:
-        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo)
+        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps)
     return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo)[0],
                          lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo)[0], T)
             for b in range(images_u8.shape[0])]
 
 
-def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None):
+def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None):
     """The encode walk behind encode_images and encode_tiled (arguments checked there): the batch is cut into the tiles of
     grid = (th, tw, ny, nx, ov) -- the untiled codec is the 1 x 1 grid of one padded_size tile, which the untiled input and
     output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
     arithmetics that are not batch invariant) at the step step_n / 16 -> the B containers of ``magic``, with near the LLDR
     containers over them.  estimate: -> the estimated container sizes (ints) from the code-length kernel instead; no range
-    coder runs.  rdo: the Lagrangian of DESIGN.md 7.1.7 (None: off), which only the encoder's symbols see."""
+    coder runs.  rdo: the Lagrangian of DESIGN.md 7.1.7 (None: off), which only the encoder's symbols see.
+    maps: the (B, hb, wb) array of _map_arg (None: the step alone): every unit is coded with its slice of its image's map
+    (_unit_maps), every base carries the qmap key of its image's map, and the result is wrapped into LLDQ (pack_mapped)."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
@@ -865,6 +1128,8 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov,
                numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
+    # with a map every image has its own header: the arithmetic string names the image's map
+    hdrs = [hdr if maps is None else dict(hdr, arithmetic=_with_qmap(arith, map_crc(maps[b]))) for b in range(B)]
     dev = next(net.parameters()).device
     img = images_u8.to(dev).contiguous()
     per, count = ny * nx, _PLANES * (L + 1)
@@ -878,27 +1143,39 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
                 x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
             else:
                 x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
+            st = step if maps is None else _unit_maps(maps, range(first, first + n), grid, L, dev)
             if near is None:
-                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, step=step, rdo=rdo)
+                s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, step=st, rdo=rdo)
             else:
-                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, step=step, rdo=rdo)
+                s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, step=st, rdo=rdo)
                 # the decoder's call on the same values
                 ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W), first=first, B=B, out=xh)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
         if estimate:
             empty = _pack_base(magic, hdr, [[b""] * count] * per)
             return [_estimated_size(empty, [e for t in tiles[b * per:(b + 1) * per] for e in t]) for b in range(B)]
-        blobs = [_pack_base(magic, hdr, tiles[b * per:(b + 1) * per]) for b in range(B)]
+        blobs = [_pack_base(magic, hdrs[b], tiles[b * per:(b + 1) * per]) for b in range(B)]
         if near is not None:
             blobs = _refine(blobs, img, xh, (H, W, th, tw, ny, nx), near, coder)
+        if maps is not None:
+            blobs = [pack_mapped(maps[b], blobs[b]) for b in range(B)]
     return blobs
 
 
-def check_header(hdr, layer, nettype, L, digest, arith):
+def check_header(hdr, layer, nettype, L, digest, arith, qmap=None):
     """The identity checks of a parsed header against the decoding net and process (ValueError naming the field).  arith:
-    the process's arithmetic string without a coder key; the header's coder and step keys are checked and set aside first."""
+    the process's arithmetic string without a coder key; the header's coder and step keys are checked and set aside first.
+    qmap: the CRC of the step map that came with the container (its LLDQ wrapper), None without one.  The header's qmap key is
+    set aside only when it equals that CRC: a base coded with a step map cannot be decoded without the map."""
     _, hdr_arith = _split_coder(hdr["arithmetic"])
     _, hdr_arith = _split_step(hdr_arith)
+    key, hdr_arith = _split_qmap(hdr_arith)
+    if key != qmap:
+        if qmap is None:
+            raise ValueError("step map: the container was coded with a step map (qmap=%08x) and cannot be decoded without its LLDQ "
+                             "wrapper, which holds the map" % key)
+        raise ValueError("step map: the container's qmap key is %s, the step map given has CRC %08x"
+                         % ("absent" if key is None else "%08x" % key, qmap))
     if hdr["layer"] != layer:
         raise ValueError("entropy layer: the container holds %s, the net is %s" % (hdr["layer"], layer))
     if hdr["netType"] != nettype:
@@ -951,15 +1228,20 @@ def decode_images(net, blobs, reduce=0, refine=True):
     reduce = k in [0, L]: the image at 1/2^k of each side, (ceil(H / 2^k), ceil(W / 2^k), 3), decoded from the xe streams
     and the levels k .. L-1 only (the module docstring); reduce=0 is the full decode.
     An LLDR container over LLDW is decoded through its base and then refined on the device (lossless or within its bound,
-    DESIGN.md 7.1.5); refine=False, or reduce > 0 (the residual lives at full resolution), gives exactly the base decode."""
+    DESIGN.md 7.1.5); refine=False, or reduce > 0 (the residual lives at full resolution), gives exactly the base decode.
+    An LLDQ container is decoded as its inner container, with its step map on the levels 0 .. L-2 that the
+    decode reaches; images with different maps are decoded together, the map being per image."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
-    refined = {}
+    refined, maps = {}, {}
     blobs = list(blobs)
     for i, b in enumerate(blobs):
+        if _magic(b) == MAPPED_MAGIC:
+            _, maps[i], b = parse_mapped(b)
+            blobs[i] = b
         if _magic(b) == REFINED_MAGIC:
             rhdr, base, units = parse_refined(b)
             if _magic(base) != MAGIC:
@@ -970,21 +1252,23 @@ def decode_images(net, blobs, reduce=0, refine=True):
                 refined[i] = (rhdr["near"], units)
     parsed = [parse_container(b) for b in blobs]
     digest, arith = weights_digest(net), arithmetic_string()
-    for hdr, _ in parsed:
-        check_header(hdr, layer, nettype, L, digest, arith)
+    for i, (hdr, _) in enumerate(parsed):
+        check_header(hdr, layer, nettype, L, digest, arith, qmap=map_crc(maps[i]) if i in maps else None)
     _prepare(net)
     nets = net.nets()
+    dev = next(net.parameters()).device
     by_size = {}
     for i, (hdr, _) in enumerate(parsed):
-        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"]), []).append(i)
+        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"], i in maps), []).append(i)
     out = [None] * len(parsed)
     with torch.no_grad():
         if k:
             inv_a, b = ll_norm(net, k)
-        for (H, W, coder, step), idx in by_size.items():
+        for (H, W, coder, step, mapped), idx in by_size.items():
             Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             units = [parsed[i][1] for i in idx]
-            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k):
+            um = _unit_maps([maps[i] for i in idx], range(len(idx)), (Hp, Wp, 1, 1, 0), L, dev) if mapped else None
+            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um):
                 g = idx[a:a + n]
                 if k == 0:
                     img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W)
@@ -1063,7 +1347,7 @@ def _tile_streams(s_xe, s_xo, j):
 
 
 def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
-                 rdo=None):
+                 rdo=None, step_map=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -1074,7 +1358,9 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     (LLDR over LLDT; the bytes do not depend on tiles_per_call either); not with overlap > 0, where the decoded pixels are
     a blend of two units.
     step, target_bytes: as encode_images, with ONE step for all tiles of a frame; a target is met by each frame's container
-    (the images of a batch are searched one at a time).  rdo: as encode_images, for every tile."""
+    (the images of a batch are searched one at a time).  rdo: as encode_images, for every tile.
+    step_map: as encode_images, the map of the whole image; a tile is coded with the slice at its origin (tile origins are
+    multiples of 2^L for plain and lapped grids alike), clamped at the image's last block -> LLDQ over LLDT / LLDO / LLDR."""
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
     if near is not None:
@@ -1082,6 +1368,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
         near = check_near(near)
         if overlap:
             raise ValueError("near: a residual layer over lapped tiles (overlap > 0) is not defined; use overlap=0")
+    maps = _map_arg(step_map, step, target_bytes, B, H, W, L)
     n, T = _rate_args(step, target_bytes, near, L)
     rdo = _rdo_arg(rdo, L)
     group = _tiles_per_call(tiles_per_call)
@@ -1092,7 +1379,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps)
 
 
 def _tiles_per_call(tiles_per_call):
@@ -1118,16 +1405,18 @@ def _gather(units, k, L):
     return s_xe, s_xo
 
 
-def _decode_groups(nets, units, th, tw, group, hdr, k):
+def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None):
     """The decode walk behind decode_images and decode_tiled: the units (stream lists of images or tiles of th x tw, all of
     the coder and step of hdr) are decoded ``group`` at a time, one per call in the arithmetics that are not batch invariant,
-    through the _decode_tiles hook -> yields (index of the group's first unit, its size n, the hook's result)."""
+    through the _decode_tiles hook -> yields (index of the group's first unit, its size n, the hook's result).
+    maps: the units' step maps (_unit_maps, one per unit) when the units were coded with one; each group then decodes with its
+    slice in place of the header's step."""
     g = group if _batch_invariant(hdr["arithmetic"]) else 1
     for a in range(0, len(units), g):
         grp = units[a:a + g]
         s_xe, s_xo = _gather(grp, k, hdr["dwtlevels"])
         yield a, len(grp), _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp), coder=hdr["coder"], first_level=k,
-                                         step=hdr["step"])
+                                         step=hdr["step"] if maps is None else maps[a:a + g])
 
 
 def _region(region, H, W):
@@ -1143,7 +1432,8 @@ def _region(region, H, W):
 
 
 def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True):
-    """LLDT or LLDO container -> (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
+    """LLDT or LLDO container (or an LLDQ over one, DESIGN.md 7.1.8: each tile decodes with its slice of the step map) ->
+    (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
     LLDO (lapped tiles): the tiles covering any pixel of the region, overlap included, are decoded in
     ascending index, each group is blended into a region-sized fp32 buffer (lldwt_ycc_tiles_blend) and the buffer is
@@ -1157,7 +1447,9 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     from . import ops
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
-    units = None
+    units = smap = None
+    if _magic(blob) == MAPPED_MAGIC:           # the inner container with its step map
+        _, smap, blob = parse_mapped(blob)
     if _magic(blob) == REFINED_MAGIC:
         rhdr, blob, units = parse_refined(blob)
         if _magic(blob) != TILED_MAGIC:
@@ -1181,10 +1473,11 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
         y0, x0 = rows[0] * th, cols[0] * tw
         h, w = min(H, (rows[-1] + 1) * th) - y0, min(W, (cols[-1] + 1) * tw) - x0
     group = _tiles_per_call(tiles_per_call)
-    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string())
+    check_header(hdr, layer, nettype, L, weights_digest(net), arithmetic_string(), qmap=None if smap is None else map_crc(smap))
     _prepare(net)
     nets = net.nets()
     dev = next(net.parameters()).device
+    um = None if smap is None else _unit_maps([smap], want, (hdr["th"], hdr["tw"], ny, nx, hdr["overlap"]), L, dev)
     with torch.no_grad():
         if k:
             inv_a, b = ll_norm(net, k)
@@ -1197,7 +1490,7 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
             acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
         else:
             out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
-        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k):
+        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um):
             if ov:                   # lapped: the raw samples are blended, then written once as the tile of a 1 x 1 grid
                 ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), want[a:a + n], acc)
             else:

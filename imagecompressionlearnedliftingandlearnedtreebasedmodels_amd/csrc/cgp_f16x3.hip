@@ -172,6 +172,11 @@ struct Cgp16Args {
     float* h1; float* h2; float* h3;
     // PERS: pairs = planes * groups; workgroup i of the grid serves pair ((i + 1) * pairs - 1) / gridDim.x (see k_cgp16)
     int pairs;
+    // MAP (lldwt_cgp16_wavefront_step_map): (batch, wf_mh, wf_mw, 2) fp32 pairs (q, inv_q), one per block of
+    // 2^wf_shift x 2^wf_shift pixels, one map for all planes and groups of an image; wf_q, wf_invq are then not read.  Last in
+    // the struct: the other instantiations read every field at the offset it has always had.
+    const float* wf_qpairs;
+    int wf_mh, wf_mw, wf_shift;
 };
 #define CGP_STAMP(i)                                                                                                    \
     if constexpr (!PERS)                                                                                            \
@@ -236,13 +241,17 @@ __device__ __forceinline__ void next_frags(const floatx16& acc, float k, const f
 // DIAG (streaming form, lldwt_set_diagnostics: timing only, WRONG results): 1 = every step reads the weight fragments of step 0
 // (same instruction stream, L1-resident weights), 2 = the inputs are constants instead of loads.  Addresses: a subset of the real ones.
 // RDO (WF, encoder only): the epilogue chooses the symbol by the rate-distortion rule of DESIGN.md 7.1.7 (rdo_symbol, common.h)
-template <int PREC, bool WF = false, bool TRAIN = false, bool PERS = false, int DIAG = 0, bool RDO = false>
+// MAP (WF): the epilogue takes (q, inv_q) of the pixel's block from the step map instead of the launch's pair.
+// The pair is loaded in the epilogue, after the chain's registers have died (only the last accumulator tile is live there), so
+// the chain itself is the scalar form's instruction for instruction; its own instantiation, the others are untouched.
+template <int PREC, bool WF = false, bool TRAIN = false, bool PERS = false, int DIAG = 0, bool RDO = false, bool MAP = false>
 __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_eu(TRAIN ? 2 : 3, TRAIN ? 2 : 3))) void k_cgp16(Cgp16Args a) {
     // (TRAIN: two waves per SIMD -- the store addresses do not fit the 168 registers of three)
     static_assert(!TRAIN || (PREC == 0 && !WF), "the training forward runs the split-fp16 arithmetic on whole images");
     static_assert(!PERS || (!WF && !TRAIN), "the persistent form is the whole-image eval chain");
     static_assert(DIAG == 0 || (!PERS && PREC == 0 && !WF && !TRAIN), "the bound-only variants are of the streaming eval chain");
     static_assert(!RDO || WF, "the rate-distortion rule belongs to the wavefront step's encoder epilogue");
+    static_assert(!MAP || WF, "the step map belongs to the wavefront step's epilogue");
     constexpr int SB = PREC == 2 ? STEP_BYTES / 2 : STEP_BYTES;
     constexpr int NW = PERS ? 12 : 4;                       // waves per workgroup
     // (PERS: the wave number as a scalar, so that its block, image and the loads' base addresses are scalars too)
@@ -551,21 +560,32 @@ __global__ __launch_bounds__(PERS ? 768 : 256) __attribute__((amdgpu_waves_per_e
                     const float sigma = acc3[nb][0] * inv3 + bias3[0], mu = acc3[nb][1] * inv3 + bias3[1];
                     // the quantiser with a step: the table is entered with sigma / q, symbol = round((y - mu) / q),
                     // value = symbol * q + mu (|symbol| < 2^12 and q = n / 16: the product is exact); q = 1 leaves every value as it was
-                    const float sb = fmaxf(sigma * a.wf_invq, 0.11f);             // GaussianConditional's scale bound (:32-33)
+                    const int i = col * (32 * NB) + nb * 32 + pl;
+                    float q, invq;
+                    if constexpr (MAP) {                                          // the host checked that the map covers the level
+                        const int py = a.wf_y0 + i, px = a.wf_t - a.wf_slope * py;
+                        const float2 pr = *reinterpret_cast<const float2*>(
+                            a.wf_qpairs + (((z % a.batch) * a.wf_mh + (py >> a.wf_shift)) * a.wf_mw + (px >> a.wf_shift)) * 2);
+                        q = pr.x;
+                        invq = pr.y;
+                    } else {
+                        q = a.wf_q;
+                        invq = a.wf_invq;
+                    }
+                    const float sb = fmaxf(sigma * invq, 0.11f);                  // GaussianConditional's scale bound (:32-33)
                     int idx = 0;
                     for (int k = 0; k < 63; ++k) idx += a.wf_table[k] < sb ? 1 : 0;   // build_indexes
-                    const int i = col * (32 * NB) + nb * 32 + pl;
                     const int64_t o = (z * a.wf_ntot + a.wf_off + i) * a.groups + g;
                     a.wf_idx[o] = idx;
                     if (a.wf_y) {                                                 // encoder: symbol = round(y - mu), value = symbol + mu
                         const int64_t e = (z * a.groups + g) * hw + pix[nb];
                         int sym;
                         if constexpr (RDO)
-                            sym = rdo_symbol(a.wf_y[e] - mu, a.wf_invq, idx,
+                            sym = rdo_symbol(a.wf_y[e] - mu, invq, idx,
                                              RdoTables{a.wf_cost, a.wf_sizes, a.wf_offsets, a.wf_ntab, a.wf_width, a.wf_k});
-                        else sym = (int)rintf((a.wf_y[e] - mu) * a.wf_invq);
+                        else sym = (int)rintf((a.wf_y[e] - mu) * invq);
                         a.wf_sym[o] = sym;
-                        a.wf_yhat[e] = (float)sym * a.wf_q + mu;
+                        a.wf_yhat[e] = (float)sym * q + mu;
                     } else {
                         a.wf_mu[(z * a.groups + g) * a.wf_n + i] = mu;
                         if (a.wf_sigma) a.wf_sigma[(z * a.groups + g) * a.wf_n + i] = sigma;
@@ -976,6 +996,18 @@ __global__ void k_wf_apply(const int* __restrict__ sym, const float* __restrict_
     yhat[(z * groups + g) * (int64_t)h * w + (int64_t)y * w + x] = (float)sym[(z * ntot + off + i) * groups + g] * q + mu[(z * groups + g) * n + i];
 }
 
+// the same with a step map: q of the pixel's block (k_cgp16 MAP)
+__global__ void k_wf_apply_map(const int* __restrict__ sym, const float* __restrict__ mu, float* __restrict__ yhat, int groups, int h,
+                               int w, int t, int slope, int y0, int n, int64_t ntot, int64_t off, const float* __restrict__ qpairs,
+                               int batch, int mh, int mw, int shift) {
+    const int64_t z = blockIdx.z;
+    const int g = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int y = y0 + i, x = t - slope * y;
+    const float q = qpairs[(((z % batch) * mh + (y >> shift)) * mw + (x >> shift)) * 2];
+    yhat[(z * groups + g) * (int64_t)h * w + (int64_t)y * w + x] = (float)sym[(z * ntot + off + i) * groups + g] * q + mu[(z * groups + g) * n + i];
+}
+
 // a quantisation step the coder accepts: q = n / 16, n an integer in [4, 1024], and inv_q = fp32(1 / q)
 static inline bool wf_step_ok(float q, float inv_q) {
     const float n = q * 16.f;
@@ -992,13 +1024,32 @@ static inline void wf_range(int t, int slope, int h, int w, int& y0, int& n) {
     n = hi >= lo ? hi - lo + 1 : 0;
 }
 
+// a step map as the entry points take it: (batch, mh, mw, 2) pairs, one per 2^shift x 2^shift pixels
+struct StepMap {
+    const float* qpairs;
+    int64_t mh, mw;
+    int shift;
+};
+
+// what the device cannot check is formed in one place on the host (ops.step_map_pairs); here: the map covers the h x w level
+static inline bool wf_map_ok(const StepMap& m, int64_t h, int64_t w) {
+    return m.qpairs && (reinterpret_cast<uintptr_t>(m.qpairs) & 7) == 0 && m.shift >= 0 && m.shift <= 30 && m.mh > 0 && m.mw > 0 &&
+           m.mh < ((int64_t)1 << 31) && m.mw < ((int64_t)1 << 31) && m.mh >= cdiv(h, (int64_t)1 << m.shift) &&
+           m.mw >= cdiv(w, (int64_t)1 << m.shift);
+}
+
 // q = n / 16 with an integer n in [4, 1024], inv_q = fp32(1 / q) from the host (both checked here: encoder and decoder must use the
 // same pair).  sigma_out: decoder only, may be null.
-// rdo: null for the nearest-level quantiser.
+// rdo: null for the nearest-level quantiser.  map: null for one step (q, inv_q); else the step map, and q, inv_q are not read.
 static int wavefront_step(const float* plc, float* yhat, const float* y, const void* packed, const float* table63, int* idx, int* sym,
                           float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h, int64_t w_, int groups, int K,
-                          uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q, float inv_q, const RdoTables* rdo, void* stream) {
-    LLDWT_REQUIRE(wf_step_ok(q, inv_q), "cgp16_wavefront_step: step %g (1 / step %g) is not n / 16 with n in [4, 1024]", (double)q, (double)inv_q);
+                          uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q, float inv_q, const RdoTables* rdo, const StepMap* map,
+                          void* stream) {
+    if (map)
+        LLDWT_REQUIRE(wf_map_ok(*map, h, w_), "cgp16_wavefront_step_map: null or misaligned step map, or a %lld x %lld map at shift %d that "
+                      "does not cover the %lld x %lld level", (long long)map->mh, (long long)map->mw, map->shift, (long long)h, (long long)w_);
+    else
+        LLDWT_REQUIRE(wf_step_ok(q, inv_q), "cgp16_wavefront_step: step %g (1 / step %g) is not n / 16 with n in [4, 1024]", (double)q, (double)inv_q);
     LLDWT_REQUIRE(!(y && sigma_out), "cgp16_wavefront_step: sigma_out is an output of the decoder mode (y == null)");
     LLDWT_REQUIRE(plc && yhat && packed && table63 && idx && (y ? sym != nullptr : mu != nullptr), "cgp16_wavefront_step: null pointer");
     LLDWT_REQUIRE(planes > 0 && batch > 0 && h > 0 && w_ > 0 && groups > 0 && (K == 3 || K == 5), "cgp16_wavefront_step: bad arguments");
@@ -1030,9 +1081,13 @@ static int wavefront_step(const float* plc, float* yhat, const float* y, const v
     a.cols = (int)cdiv(a.wf_n, 32 * NB);
     a.stamps = nullptr;
     a.pairs = 0;
+    a.wf_qpairs = map ? map->qpairs : nullptr;
+    a.wf_mh = map ? (int)map->mh : 0; a.wf_mw = map ? (int)map->mw : 0; a.wf_shift = map ? map->shift : 0;
     dim3 grid((unsigned)cdiv(a.cols, 4), (unsigned)groups, (unsigned)(planes * batch));
     // always the fp32-accurate arithmetic: encoder and decoder must agree bit for bit whatever the precision mode of the process
-    if (rdo) hipLaunchKernelGGL((k_cgp16<0, true, false, false, 0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    if (map && rdo) hipLaunchKernelGGL((k_cgp16<0, true, false, false, 0, true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (map) hipLaunchKernelGGL((k_cgp16<0, true, false, false, 0, false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (rdo) hipLaunchKernelGGL((k_cgp16<0, true, false, false, 0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((k_cgp16<0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("cgp16_wavefront_step");
 }
@@ -1042,7 +1097,7 @@ extern "C" int lldwt_cgp16_wavefront_step_q(const float* plc, float* yhat, const
                                             int64_t w_, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off, float q,
                                             float inv_q, void* stream) {
     return wavefront_step(plc, yhat, y, packed, table63, idx, sym, mu, sigma_out, planes, batch, h, w_, groups, K, tap_mask, t, ntot, off,
-                          q, inv_q, nullptr, stream);
+                          q, inv_q, nullptr, nullptr, stream);
 }
 
 // the encoder step with rate-distortion optimised quantisation; the decoder is the entry point above
@@ -1057,7 +1112,28 @@ extern "C" int lldwt_cgp16_wavefront_step_rdo(const float* plc, float* yhat, con
     LLDWT_REQUIRE(rdo_k_ok(k), "cgp16_wavefront_step_rdo: k %g is not (m / 64) * 2^-16 with an integer m in [1, %d]", (double)k, RDO_M_MAX);
     const RdoTables rdo{cost, sizes, offsets, ntab, width, k};
     return wavefront_step(plc, yhat, y, packed, table63, idx, sym, mu, sigma_out, planes, batch, h, w_, groups, K, tap_mask, t, ntot, off,
-                          q, inv_q, &rdo, stream);
+                          q, inv_q, &rdo, nullptr, stream);
+}
+
+// the step with a step map: both modes of lldwt_cgp16_wavefront_step_q, and with cost != null the encoder of
+// lldwt_cgp16_wavefront_step_rdo
+extern "C" int lldwt_cgp16_wavefront_step_map(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                              int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch,
+                                              int64_t h, int64_t w_, int groups, int K, uint32_t tap_mask, int t, int64_t ntot,
+                                              int64_t off, const float* qpairs, int64_t mh, int64_t mw, int shift,
+                                              const int32_t* cost, const int32_t* sizes, const int32_t* offsets, int32_t ntab,
+                                              int32_t width, float k, void* stream) {
+    const StepMap map{qpairs, mh, mw, shift};
+    if (!cost)
+        return wavefront_step(plc, yhat, y, packed, table63, idx, sym, mu, sigma_out, planes, batch, h, w_, groups, K, tap_mask, t, ntot,
+                              off, 1.f, 1.f, nullptr, &map, stream);
+    LLDWT_REQUIRE(y, "cgp16_wavefront_step_map: rdo is a choice of the encoder (y == null is the decoder: pass no cost tables)");
+    LLDWT_REQUIRE(sizes && offsets, "cgp16_wavefront_step_map: null cost table pointer");
+    LLDWT_REQUIRE(ntab > 0 && width > 0, "cgp16_wavefront_step_map: bad cost table sizes (%d x %d)", ntab, width);
+    LLDWT_REQUIRE(rdo_k_ok(k), "cgp16_wavefront_step_map: k %g is not (m / 64) * 2^-16 with an integer m in [1, %d]", (double)k, RDO_M_MAX);
+    const RdoTables rdo{cost, sizes, offsets, ntab, width, k};
+    return wavefront_step(plc, yhat, y, packed, table63, idx, sym, mu, sigma_out, planes, batch, h, w_, groups, K, tap_mask, t, ntot, off,
+                          1.f, 1.f, &rdo, &map, stream);
 }
 
 // the unit step: multiplying by 1.0f changes no bit, so these are the bits this entry point has always produced
@@ -1080,6 +1156,25 @@ extern "C" int lldwt_wavefront_apply_q(const int* sym, const float* mu, float* y
     dim3 grid((unsigned)cdiv(n, 64), (unsigned)groups, (unsigned)(planes * batch));
     hipLaunchKernelGGL(k_wf_apply, grid, dim3(64), 0, (hipStream_t)stream, sym, mu, yhat, groups, (int)h, (int)w_, t, slope, y0, n, ntot, off, q);
     return check_launch("wavefront_apply");
+}
+
+extern "C" int lldwt_wavefront_apply_map(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h,
+                                         int64_t w_, int groups, int K, int t, int64_t ntot, int64_t off, const float* qpairs,
+                                         int64_t mh, int64_t mw, int shift, void* stream) {
+    LLDWT_REQUIRE(sym && mu && yhat && planes > 0 && batch > 0 && h > 0 && w_ > 0 && groups > 0 && (K == 3 || K == 5), "wavefront_apply_map: bad arguments");
+    LLDWT_REQUIRE(planes * batch <= 65535 && groups <= 65535, "wavefront_apply_map: grid too large");
+    const StepMap map{qpairs, mh, mw, shift};
+    LLDWT_REQUIRE(wf_map_ok(map, h, w_), "wavefront_apply_map: null or misaligned step map, or a %lld x %lld map at shift %d that does not "
+                  "cover the %lld x %lld level", (long long)mh, (long long)mw, shift, (long long)h, (long long)w_);
+    const int slope = K / 2 + 1;
+    int y0, n;
+    wf_range(t, slope, (int)h, (int)w_, y0, n);
+    if (n == 0) return LLDWT_OK;
+    LLDWT_REQUIRE(off >= 0 && off + n <= ntot, "wavefront_apply_map: step does not fit");
+    dim3 grid((unsigned)cdiv(n, 64), (unsigned)groups, (unsigned)(planes * batch));
+    hipLaunchKernelGGL(k_wf_apply_map, grid, dim3(64), 0, (hipStream_t)stream, sym, mu, yhat, groups, (int)h, (int)w_, t, slope, y0, n, ntot,
+                       off, qpairs, (int)batch, (int)mh, (int)mw, shift);
+    return check_launch("wavefront_apply_map");
 }
 
 extern "C" int lldwt_wavefront_apply(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h,

@@ -21,6 +21,10 @@ struct QuantArgs {
     int lvec;                                    // VEC 4: the four level elements of a thread are one aligned float4 (s == 1)
     float q, inv_q;
     RdoTables rdo;                               // RDO (lldwt_gauss_quantise_rdo): the code-length tables and k of DESIGN.md 7.1.7
+    // MAP (lldwt_gauss_quantise_map): (units, mh, mw, 2) fp32 pairs (q, inv_q), one per block of 2^shift x 2^shift
+    // level positions; stream z reads the map of unit z % units.  q, inv_q above are not read.
+    const float* qpairs;
+    int units, mh, mw, shift;
 };
 
 // the normative quantiser (the epilogue of k_cgp16's wavefront mode, csrc/cgp_f16x3.hip, is the same three lines)
@@ -33,7 +37,8 @@ __device__ __forceinline__ int cdf_index(float sigma, float inv_q, const float (
 }
 
 // RDO: the encoder's symbol is chosen by rdo_symbol (common.h) between the nearest level and the one next to it toward zero
-template <int VEC, bool RDO = false>
+// MAP: every element takes the pair of its block of the step map instead of the launch's one pair; the arithmetic is the same
+template <int VEC, bool RDO = false, bool MAP = false>
 __global__ __launch_bounds__(NT) void k_gauss_quantise(QuantArgs a) {
     const int64_t hw = (int64_t)a.h * a.w;
     const int64_t v = ((int64_t)blockIdx.x * NT + threadIdx.x) * VEC;          // first element of this thread inside the (z, c) grid
@@ -46,8 +51,23 @@ __global__ __launch_bounds__(NT) void k_gauss_quantise(QuantArgs a) {
     const float* sg = a.params + ((z * 2 * a.C + 2 * c) * hw + v);
     const int i = (int)(v / a.w), j = (int)(v - (int64_t)i * a.w);               // VEC 4: w % 4 == 0, the four share the row
     const int64_t lv = zc * a.H * a.W + (int64_t)(a.r0 + a.s * i) * a.W + a.c0 + a.s * j;
-    float sigma[VEC], mu[VEC], val[VEC];
+    float sigma[VEC], mu[VEC], val[VEC], q[VEC], inv_q[VEC];
     int sym[VEC], idx[VEC];
+    if constexpr (MAP) {                                                        // the host checked that the map covers the level
+        const float* row = a.qpairs + ((int64_t)(z % a.units) * a.mh + ((a.r0 + a.s * i) >> a.shift)) * a.mw * 2;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float2 pr = *reinterpret_cast<const float2*>(row + 2 * ((a.c0 + a.s * (j + e)) >> a.shift));
+            q[e] = pr.x;
+            inv_q[e] = pr.y;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            q[e] = a.q;
+            inv_q[e] = a.inv_q;
+        }
+    }
     if constexpr (VEC == 4) {
         const float4 s4 = *reinterpret_cast<const float4*>(sg), m4 = *reinterpret_cast<const float4*>(sg + hw);
         sigma[0] = s4.x; sigma[1] = s4.y; sigma[2] = s4.z; sigma[3] = s4.w;
@@ -66,10 +86,10 @@ __global__ __launch_bounds__(NT) void k_gauss_quantise(QuantArgs a) {
         }
         if constexpr (RDO) {                                                     // the index does not depend on the choice
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) sym[e] = rdo_symbol(val[e] - mu[e], a.inv_q, cdf_index(sigma[e], a.inv_q, tab), a.rdo);
+            for (int e = 0; e < VEC; ++e) sym[e] = rdo_symbol(val[e] - mu[e], inv_q[e], cdf_index(sigma[e], inv_q[e], tab), a.rdo);
         } else {
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) sym[e] = (int)rintf((val[e] - mu[e]) * a.inv_q);
+            for (int e = 0; e < VEC; ++e) sym[e] = (int)rintf((val[e] - mu[e]) * inv_q[e]);
         }
     } else if (a.sym_in) {
         if constexpr (VEC == 4) {
@@ -84,8 +104,8 @@ __global__ __launch_bounds__(NT) void k_gauss_quantise(QuantArgs a) {
     }
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-        idx[e] = cdf_index(sigma[e], a.inv_q, tab);
-        val[e] = (float)sym[e] * a.q + mu[e];
+        idx[e] = cdf_index(sigma[e], inv_q[e], tab);
+        val[e] = (float)sym[e] * q[e] + mu[e];
     }
     if constexpr (VEC == 4) {
         *reinterpret_cast<int4*>(a.idx + zc * hw + v) = make_int4(idx[0], idx[1], idx[2], idx[3]);
@@ -143,15 +163,22 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 }  // namespace
 
-// rdo: null for the plain quantiser
+// a step map as the entry points take it
+struct StepMap {
+    const float* qpairs;
+    int64_t units, mh, mw;
+    int shift;
+};
+
+// rdo: null for the plain quantiser.  map: null for one step (q, inv_q), else the step map, and q, inv_q are not read.
 static int gauss_quantise(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
                           int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W,
-                          int r0, int c0, int stride, float q, float inv_q, const RdoTables* rdo, void* stream) {
+                          int r0, int c0, int stride, float q, float inv_q, const RdoTables* rdo, const StepMap* map, void* stream) {
     LLDWT_REQUIRE(params && table63 && idx, "gauss_quantise: null pointer");
     LLDWT_REQUIRE(!(y && sym_in), "gauss_quantise: give y (encoder) or sym_in (decoder), not both");
     LLDWT_REQUIRE((level != nullptr) == (y || sym_in), "gauss_quantise: level goes with y or sym_in (neither: the indexes only)");
     LLDWT_REQUIRE(!y || sym_out, "gauss_quantise: the encoder needs sym_out");
-    {
+    if (!map) {
         const float n = q * 16.f;
         LLDWT_REQUIRE(n >= 4.f && n <= 1024.f && n == (float)(int)n && inv_q == (float)(1.0 / (double)q),
                       "gauss_quantise: step %g (1 / step %g) is not n / 16 with n in [4, 1024]", (double)q, (double)inv_q);
@@ -163,15 +190,35 @@ static int gauss_quantise(const float* params, const float* y, const int32_t* sy
                       H * W < ((int64_t)1 << 31),
                   "gauss_quantise: the grid (%d, %d, stride %d) of %lld x %lld does not fit the %lld x %lld level", r0, c0, stride,
                   (long long)h, (long long)w, (long long)H, (long long)W);
+    if (map) {
+        LLDWT_REQUIRE(map->qpairs && (reinterpret_cast<uintptr_t>(map->qpairs) & 7) == 0,
+                      "gauss_quantise_map: null step map (or one not aligned to its pairs)");
+        LLDWT_REQUIRE(map->units > 0 && streams % map->units == 0, "gauss_quantise_map: %lld streams are not whole planes of %lld units",
+                      (long long)streams, (long long)map->units);
+        LLDWT_REQUIRE(map->shift >= 0 && map->shift <= 30 && map->mh > 0 && map->mw > 0 && map->mh < ((int64_t)1 << 31) &&
+                          map->mw < ((int64_t)1 << 31) && map->mh >= cdiv(H, (int64_t)1 << map->shift) &&
+                          map->mw >= cdiv(W, (int64_t)1 << map->shift),
+                      "gauss_quantise_map: a %lld x %lld map at shift %d does not cover the %lld x %lld level", (long long)map->mh,
+                      (long long)map->mw, map->shift, (long long)H, (long long)W);
+    }
     QuantArgs a;
     a.params = params; a.y = y; a.sym_in = sym_in; a.table = table63; a.idx = idx; a.sym_out = sym_out; a.level = level;
     a.C = channels; a.h = (int)h; a.w = (int)w; a.H = (int)H; a.W = (int)W; a.r0 = r0; a.c0 = c0; a.s = stride;
     a.q = q; a.inv_q = inv_q;
     a.rdo = rdo ? *rdo : RdoTables{nullptr, nullptr, nullptr, 0, 0, 0.f};
+    a.qpairs = map ? map->qpairs : nullptr;
+    a.units = map ? (int)map->units : 1; a.mh = map ? (int)map->mh : 0; a.mw = map ? (int)map->mw : 0; a.shift = map ? map->shift : 0;
     const bool vec = w % 4 == 0 && aligned16(params) && aligned16(idx) && (!sym_in || aligned16(sym_in)) && (!sym_out || aligned16(sym_out));
     a.lvec = vec && stride == 1 && W % 4 == 0 && c0 % 4 == 0 && (!level || aligned16(level)) && (!y || aligned16(y));
     const int per = vec ? 4 : 1;
     dim3 grid((unsigned)cdiv(cdiv(h * w, per), NT), (unsigned)(streams * channels));
+    if (map) {
+        if (rdo && vec) hipLaunchKernelGGL((k_gauss_quantise<4, true, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
+        else if (rdo) hipLaunchKernelGGL((k_gauss_quantise<1, true, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
+        else if (vec) hipLaunchKernelGGL((k_gauss_quantise<4, false, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((k_gauss_quantise<1, false, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
+        return check_launch("gauss_quantise_map");
+    }
     if (rdo && vec) hipLaunchKernelGGL((k_gauss_quantise<4, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
     else if (rdo) hipLaunchKernelGGL((k_gauss_quantise<1, true>), grid, dim3(NT), 0, (hipStream_t)stream, a);
     else if (vec) hipLaunchKernelGGL(k_gauss_quantise<4>, grid, dim3(NT), 0, (hipStream_t)stream, a);
@@ -183,7 +230,7 @@ extern "C" int lldwt_gauss_quantise(const float* params, const float* y, const i
                                     int32_t* sym_out, float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H,
                                     int64_t W, int r0, int c0, int stride, float q, float inv_q, void* stream) {
     return gauss_quantise(params, y, sym_in, table63, idx, sym_out, level, streams, channels, h, w, H, W, r0, c0, stride, q, inv_q,
-                          nullptr, stream);
+                          nullptr, nullptr, stream);
 }
 
 // the encoder with rate-distortion optimised quantisation: encoder mode only, the decoder is
@@ -198,7 +245,27 @@ extern "C" int lldwt_gauss_quantise_rdo(const float* params, const float* y, con
     LLDWT_REQUIRE(rdo_k_ok(k), "gauss_quantise_rdo: k %g is not (m / 64) * 2^-16 with an integer m in [1, %d]", (double)k, RDO_M_MAX);
     const RdoTables rdo{cost, sizes, offsets, ntab, width, k};
     return gauss_quantise(params, y, nullptr, table63, idx, sym_out, level, streams, channels, h, w, H, W, r0, c0, stride, q, inv_q, &rdo,
-                          stream);
+                          nullptr, stream);
+}
+
+// the quantiser with a step map: the three modes of lldwt_gauss_quantise, and with cost != null the encoder of
+// lldwt_gauss_quantise_rdo
+extern "C" int lldwt_gauss_quantise_map(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
+                                        int32_t* sym_out, float* level, int64_t streams, int64_t units, int channels, int64_t h,
+                                        int64_t w, int64_t H, int64_t W, int r0, int c0, int stride, const float* qpairs, int64_t mh,
+                                        int64_t mw, int shift, const int32_t* cost, const int32_t* sizes, const int32_t* offsets,
+                                        int32_t ntab, int32_t width, float k, void* stream) {
+    const StepMap map{qpairs, units, mh, mw, shift};
+    if (!cost)
+        return gauss_quantise(params, y, sym_in, table63, idx, sym_out, level, streams, channels, h, w, H, W, r0, c0, stride, 1.f, 1.f,
+                              nullptr, &map, stream);
+    LLDWT_REQUIRE(y && level && sym_out, "gauss_quantise_map: rdo is a choice of the encoder (y, level and sym_out must be given)");
+    LLDWT_REQUIRE(sizes && offsets, "gauss_quantise_map: null cost table pointer");
+    LLDWT_REQUIRE(ntab > 0 && width > 0, "gauss_quantise_map: bad cost table sizes (%d x %d)", ntab, width);
+    LLDWT_REQUIRE(rdo_k_ok(k), "gauss_quantise_map: k %g is not (m / 64) * 2^-16 with an integer m in [1, %d]", (double)k, RDO_M_MAX);
+    const RdoTables rdo{cost, sizes, offsets, ntab, width, k};
+    return gauss_quantise(params, y, nullptr, table63, idx, sym_out, level, streams, channels, h, w, H, W, r0, c0, stride, 1.f, 1.f,
+                          &rdo, &map, stream);
 }
 
 extern "C" int lldwt_code_cost(const int32_t* sym, const int32_t* idx, int64_t streams, int64_t n, const int32_t* cost, int32_t ntab,

@@ -154,14 +154,45 @@ def _coarse_strings(strings_xo_list, L, first_level):
     return [None] * k + s[len(s) - (L - k):]
 
 
-def _check_step(step, L):
+def _check_step(step, L, layers=None):
     """The quantisation step of a coded layer's compress_planes / decompress_planes -> the step as a float.
     It reaches the levels 0 .. L-2, whose Gaussian parameters are conditioned on a decoded parent; xe and the coarsest level
-    keep the unit step, so with fewer than two levels there is nothing it could apply to."""
+    keep the unit step, so with fewer than two levels there is nothing it could apply to.
+    A tensor is a step map (_check_step_map) -> its pairs on the layers' device; _level_step hands them to the levels."""
+    if isinstance(step, torch.Tensor):
+        return _check_step_map(step, L).to(next(layers[0].parameters()).device).contiguous()
     q, _ = ops.step_pair(step)
     if q != 1.0 and L < 2:
         raise ValueError("step: a step other than 1 needs dwtlevels >= 2 (it applies to the levels below the coarsest; got %d)" % L)
     return q
+
+
+def _check_step_map(step_map, L):
+    """A step map where a coded layer takes a step: an integer tensor (B, mh, mw) of n = 16 * step, one map per
+    image of the call, already cut to the image's coded extent -- entry (i, j) is the step of the block of 2^L x 2^L pixels at
+    (i, j), i.e. of one coefficient of the coarsest level -> its (B, mh, mw, 2) pairs (ops.step_map_pairs; on the host, the
+    layer moves them to its device).  ValueError naming step_map."""
+    if step_map.dim() != 3 or step_map.dtype.is_floating_point or step_map.dtype == torch.bool:
+        raise ValueError("step_map: an integer tensor (B, mh, mw) of n = 16 * step (got %s %s)" % (step_map.dtype, tuple(step_map.shape)))
+    if L < 2:
+        raise ValueError("step_map: a step map needs dwtlevels >= 2 (it applies to the levels below the coarsest; got %d)" % L)
+    return ops.step_map_pairs(step_map)
+
+
+def _level_step(step, L, i, shape, dev):
+    """The step argument of level i's coding function: the number, or the ops.StepMap of the pairs at that level's shift,
+    L - 1 - i (level i has 2^(L-1-i) samples per side for each of the coarsest level's).  shape: the level's (P,B,C,h,w)."""
+    if not isinstance(step, torch.Tensor):
+        return step
+    if step.shape[0] != shape[1]:
+        raise ValueError("step_map: %d maps for %d images" % (step.shape[0], shape[1]))
+    s = L - 1 - i
+    if (step.shape[1] << s) < shape[3] or (step.shape[2] << s) < shape[4]:
+        raise ValueError("step_map: %d x %d blocks do not cover level %d of %d x %d samples" % (step.shape[1], step.shape[2], i,
+                                                                                                 shape[3], shape[4]))
+    if step.device != dev:
+        raise ValueError("step_map: the pairs are not on the coding device")
+    return ops.StepMap(step, s)
 
 
 def _check_rdo(rdo, L):
@@ -282,7 +313,7 @@ class onlyEZWT(_EntropyLayerBase):
         """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first)."""
         from . import entropy_coding as ec
         L = len(out_xo_list)
-        step = _check_step(step, L)
+        step = _check_step(step, L, layers)
         rdo = _check_rdo(rdo, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
@@ -294,7 +325,8 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 s, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, out_xo_list[i],
-                                                 out_xo_list[i].shape, tabs, coder=coder, step=step, rdo=rdo)
+                                                 out_xo_list[i].shape, tabs, coder=coder,
+                                                 step=_level_step(step, L, i, out_xo_list[i].shape, ms.device), rdo=rdo)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -308,7 +340,7 @@ class onlyEZWT(_EntropyLayerBase):
         levels k .. L-1 (_coarse_strings)."""
         from . import entropy_coding as ec
         L = len(shapes_xo)
-        step = _check_step(step, L)
+        step = _check_step(step, L, layers)
         strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
@@ -322,7 +354,8 @@ class onlyEZWT(_EntropyLayerBase):
                     l.ent_out_xo_list[i].update_scale_table(get_scale_table())
                 ms = onlyEZWT._level_params(layers, i, q)
                 _, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, None, shapes_xo[i], tabs,
-                                                 strings_xo_list[i], coder=coder, step=step)
+                                                 strings_xo_list[i], coder=coder,
+                                                 step=_level_step(step, L, i, shapes_xo[i], ms.device))
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -488,7 +521,7 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         from . import entropy_coding as ec
         tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
         L = len(out_xo_list)
-        step = _check_step(step, L)
+        step = _check_step(step, L, layers)
         rdo = _check_rdo(rdo, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], out_xe,
@@ -500,12 +533,13 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
                 x = out_xo_list[i]
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, x.shape[2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
+                st_i = _level_step(step, L, i, x.shape, plc.device)
                 if packed[1] is not None:       # the reference's cgp widths: one fused launch per wavefront step
-                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder, step=step,
+                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder, step=st_i,
                                               rdo=rdo)
                 else:
                     s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs, coder=coder,
-                                                         step=step, rdo=rdo)
+                                                         step=st_i, rdo=rdo)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -520,7 +554,7 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         from . import entropy_coding as ec
         tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
         L = len(shapes_xo)
-        step = _check_step(step, L)
+        step = _check_step(step, L, layers)
         strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], None, shape_xe, tabs,
@@ -533,12 +567,13 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
             for i in range(L - 2, first_level - 1, -1):
                 plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, shapes_xo[i][2])
                 em_i = [l.ent_out_xo_list[i] for l in layers]
+                st_i = _level_step(step, L, i, shapes_xo[i], plc.device)
                 if packed[1] is not None:
                     _, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, None, shapes_xo[i], tabs, strings_xo_list[i], coder=coder,
-                                              step=step)
+                                              step=st_i)
                 else:
                     _, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, None, shapes_xo[i], tabs,
-                                                      strings_xo_list[i], coder=coder, step=step)
+                                                      strings_xo_list[i], coder=coder, step=st_i)
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -670,7 +705,7 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(out_xo_list)
-        step = _check_step(step, L)
+        step = _check_step(step, L, layers)
         rdo = _check_rdo(rdo, L)
         with torch.no_grad():
             s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
@@ -680,7 +715,7 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
                 x = out_xo_list[L - i - 2]
                 ems, tabs = cls._level_models(layers, i, L)
                 s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs, coder=coder,
-                                             step=step, rdo=rdo)
+                                             step=_level_step(step, L, L - i - 2, x.shape, x.device), rdo=rdo)
                 s_list.append(s)
                 q_list.append(q)
         s_list.reverse()
@@ -695,7 +730,7 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
         cls = DWTConditioned2EntropyLayerZTBlock
         cls._require_clrch1(layers)
         L = len(shapes_xo)
-        step = _check_step(step, L)
+        step = _check_step(step, L, layers)
         strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
         with torch.no_grad():
             _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
@@ -706,7 +741,8 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
             for i in range(L - 1 - first_level):          # i counts from the coarse end: level L - i - 2 >= first_level
                 ems, tabs = cls._level_models(layers, i, L)
                 _, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, None, shapes_xo[L - i - 2], tabs,
-                                             strings_xo_list[L - i - 2], coder=coder, step=step)
+                                             strings_xo_list[L - i - 2], coder=coder,
+                                             step=_level_step(step, L, L - i - 2, shapes_xo[L - i - 2], q.device))
                 q_list.append(q)
         q_list.reverse()
         return xe, q_list
@@ -1092,12 +1128,14 @@ def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None
     decode_strings_planes makes (the codec's residual layer).
     step: the quantisation step of the levels 0 .. L-2 (n / 16, 1 = the trained operating point).
     rdo: the Lagrangian of rate-distortion optimised quantisation on the same levels (m / 64, None or 0: off).
-    An encoder's choice: the strings decode with decode_strings_planes as ever."""
+    An encoder's choice: the strings decode with decode_strings_planes as ever.
+    step may be a step map instead: an integer tensor (B, Hp >> L, Wp >> L) of n = 16 * step, one entry per
+    coefficient of the coarsest level of each image; decode_strings_planes takes the same tensor."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "compress_planes"):
         raise NotImplementedError(_NOT_CODED)
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
-    kw = {} if step == 1.0 else {"step": step}
+    kw = {"step": step} if isinstance(step, torch.Tensor) or step != 1.0 else {}
     if not (rdo is None or rdo == 0):
         kw["rdo"] = rdo
     s_xe, s_xo, xe_q, xo_q = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder, **kw)
@@ -1118,7 +1156,8 @@ def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host",
     aenc = [n.autoencoder for n in nets]
     k = int(first_level)
     shape_xe, shapes_xo = encode_shapes(aenc, B, Hp, Wp)
-    kw = {} if step == 1.0 else {"step": step}              # the step the strings were coded with (the container's header)
+    # the step, or the step map, the strings were coded with (the container's header)
+    kw = {"step": step} if isinstance(step, torch.Tensor) or step != 1.0 else {}
     xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder, first_level=k, **kw)
     assert [tuple(t.shape) for t in xo] == [tuple(sh) for sh in shapes_xo[k:]]
     return decode_planes(aenc, xe, xo, first_level=k)

@@ -226,7 +226,23 @@ def _finish_step(emodel, sink, sigma, mu, yv, step=1.0, rdo=None):
     """sigma, mu (P,B,g,N); yv (P,B,g,N) or None when decoding -> dequantised values (P,B,g,N).  step != 1: the quantiser
     of DESIGN.md 7.1.6 restated in fp32 tensor ops (the table entered with sigma / q, round((y - mu) / q), symbol * q + mu).
     rdo (encoder only): (k, cost, sizes, offsets) of _rdo_args -- the symbol is chosen by the rule of DESIGN.md 7.1.7, restated
-    in tensor ops (ops.rdo_lookup, ops.rdo_choose)."""
+    in tensor ops (ops.rdo_lookup, ops.rdo_choose).
+    step may also be a pair (q, inv_q) of fp32 tensors that broadcast against (P,B,g,N): the per-pixel pairs gathered from a step
+    map (_pixel_pairs); the arithmetic is the same, elementwise."""
+    if isinstance(step, tuple):
+        q, inv_q = step
+        idx = emodel.build_indexes(sigma * inv_q)
+        sym = None
+        if yv is not None:
+            v = (yv - mu) * inv_q
+            sym = torch.round(v)
+            if rdo is not None:
+                k, cost, sizes, offsets = rdo
+                s1 = sym - torch.sign(sym)
+                sym = ops.rdo_choose(v, sym, ops.rdo_lookup(cost, sizes, offsets, idx, sym), ops.rdo_lookup(cost, sizes, offsets, idx, s1), k)
+            sym = sym.int().permute(0, 1, 3, 2).contiguous()
+        sym = sink.step(idx.permute(0, 1, 3, 2).contiguous(), sym)
+        return sym.permute(0, 1, 3, 2).float() * q + mu
     if rdo is not None and yv is not None:
         q, inv_q = ops.step_pair(step)
         idx = emodel.build_indexes(sigma * inv_q)                                       # (P,B,g,N); does not depend on the choice
@@ -251,6 +267,13 @@ def _finish_step(emodel, sink, sigma, mu, yv, step=1.0, rdo=None):
         sym = torch.round((yv - mu) * inv_q).int().permute(0, 1, 3, 2).contiguous()
     sym = sink.step(idx, sym)
     return sym.permute(0, 1, 3, 2).float() * q + mu
+
+
+def _pixel_pairs(smap, h, w):
+    """ops.StepMap, pixel coordinates h, w (N) of a level -> (q, inv_q), each (1,B,1,N): the pairs of the pixels' blocks, for
+    _finish_step."""
+    pr = smap.pairs[:, h >> smap.shift, w >> smap.shift]                              # (B,N,2)
+    return pr[None, :, None, :, 0], pr[None, :, None, :, 1]
 
 
 def code_crop_stack(seq_stack, emodels, seqs, y, shape, tables, strings=None, coder="host"):
@@ -306,12 +329,16 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     step: the quantisation step q of DESIGN.md 7.1.6 (lldwt_cgp16_wavefront_step_q / lldwt_wavefront_apply_q; the unit step
     goes through them too and gives the bits of the entry points without a step).
     rdo: the Lagrangian of DESIGN.md 7.1.7 (None or 0: off); the encoder's steps then go through
-    lldwt_cgp16_wavefront_step_rdo with the level's cost tables, the decoder ignores it."""
+    lldwt_cgp16_wavefront_step_rdo with the level's cost tables, the decoder ignores it.
+    step may be an ops.StepMap over the level: every launch then goes through lldwt_cgp16_wavefront_step_map /
+    lldwt_wavefront_apply_map, with or without the cost tables; the schedule is the same."""
     import ctypes as C
     from ... import _lib
     lib = _lib.load()
-    q, inv_q = ops.step_pair(step)
     P, B, G, H, W = shape
+    if isinstance(step, ops.StepMap):
+        return _code_tree_level_map(lib, emodels, plc, packed16, K, tap_bits, y, shape, tables, strings, coder, step, rdo)
+    q, inv_q = ops.step_pair(step)
     dev = plc.device
     slope = K // 2 + 1
     starts = _step_offsets(H, W, slope)
@@ -378,12 +405,77 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     return None, yhat
 
 
+def _code_tree_level_map(lib, emodels, plc, packed16, K, tap_bits, y, shape, tables, strings, coder, smap, rdo):
+    """code_tree_level with a step map: the same three schedules on the map entry points."""
+    import ctypes as C
+    P, B, G, H, W = shape
+    dev = plc.device
+    starts = _step_offsets(H, W, K // 2 + 1)
+    nsteps, ntot = len(starts) - 1, H * W
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    table63 = emodels[0].scale_table.to(dev).float()[:63].contiguous()
+    yhat = torch.zeros(P, B, G, H, W, device=dev, dtype=torch.float32)
+    sink = _make_sink(coder, P, B, tables, strings, ntot * G, dev)
+    ptr = lambda t_: C.c_void_p(t_.data_ptr())
+    m = ops._map_args(smap, B, H, W)
+    no_rdo = (None, None, None, 0, 0, 0.0)
+
+    def step_launch(yc, idx, sym, mu, t, n, off, ra):
+        ops.check(lib.lldwt_cgp16_wavefront_step_map(ptr(plc), ptr(yhat), yc, ptr(packed16), ptr(table63), ptr(idx), sym, mu, None, P, B,
+                                                     H, W, G, K, int(tap_bits), t, n, off, *m, *ra, st), "cgp16_wavefront_step_map")
+
+    if not sink.decoding:
+        yc = y.contiguous()
+        idx_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
+        sym_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
+        ra = _rdo_args(rdo, tables, dev)
+        if ra is not None:
+            k, cost, csizes, coffs = ra
+            ra = (ptr(cost), ptr(csizes), ptr(coffs), cost.shape[0], cost.shape[1], k)
+        for t in range(nsteps):
+            step_launch(ptr(yc), idx_all, ptr(sym_all), None, t, ntot, starts[t], ra or no_rdo)
+        sink.idx, sink.sym = [idx_all], [sym_all]
+        return sink.flush(), yhat
+    nmax = max(starts[t + 1] - starts[t] for t in range(nsteps))
+    Z = P * B
+    idx_d = torch.empty(Z * nmax * G, device=dev, dtype=torch.int32)
+    sym_d = torch.empty(Z * nmax * G, device=dev, dtype=torch.int32)
+    mu_d = torch.empty(Z * G * nmax, device=dev, dtype=torch.float32)
+    host = coder != "gpu"
+    if host:
+        idx_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
+        sym_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
+        handles = (C.c_void_p * Z)(*[sink.dec[p][b]._h for p in range(P) for b in range(B)])
+        cdf, sizes, offs = tables.cdf, tables.sizes, tables.offsets
+        pv = lambda a_: a_.ctypes.data_as(C.c_void_p)
+    for t in range(nsteps):
+        n = starts[t + 1] - starts[t]
+        if n == 0:
+            continue
+        step_launch(None, idx_d, None, ptr(mu_d), t, n, 0, no_rdo)
+        if host:
+            cnt = Z * n * G
+            idx_h[:cnt].copy_(idx_d[:cnt], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            ops.check(lib.lldwt_rans_decode_multi(handles, Z, C.c_void_p(idx_h.data_ptr()), n * G, n * G, pv(cdf), cdf.shape[0],
+                                                  cdf.shape[1], pv(sizes), pv(offs), C.c_void_p(sym_h.data_ptr())), "rans_decode_multi")
+            sink.note(idx_h[:cnt].numpy(), sym_h[:cnt].numpy())
+            sym_d[:cnt].copy_(sym_h[:cnt], non_blocking=True)
+        else:
+            sink.dec.pop(idx_d, n * G, n * G, sym_d)
+        ops.check(lib.lldwt_wavefront_apply_map(ptr(sym_d), ptr(mu_d), ptr(yhat), P, B, H, W, G, K, t, n, 0, *m, st), "wavefront_apply_map")
+    if not host:
+        sink.finish()
+    return None, yhat
+
+
 def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, shape, tables, strings=None, coder="host",
                             step=1.0, rdo=None):
     """A level with tree context + masked KxK context + cgp (:402-417 / :440-454 with kernel size 5).  plc: (P,B,G*81,H,W)
     tree-context features of the (decoded) parent; cgp_packed/dims: the cgp stack with the masked conv folded into its
     first layer (_fold_csc_into_cgp).  The host-stepped schedule (a handful of tensor ops and launches per step) for cgp widths
-    other than the reference's 93 -> 162 -> 54 -> 18 -> 2, which the fused step kernel of code_tree_level is built for."""
+    other than the reference's 93 -> 162 -> 54 -> 18 -> 2, which the fused step kernel of code_tree_level is built for.
+    step may be an ops.StepMap over the level: each step gathers its pixels' pairs from it (_pixel_pairs)."""
     P, B, G, H, W = shape
     dev = plc.device
     R = K // 2
@@ -392,6 +484,8 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
     hs, ws, starts = wavefront(H, W, R + 1, dev)
     sink = _make_sink(coder, P, B, tables, strings, H * W * G, dev)
     ra = None if sink.decoding else _rdo_args(rdo, tables, dev)
+    if isinstance(step, ops.StepMap):
+        ops._map_args(step, B, H, W)                                                        # the map must cover the level
     yhat = torch.zeros(P, B, G, H + 2 * R, W + 2 * R, device=dev, dtype=torch.float32)
     dy = torch.tensor([t[0] for t in taps], device=dev)
     dx = torch.tensor([t[1] for t in taps], device=dev)
@@ -408,7 +502,8 @@ def code_tree_level_generic(emodels, plc, cgp_packed, cgp_dims, K, tap_bits, y, 
         xarg = (yv if yv is not None else torch.zeros(P, B, G, N, device=dev)).reshape(P, B, G, 1, N).contiguous()
         _, params = ops.cgp_rate(cat, xarg, cgp_packed, cgp_dims, want_params=True)   # (P,B,2G,1,N)
         sigma, mu = params[:, :, 0::2, 0, :], params[:, :, 1::2, 0, :]
-        yhat[:, :, :, h + R, w + R] = _finish_step(emodels[0], sink, sigma, mu, yv, step, ra)
+        yhat[:, :, :, h + R, w + R] = _finish_step(emodels[0], sink, sigma, mu, yv,
+                                                   _pixel_pairs(step, h, w) if isinstance(step, ops.StepMap) else step, ra)
     out = yhat[:, :, :, R:-R, R:-R].contiguous()
     if sink.decoding:
         sink.finish()
@@ -430,7 +525,8 @@ def code_ztblock_level(emodels, packs, parent, y, shape, tables, strings=None, c
     Index, symbol and the dequantised value written into the phase's positions of the level are one launch of
     lldwt_gauss_quantise per phase (two in the decoder: the indexes before the symbols are popped, the values after), with
     the quantisation step of DESIGN.md 7.1.6; the three subbands' models carry one scale table.  rdo: the Lagrangian of DESIGN.md
-    7.1.7 for the encoder's launches (None or 0: off); the decoder ignores it.
+    7.1.7 for the encoder's launches (None or 0: off); the decoder ignores it.  step may be an ops.StepMap over the level
+    (lldwt_gauss_quantise_map forms each phase position's block).
     -> (strings or None, dequantised (P,B,3,2h,2w))."""
     P, B, G, H, W = shape
     h2, w2 = H // 2, W // 2
@@ -514,7 +610,8 @@ def code_gaussian_parallel(emodels, params, y, shape, tables, strings=None, code
     """A level whose (sigma, mu) depend only on already decoded tensors (onlyEZWT: the tree context of the parent level,
     LiftingBasedDWT_net.py:822-835): fully parallel -- indexes and symbols of the whole tensor in one pass, raster order.
     params (P,B,2C,h,w): sigma on the even, mu on the odd channels.  rdo: the Lagrangian of DESIGN.md 7.1.7 for the encoder's
-    launch (None or 0: off); the decoder ignores it.  -> (strings or None, dequantised (P,B,C,h,w))."""
+    launch (None or 0: off); the decoder ignores it.  step: a number or an ops.StepMap over the level.
+    -> (strings or None, dequantised (P,B,C,h,w))."""
     P, B, Cc, H, W = shape
     params = params.contiguous()
     table63 = emodels[0].scale_table.to(params.device).float()[:63].contiguous()

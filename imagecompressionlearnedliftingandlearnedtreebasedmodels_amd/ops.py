@@ -3,6 +3,7 @@
 Tensor convention: "plane-major" (P, B, C, h, w) fp32 contiguous CUDA(HIP) tensors; P = number of per-plane networks
 (3 for clrch == 1), parameters stacked on a leading P axis.
 """
+import collections
 import ctypes as C
 import os
 
@@ -1022,6 +1023,46 @@ def step_pair(step):
     return q, float(torch.tensor(1.0 / q, dtype=torch.float32))
 
 
+class StepMap(collections.namedtuple("StepMap", "pairs shift")):
+    """A step map as a level sees it: pairs (units, mh, mw, 2) fp32 device tensor of step_map_pairs, one map
+    per unit (image or tile), and shift: position (y, x) of the level takes the pair at (y >> shift, x >> shift).  The coding
+    functions take one wherever they take a step."""
+    __slots__ = ()
+
+
+def step_map_pairs(n_u16, device=None):
+    """The integer step map n (any shape, integers in [4, 1024]; step = n / 16) -> a float32 tensor of that shape + (2,) holding
+    (q, inv_q) per entry, by the rule of step_pair: q = n / 16 (exact) and inv_q = fp32(1 / q), the division in float64 on the
+    host.  The ONE place where the pairs of a map are formed: the kernels cannot check device data, and encoder and decoder
+    must use the same pairs.  ValueError naming step_map for any other value."""
+    import numpy as np
+    n = n_u16.cpu().numpy() if isinstance(n_u16, torch.Tensor) else np.asarray(n_u16)
+    if n.dtype.kind not in "iu":
+        raise ValueError("step_map: the map holds integers n with step = n / %d (got dtype %s)" % (STEP_DENOM, n.dtype))
+    n = n.astype(np.int64)
+    if n.size == 0 or int(n.min()) < STEP_N_MIN or int(n.max()) > STEP_N_MAX:
+        raise ValueError("step_map: every entry must be an integer n in [%d, %d] (step = n / %d)" % (STEP_N_MIN, STEP_N_MAX, STEP_DENOM))
+    q = n.astype(np.float64) / STEP_DENOM
+    pairs = np.stack((q.astype(np.float32), (1.0 / q).astype(np.float32)), -1)
+    t = torch.from_numpy(np.ascontiguousarray(pairs))
+    return t if device is None else t.to(device)
+
+
+def _map_args(step, units, h, w):
+    """The (qpairs, mh, mw, shift) arguments of the map entry points from a StepMap, checked against the units and the h x w level
+    it is to cover (the entry points check the cover again)."""
+    pairs, shift = step
+    if not (isinstance(pairs, torch.Tensor) and pairs.is_cuda and pairs.dtype == torch.float32 and pairs.is_contiguous()
+            and pairs.dim() == 4 and pairs.shape[0] == units and pairs.shape[3] == 2):
+        raise _lib.LLDWTError("step map: the pairs must be a contiguous (%d, mh, mw, 2) float32 device tensor (ops.step_map_pairs)"
+                              % units)
+    shift = int(shift)
+    if shift < 0 or (pairs.shape[1] << shift) < h or (pairs.shape[2] << shift) < w:
+        raise _lib.LLDWTError("step map: %d x %d blocks at shift %d do not cover the %d x %d level"
+                              % (pairs.shape[1], pairs.shape[2], shift, h, w))
+    return C.c_void_p(pairs.data_ptr()), pairs.shape[1], pairs.shape[2], shift
+
+
 RDO_DENOM = 64                       # a Lagrangian of rate-distortion optimised quantisation is m / RDO_DENOM, m in [1, RDO_M_MAX]
 RDO_M_MAX = 256
 
@@ -1071,10 +1112,13 @@ def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=Non
     (P,B,C,h,w) int32.  Decoder: sym (P,B,C,h,w) int32 -> (idx, sym).  Neither (level None too): -> (idx, None), what the
     decoder needs before it can pop the symbols.  table63: the scale table's first 63 entries.
     rdo: encoder only, (k, cost, sizes, offsets) -- k of rdo_scale and the int32 device tensors of cost_table /
-    entropy_coding.device_cost_tables: the symbols are chosen by the rule of DESIGN.md 7.1.7 (lldwt_gauss_quantise_rdo)."""
+    entropy_coding.device_cost_tables: the symbols are chosen by the rule of DESIGN.md 7.1.7 (lldwt_gauss_quantise_rdo).
+    step: a number, or a StepMap over the level (one map per image b of B): every position then takes the pair
+    of its block, in all three modes and with rdo (lldwt_gauss_quantise_map)."""
     P, B, C2, h, w = params.shape
     Cc = C2 // 2
-    q, inv_q = step_pair(step)
+    smap = step if isinstance(step, StepMap) else None
+    q, inv_q = (1.0, 1.0) if smap is not None else step_pair(step)
     if rdo is not None and y is None:
         raise _lib.LLDWTError("gauss_quantise: rdo is a choice of the encoder (give y)")
     if (y is not None and sym is not None) or (level is None) != (y is None and sym is None):
@@ -1098,6 +1142,13 @@ def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=Non
                 raise _lib.LLDWTError("gauss_quantise: the rdo tables must be contiguous int32 device tensors")
         if cost.dim() != 2 or sizes.numel() != cost.shape[0] or offsets.numel() != cost.shape[0]:
             raise _lib.LLDWTError("gauss_quantise: rdo needs cost (T, width) with T sizes and offsets")
+    if smap is not None:
+        ra = (p(cost), p(sizes), p(offsets), cost.shape[0], cost.shape[1], float(k)) if rdo is not None else (None, None, None, 0, 0, 0.0)
+        check(_lib.load().lldwt_gauss_quantise_map(_chk(params, "params"), _opt(y, "y"), p(sym), _chk(table63, "table63"), p(idx), p(out),
+                                                   _opt(level, "level"), P * B, B, Cc, h, w, H, W, int(r0), int(c0), int(stride),
+                                                   *_map_args(smap, B, H, W), *ra, _stream()), "gauss_quantise_map")
+        return idx, (out if y is not None else None if sym is None else sym.reshape(P, B, Cc, h, w))
+    if rdo is not None:
         check(_lib.load().lldwt_gauss_quantise_rdo(_chk(params, "params"), _chk(y, "y"), _chk(table63, "table63"), p(idx), p(out),
                                                    _chk(level, "level"), P * B, Cc, h, w, H, W, int(r0), int(c0), int(stride), q,
                                                    inv_q, p(cost), p(sizes), p(offsets), cost.shape[0], cost.shape[1], float(k),

@@ -565,6 +565,30 @@ int lldwt_gauss_quantise_rdo(const float* params, const float* y, const float* t
                              float* level, int64_t streams, int channels, int64_t h, int64_t w, int64_t H, int64_t W, int r0,
                              int c0, int stride, float q, float inv_q, const int32_t* cost, const int32_t* sizes,
                              const int32_t* offsets, int32_t ntab, int32_t width, float k, void* stream);
+/* Region-of-interest coding: the three places where a step is applied, with a step MAP instead of one step.
+ * qpairs (units, mh, mw, 2) fp32: per block of 2^shift x 2^shift positions of the level the pair (q, inv_q) of 7.1.6, one map
+ * for all planes and channels of a unit -- the image (or tile) z % units of the Z = planes * units tensors (for the wavefront
+ * entry points units == batch).  The position (y, x) of the level takes the pair at (y >> shift, x >> shift); the arithmetic
+ * per coefficient is that of the entry points above with this pair.  The map must cover the level: mh >= ceil(h / 2^shift) and
+ * mw >= ceil(w / 2^shift) of the level's h x w (for lldwt_gauss_quantise_map its H x W), else LLDWT_EINVAL, as is a null or
+ * not 8-byte aligned qpairs.  The pairs are device data, which no entry point can check: they are formed in one place on the
+ * host, from the integer map, with the rule of a single step.
+ * cost == null: the nearest-level quantiser in every mode of the scalar entry point (sizes, offsets, ntab, width, k ignored).
+ * cost != null: the encoder with the rule of 7.1.7 and each coefficient's own inv_q; y == null is then LLDWT_EINVAL. */
+int lldwt_cgp16_wavefront_step_map(const float* plc, float* yhat, const float* y, const void* packed, const float* table63,
+                                   int* idx, int* sym, float* mu, float* sigma_out, int64_t planes, int64_t batch, int64_t h,
+                                   int64_t w, int groups, int K, uint32_t tap_mask, int t, int64_t ntot, int64_t off,
+                                   const float* qpairs, int64_t mh, int64_t mw, int shift, const int32_t* cost,
+                                   const int32_t* sizes, const int32_t* offsets, int32_t ntab, int32_t width, float k,
+                                   void* stream);
+int lldwt_wavefront_apply_map(const int* sym, const float* mu, float* yhat, int64_t planes, int64_t batch, int64_t h, int64_t w,
+                              int groups, int K, int t, int64_t ntot, int64_t off, const float* qpairs, int64_t mh, int64_t mw,
+                              int shift, void* stream);
+int lldwt_gauss_quantise_map(const float* params, const float* y, const int32_t* sym_in, const float* table63, int32_t* idx,
+                             int32_t* sym_out, float* level, int64_t streams, int64_t units, int channels, int64_t h, int64_t w,
+                             int64_t H, int64_t W, int r0, int c0, int stride, const float* qpairs, int64_t mh, int64_t mw,
+                             int shift, const int32_t* cost, const int32_t* sizes, const int32_t* offsets, int32_t ntab,
+                             int32_t width, float k, void* stream);
 /* Code length of `streams` streams of n (sym, idx) pairs under quantised tables, for the byte-target search: sums[z] += sum of
  * cost[idx][sym - offsets[idx]] with cost (ntab, width) int32 in units of 2^-16 bit, and esc_cost for a symbol outside
  * [0, sizes[idx] - 2) or an index outside [0, ntab), which escapes[z] counts.  sums and escapes (int64) must be ZERO on entry;

@@ -25,6 +25,12 @@
                                            (q^2 per bit; try 0.203125 = 13 / 64): fewer bytes for a little more error.  The
                                            encoder's choice alone: nothing in the container tells, decode needs no option
 
+    encode --roi y0,x0,h,w:Q               region-of-interest coding: the blocks of 2^dwtlevels pixels that the rectangle touches
+                                           are coded at the step Q, the rest at --step (default 1).  Repeatable, later ones
+                                           override earlier ones; writes an LLDQ container around what the other options
+                                           select.  Not with --target-bytes / --target-bpp.  decode needs no option; info
+                                           prints the map's size, its steps and the share of blocks at each
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -104,6 +110,8 @@ def main(argv=None):
     rate.add_argument("--target-bpp", type=float, metavar="R", help="the same for R bits per pixel")
     sub.choices["encode"].add_argument("--rdo", type=float, metavar="R",
                                        help="rate-distortion optimised quantisation, Lagrangian m / 64 in (0, 4] (default off)")
+    sub.choices["encode"].add_argument("--roi", action="append", metavar="Y0,X0,H,W:Q",
+                                       help="code this rectangle at the step Q, the rest at --step (repeatable; writes LLDQ)")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
                                        help="decode the base layer of a refined (LLDR) container only")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
@@ -120,7 +128,17 @@ def main(argv=None):
 
     if a.cmd == "info":
         with open(a.src, "rb") as f:
-            hdr = codec.read_header(f.read())
+            blob = f.read()
+        hdr = codec.read_header(blob)
+        if "inner" in hdr:                     # LLDQ: the map, then the inner container's
+            import numpy as np
+            m = codec.parse_mapped(blob)[1]
+            print("%-15s %d x %d blocks of %d x %d pixels, CRC %08x" % ("step map", hdr["hb"], hdr["wb"], 1 << hdr["block"],
+                                                                     1 << hdr["block"], hdr["map_crc"]))
+            vals, counts = np.unique(m, return_counts=True)
+            for v, c in zip(vals.tolist(), counts.tolist()):
+                print("%-15s %g: %d blocks (%.1f %%)" % ("  step", v / codec.STEP_DENOM, c, 100.0 * c / m.size))
+            hdr = hdr["inner"]
         if "base" in hdr:                      # LLDR: the layer's own fields and the byte split, then the base container's
             print("%-15s %s" % ("near", "0 (lossless)" if hdr["near"] == 0 else "%d (every sample within %d)" % (hdr["near"],
                                                                                                             hdr["near"])))
@@ -167,6 +185,22 @@ def main(argv=None):
             kw["target_bytes"] = codec.target_bpp_bytes(a.target_bpp, img.shape[0], img.shape[1])
         if a.rdo is not None:
             kw["rdo"] = a.rdo
+        if a.roi:
+            if a.target_bytes is not None or a.target_bpp is not None:
+                print("--roi cannot be combined with --target-bytes / --target-bpp (a byte target over a step map is not defined)",
+                      file=sys.stderr)
+                return 2
+            regions = []
+            for r in a.roi:
+                try:
+                    rect, q = r.split(":")
+                    regions.append(tuple(int(v) for v in rect.split(",")) + (float(q),))
+                    assert len(regions[-1]) == 5
+                except (ValueError, AssertionError):
+                    print("--roi takes y0,x0,h,w:Q (got %r)" % r, file=sys.stderr)
+                    return 2
+            kw["step_map"] = codec.step_map_from_regions(img.shape[0], img.shape[1], codec.describe(net)[2], kw.pop("step", 1.0),
+                                                         regions)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tile is None:
@@ -186,6 +220,9 @@ def main(argv=None):
         H, W = img.shape[:2]
         print("encoded %dx%d: %d bytes, %.4f bpp, %.3f s" % (W, H, len(blob), len(blob) * 8 / (H * W), dt))
         hdr = codec.read_header(blob)
+        if "inner" in hdr:
+            print("step map: %d x %d blocks, steps %g .. %g" % (hdr["hb"], hdr["wb"], hdr["step_min"], hdr["step_max"]))
+            hdr = hdr["inner"]
         if "base" in hdr:
             print("near %d: base %d bytes, residual %d bytes" % (hdr["near"], hdr["base_bytes"], hdr["residual_bytes"]))
             hdr = hdr["base"]
@@ -199,9 +236,8 @@ def main(argv=None):
         with open(a.src, "rb") as f:
             blob = f.read()
         kw = {"refine": False} if a.base_only else {}
-        tiled = blob[:4] in (codec.TILED_MAGIC, codec.LAPPED_MAGIC)
-        if blob[:4] == codec.REFINED_MAGIC:
-            tiled = "ny" in codec.read_header(blob)["base"]
+        inner = codec.read_header(blob)["inner"] if blob[:4] == codec.MAPPED_MAGIC else codec.read_header(blob)
+        tiled = "ny" in inner.get("base", inner)
         region = None
         if a.region is not None:
             if not tiled:
