@@ -36,6 +36,10 @@ struct WgradArgs {
 
 // 4-byte aligned float4: global_load_dwordx4 without the 16-byte alignment promise (rows start at any pixel)
 struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };
+// 16 readable bytes: the address a dwordx4 load is issued from when its 4-pixel segment is not wholly inside the image (the
+// value is discarded).  An address inside the tensor does not serve: the last image's dY / X block can be shorter than 16
+// bytes from there on (one channel of 1 x 1 .. 1 x 3 pixels; the last row block of k_wgrad1x1 in the last chunk of its image).
+__device__ __attribute__((aligned(16))) float g_wg_pad16[4];
 
 template <int KS, int MT, int NT>
 __global__ __launch_bounds__(256) void k_conv_wgrad(WgradArgs a) {
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(WgradArgs a) {
         const int gy_ = y0 + rq_ / (WG_TW / 4), gx_ = x0 + 4 * (rq_ % (WG_TW / 4));                              \
         const int co_ = choff_[c_];                                                                              \
         const bool ok4_ = co_ >= 0 && gy_ < h && gx_ + 3 < w;                                                    \
-        raw_ = *reinterpret_cast<const f4u*>(base_ + (ok4_ ? co_ * (cstride_) + (int64_t)gy_ * (wrow_) + gx_ : 0)); \
+        raw_ = *reinterpret_cast<const f4u*>(ok4_ ? base_ + (co_ * (cstride_) + (int64_t)gy_ * (wrow_) + gx_) : g_wg_pad16); \
     }
 #define LLDWT_WG_FIX4(dst_, raw_, base_, choff_, cstride_, wrow_, iv_)                                           \
     {                                                                                                            \
@@ -651,7 +655,7 @@ __global__ __launch_bounds__(256) void k_wgrad1x1(W1Args a) {
             const int ch = isa ? row : row - MR;
             const bool ok = (isa ? m0 + ch < cout_g : ch < cin_g) && v4 + 3 < npx;
             const float* src = isa ? dyz : (ch < csp ? xz : xz2);
-            raw[r] = *reinterpret_cast<const f4u*>(ok ? src + (int64_t)ch * hw + v4 : (isa ? dyz : xz));
+            raw[r] = *reinterpret_cast<const f4u*>(ok ? src + (int64_t)ch * hw + v4 : g_wg_pad16);
         }
         __syncthreads();                                   // the previous chunk's LDS reads are done
 #pragma unroll
@@ -910,6 +914,7 @@ extern "C" int lldwt_conv2d_wgrad(const float* x, const float* dy, float* dw, fl
     LLDWT_REQUIRE(planes > 0 && batch > 0 && h > 0 && w_ > 0 && planes <= 65535, "conv2d_wgrad: bad dims");
     LLDWT_REQUIRE(!d->upsample2 || (h % 2 == 0 && w_ % 2 == 0), "conv2d_wgrad: upsample2 needs even dims");
     LLDWT_REQUIRE(d->oc_block > 0 && d->ytot >= d->cout, "conv2d_wgrad: bad output placement");
+    LLDWT_REQUIRE(d->ic_block == 0 || (d->ic_block > 0 && d->xtot >= d->cin), "conv2d_wgrad: bad input placement");
     hipStream_t st = (hipStream_t)stream;
     WgradArgs a;
     a.x = x; a.dy = dy; a.dw = dw; a.db = dbias; a.d = *d;

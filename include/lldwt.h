@@ -329,7 +329,7 @@ int lldwt_subband_mlp_bwd_w(const float* x, const float* gy, float* gx, int64_t 
  *   y[z, oc', :, :] = act( bias[oc] + sum_{ic,ky,kx} w[oc, ic, ky, kx] * x[z, g*cin_g + ic, .+ky-K/2, .+kx-K/2] )
  * zero padded, stride 1.  x: (Z,cin,h,w) (if upsample2: (Z,cin,h/2,w/2), read through the nearest-neighbour 2x
  * upsampling of LiftingBasedDWT_net.py:348,367,822,835).  w: (planes,cout,cin/groups,K,K) (if transposed:
- * ConvTranspose2d layout (planes,cin,cout,K,K), groups must be 1), bias (planes,cout) or NULL.
+ * ConvTranspose2d layout (planes,cin,cout/groups,K,K), any groups), bias (planes,cout) or NULL.
  * tap_mask: bit (ky*K+kx) set = tap is live (MaskedConv2d type A/B; the caller has already applied
  * weight *= mask as the reference does); pass (1<<K*K)-1 for a dense conv.
  * Output channel placement (removes the chunk/cat regrouping of LiftingBasedDWT_net.py:357-359):
