@@ -121,6 +121,13 @@ an LLDQ whose key and map disagree is refused.  ``step_map`` composes with ``cod
 (a tile codes with the slice of the map at its origin, clamped as above) and excludes ``step`` and ``target_bytes``.  The
 decoders take an LLDQ wherever they take its inner container, with ``region``, ``reduce`` and ``refine``.
 
+Quality-targeted coding (``encode_images(..., target_psnr=P)`` / ``target_msssim=M``, the same on ``encode_tiled``, DESIGN.md
+7.1.9): the encoder searches STEP_GRID for a step whose decoded image meets the target while the next coarser grid step does
+not -- the coarsest step that meets it where quality falls monotonically along the grid.  PSNR is judged in integers: the exact
+SSE of the bytes the decoder would write (lldwt_ycc_tiles_sq_err on the encoder's own reconstruction) against
+``psnr_sse_bound(P, H, W)``.  At most 7 probes without a range coder, then one real encode; the container is that of
+``step=<chosen>`` byte for byte and records nothing.  Excludes ``step``, ``step_map``, ``target_bytes`` and ``near``.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -1021,7 +1028,98 @@ def _unit_maps(maps, units, grid, L, dev):
     return torch.from_numpy(np.stack(out).astype(np.int32)).to(dev)
 
 
-SEARCH_STATS = {}          # diagnostics: the last byte-target search's probes (estimates), real encodes and chosen step
+def psnr_sse_bound(psnr, H, W):
+    """The largest sum of squared byte errors over the 3 H W samples of an H x W uint8 RGB image at which its PSNR,
+    10 log10(255^2 * 3 H W / SSE) as ``quality`` reports it, is still at least ``psnr`` dB: floor(3 H W * 65025 / 10^(psnr / 10))
+    in float64.  The encoder of target_psnr and its tests call this one function, so that "meets the target" is the integer
+    comparison SSE <= bound.  ValueError naming target_psnr unless psnr is a finite number > 0."""
+    import math
+    try:
+        p = float(psnr)
+    except (TypeError, ValueError):
+        raise ValueError("target_psnr must be a finite number of dB > 0 (got %r)" % (psnr,)) from None
+    if not (p == p and 0 < p < float("inf")) or int(H) < 1 or int(W) < 1:
+        raise ValueError("target_psnr must be a finite number of dB > 0, for an image of positive size (got %r, %r x %r)"
+                         % (psnr, H, W))
+    return int(math.floor(3.0 * int(H) * int(W) * 65025.0 / 10.0 ** (p / 10.0)))
+
+
+def sse_psnr(sse, H, W):
+    """The PSNR in dB of an H x W uint8 RGB image whose squared byte errors sum to ``sse``; inf at 0 (as ``quality``)."""
+    import math
+    return float("inf") if sse == 0 else 10.0 * math.log10(65025.0 * 3.0 * H * W / sse)
+
+
+def _meets_psnr(sse, psnr, H, W):
+    """The predicate of target_psnr: the integer SSE of a decoded image is within psnr_sse_bound."""
+    return int(sse) <= psnr_sse_bound(psnr, H, W)
+
+
+def _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H=None, W=None):
+    """The quality arguments of encode_images / encode_tiled, checked on the host (ValueError naming the argument) -> None (no
+    target), ("psnr", P) or ("msssim", M).  One of target_psnr, target_msssim, target_bytes, step, step_map at most; no target
+    with near (the residual layer sets the quality); L >= 2 (the step reaches no level otherwise); P a finite number > 0,
+    0 < M < 1; target_msssim needs min(H, W) >= ops.ms_ssim_min_side(5) when the size is given."""
+    if target_psnr is None and target_msssim is None:
+        return None
+    name = "target_psnr" if target_psnr is not None else "target_msssim"
+    if target_psnr is not None and target_msssim is not None:
+        raise ValueError("target_psnr and target_msssim: give one of them (each chooses the step)")
+    for other, val in (("target_bytes", target_bytes), ("step", step), ("step_map", step_map)):
+        if val is not None:
+            raise ValueError("%s and %s: give one of them (a quality target chooses the step%s)"
+                             % (name, other, "; a target over a step map is not defined" if other == "step_map" else ""))
+    if near is not None:
+        raise ValueError("%s: not with near (the residual layer, not the step, sets the quality of the decoded image)" % name)
+    if L < 2:
+        raise ValueError("%s: the search varies the step, which needs dwtlevels >= 2 (the net has %d)" % (name, L))
+    try:
+        v = float(target_psnr if target_psnr is not None else target_msssim)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number (got %r)" % (name, target_psnr if target_psnr is not None else target_msssim)) from None
+    if target_psnr is not None:
+        if not (v == v and 0 < v < float("inf")):
+            raise ValueError("target_psnr must be a finite number of dB > 0 (got %r)" % (target_psnr,))
+        return "psnr", v
+    if not (v == v and 0 < v < 1):
+        raise ValueError("target_msssim must be a number in (0, 1) (got %r)" % (target_msssim,))
+    if H is not None and W is not None:
+        from .ops import ms_ssim_min_side
+        if min(H, W) < ms_ssim_min_side(5):
+            raise ValueError("target_msssim: MS-SSIM over five scales needs sides of at least %d pixels (the image is %d x %d)"
+                             % (ms_ssim_min_side(5), H, W))
+    return "msssim", v
+
+
+def _search_quality(meets, fail=None):
+    """The quality target of DESIGN.md 7.1.9 over the indexes k of STEP_GRID.  meets(k) -> whether the image decoded at step
+    STEP_GRID[k] / 16 meets the target; it is called at most once per k (the probes are memoised) and at most
+    1 + ceil(log2 33) = 7 times.  Index 0 is probed first: if the finest step misses, ``fail()`` gives the exception to raise
+    (a ValueError by default).  Then a bisection with the invariant "meets(lo), and hi == 33 or not meets(hi)" from lo = 0,
+    hi = 33 until hi == lo + 1 -> (lo, number of probes): index lo meets the target and the next coarser one does not (or lo is
+    the coarsest), whether or not the quality is monotone along the grid; where it falls monotonically, lo is the coarsest
+    step that meets the target."""
+    memo = {}
+
+    def probe(k):
+        if k not in memo:
+            memo[k] = bool(meets(k))
+        return memo[k]
+    if not probe(0):
+        raise (fail() if fail is not None else ValueError("the quality target cannot be met at the finest step"))
+    lo, hi = 0, len(STEP_GRID)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if probe(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo, len(memo)
+
+
+# diagnostics: the last search's probes (estimates), real encodes, chosen step and container size; after a quality target also
+# the chosen step's "sse" or "msssim" and, under "images", one such dict per image of the batch
+SEARCH_STATS = {}
 
 
 def _search_step(estimate, encode, T):
@@ -1068,7 +1166,8 @@ def _estimated_size(empty, estimates):
     return len(empty) + sum(e + len(leb128_encode(e)) - 1 for e in estimates)
 
 
-def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None):
+def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None,
+                  target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -1082,10 +1181,19 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     write the same bytes as ever.  The encoder's choice only: no header key, and the containers decode as any other.
     step_map: a step per block of 2^L x 2^L pixels: (hb, wb) steps for the whole batch or (B, hb, wb)
     (check_step_map, step_map_from_regions) -> LLDQ containers around what the other arguments select.  Not with step or
-    target_bytes."""
+    target_bytes.
+    target_psnr = P (dB) or target_msssim = M (0 < M < 1) instead of any of step, target_bytes, step_map, and not with near
+    (DESIGN.md 7.1.9): per image, a step of STEP_GRID whose decoded image -- the one decode_images returns -- meets the target
+    while the next coarser grid step does not (or which is the coarsest); where the quality falls monotonically along the
+    grid that is the coarsest step that meets it.  PSNR is met iff the integer SSE of the decoded bytes is at most
+    psnr_sse_bound(P, H, W); MS-SSIM (the channel mean ``quality`` reports, sides >= 161) iff the value is >= M -- its sums
+    are double atomics, so a target within rounding of a probe's value may resolve either way.  At most 7 probes without a
+    range coder, then ONE real encode: the container is byte for byte that of step=<chosen>, nothing is recorded.
+    ValueError naming the target and the best achievable value if the finest step misses it."""
     from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
+    target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
         from .residual import check_near
         near = check_near(near)
@@ -1093,17 +1201,100 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     n, T = _rate_args(step, target_bytes, near, L)
     rdo = _rdo_arg(rdo, L)
     Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None):
-    """_encode at the step step_n / 16, or with a byte target T the search of _search_step, one image at a time.  walk: the
-    (magic, grid, group, coder) of _encode.  rdo: probes and real encodes alike."""
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None):
+    """_encode at the step step_n / 16, or with a byte target T the search of _search_step, or with a quality target (the
+    pair of _quality_args) that of _encode_at_quality, one image at a time.  walk: the (magic, grid, group, coder) of _encode.
+    rdo: probes and real encodes alike."""
+    if target is not None:
+        return _encode_at_quality(net, images_u8, walk, rdo, target)
     if T is None:
         return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps)
     return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo)[0],
                          lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo)[0], T)
             for b in range(images_u8.shape[0])]
+
+
+def _probe_quality(net, image_u8, magic, grid, group, step_n, rdo, kind):
+    """One probe of a quality target: ONE image (1,H,W,3) goes through the encode walk of _encode at the step
+    step_n / 16 with the estimating sink (no range coder runs) and the encoder's own reconstruction, which is the decoder's
+    (encode_strings_planes(..., recon=True)), and the image decode_images / decode_tiled would return for that container is
+    measured on the device: kind "psnr" -> its exact integer SSE against the original (lldwt_ycc_tiles_sq_err; no image is
+    written), kind "msssim" -> the channel mean of ops.ms_ssim on the u8 pair, as ``quality`` computes it.  Plain tiles are
+    measured on their in-image rectangles; lapped tiles are blended in ascending tile index into an fp32 frame
+    (ops.ycc_tiles_blend), which is then taken as the tile of a 1 x 1 grid, as decode_tiled finishes such a frame."""
+    import torch
+    from . import ops
+    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    from .graphs.models.entropy_coding import ESTIMATE
+    _, H, W = _check_images(image_u8)
+    th, tw, ny, nx, ov = grid
+    nets = net.nets()
+    step = step_n / STEP_DENOM
+    _prepare(net)
+    dev = next(net.parameters()).device
+    img = image_u8.to(dev).contiguous()
+    per = ny * nx
+    g = group if _batch_invariant(arithmetic_string("host", step)) else 1
+    with torch.no_grad():
+        sse = torch.zeros(1, dtype=torch.int64, device=dev)
+        acc = torch.zeros(3, 1, 1, H, W, device=dev, dtype=torch.float32) if ov else None
+        rec = torch.empty_like(img) if kind == "msssim" and not ov else None
+        for first in range(0, per, g):
+            n = min(g, per - first)
+            if ov:
+                x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
+            else:
+                x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)
+            xhat = encode_strings_planes(nets, x, coder=ESTIMATE, recon=True, step=step, rdo=rdo)[2].contiguous()
+            if ov:
+                ops.ycc_tiles_blend(xhat, (H, W, th, tw, ov, ny, nx), (0, 0, H, W), list(range(first, first + n)), acc)
+            elif kind == "psnr":
+                ops.ycc_tiles_sq_err(xhat, (H, W, th, tw, ny, nx), img, first=first, out=sse)
+            else:
+                ops.ycc_tiles_to_u8hwc(xhat, (H, W, th, tw, ny, nx), (0, 0, H, W), first=first, out=rec)
+        if kind == "psnr":
+            if ov:
+                ops.ycc_tiles_sq_err(acc, (H, W, H, W, 1, 1), img, out=sse)
+            return int(sse.item())
+        if ov:
+            rec = ops.ycc_tiles_to_u8hwc(acc, (H, W, H, W, 1, 1), (0, 0, H, W))
+        return float(ops.ms_ssim(ops.u8hwc_to_f32chw(img), ops.u8hwc_to_f32chw(rec), offset=0.0).mean(1).item())
+
+
+def _encode_at_quality(net, images_u8, walk, rdo, target):
+    """The quality target of DESIGN.md 7.1.9, one image (or one tiled frame) at a time: _search_quality over probes of
+    _probe_quality, then ONE real encode at the chosen step -- the container of encode_*(..., step=<chosen>) byte for byte.
+    walk: the (magic, grid, group, coder) of _encode; target: the pair of _quality_args; rdo: probes and the encode alike."""
+    magic, grid, group, coder = walk
+    kind, want = target
+    B, H, W = _check_images(images_u8)
+    bound = psnr_sse_bound(want, H, W) if kind == "psnr" else None
+    blobs, stats = [], []
+    for b in range(B):
+        img, vals = images_u8[b:b + 1], {}
+
+        def meets(k):
+            vals[k] = _probe_quality(net, img, magic, grid, group, STEP_GRID[k], rdo, kind)
+            return vals[k] <= bound if kind == "psnr" else vals[k] >= want
+
+        def fail():
+            q0 = STEP_GRID[0] / STEP_DENOM
+            if kind == "psnr":
+                return ValueError("target_psnr: %g dB cannot be met; at the finest step %g the best is %.2f dB"
+                                  % (want, q0, sse_psnr(vals[0], H, W)))
+            return ValueError("target_msssim: %g cannot be met; at the finest step %g the best is %.6f" % (want, q0, vals[0]))
+        k, probes = _search_quality(meets, fail)
+        blob = _encode(net, img, magic, grid, group, coder, None, STEP_GRID[k], rdo=rdo)[0]
+        blobs.append(blob)
+        stats.append({"probes": probes, "encodes": 1, "step": STEP_GRID[k] / STEP_DENOM, "bytes": len(blob),
+                      "sse" if kind == "psnr" else "msssim": vals[k]})
+    for key in ("sse", "msssim"):
+        SEARCH_STATS.pop(key, None)
+    SEARCH_STATS.update(stats[-1], images=stats)
+    return blobs
 
 
 def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None):
@@ -1347,7 +1538,7 @@ def _tile_streams(s_xe, s_xo, j):
 
 
 def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
-                 rdo=None, step_map=None):
+                 rdo=None, step_map=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -1360,9 +1551,13 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     step, target_bytes: as encode_images, with ONE step for all tiles of a frame; a target is met by each frame's container
     (the images of a batch are searched one at a time).  rdo: as encode_images, for every tile.
     step_map: as encode_images, the map of the whole image; a tile is coded with the slice at its origin (tile origins are
-    multiples of 2^L for plain and lapped grids alike), clamped at the image's last block -> LLDQ over LLDT / LLDO / LLDR."""
+    multiples of 2^L for plain and lapped grids alike), clamped at the image's last block -> LLDQ over LLDT / LLDO / LLDR.
+    target_psnr, target_msssim: as encode_images, with ONE step for all tiles of a frame, met by the image decode_tiled returns
+    for the frame: the tiles' in-image rectangles, or with overlap > 0 the blended frame.  The result does
+    not depend on tiles_per_call."""
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
+    target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
         from .residual import check_near
         near = check_near(near)
@@ -1379,7 +1574,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target)
 
 
 def _tiles_per_call(tiles_per_call):

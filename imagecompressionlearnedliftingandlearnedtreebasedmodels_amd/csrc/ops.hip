@@ -116,11 +116,13 @@ struct LLAffine {
 
 // One pixel of plane-major YCbCr (slot j of n, offset p in its plane) -> 3 bytes of uint8 RGB: k_ycc_to_rgb(clamp=1), then
 // floor((v + 0.5) * 255 + 0.5) in fp32 (v in [-0.5, 0.5], so the byte is in [0, 255]).  AFFINE: each plane's sample goes
-// through the LLAffine map first.
+// through the LLAffine map first.  The one statement of the decoder's bytes: the store kernels write them (ycc_px_to_u8),
+// k_ycc_tiles_sq_err measures them.
+struct U8x3 {
+    uint8_t r, g, b;
+};
 template <bool AFFINE>
-__device__ __forceinline__ void ycc_px_to_u8(const float* __restrict__ ycc, int64_t n, int64_t j, int64_t hw, int64_t p,
-                                             uint8_t* __restrict__ d, LLAffine af) {
-    float s0 = ycc[(0 * n + j) * hw + p], cb = ycc[(1 * n + j) * hw + p], cr = ycc[(2 * n + j) * hw + p];
+__device__ __forceinline__ U8x3 ycc_vals_u8(float s0, float cb, float cr, LLAffine af) {
     if (AFFINE) {
         s0 = (s0 - af.b[0]) * af.inv_a[0];
         cb = (cb - af.b[1]) * af.inv_a[1];
@@ -134,9 +136,19 @@ __device__ __forceinline__ void ycc_px_to_u8(const float* __restrict__ ycc, int6
     rr = fminf(fmaxf(rr, -0.5f), 0.5f);
     g = fminf(fmaxf(g, -0.5f), 0.5f);
     bl = fminf(fmaxf(bl, -0.5f), 0.5f);
-    d[0] = (uint8_t)floorf((rr + 0.5f) * 255.0f + 0.5f);
-    d[1] = (uint8_t)floorf((g + 0.5f) * 255.0f + 0.5f);
-    d[2] = (uint8_t)floorf((bl + 0.5f) * 255.0f + 0.5f);
+    U8x3 v;
+    v.r = (uint8_t)floorf((rr + 0.5f) * 255.0f + 0.5f);
+    v.g = (uint8_t)floorf((g + 0.5f) * 255.0f + 0.5f);
+    v.b = (uint8_t)floorf((bl + 0.5f) * 255.0f + 0.5f);
+    return v;
+}
+template <bool AFFINE>
+__device__ __forceinline__ void ycc_px_to_u8(const float* __restrict__ ycc, int64_t n, int64_t j, int64_t hw, int64_t p,
+                                             uint8_t* __restrict__ d, LLAffine af) {
+    const U8x3 v = ycc_vals_u8<AFFINE>(ycc[(0 * n + j) * hw + p], ycc[(1 * n + j) * hw + p], ycc[(2 * n + j) * hw + p], af);
+    d[0] = v.r;
+    d[1] = v.g;
+    d[2] = v.b;
 }
 
 // plane-major (3,n,1,th,tw) YCbCr of n tiles (tile of slot j: tiles[j], or first + j when tiles is null) -> uint8 HWC RGB
@@ -164,6 +176,79 @@ __global__ void k_ycc_tiles_to_u8hwc(const float* __restrict__ ycc, const int32_
     if (gy >= H || gx >= W || gy < y0 || gy >= y0 + h || gx < x0 || gx >= x0 + w) return;
     ycc_px_to_u8<AFFINE>(ycc, n, j, hw, (int64_t)blockIdx.y * tw + x, dst + (((int64_t)b * h + (gy - y0)) * w + (gx - x0)) * 3,
                          af);
+}
+
+// Exact squared error of the bytes k_ycc_tiles_to_u8hwc would write for the whole image against the original src (B,H,W,3)
+// (lldwt_ycc_tiles_sq_err): sse[b] += sum over the in-image pixels of the tiles of image b of the three
+// squared byte differences; no image is written.  Grid (cdiv(tw,256), cdiv(th, SQE_ROWS * strips), n): a workgroup covers 256
+// columns of ``strips`` strips of SQE_ROWS rows of ONE tile, so it has one destination.  Per strip a thread first issues the
+// loads of all its rows (a row past the strip's last re-reads that one and is not counted: straight-line code, every load in
+// flight before the first use), then adds its column's rows into a uint32 (at most SQE_MAX_STRIPS * SQE_ROWS * 3 * 255^2).
+// The wave adds by shuffles (still below 2^32, asserted), the waves meet in LDS and the workgroup issues one 64-bit atomic.
+// Integer sums: the value does not depend on the order of the additions.  A tile index outside the B x ny x nx grid adds
+// nothing.  strips is the launcher's choice (sq_err_strips): the atomics of a batch land on one cache line and serialise there.
+constexpr int SQE_NT = 256, SQE_ROWS = 8, SQE_MAX_STRIPS = 8;
+static_assert((uint64_t)SQE_MAX_STRIPS * SQE_ROWS * 3 * 65025 * 64 < (1ull << 32), "a wave's partial sum must fit uint32");
+__global__ __launch_bounds__(SQE_NT) void k_ycc_tiles_sq_err(const float* __restrict__ ycc, const int32_t* __restrict__ tiles,
+                                                             int64_t first, int64_t n, int64_t B, int64_t H, int64_t W, int64_t th,
+                                                             int64_t tw, int64_t ny, int64_t nx, int strips,
+                                                             const uint8_t* __restrict__ src, unsigned long long* __restrict__ sse) {
+    __shared__ uint32_t part[SQE_NT / 64];
+    const int64_t j = blockIdx.z, hw = th * tw;
+    const int64_t t = tiles ? (int64_t)tiles[j] : first + j;
+    if (t < 0 || t >= B * ny * nx) return;                                       // block-uniform
+    const uint32_t per = (uint32_t)(ny * nx), b = (uint32_t)t / per, r = (uint32_t)t - b * per;
+    const uint32_t ty = r / (uint32_t)nx, tx = r - ty * (uint32_t)nx;
+    const int64_t x = blockIdx.x * (int64_t)SQE_NT + threadIdx.x, gx = (int64_t)tx * tw + x;
+    const bool inside = x < tw && gx < W;
+    const LLAffine none = {{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}};
+    uint32_t acc = 0;
+    for (int st = 0; st < strips; ++st) {
+        const int64_t r0 = ((int64_t)blockIdx.y * strips + st) * SQE_ROWS, gy0 = (int64_t)ty * th + r0;
+        int64_t rows = th - r0 < H - gy0 ? th - r0 : H - gy0;                    // rows of this strip inside tile and image
+        if (rows > SQE_ROWS) rows = SQE_ROWS;
+        if (rows <= 0) break;                                                    // block-uniform: the later strips lie outside too
+        if (!inside) continue;
+        const uint8_t* s = src + (((int64_t)b * H + gy0) * W + gx) * 3;
+        const float* y = ycc + j * hw + r0 * tw + x;
+        float v0[SQE_ROWS], v1[SQE_ROWS], v2[SQE_ROWS];
+        uint8_t o0[SQE_ROWS], o1[SQE_ROWS], o2[SQE_ROWS];
+#pragma unroll
+        for (int i = 0; i < SQE_ROWS; ++i) {
+            const int64_t ri = i < rows ? i : rows - 1;                          // block-uniform; always inside tile and image
+            v0[i] = y[ri * tw];
+            v1[i] = y[n * hw + ri * tw];
+            v2[i] = y[2 * n * hw + ri * tw];
+            o0[i] = s[ri * W * 3];
+            o1[i] = s[ri * W * 3 + 1];
+            o2[i] = s[ri * W * 3 + 2];
+        }
+#pragma unroll
+        for (int i = 0; i < SQE_ROWS; ++i) {
+            const U8x3 v = ycc_vals_u8<false>(v0[i], v1[i], v2[i], none);
+            const int d0 = (int)v.r - (int)o0[i], d1 = (int)v.g - (int)o1[i], d2 = (int)v.b - (int)o2[i];
+            acc += i < rows ? (uint32_t)(d0 * d0 + d1 * d1 + d2 * d2) : 0u;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0;
+#pragma unroll
+        for (int w = 0; w < SQE_NT / 64; ++w) sum += part[w];
+        if (sum) atomicAdd(sse + b, sum);
+    }
+}
+// Strips per workgroup of k_ycc_tiles_sq_err: doubled up to SQE_MAX_STRIPS while at least SQE_MIN_WGS workgroups remain (16 per
+// CU of an MI355X), so a small frame keeps the chip busy and a batch of large frames issues a few thousand atomics, not tens of
+// thousands: they land on one cache line and serialise there at about 12 ns each.
+constexpr int64_t SQE_MIN_WGS = 4096;
+static int sq_err_strips(int64_t th, int64_t tw, int64_t n) {
+    int strips = 1;
+    while (strips < SQE_MAX_STRIPS && cdiv(tw, SQE_NT) * cdiv(th, SQE_ROWS * 2 * strips) * n >= SQE_MIN_WGS) strips *= 2;
+    return strips;
 }
 
 // The tiles of one axis that cover the global position g (n tiles of t at the stride s = t - ov, the grid covering g): the
@@ -1311,6 +1396,22 @@ extern "C" int lldwt_ll_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, i
     }
     return ycc_tiles_to_u8hwc<true>("ll_tiles_to_u8hwc", ycc, tiles, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, dst, af,
                                     stream);
+}
+extern "C" int lldwt_ycc_tiles_sq_err(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H,
+                                      int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, const uint8_t* src, uint64_t* sse,
+                                      void* stream) {
+    LLDWT_REQUIRE(ycc && src && sse, "ycc_tiles_sq_err: null pointer");
+    LLDWT_REQUIRE(B > 0 && H > 0 && W > 0 && ny > 0 && nx > 0 && n > 0, "ycc_tiles_sq_err: bad arguments");
+    LLDWT_REQUIRE(th >= 1 && tw >= 1, "ycc_tiles_sq_err: tile size %lld x %lld", (long long)th, (long long)tw);
+    LLDWT_REQUIRE(tiles || (first >= 0 && first + n <= B * ny * nx), "ycc_tiles_sq_err: tile range outside the grid");
+    LLDWT_REQUIRE(ny * th >= H && nx * tw >= W, "ycc_tiles_sq_err: the grid does not cover the image");
+    LLDWT_REQUIRE(n <= 65535 && cdiv(th, SQE_ROWS) <= 65535 && tw <= (1ll << 30) && B * ny * nx < (1ll << 31),
+                  "ycc_tiles_sq_err: grid too large");
+    const int strips = sq_err_strips(th, tw, n);
+    hipLaunchKernelGGL(k_ycc_tiles_sq_err, dim3((unsigned)cdiv(tw, SQE_NT), (unsigned)cdiv(th, SQE_ROWS * strips), (unsigned)n),
+                       dim3(SQE_NT), 0, (hipStream_t)stream, ycc, tiles, first, n, B, H, W, th, tw, ny, nx, strips, src,
+                       (unsigned long long*)sse);
+    return check_launch("ycc_tiles_sq_err");
 }
 // the geometry both lapped entry points require: ov a power of two with 2 * ov <= min(th, tw), and the
 // grid at the stride (th - ov, tw - ov) covering the image

@@ -196,6 +196,37 @@ def ll_tiles_to_u8hwc(y, grid, region, inv_a, b, tiles=None, first=0, B=1, out=N
     return _tiles_to_u8hwc("ll_tiles_to_u8hwc", y, grid, region, (inv_a, b), tiles, first, B, out)
 
 
+def ycc_tiles_sq_err(y, grid, src, tiles=None, first=0, B=1, out=None):
+    """The exact squared error of the bytes ycc_tiles_to_u8hwc(y, grid, (0, 0, H, W), ...) would write against the original
+    src (B,H,W,3) uint8, per image, without writing them (lldwt_ycc_tiles_sq_err) -> the (B,) int64 device
+    tensor of sums.  y: plane-major (3,n,1,th,tw) decoded tiles; grid = (H, W, th, tw, ny, nx); tiles: the n tile indexes
+    (list; an index outside [0, B * ny * nx) adds nothing), or None for first .. first+n-1.  out: a (B,) int64 device tensor
+    that is added to (several calls may feed one sum); None: a zeroed one.  Integer sums: exact and reproducible."""
+    who = "ycc_tiles_sq_err"
+    H, W, th, tw, ny, nx = grid
+    if not (isinstance(y, torch.Tensor) and y.dim() == 5 and y.shape[0] == 3 and y.shape[2] == 1):
+        raise _lib.LLDWTError("%s: y must be (3,n,1,th,tw)" % who)
+    _, n, _, yh, yw = y.shape
+    if (yh, yw) != (th, tw):
+        raise _lib.LLDWTError("%s: tiles are %d x %d, the grid says %d x %d" % (who, yh, yw, th, tw))
+    if _u8hwc(src, who) != (B, H, W):
+        raise _lib.LLDWTError("%s: src is %s, the grid says (%d,%d,%d,3)" % (who, tuple(src.shape), B, H, W))
+    tptr = C.c_void_p(0)
+    if tiles is not None:
+        if len(tiles) != n or any(not -(1 << 31) <= t < 1 << 31 for t in tiles):
+            raise _lib.LLDWTError("%s: need %d tile indexes that fit 32 bits" % (who, n))
+        tiles = torch.tensor(list(tiles), dtype=torch.int32).to(y.device)
+        tptr = C.c_void_p(tiles.data_ptr())
+    if out is None:
+        out = torch.zeros(B, device=y.device, dtype=torch.int64)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous()
+            and tuple(out.shape) == (B,)):
+        raise _lib.LLDWTError("%s: out must be a contiguous (%d,) int64 device tensor" % (who, B))
+    check(_lib.load().lldwt_ycc_tiles_sq_err(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, C.c_void_p(src.data_ptr()),
+                                             C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
+
+
 def u8hwc_to_ycc_tiles_lapped(src, th, tw, ov, ny, nx, first, n):
     """u8hwc_to_ycc_tiles on a lapped grid: tile (ty, tx) starts at (ty * (th - ov), tx * (tw - ov)), so neighbours share ov
     pixels (lldwt_u8hwc_to_ycc_tiles_lapped; bitwise u8hwc_to_ycc_pad of the replicate-padded crop)."""

@@ -86,6 +86,13 @@ int lldwt_u8hwc_to_f32chw(const uint8_t* src, float* dst, int64_t B, int64_t H, 
  *   (s - b[p]) * inv_a[p] (inv_a, b: 3 host floats each, lifting_dwt_nets.ll_affine) before the same colour and u8 rule.
  *   Refuses a non-finite or zero inv_a, a non-finite b, and every grid / region lldwt_ycc_tiles_to_u8hwc refuses.
  *   With inv_a = 1, b = 0 the bytes are those of lldwt_ycc_tiles_to_u8hwc.
+ * lldwt_ycc_tiles_sq_err: the exact squared error of the bytes lldwt_ycc_tiles_to_u8hwc would write with the region being
+ *   the whole image: for every in-image pixel of the tiles tiles[0..n-1] (NULL: first .. first+n-1) the
+ *   three bytes are formed by the same device function and their squared differences to src (B,H,W,3) uint8 are added to
+ *   sse[b], b the tile's image; sse: B device uint64, which the caller zeroes (the entry point accumulates).  No image is
+ *   written.  A tile index outside [0, B * ny * nx) adds nothing.  Integer sums and 64-bit integer atomics: the value is
+ *   exact and does not depend on the order of arrival.  The 1 x 1 grid (tiles == NULL, th = Hp, tw = Wp) is the untiled
+ *   codec's case and, over the blended buffer of lldwt_ycc_tiles_blend, the lapped one.  n <= 65535, th <= 8 * 65535.
  * Every tile entry point requires ny * th >= H and nx * tw >= W.                                                                                                   */
 int lldwt_u8hwc_to_ycc_tiles(const uint8_t* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw,
                              int64_t ny, int64_t nx, int64_t first, int64_t n, void* stream);
@@ -95,6 +102,8 @@ int lldwt_ycc_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t fir
 int lldwt_ll_tiles_to_u8hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
                             int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
                             const float* inv_a, const float* b, uint8_t* dst, void* stream);
+int lldwt_ycc_tiles_sq_err(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                           int64_t th, int64_t tw, int64_t ny, int64_t nx, const uint8_t* src, uint64_t* sse, void* stream);
 /* Lapped tile grid (codec.py encode_tiled(..., overlap=ov)): ny x nx tiles of th x tw at the stride
  * (sh, sw) = (th - ov, tw - ov); tile (ty, tx) covers rows [ty*sh, ty*sh + th) and columns [tx*sw, tx*sw + tw), so
  * neighbours share a band of ov pixels.  Both entry points require ov to be a power of two with 2 * ov <= min(th, tw)

@@ -21,6 +21,11 @@
                                            (1: the trained operating point); decode reads the step from the header
     encode --target-bytes T | --target-bpp R   chooses the finest step of the quarter-octave grid whose container is at most
                                            T bytes (R bits per pixel: T = floor(R * H * W / 8)); info prints the step
+    encode --target-psnr DB | --target-msssim M   chooses a step of the same grid whose decoded image has at least DB dB of
+                                           PSNR (or an MS-SSIM of at least M, sides >= 161) while the next coarser grid step
+                                           does not: the coarsest step that meets the target where quality falls along the
+                                           grid.  Prints the chosen step and the achieved value.  Not with --step,
+                                           --target-bytes / --target-bpp, --roi, --near or --lossless
     encode --rdo R                         rate-distortion optimised quantisation with the Lagrangian R = m / 64 in (0, 4]
                                            (q^2 per bit; try 0.203125 = 13 / 64): fewer bytes for a little more error.  The
                                            encoder's choice alone: nothing in the container tells, decode needs no option
@@ -108,6 +113,9 @@ def main(argv=None):
     rate.add_argument("--step", type=float, metavar="Q", help="quantisation step n / 16 in [0.25, 64] (default 1)")
     rate.add_argument("--target-bytes", type=int, metavar="T", help="finest grid step whose container is at most T bytes")
     rate.add_argument("--target-bpp", type=float, metavar="R", help="the same for R bits per pixel")
+    rate.add_argument("--target-psnr", type=float, metavar="DB",
+                      help="a grid step whose decoded image has at least DB dB while the next coarser one does not")
+    rate.add_argument("--target-msssim", type=float, metavar="M", help="the same for an MS-SSIM of at least M in (0, 1)")
     sub.choices["encode"].add_argument("--rdo", type=float, metavar="R",
                                        help="rate-distortion optimised quantisation, Lagrangian m / 64 in (0, 4] (default off)")
     sub.choices["encode"].add_argument("--roi", action="append", metavar="Y0,X0,H,W:Q",
@@ -183,12 +191,20 @@ def main(argv=None):
             kw["target_bytes"] = a.target_bytes
         elif a.target_bpp is not None:
             kw["target_bytes"] = codec.target_bpp_bytes(a.target_bpp, img.shape[0], img.shape[1])
+        elif a.target_psnr is not None:
+            kw["target_psnr"] = a.target_psnr
+        elif a.target_msssim is not None:
+            kw["target_msssim"] = a.target_msssim
         if a.rdo is not None:
             kw["rdo"] = a.rdo
         if a.roi:
             if a.target_bytes is not None or a.target_bpp is not None:
                 print("--roi cannot be combined with --target-bytes / --target-bpp (a byte target over a step map is not defined)",
                       file=sys.stderr)
+                return 2
+            if a.target_psnr is not None or a.target_msssim is not None:
+                print("--roi cannot be combined with --target-psnr / --target-msssim (a quality target over a step map is not "
+                      "defined)", file=sys.stderr)
                 return 2
             regions = []
             for r in a.roi:
@@ -228,6 +244,14 @@ def main(argv=None):
             hdr = hdr["base"]
         if hdr["step"] != 1.0:
             print("step: %g" % hdr["step"])
+        if a.target_psnr is not None:
+            st = codec.SEARCH_STATS
+            print("target %g dB: step %g, %.4f dB (SSE %d), %d probes, %d encode"
+                  % (a.target_psnr, st["step"], codec.sse_psnr(st["sse"], H, W), st["sse"], st["probes"], st["encodes"]))
+        elif a.target_msssim is not None:
+            st = codec.SEARCH_STATS
+            print("target ms-ssim %g: step %g, %.6f (%.4f dB), %d probes, %d encode"
+                  % (a.target_msssim, st["step"], st["msssim"], codec.msssim_db(st["msssim"]), st["probes"], st["encodes"]))
         if a.tile is not None:
             print("tiles: %d x %d of %dx%d" % (hdr["ny"], hdr["nx"], hdr["tw"], hdr["th"]))
             if hdr["overlap"]:

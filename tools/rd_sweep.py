@@ -7,11 +7,19 @@ Per step: container bytes, bits per pixel, PSNR and MS-SSIM of the decoded image
 container that the step cannot move -- the header, the xe streams and the streams of the coarsest level, which keep the unit
 step.  Without --image the input is a synthetic --size x --size image: smooth colour fields plus noise, seeded.  The config
 and checkpoint are those of tools/codec.py.  --rdo R: every encode with rate-distortion optimised quantisation at the Lagrangian
-R = m / 64; run the sweep with and without it to see what it buys at each step."""
+R = m / 64; run the sweep with and without it to see what it buys at each step.
+
+    python tools/rd_sweep.py --config cfg.json --psnr-targets 30,35,40 [--byte-target] ...
+
+--psnr-targets: instead of the step table, one row per PSNR target: the chosen step, the container bytes, the
+achieved PSNR, the probes, the wall time of the targeted encode and of one plain encode at the chosen step; --byte-target adds
+the wall time of target_bytes set to that container's size, with its probes + real encodes.  A target the finest step misses
+prints the encoder's message."""
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 
@@ -51,6 +59,40 @@ def sweep(net, img, steps, coder="host", rdo=None):
     return rows
 
 
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def psnr_targets(net, img, targets, coder="host", rdo=None, byte_target=False):
+    """-> list of dicts, one per PSNR target: target, step, bytes, psnr, probes, seconds, plain_seconds and, with byte_target,
+    bytes_seconds / bytes_probes / bytes_encodes / bytes_step; or target and error when the finest step misses the target."""
+    H, W = img.shape[1:3]
+    kw = dict(coder=coder, **({} if rdo is None else {"rdo": rdo}))
+    codec.encode_images(net, img, step=1.0, **kw)                      # warm-up: tables, workspaces
+    rows = []
+    for P in targets:
+        try:
+            blob, dt = _timed(lambda: codec.encode_images(net, img, target_psnr=P, **kw)[0])
+        except ValueError as e:
+            rows.append(dict(target=P, error=str(e)))
+            continue
+        st = dict(codec.SEARCH_STATS)
+        plain, dp = _timed(lambda: codec.encode_images(net, img, step=st["step"], **kw)[0])
+        assert plain == blob
+        row = dict(target=P, step=st["step"], bytes=len(blob), psnr=codec.sse_psnr(st["sse"], H, W), probes=st["probes"],
+                   seconds=dt, plain_seconds=dp)
+        if byte_target:
+            _, db = _timed(lambda: codec.encode_images(net, img, target_bytes=len(blob), **kw)[0])
+            bs = codec.SEARCH_STATS
+            row.update(bytes_seconds=db, bytes_probes=bs["probes"], bytes_encodes=bs["encodes"], bytes_step=bs["step"])
+        rows.append(row)
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True)
@@ -60,11 +102,30 @@ def main(argv=None):
     ap.add_argument("--steps", default="0.25,0.5,1,2,4,8,16,32,64")
     ap.add_argument("--coder", choices=("host", "gpu"), default="host")
     ap.add_argument("--rdo", type=float, metavar="R", help="rate-distortion optimised quantisation, Lagrangian m / 64 (default off)")
+    ap.add_argument("--psnr-targets", metavar="DB,DB,...", help="one row per PSNR target instead of the step table")
+    ap.add_argument("--byte-target", action="store_true", help="with --psnr-targets: also time target_bytes at the chosen size")
     ap.add_argument("--json", action="store_true", help="print one JSON line per step instead of the table")
     a = ap.parse_args(argv)
     from codec import _load_rgb, build_net            # tools/codec.py
     net = build_net(a.config, a.checkpoint)
     img = _load_rgb(a.image)[None] if a.image else synthetic(a.size)
+    if a.psnr_targets:
+        rows = psnr_targets(net, img, [float(v) for v in a.psnr_targets.split(",")], a.coder, a.rdo, a.byte_target)
+        if a.json:
+            for r in rows:
+                print(json.dumps(r))
+            return 0
+        print("%9s %8s %10s %10s %7s %9s %9s%s" % ("target dB", "step", "bytes", "psnr dB", "probes", "seconds", "plain s",
+                                                  "  bytes s (probes + encodes, step)" if a.byte_target else ""))
+        for r in rows:
+            if "error" in r:
+                print("%9g %s" % (r["target"], r["error"]))
+                continue
+            tail = "  %7.3f (%d + %d, %g)" % (r["bytes_seconds"], r["bytes_probes"], r["bytes_encodes"], r["bytes_step"]) \
+                if a.byte_target else ""
+            print("%9g %8g %10d %10.4f %7d %9.3f %9.3f%s" % (r["target"], r["step"], r["bytes"], r["psnr"], r["probes"],
+                                                             r["seconds"], r["plain_seconds"], tail))
+        return 0
     rows = sweep(net, img, [float(v) for v in a.steps.split(",")], a.coder, a.rdo)
     if a.json:
         for r in rows:
