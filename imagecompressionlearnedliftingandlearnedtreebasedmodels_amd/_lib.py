@@ -201,6 +201,9 @@ SIGNATURES = {
     "lldwt_resid_analyse": (_i, [_p, _p, _p] + [_i64] * 15 + [_i] + [_p] * 6),
     "lldwt_resid_contexts": (_i, [_p, _p] + [_i64] * 15 + [_p] * 4),
     "lldwt_resid_apply": (_i, [_p, _p] + [_i64] * 15 + [_i] + [_p] * 4),
+    "lldwt_layer_encode": (_i, [_p] * 7 + [_i64, _i, _i64, _i64, _f, _f, _f, _f, _i, _p]),
+    "lldwt_layer_rows": (_i, [_p] * 5 + [_i64, _i, _i64, _i64, _f, _f, _i, _p]),
+    "lldwt_layer_apply": (_i, [_p] * 4 + [_i64, _i, _i64, _i64, _f, _f, _p]),
 }
 
 _lib = None

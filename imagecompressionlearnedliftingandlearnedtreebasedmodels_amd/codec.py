@@ -128,6 +128,29 @@ SSE of the bytes the decoder would write (lldwt_ycc_tiles_sq_err on the encoder'
 ``psnr_sse_bound(P, H, W)``.  At most 7 probes without a range coder, then one real encode; the container is that of
 ``step=<chosen>`` byte for byte and records nothing.  Excludes ``step``, ``step_map``, ``target_bytes`` and ``near``.
 
+Quality layers (``encode_images(..., step=q, layers=m)``, the same on ``encode_tiled``, DESIGN.md 7.1.10, quality_layers.py): SNR
+scalability.  The container holds the unchanged base of ``step=q`` plus m refinement layers; layer j brings every coefficient of
+the levels 0 .. L-2 from the step q / 3^(j-1) to q / 3^j with one symbol of {-1, 0, +1}, coded under tables conditioned on the
+decoded base alone, so a layer decodes in a few parallel launches per level.  ``decode_images`` / ``decode_tiled(..., layers=j)``
+decode the base plus the first j layers (default: all), ``layer_bytes`` gives the bytes each prefix reads and ``truncate_layers``
+cuts a container to a prefix.  Layered container, version 1:
+
+    magic             4 bytes   b"LLDP"
+    format version    u8        1
+    m                 u8        the number of layers, 1..4, with n / 3^m >= 1 for the base step n / 16
+    K                 u8        8: bell positions 0 .. K have a table row each
+    table CRC32       u32       zlib.crc32 of the quantised rows as little-endian int32 (quality_layers.Tables.cdf)
+    base length       LEB128
+    base container    the complete LLDW or LLDT container, as encode_images / encode_tiled write it without ``layers``
+    unit count        u32       1 over LLDW, ny * nx over LLDT
+    stream lengths    LEB128 varints, layer-major; per layer unit-major in tile order; per unit 3 (L - 1): plane-major, levels 0 .. L-2
+    payload           the streams in the same order, coded by the base container's coder
+    CRC32             u32       zlib.crc32 of every byte before it
+
+``layers`` composes with ``coder``, ``step``, ``rdo``, tiles, ``region``, ``tiles_per_call`` and ``reduce`` (the levels the decode
+reaches are refined, finer levels' streams are never touched) and excludes ``near``, ``step_map``, ``overlap > 0`` and the three
+targets; ``layers=None`` and ``layers=0`` write the containers above byte for byte.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -165,6 +188,9 @@ _BASE = {MAGIC: (FORMAT_VERSION, _FIXED), TILED_MAGIC: (TILED_FORMAT_VERSION, _T
 MAPPED_MAGIC = b"LLDQ"
 MAPPED_FORMAT_VERSION = 1
 _QFIXED = struct.Struct("<4sBBHHI")            # magic, version, block log2, hb, wb, map CRC32
+LAYERED_MAGIC = b"LLDP"
+LAYERED_FORMAT_VERSION = 1
+_PFIXED = struct.Struct("<4sBBBI")             # magic, version, m, K, table CRC32
 _PLANES = 3
 # coder name of the API -> value of the arithmetic string's "coder" key (None: the key is absent)
 CODER_KEYS = {"host": None, "gpu": "irans32"}
@@ -761,6 +787,101 @@ def parse_refined(blob, check_tables=True):
     return hdr, base, units
 
 
+def _check_layered_base(bh, m):
+    """The base header of an LLDP container against its layer count m (ValueError naming the field): a level below the coarsest
+    must exist, the base carries one step (no step map), and the finest step n / (16 * 3^m) stays at or above 1 / 16."""
+    from .quality_layers import MAX_LAYERS
+    if not 1 <= m <= MAX_LAYERS:
+        raise ValueError("m: a layered container holds 1 .. %d quality layers (got %d)" % (MAX_LAYERS, m))
+    if bh["dwtlevels"] < 2:
+        raise ValueError("base container: quality layers refine the levels below the coarsest, which needs dwtlevels >= 2 (the "
+                         "base has %d)" % bh["dwtlevels"])
+    if _split_qmap(bh["arithmetic"])[0] is not None:
+        raise ValueError("base container: quality layers go over a base coded with one step, not a step map")
+    n = int(round(bh["step"] * STEP_DENOM))
+    if n < 3 ** m:
+        raise ValueError("m: %d layers need a base step n / 16 with n / 3^m >= 1 (the base has n = %d)" % (m, n))
+    return n
+
+
+def pack_layered(table_crc, base, layers):
+    """table_crc: quality_layers.tables().crc; base: a complete LLDW or LLDT container; layers[j - 1][u]: the 3 (L - 1) streams
+    of layer j and unit u (plane-major, inside a plane the levels 0 .. L-2) -> LLDP container."""
+    from .quality_layers import K
+    if _magic(base) not in (MAGIC, TILED_MAGIC):
+        raise ValueError("base container: quality layers go over an LLDW or LLDT container")
+    bh = read_header(base)
+    m = len(layers)
+    _check_layered_base(bh, m)
+    units, per = bh.get("ny", 1) * bh.get("nx", 1), _PLANES * (bh["dwtlevels"] - 1)
+    if any(len(lay) != units or any(len(u) != per for u in lay) for lay in layers):
+        raise ValueError("stream count: every layer holds %d units of %d streams" % (units, per))
+    body = _PFIXED.pack(LAYERED_MAGIC, LAYERED_FORMAT_VERSION, m, K, table_crc & 0xFFFFFFFF)
+    body += leb128_encode(len(base)) + bytes(base) + struct.pack("<I", units)
+    return _seal(body + _pack_streams([bytes(s) for lay in layers for u in lay for s in u]))
+
+
+def parse_layered(blob, check_tables=True):
+    """LLDP container -> (header dict, base container bytes, layers), layers[j - 1][u] being the 3 (L - 1) streams of layer j and
+    unit u.  The header carries layers (m), K, table_crc, base (the nested base header), units, base_bytes, stream_lengths and
+    layer_bytes (``layer_bytes``).  Every check raises ValueError naming the field, on the host: magic, version, CRC,
+    truncation, m in 1..4, K, the base (parsed by its own parser; LLDW or LLDT with dwtlevels >= 2 and one step), n / 3^m >= 1,
+    the unit count, the stream lengths and -- with check_tables -- the table CRC32 against this process's tables."""
+    from . import quality_layers
+    blob, end = _open(blob, LAYERED_MAGIC, LAYERED_FORMAT_VERSION, _PFIXED.size + 1 + 4)
+    _, _, m, K, table_crc = _PFIXED.unpack_from(blob, 0)
+    if not 1 <= m <= quality_layers.MAX_LAYERS:
+        raise ValueError("m: the container holds %d quality layers, a layered container has 1 .. %d" % (m, quality_layers.MAX_LAYERS))
+    if K != quality_layers.K:
+        raise ValueError("K: the container's tables have bell positions 0 .. %d, this decoder's 0 .. %d" % (K, quality_layers.K))
+    try:
+        blen, pos = leb128_decode(blob, _PFIXED.size, end)
+    except ValueError:
+        raise ValueError("base length: container truncated or varint too long") from None
+    if pos + blen + 4 > end:
+        raise ValueError("base length: container truncated inside the base container (%d bytes announced, %d left)"
+                         % (blen, max(0, end - pos)))
+    base = blob[pos:pos + blen]
+    if _magic(base) not in (MAGIC, TILED_MAGIC):
+        raise ValueError("base container: quality layers go over an LLDW or LLDT container (got magic %r)" % base[:4])
+    bh = read_header(base)
+    _check_layered_base(bh, m)
+    pos += blen
+    base_end = pos
+    count = struct.unpack_from("<I", blob, pos)[0]
+    pos += 4
+    units, per = bh.get("ny", 1) * bh.get("nx", 1), _PLANES * (bh["dwtlevels"] - 1)
+    if count != units:
+        raise ValueError("unit count: the container holds %d units, the base has %d" % (count, units))
+    streams, lengths = _parse_streams(blob, pos, end, m * units * per)
+    if check_tables and quality_layers.tables().crc != table_crc:
+        raise ValueError("table CRC32: the container's layer tables have CRC %08x, this platform builds %08x; the streams "
+                         "cannot be decoded here" % (table_crc, quality_layers.tables().crc))
+    layers = [[streams[(j * units + u) * per:(j * units + u + 1) * per] for u in range(units)] for j in range(m)]
+    payload = end - sum(lengths)
+    sizes = [base_end] + [payload + sum(lengths[:(j + 1) * units * per]) for j in range(m)]
+    hdr = dict(version=LAYERED_FORMAT_VERSION, layers=m, K=K, table_crc=table_crc, base=bh, units=units, base_bytes=blen,
+               stream_lengths=lengths, layer_bytes=sizes)
+    return hdr, base, layers
+
+
+def layer_bytes(blob):
+    """LLDP container -> list of m + 1 ints: entry j is the number of container bytes a decode of the base plus the first j
+    layers reads.  Entry 0 ends with the embedded base container; entry j >= 1 is every byte before the payload (the fields
+    around the base and all stream lengths) plus the streams of the layers 1 .. j.  The 4-byte CRC32 trailer is not counted.
+    CPU only."""
+    return list(parse_layered(blob, check_tables=False)[0]["layer_bytes"])
+
+
+def truncate_layers(blob, j):
+    """LLDP container -> a valid container holding its first j layers (0 <= j <= m): for j = 0 the base container itself, else
+    an LLDP container with m = j whose streams are the first j layers' bytes.  CPU only."""
+    hdr, base, layers = parse_layered(blob, check_tables=False)
+    if isinstance(j, bool) or not isinstance(j, int) or not 0 <= j <= hdr["layers"]:
+        raise ValueError("layers: the container holds %d layers, asked to keep %r" % (hdr["layers"], j))
+    return bytes(base) if j == 0 else pack_layered(hdr["table_crc"], base, layers[:j])
+
+
 def _magic(blob):
     return bytes(blob[:4]) if isinstance(blob, (bytes, bytearray, memoryview)) else None
 
@@ -771,7 +892,10 @@ def read_header(blob):
     (parse_mapped).  A tiled
     header carries ``overlap``: 0 for LLDT.  An LLDR header carries ``near``, ``residual_bytes`` and the nested base header
     under ``base`` (parse_refined; the table CRC is compared by the decoders).  Raises ValueError as parse_container /
-    parse_tiled / parse_lapped / parse_refined."""
+    parse_tiled / parse_lapped / parse_refined.  An LLDP header carries ``layers`` (the number of quality layers m),
+    ``layer_bytes`` and the nested base header under ``base`` (parse_layered; the table CRC is compared by the decoders)."""
+    if _magic(blob) == LAYERED_MAGIC:
+        return parse_layered(blob, check_tables=False)[0]
     if _magic(blob) == MAPPED_MAGIC:
         return parse_mapped(blob)[0]
     if _magic(blob) == REFINED_MAGIC:
@@ -964,6 +1088,29 @@ def _rdo_arg(rdo, L):
         raise ValueError("rdo: rate-distortion optimised quantisation needs dwtlevels >= 2 (it applies to the levels below the "
                          "coarsest; the net has %d)" % L)
     return m / RDO_DENOM if m else None
+
+
+def _layer_args(layers, step, L, near=None, step_map=None, overlap=0, target_bytes=None, target_psnr=None, target_msssim=None):
+    """The layers argument of encode_images / encode_tiled, checked on the host before the other arguments -> m (0: none).
+    ValueError naming the pair for everything the layers do not compose with: near (the residual layer sits on the base's
+    pixels, which the layers change), step_map (a layer's step is one number per level), overlap > 0, and the three targets
+    (they choose a step for a single-rate container); also without a level that carries a step (dwtlevels < 2) and for a step
+    below 3^m / 16."""
+    from .quality_layers import check_layers, check_step_divides
+    m = check_layers(layers)
+    if m == 0:
+        return 0
+    for name, val in (("near", near), ("step_map", step_map), ("target_bytes", target_bytes), ("target_psnr", target_psnr),
+                      ("target_msssim", target_msssim)):
+        if val is not None:
+            raise ValueError("layers and %s: quality layers do not compose with %s" % (name, name))
+    if overlap:
+        raise ValueError("layers and overlap: quality layers over lapped tiles (overlap > 0) are not defined; use overlap=0")
+    if L < 2:
+        raise ValueError("layers: quality layers refine the levels below the coarsest, which needs dwtlevels >= 2 (the net has "
+                         "%d)" % L)
+    check_step_divides(check_step(step), m)
+    return m
 
 
 def _rate_args(step, target_bytes, near, L):
@@ -1167,7 +1314,7 @@ def _estimated_size(empty, estimates):
 
 
 def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None,
-                  target_psnr=None, target_msssim=None):
+                  layers=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -1189,10 +1336,14 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     psnr_sse_bound(P, H, W); MS-SSIM (the channel mean ``quality`` reports, sides >= 161) iff the value is >= M -- its sums
     are double atomics, so a target within rounding of a probe's value may resolve either way.  At most 7 probes without a
     range coder, then ONE real encode: the container is byte for byte that of step=<chosen>, nothing is recorded.
-    ValueError naming the target and the best achievable value if the finest step misses it."""
+    ValueError naming the target and the best achievable value if the finest step misses it.
+    layers = m in 1..4: LLDP containers holding the container of the other arguments byte for byte plus m
+    quality layers, layer j refining the levels 0 .. L-2 to the step q / 3^j; decode_images(..., layers=j) decodes any prefix.
+    With coder, step (n / 3^m >= 1) and rdo; not with near, step_map or a target.  None and 0 write the bytes above."""
     from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
+    m = _layer_args(layers, step, L, near, step_map, 0, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
         from .residual import check_near
@@ -1201,17 +1352,17 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     n, T = _rate_args(step, target_bytes, near, L)
     rdo = _rdo_arg(rdo, L)
     Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None):
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0):
     """_encode at the step step_n / 16, or with a byte target T the search of _search_step, or with a quality target (the
     pair of _quality_args) that of _encode_at_quality, one image at a time.  walk: the (magic, grid, group, coder) of _encode.
-    rdo: probes and real encodes alike."""
+    rdo: probes and real encodes alike.  layers: the number of quality layers (_layer_args: no target then)."""
     if target is not None:
         return _encode_at_quality(net, images_u8, walk, rdo, target)
     if T is None:
-        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps)
+        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps, layers=layers)
     return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo)[0],
                          lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo)[0], T)
             for b in range(images_u8.shape[0])]
@@ -1297,7 +1448,20 @@ def _encode_at_quality(net, images_u8, walk, rdo, target):
     return blobs
 
 
-def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None):
+def _unit_layers(lay, j, L):
+    """The layer streams of unit j of an encode_strings_planes(..., layers=...) result, lay[jj][i][p][b] -> per layer the
+    3 (L - 1) streams in the LLDP order: plane-major, inside a plane the levels 0 .. L-2."""
+    return [[lay[jj][i][p][j] for p in range(_PLANES) for i in range(L - 1)] for jj in range(len(lay))]
+
+
+def _gather_layers(units, k, L):
+    """The layer streams of a group of units (each as _unit_layers gives them) -> lay[jj][i][p][b] as decode_strings_planes
+    takes them at first_level = k: the entries of the levels below k are None, their streams are never touched."""
+    return [[None if i < k else [[u[jj][p * (L - 1) + i] for u in units] for p in range(_PLANES)] for i in range(L - 1)]
+            for jj in range(len(units[0]))]
+
+
+def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None, layers=0):
     """The encode walk behind encode_images and encode_tiled (arguments checked there): the batch is cut into the tiles of
     grid = (th, tw, ny, nx, ov) -- the untiled codec is the 1 x 1 grid of one padded_size tile, which the untiled input and
     output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
@@ -1305,7 +1469,9 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     containers over them.  estimate: -> the estimated container sizes (ints) from the code-length kernel instead; no range
     coder runs.  rdo: the Lagrangian of DESIGN.md 7.1.7 (None: off), which only the encoder's symbols see.
     maps: the (B, hb, wb) array of _map_arg (None: the step alone): every unit is coded with its slice of its image's map
-    (_unit_maps), every base carries the qmap key of its image's map, and the result is wrapped into LLDQ (pack_mapped)."""
+    (_unit_maps), every base carries the qmap key of its image's map, and the result is wrapped into LLDQ (pack_mapped).
+    layers: m > 0 quality layers (without near, maps or estimate): every group's layer streams are coded right
+    after its base, from the group's own tensors, and the containers are wrapped into LLDP (pack_layered)."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
@@ -1325,7 +1491,7 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     img = images_u8.to(dev).contiguous()
     per, count = ny * nx, _PLANES * (L + 1)
     g = group if _batch_invariant(arith) else 1
-    tiles = []
+    tiles, unit_layers = [], []
     xh = torch.empty_like(img) if near is not None else None
     with torch.no_grad():
         for first in range(0, B * per, g):
@@ -1335,7 +1501,10 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
             else:
                 x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
             st = step if maps is None else _unit_maps(maps, range(first, first + n), grid, L, dev)
-            if near is None:
+            if layers:
+                s_xe, s_xo, lay = encode_strings_planes(nets, x, coder=coder, step=st, rdo=rdo, layers=(step_n, layers))
+                unit_layers += [_unit_layers(lay, j, L) for j in range(n)]
+            elif near is None:
                 s_xe, s_xo = encode_strings_planes(nets, x, coder=ESTIMATE if estimate else coder, step=st, rdo=rdo)
             else:
                 s_xe, s_xo, xhat = encode_strings_planes(nets, x, coder=coder, recon=True, step=st, rdo=rdo)
@@ -1348,6 +1517,11 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
         blobs = [_pack_base(magic, hdrs[b], tiles[b * per:(b + 1) * per]) for b in range(B)]
         if near is not None:
             blobs = _refine(blobs, img, xh, (H, W, th, tw, ny, nx), near, coder)
+        if layers:
+            from . import quality_layers
+            crc = quality_layers.tables().crc
+            blobs = [pack_layered(crc, blobs[b], [[u[jj] for u in unit_layers[b * per:(b + 1) * per]] for jj in range(layers)])
+                     for b in range(B)]
         if maps is not None:
             blobs = [pack_mapped(maps[b], blobs[b]) for b in range(B)]
     return blobs
@@ -1413,7 +1587,7 @@ def ll_norm(net, k):
     return torch.tensor(inv, dtype=torch.float32).tolist(), torch.tensor(b, dtype=torch.float32).tolist()
 
 
-def decode_images(net, blobs, reduce=0, refine=True):
+def decode_images(net, blobs, reduce=0, refine=True, layers=None):
     """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
     first; then containers of equal (H, W), coder and quantisation step are decoded together (both come from each header).
     reduce = k in [0, L]: the image at 1/2^k of each side, (ceil(H / 2^k), ceil(W / 2^k), 3), decoded from the xe streams
@@ -1421,15 +1595,30 @@ def decode_images(net, blobs, reduce=0, refine=True):
     An LLDR container over LLDW is decoded through its base and then refined on the device (lossless or within its bound,
     DESIGN.md 7.1.5); refine=False, or reduce > 0 (the residual lives at full resolution), gives exactly the base decode.
     An LLDQ container is decoded as its inner container, with its step map on the levels 0 .. L-2 that the
-    decode reaches; images with different maps are decoded together, the map being per image."""
+    decode reaches; images with different maps are decoded together, the map being per image.
+    An LLDP container over LLDW is decoded through its base plus its first ``layers`` quality layers (None:
+    all it holds; 0: exactly the base decode); with reduce = k the levels k .. L-2 are refined and the streams of finer levels
+    are never touched.  ``layers`` above a container's count, or other than None / 0 for a container without layers, is a
+    ValueError."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
-    refined, maps = {}, {}
+    refined, maps, layered = {}, {}, {}
     blobs = list(blobs)
     for i, b in enumerate(blobs):
+        if _magic(b) == LAYERED_MAGIC:
+            phdr, b, lay = parse_layered(b)
+            if _magic(b) != MAGIC:
+                raise ValueError("base container: decode_images takes an LLDP over LLDW; this one is over %s (decode_tiled)"
+                                 % bytes(b[:4]).decode("ascii", "replace"))
+            blobs[i] = b
+            j = _layers_arg(layers, phdr["layers"])
+            if j:
+                layered[i] = [lay[jj][0] for jj in range(j)]
+        else:
+            _layers_arg(layers, 0)
         if _magic(b) == MAPPED_MAGIC:
             _, maps[i], b = parse_mapped(b)
             blobs[i] = b
@@ -1450,16 +1639,17 @@ def decode_images(net, blobs, reduce=0, refine=True):
     dev = next(net.parameters()).device
     by_size = {}
     for i, (hdr, _) in enumerate(parsed):
-        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"], i in maps), []).append(i)
+        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"], i in maps, len(layered.get(i, ()))), []).append(i)
     out = [None] * len(parsed)
     with torch.no_grad():
         if k:
             inv_a, b = ll_norm(net, k)
-        for (H, W, coder, step, mapped), idx in by_size.items():
+        for (H, W, coder, step, mapped, nlay), idx in by_size.items():
             Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             units = [parsed[i][1] for i in idx]
             um = _unit_maps([maps[i] for i in idx], range(len(idx)), (Hp, Wp, 1, 1, 0), L, dev) if mapped else None
-            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um):
+            ul = [layered[i] for i in idx] if nlay else None
+            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um, ul):
                 g = idx[a:a + n]
                 if k == 0:
                     img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W)
@@ -1538,7 +1728,7 @@ def _tile_streams(s_xe, s_xo, j):
 
 
 def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
-                 rdo=None, step_map=None, target_psnr=None, target_msssim=None):
+                 rdo=None, step_map=None, layers=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -1554,9 +1744,12 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     multiples of 2^L for plain and lapped grids alike), clamped at the image's last block -> LLDQ over LLDT / LLDO / LLDR.
     target_psnr, target_msssim: as encode_images, with ONE step for all tiles of a frame, met by the image decode_tiled returns
     for the frame: the tiles' in-image rectangles, or with overlap > 0 the blended frame.  The result does
-    not depend on tiles_per_call."""
+    not depend on tiles_per_call.
+    layers: as encode_images, every tile being a unit with its own layer streams (LLDP over LLDT; not with overlap > 0), so a
+    region decodes the refinement of the tiles it touches only."""
     layer, nettype, L = describe(net)
     B, H, W = _check_images(images_u8)
+    m = _layer_args(layers, step, L, near, step_map, overlap, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
         from .residual import check_near
@@ -1574,7 +1767,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m)
 
 
 def _tiles_per_call(tiles_per_call):
@@ -1584,11 +1777,13 @@ def _tiles_per_call(tiles_per_call):
     return int(tiles_per_call)
 
 
-def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step=1.0):
+def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step=1.0, layers=None):
     """One group of n tiles -> xhat (3,n,1,th,tw), or at first_level = k the LL band (3,n,1,th>>k,tw>>k)
-    (decode_strings_planes; a module-level hook so the number of tiles a decode touches can be counted)."""
+    (decode_strings_planes; a module-level hook so the number of tiles a decode touches can be counted).  layers: the
+    (streams, n of the base step, layer count) of decode_strings_planes, given only for a decode with quality layers."""
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
-    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, step=step)
+    kw = {} if layers is None else {"layers": layers}
+    return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, step=step, **kw)
 
 
 def _gather(units, k, L):
@@ -1600,18 +1795,35 @@ def _gather(units, k, L):
     return s_xe, s_xo
 
 
-def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None):
+def _layers_arg(layers, m):
+    """The layers argument of a decode against a container of m quality layers (0: none) -> the count to decode (None: all).
+    ValueError naming layers."""
+    if layers is None:
+        return m
+    if isinstance(layers, bool) or not isinstance(layers, int) or not 0 <= layers <= m:
+        raise ValueError("layers must be an integer in [0, %d], the quality layers the container holds (got %r)" % (m, layers))
+    return layers
+
+
+def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None, layers=None):
     """The decode walk behind decode_images and decode_tiled: the units (stream lists of images or tiles of th x tw, all of
     the coder and step of hdr) are decoded ``group`` at a time, one per call in the arithmetics that are not batch invariant,
     through the _decode_tiles hook -> yields (index of the group's first unit, its size n, the hook's result).
     maps: the units' step maps (_unit_maps, one per unit) when the units were coded with one; each group then decodes with its
-    slice in place of the header's step."""
+    slice in place of the header's step.
+    layers: (per unit its layer streams in the LLDP order, truncated to the count j > 0 to decode) of a layered decode (DESIGN.md
+    7.1.10): each group's levels k .. L-2 are refined with its own streams before the inverse transform."""
     g = group if _batch_invariant(hdr["arithmetic"]) else 1
+    L = hdr["dwtlevels"]
     for a in range(0, len(units), g):
         grp = units[a:a + g]
-        s_xe, s_xo = _gather(grp, k, hdr["dwtlevels"])
+        s_xe, s_xo = _gather(grp, k, L)
+        kw = {}
+        if layers is not None:
+            lay = _gather_layers(layers[a:a + g], k, L)
+            kw["layers"] = (lay, int(round(hdr["step"] * STEP_DENOM)), len(lay))
         yield a, len(grp), _decode_tiles(nets, s_xe, s_xo, th, tw, len(grp), coder=hdr["coder"], first_level=k,
-                                         step=hdr["step"] if maps is None else maps[a:a + g])
+                                         step=hdr["step"] if maps is None else maps[a:a + g], **kw)
 
 
 def _region(region, H, W):
@@ -1626,7 +1838,7 @@ def _region(region, H, W):
     return y0, x0, h, w
 
 
-def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True):
+def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True, layers=None):
     """LLDT or LLDO container (or an LLDQ over one, DESIGN.md 7.1.8: each tile decodes with its slice of the step map) ->
     (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
@@ -1637,12 +1849,22 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     image, each tile covers th>>k x tw>>k of its pixels and is written by lldwt_ll_tiles_to_u8hwc.
     LLDR over LLDT: the base and residual streams of the touched tiles are decoded and the region is cut from their refined
     rectangles; refine=False, or reduce > 0, gives exactly the base decode.
+    LLDP over LLDT: the touched tiles are decoded with their first ``layers`` quality layers (None: all, 0: the
+    base decode), as decode_images; only those tiles' layer streams are read.
     Every check (container, region, identity) runs on the host before any GPU work."""
     import torch
     from . import ops
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
-    units = smap = None
+    units = smap = lay = None
+    if _magic(blob) == LAYERED_MAGIC:
+        phdr, blob, lay = parse_layered(blob)
+        if _magic(blob) != TILED_MAGIC:
+            raise ValueError("base container: decode_tiled takes an LLDP over LLDT; this one is over %s (decode_images)"
+                             % bytes(blob[:4]).decode("ascii", "replace"))
+        lay = lay[:_layers_arg(layers, phdr["layers"])] or None
+    else:
+        _layers_arg(layers, 0)
     if _magic(blob) == MAPPED_MAGIC:           # DESIGN.md 7.1.8: the inner container with its step map
         _, smap, blob = parse_mapped(blob)
     if _magic(blob) == REFINED_MAGIC:
@@ -1685,7 +1907,8 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
             acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
         else:
             out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
-        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um):
+        ul = None if lay is None else [[lay[jj][t] for jj in range(len(lay))] for t in want]
+        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um, ul):
             if ov:                   # lapped: the raw samples are blended, then written once as the tile of a 1 x 1 grid
                 ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), want[a:a + n], acc)
             else:

@@ -1119,7 +1119,7 @@ def compress_planes(nets, x):
     return xhat, s_xe, s_xo
 
 
-def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None):
+def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None, layers=None):
     """The encoder half of compress_planes: encode -> the entropy layer's compress_planes, no decoding.
     x (P,B,C,H,W) -> (strings_xe[p][b], [strings_xo[p][b]] finest first).  coder: "host" (rans64 on the host) or "gpu"
     (irans32 on the device); the symbols are the same, the bytes differ.
@@ -1130,7 +1130,10 @@ def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None
     rdo: the Lagrangian of rate-distortion optimised quantisation on the same levels (m / 64, None or 0: off).
     An encoder's choice: the strings decode with decode_strings_planes as ever.
     step may be a step map instead: an integer tensor (B, Hp >> L, Wp >> L) of n = 16 * step, one entry per
-    coefficient of the coarsest level of each image; decode_strings_planes takes the same tensor."""
+    coefficient of the coarsest level of each image; decode_strings_planes takes the same tensor.
+    layers = (n, m): the base step is n / 16 (a number, not a map) and m quality layers refine the levels 0 .. L-2 on top of it
+     -> one more result after the others, lay[j - 1][i][p][b]: the stream of layer j, level i
+    (quality_layers.encode_units).  The base strings are those of the call without ``layers``."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "compress_planes"):
         raise NotImplementedError(_NOT_CODED)
@@ -1139,17 +1142,23 @@ def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None
     if not (rdo is None or rdo == 0):
         kw["rdo"] = rdo
     s_xe, s_xo, xe_q, xo_q = type(em[0]).compress_planes(em, out_xe, out_xo, coder=coder, **kw)
+    res = (s_xe, s_xo)
     if recon:
-        return s_xe, s_xo, decode_planes([n.autoencoder for n in nets], xe_q, xo_q)
-    return s_xe, s_xo
+        res += (decode_planes([n.autoencoder for n in nets], xe_q, xo_q),)
+    if layers is not None:
+        from ... import quality_layers
+        res += (quality_layers.encode_units(em, out_xo, xo_q, layers[0], layers[1], coder)[0],)
+    return res
 
 
-def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0, step=1.0):
+def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0, step=1.0, layers=None):
     """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them, with the same coder) ->
     xhat (P,B,C,Hp,Wp).
     Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes).
     first_level = k: strings_xo holds all L levels or only the levels k .. L-1, which are the only ones decoded, and the result
-    is the decoded LL band at level k, (P,B,C,Hp>>k,Wp>>k) (decode_planes; lifting_dwt_nets.ll_affine gives its scale)."""
+    is the decoded LL band at level k, (P,B,C,Hp>>k,Wp>>k) (decode_planes; lifting_dwt_nets.ll_affine gives its scale).
+    layers = (lay, n, j): the first j quality layers of encode_strings_planes(..., layers=(n, m)), lay[jj - 1][i][p][b], refine
+    the decoded levels k .. L-2 before the inverse transform; the entries of finer levels are never read."""
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "decompress_planes"):
         raise NotImplementedError(_NOT_CODED)
@@ -1160,6 +1169,9 @@ def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host",
     kw = {"step": step} if isinstance(step, torch.Tensor) or step != 1.0 else {}
     xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder, first_level=k, **kw)
     assert [tuple(t.shape) for t in xo] == [tuple(sh) for sh in shapes_xo[k:]]
+    if layers is not None and layers[2] > 0:
+        from ... import quality_layers
+        xo = quality_layers.decode_units(em, [None] * k + list(xo), layers[0], layers[1], layers[2], coder, first_level=k)[k:]
     return decode_planes(aenc, xe, xo, first_level=k)
 
 

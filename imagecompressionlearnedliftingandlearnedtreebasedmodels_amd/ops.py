@@ -1191,6 +1191,81 @@ def gauss_quantise(params, table63, level, r0, c0, stride, step, y=None, sym=Non
     return idx, (out if y is not None else None if sym is None else sym.reshape(P, B, Cc, h, w))
 
 
+LAYER_DIVISOR = 3                    # a quality layer divides the step by 3: a mid-tread bin splits exactly into three (7.1.10)
+
+
+def layer_pair(n, j):
+    """The step of quality layer j over a base of step n / 16 (j = 0: the base) -> (q_j, inv_q_j) as Python
+    floats holding fp32 values: q_j = fp32(n / (16 * 3^j)), the division in float64, and inv_q_j = fp32(1 / q_j) with the
+    division in float64 on the rounded q_j.  The ONE place where the pairs are formed; j = 0 gives step_pair(n / 16).  How many
+    layers a step may carry is the codec's rule (n / 3^m >= 1), not checked here."""
+    import numpy as np
+    n, j = int(n), int(j)
+    if not (STEP_N_MIN <= n <= STEP_N_MAX and 0 <= j <= 8):
+        raise ValueError("layers: layer %d over the step %d / %d is not defined (n in [%d, %d], j in [0, 8])"
+                         % (j, n, STEP_DENOM, STEP_N_MIN, STEP_N_MAX))
+    q = np.float32(float(n) / float(STEP_DENOM * LAYER_DIVISOR ** j))
+    return float(q), float(np.float32(1.0 / float(q)))
+
+
+def _layer_level(who, v, params, table63):
+    if v.dim() != 5 or params.dim() != 5 or tuple(params.shape) != (v.shape[0], v.shape[1], 2 * v.shape[2], v.shape[3], v.shape[4]):
+        raise _lib.LLDWTError("%s: level %s and params %s do not belong together" % (who, tuple(v.shape), tuple(params.shape)))
+    if table63.numel() != 63:
+        raise _lib.LLDWTError("%s: the table must hold 63 entries (got %d)" % (who, table63.numel()))
+    P, B, G, h, w = v.shape
+    return P * B, G, h, w
+
+
+def _i32(t, shape, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == shape.numel()):
+        raise _lib.LLDWTError("%s must be a contiguous int32 device tensor of %d values" % (name, shape.numel()))
+    return C.c_void_p(t.data_ptr())
+
+
+def layer_encode(y, v_prev, params, table63, prev, cur, K):
+    """The encoder of a quality layer on a level (lldwt_layer_encode).  y, v_prev (P,B,G,h,w): the
+    coefficients and the level at the previous step; params (P,B,2G,h,w); prev, cur: the pairs of layer_pair for the previous
+    and this layer -> (sym, row, v): the coded symbols and table rows (P,B,G,h,w) int32 and the level at this layer's step."""
+    Z, G, h, w = _layer_level("layer_encode", v_prev, params, table63)
+    if y.shape != v_prev.shape:
+        raise _lib.LLDWTError("layer_encode: y %s and the level %s differ in shape" % (tuple(y.shape), tuple(v_prev.shape)))
+    sym = torch.empty(v_prev.shape, device=v_prev.device, dtype=torch.int32)
+    row = torch.empty_like(sym)
+    v = torch.empty_like(v_prev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    check(_lib.load().lldwt_layer_encode(_chk(y, "y"), _chk(v_prev, "v_prev"), _chk(params, "params"), _chk(table63, "table63"),
+                                         p(sym), p(row), p(v), Z, G, h, w, prev[0], prev[1], cur[0], cur[1], int(K), _stream()),
+          "layer_encode")
+    return sym, row, v
+
+
+def layer_rows(v_prev, params, table63, prev, K):
+    """The decoder's half before the symbols are popped (lldwt_layer_rows): -> (row, sign), (P,B,G,h,w) int32."""
+    Z, G, h, w = _layer_level("layer_rows", v_prev, params, table63)
+    row = torch.empty(v_prev.shape, device=v_prev.device, dtype=torch.int32)
+    sign = torch.empty_like(row)
+    check(_lib.load().lldwt_layer_rows(_chk(v_prev, "v_prev"), _chk(params, "params"), _chk(table63, "table63"),
+                                       C.c_void_p(row.data_ptr()), C.c_void_p(sign.data_ptr()), Z, G, h, w, prev[0], prev[1], int(K),
+                                       _stream()), "layer_rows")
+    return row, sign
+
+
+def layer_apply(v_prev, sym, sign, cur, out=None):
+    """The decoder's half after (lldwt_layer_apply): v_prev (P,B,G,h,w), sym the popped symbols and sign of layer_rows (int32, as
+    many values) -> v = v_prev + sign * sym * q (out: where to write it, v_prev itself allowed)."""
+    if v_prev.dim() != 5:
+        raise _lib.LLDWTError("layer_apply: the level must be (P,B,G,h,w) (got %s)" % (tuple(v_prev.shape),))
+    P, B, G, h, w = v_prev.shape
+    v = torch.empty_like(v_prev) if out is None else out
+    if v.shape != v_prev.shape:
+        raise _lib.LLDWTError("layer_apply: out %s and the level %s differ in shape" % (tuple(v.shape), tuple(v_prev.shape)))
+    check(_lib.load().lldwt_layer_apply(_chk(v_prev, "v_prev"), _i32(sym, v_prev.shape, "layer_apply: sym"),
+                                        _i32(sign, v_prev.shape, "layer_apply: sign"), _chk(v, "out"), P * B, G, h, w, cur[0], cur[1],
+                                        _stream()), "layer_apply")
+    return v
+
+
 def cost_table(cdf, sizes):
     """Quantised CDF tables (host int32 arrays: cdf (T, width), sizes (T)) -> (T, width) int32 numpy array for code_cost:
     round(-log2(freq / 65536) * 2^16) for the sizes[t] - 2 symbols of table t, COST_ESCAPE elsewhere."""

@@ -854,6 +854,29 @@ int lldwt_resid_apply(const uint8_t* xh, const int32_t* tiles, int64_t first, in
                       int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w, int64_t uh,
                       int64_t uw, int d, const int32_t* sym, uint8_t* dst, uint64_t* cs_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Quality layers of the codec (SNR refinement of the levels that carry a step; DESIGN.md 7.1.10, csrc/layers.hip).
+ * Element-wise over a level (streams, channels, h, w) fp32 with its Gaussian parameters (streams, 2 channels, h, w), sigma of
+ * channel c on 2c and mu on 2c + 1, and table63 the scale table's first 63 entries (the layout of lldwt_gauss_quantise).
+ * A layer takes the level from the step q_prev to q; both come as pairs (q, fp32(1 / q)) formed on the host (the division in
+ * double), else LLDWT_EINVAL.  All arithmetic is fp32 with every product rounded before it is added (no fused multiply-add):
+ *   idx  = #(table63 < max(sigma * inv_q_prev, 0.11))
+ *   m    = rint((v_prev - mu) * inv_q_prev), a = min(|m|, K), sign = m < 0 ? -1 : +1
+ *   row  = idx * (K + 1) + a                                   (the table of the coded symbol, K in [1, LLDWT_LAYER_MAX_K])
+ *   t    = clamp(rint((y - v_prev) * inv_q), -1, 1), v_out = v_prev + t * q, coded symbol = sign * t
+ * lldwt_layer_encode writes sym, row (int32) and v_out; lldwt_layer_rows writes row and sign (int32, +1 / -1) from v_prev and
+ * params alone, which a decoder needs before it can pop the symbols; lldwt_layer_apply writes v_out = v_prev + sign * sym * q
+ * (a symbol outside {-1, 0, +1} is clamped).  v_out may be v_prev.  One 16-byte access per array and thread where w % 4 == 0
+ * and every array is 16-byte aligned, one element per thread otherwise.  streams * channels <= 65535.  Nothing synchronises. */
+#define LLDWT_LAYER_MAX_K 255
+int lldwt_layer_encode(const float* y, const float* v_prev, const float* params, const float* table63, int32_t* sym, int32_t* row,
+                       float* v_out, int64_t streams, int channels, int64_t h, int64_t w, float q_prev, float inv_q_prev, float q,
+                       float inv_q, int K, void* stream);
+int lldwt_layer_rows(const float* v_prev, const float* params, const float* table63, int32_t* row, int32_t* sign, int64_t streams,
+                     int channels, int64_t h, int64_t w, float q_prev, float inv_q_prev, int K, void* stream);
+int lldwt_layer_apply(const float* v_prev, const int32_t* sym, const int32_t* sign, float* v_out, int64_t streams, int channels,
+                      int64_t h, int64_t w, float q, float inv_q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

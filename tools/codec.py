@@ -36,6 +36,12 @@
                                            select.  Not with --target-bytes / --target-bpp.  decode needs no option; info
                                            prints the map's size, its steps and the share of blocks at each
 
+    encode --layers M                      adds M quality layers (1..4) over the container of --step Q: layer j refines the levels
+                                           below the coarsest to the step Q / 3^j (Q * 16 / 3^M >= 1), writing an LLDP container.
+                                           Not with --near / --lossless, --roi, --overlap or a target
+    decode --layers J                      decodes the base plus the first J layers (default: all the container holds); info
+                                           prints the bytes each prefix reads
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -120,6 +126,10 @@ def main(argv=None):
                                        help="rate-distortion optimised quantisation, Lagrangian m / 64 in (0, 4] (default off)")
     sub.choices["encode"].add_argument("--roi", action="append", metavar="Y0,X0,H,W:Q",
                                        help="code this rectangle at the step Q, the rest at --step (repeatable; writes LLDQ)")
+    sub.choices["encode"].add_argument("--layers", type=int, metavar="M",
+                                       help="add M quality layers (1..4) that refine the step by 3 each (writes LLDP)")
+    sub.choices["decode"].add_argument("--layers", type=int, metavar="J",
+                                       help="decode the base plus the first J quality layers of an LLDP container (default: all)")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
                                        help="decode the base layer of a refined (LLDR) container only")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
@@ -147,7 +157,14 @@ def main(argv=None):
             for v, c in zip(vals.tolist(), counts.tolist()):
                 print("%-15s %g: %d blocks (%.1f %%)" % ("  step", v / codec.STEP_DENOM, c, 100.0 * c / m.size))
             hdr = hdr["inner"]
-        if "base" in hdr:                      # LLDR: the layer's own fields and the byte split, then the base container's
+        if "layers" in hdr:                    # LLDP: the layer count and the bytes each prefix reads, then the base container's
+            print("%-15s %d (bell positions 0 .. %d, table CRC %08x)" % ("layers", hdr["layers"], hdr["K"], hdr["table_crc"]))
+            print("%-15s %d" % ("units", hdr["units"]))
+            print("%-15s %d" % ("base_bytes", hdr["base_bytes"]))
+            for j, n in enumerate(hdr["layer_bytes"]):
+                print("%-15s step %g: %d bytes" % ("layers %d" % j, hdr["base"]["step"] / 3 ** j, n))
+            hdr = hdr["base"]
+        elif "base" in hdr:                    # LLDR: the layer's own fields and the byte split, then the base container's
             print("%-15s %s" % ("near", "0 (lossless)" if hdr["near"] == 0 else "%d (every sample within %d)" % (hdr["near"],
                                                                                                             hdr["near"])))
             print("%-15s %d" % ("units", hdr["units"]))
@@ -197,6 +214,8 @@ def main(argv=None):
             kw["target_msssim"] = a.target_msssim
         if a.rdo is not None:
             kw["rdo"] = a.rdo
+        if a.layers is not None:
+            kw["layers"] = a.layers
         if a.roi:
             if a.target_bytes is not None or a.target_bpp is not None:
                 print("--roi cannot be combined with --target-bytes / --target-bpp (a byte target over a step map is not defined)",
@@ -239,7 +258,10 @@ def main(argv=None):
         if "inner" in hdr:
             print("step map: %d x %d blocks, steps %g .. %g" % (hdr["hb"], hdr["wb"], hdr["step_min"], hdr["step_max"]))
             hdr = hdr["inner"]
-        if "base" in hdr:
+        if "layers" in hdr:
+            print("layers %d: bytes read by each prefix %s" % (hdr["layers"], hdr["layer_bytes"]))
+            hdr = hdr["base"]
+        elif "base" in hdr:
             print("near %d: base %d bytes, residual %d bytes" % (hdr["near"], hdr["base_bytes"], hdr["residual_bytes"]))
             hdr = hdr["base"]
         if hdr["step"] != 1.0:
@@ -260,6 +282,8 @@ def main(argv=None):
         with open(a.src, "rb") as f:
             blob = f.read()
         kw = {"refine": False} if a.base_only else {}
+        if a.layers is not None:
+            kw["layers"] = a.layers
         inner = codec.read_header(blob)["inner"] if blob[:4] == codec.MAPPED_MAGIC else codec.read_header(blob)
         tiled = "ny" in inner.get("base", inner)
         region = None
