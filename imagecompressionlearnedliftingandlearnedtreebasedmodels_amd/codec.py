@@ -151,6 +151,19 @@ cuts a container to a prefix.  Layered container, version 1:
 reaches are refined, finer levels' streams are never touched) and excludes ``near``, ``step_map``, ``overlap > 0`` and the three
 targets; ``layers=None`` and ``layers=0`` write the containers above byte for byte.
 
+Chroma formats (``encode_images(..., chroma="420" | "400")``, the same on ``encode_tiled``): "420" codes Y at
+full size and Cb, Cr at half size -- 1.5 planes of coefficients instead of 3; "400" codes a (B,H,W,1) greyscale image as one
+plane.  With pd = lifting_dwt_nets.padded_dims, a 4:2:0 image (or tile share) of H x W codes chroma planes of (Hc, Wc) =
+pd(ceil(H / 2), ceil(W / 2)) and a luma plane of (2 Hc, 2 Wc) (``chroma_sizes``).  A chroma sample is ((c00 + c01) + (c10 +
+c11)) * 0.25 over its 2 x 2 pixels; the decoder interpolates with the weights 3/4 and 1/4 toward the nearer and the farther
+sample, clamped at the tile's own plane (csrc/chroma.hip; tests/chroma_ref.py states both in torch).  Plane p is coded by the
+net's plane p alone, so its streams are those of ``encode_strings_planes([nets[p]], x_p)``.  The format is one more key of the
+arithmetic string, ``chroma=420`` or ``chroma=400``, absent for "444": ``chroma=None`` and ``"444"`` write the containers above
+byte for byte, there is no new container type, the stream count is 3 (L + 1) for 4:2:0 and L + 1 for 4:0:0, and a parsed
+header holds ``chroma`` only when the key is present (readers use ``hdr.get("chroma", "444")``).  Composes with ``coder``,
+``step``, ``target_bytes``, ``rdo``, tiles, ``region``, ``tiles_per_call`` and ``reduce``; excludes ``near``, ``layers``,
+``step_map``, ``overlap > 0`` and the quality targets, and LLDR / LLDQ / LLDP / LLDO containers over such a base are refused.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -285,6 +298,48 @@ def _with_qmap(arith, crc):
     return ",".join(sorted((arith.split(",") if arith else []) + ["qmap=%08x" % (crc & 0xFFFFFFFF)]))
 
 
+# chroma formats: the API's names -> planes coded; the arithmetic string's "chroma" key holds the name and is
+# absent for "444"
+CHROMA_PLANES = {"444": 3, "420": 3, "400": 1}
+
+
+def check_chroma(chroma):
+    """The chroma argument of the API -> "444", "420" or "400" (None -> "444").  ValueError naming chroma otherwise."""
+    if chroma is None:
+        return "444"
+    if not isinstance(chroma, str) or chroma not in CHROMA_PLANES:
+        raise ValueError("chroma must be one of %s (got %r)" % (", ".join('"%s"' % c for c in sorted(CHROMA_PLANES, reverse=True)),
+                                                                 chroma))
+    return chroma
+
+
+def _split_chroma(arith):
+    """arithmetic string -> (chroma format, the string without the chroma key); "444" when the key is absent.  ValueError naming
+    chroma if the key occurs twice or its value is not 420 or 400 (4:4:4 is written by leaving the key out)."""
+    parts = arith.split(",") if arith else []
+    vals = [p[len("chroma="):] for p in parts if p.startswith("chroma=")]
+    if not vals:
+        return "444", arith
+    if len(vals) != 1 or vals[0] not in ("420", "400"):
+        raise ValueError("chroma: unknown chroma format %r in the arithmetic string (this decoder reads 420 and 400, once; 4:4:4 "
+                         "has no key)" % ",".join(vals))
+    return vals[0], ",".join(p for p in parts if not p.startswith("chroma="))
+
+
+def _with_chroma(arith, chroma):
+    """The arithmetic string (without a chroma key) with the key of the format merged in at its sorted place; "444": unchanged."""
+    if check_chroma(chroma) == "444":
+        return arith
+    return ",".join(sorted((arith.split(",") if arith else []) + ["chroma=%s" % chroma]))
+
+
+def _no_chroma(bh, what):
+    """Refuses a base header that carries a chroma key under a wrapper or lapped container (``what`` names it and the argument
+    it stands for): those layers have no 4:2:0 / 4:0:0 form."""
+    if "chroma" in bh:
+        raise ValueError("chroma: the base container is coded with chroma=%s, which does not compose with %s" % (bh["chroma"], what))
+
+
 def _blocks(v, L):
     """ceil(v / 2^L): blocks of a step map along a side of v pixels."""
     return -(-int(v) >> L)
@@ -360,6 +415,7 @@ def pack_mapped(map_n, inner):
     if _magic(inner) not in (MAGIC, TILED_MAGIC, LAPPED_MAGIC, REFINED_MAGIC):
         raise ValueError("inner container: a step map goes over an LLDW, LLDT, LLDO or LLDR container")
     bh = _base_header(read_header(inner))
+    _no_chroma(bh, "a step map (step_map)")
     L, hb, wb = bh["dwtlevels"], a.shape[0], a.shape[1]
     if (hb, wb) != (_blocks(bh["H"], L), _blocks(bh["W"], L)) or hb > 0xFFFF or wb > 0xFFFF:
         raise ValueError("hb, wb: a %d x %d map for an inner container of %d x %d pixels at %d levels" % (hb, wb, bh["H"], bh["W"], L))
@@ -434,6 +490,7 @@ def parse_mapped(blob):
         raise ValueError("inner container: a step map goes over an LLDW, LLDT, LLDO or LLDR container (got magic %r)" % inner[:4])
     ih = parse_refined(inner, check_tables=False)[0] if _magic(inner) == REFINED_MAGIC else _parse_base(_magic(inner), inner)[0]
     bh = _base_header(ih)
+    _no_chroma(bh, "a step map (step_map)")
     if block != bh["dwtlevels"]:
         raise ValueError("block log2: the container holds %d, the inner container has dwtlevels %d" % (block, bh["dwtlevels"]))
     if block < 2:
@@ -597,14 +654,19 @@ def _check_overlap(L, th, tw, ov):
                          % (ov, th, tw))
 
 
-def _check_grid(nettype, L, H, W, th, tw, ny, nx, ov=None):
+def _check_grid(nettype, L, H, W, th, tw, ny, nx, ov=None, chroma="444"):
     """The grid fields of an LLDT (ov = None) or LLDO header against the image size and the transform (ValueError naming
     the field): the overlap rule of a lapped grid, then along each axis of n tiles of t at the stride s = t - ov (s = t for
-    LLDT): (n - 1) s + t >= size, and for n >= 2 the last tile is needed, (n - 2) s + t < size."""
+    LLDT): (n - 1) s + t >= size, and for n >= 2 the last tile is needed, (n - 2) s + t < size.  chroma "420": the half of the
+    tile, its chroma plane, must be a size the transform accepts (chroma_sizes)."""
     from .graphs.layers.lifting_dwt_nets import padded_dims
     if th < 1 or tw < 1 or ny < 1 or nx < 1:
         raise ValueError("tile grid: th, tw, ny, nx must be positive (got %d, %d, %d, %d)" % (th, tw, ny, nx))
-    if padded_dims(L, nettype == "CDF97", th, tw) != (th, tw):
+    if chroma == "420":
+        if th % 2 or tw % 2 or padded_dims(L, nettype == "CDF97", th // 2, tw // 2) != (th // 2, tw // 2):
+            raise ValueError("tile size: the chroma plane of a %d x %d tile with chroma=420, %g x %g, is not a size the %s "
+                             "transform at %d levels accepts" % (th, tw, th / 2, tw / 2, nettype, L))
+    elif padded_dims(L, nettype == "CDF97", th, tw) != (th, tw):
         raise ValueError("tile size: %d x %d is not a size the %s transform at %d levels accepts" % (th, tw, nettype, L))
     if ov is not None:
         _check_overlap(L, th, tw, ov)
@@ -628,12 +690,15 @@ def _pack_base(magic, hdr, units):
     the parser refuses a count other than 3 (L + 1)), ny * nx of 3 (L + 1) streams in raster order of (ty, tx) otherwise."""
     version, fixed = _BASE[magic]
     L, grid = hdr["dwtlevels"], ()
+    chroma = _split_chroma(hdr["arithmetic"])[0]
     if magic == MAGIC:
         count = len(units[0])
     else:
-        count = _PLANES * (L + 1)
+        count = CHROMA_PLANES[chroma] * (L + 1)
         grid = (hdr["th"], hdr["tw"], hdr["ny"], hdr["nx"]) + ((hdr["overlap"],) if magic == LAPPED_MAGIC else ())
-        _check_grid(hdr["netType"], L, hdr["H"], hdr["W"], *grid)
+        if magic == LAPPED_MAGIC and chroma != "444":
+            raise ValueError("chroma: chroma=%s does not compose with lapped tiles (overlap)" % chroma)
+        _check_grid(hdr["netType"], L, hdr["H"], hdr["W"], *grid, chroma=chroma)
         if hdr["ny"] > 0xFFFF or hdr["nx"] > 0xFFFF:
             raise ValueError("tile grid: ny, nx must fit 16 bits")
         if len(units) != hdr["ny"] * hdr["nx"] or any(len(u) != count for u in units):
@@ -655,12 +720,17 @@ def _parse_base(magic, blob):
     blob, end = _open(blob, magic, version, fixed.size + 1 + 16 + 1)
     _, _, layer, nettype, L, H, W, *grid, numerics = fixed.unpack_from(blob, 0)
     _check_model_fields(layer, nettype, L, H, W)
-    if grid:
-        _check_grid(_NETTYPE_NAMES[nettype], L, H, W, *grid)
     arith, digest, count, pos = _parse_identity(blob, fixed.size, end)
-    if count != _PLANES * (L + 1):
-        raise ValueError("stream count %d%s does not match dwtlevels %d (expected %d)"
-                         % (count, " per tile" if grid else "", L, _PLANES * (L + 1)))
+    chroma, _ = _split_chroma(arith)
+    if magic == LAPPED_MAGIC and chroma != "444":
+        raise ValueError("chroma: the container is coded with chroma=%s, which does not compose with lapped tiles (overlap)"
+                         % chroma)
+    if grid:
+        _check_grid(_NETTYPE_NAMES[nettype], L, H, W, *grid, chroma=chroma)
+    if count != CHROMA_PLANES[chroma] * (L + 1):
+        raise ValueError("stream count %d%s does not match dwtlevels %d%s (expected %d)"
+                         % (count, " per tile" if grid else "", L, "" if chroma == "444" else " with chroma=%s" % chroma,
+                            CHROMA_PLANES[chroma] * (L + 1)))
     coder, _ = _split_coder(arith)
     step_n, _ = _split_step(arith)
     n = grid[2] * grid[3] if grid else 1
@@ -668,6 +738,8 @@ def _parse_base(magic, blob):
     hdr = dict(version=version, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
                numerics=numerics, arithmetic=arith, coder=coder, step=step_n / STEP_DENOM, digest=digest,
                stream_lengths=lengths, header_bytes=end - sum(lengths))
+    if chroma != "444":                               # only with the key: a key-less header is what it was
+        hdr["chroma"] = chroma
     if grid:
         hdr.update(th=grid[0], tw=grid[1], ny=grid[2], nx=grid[3], overlap=grid[4] if magic == LAPPED_MAGIC else 0,
                    streams_per_tile=count)
@@ -717,6 +789,7 @@ def pack_refined(near, table_crc, base, units):
     if _magic(base) not in (MAGIC, TILED_MAGIC):
         raise ValueError("base container: a residual layer goes over an LLDW or LLDT container")
     bh = read_header(base)
+    _no_chroma(bh, "a residual layer (near)")
     if len(units) != bh.get("ny", 1) * bh.get("nx", 1):
         raise ValueError("unit count: %d units for a base of %d" % (len(units), bh.get("ny", 1) * bh.get("nx", 1)))
     body = bytearray(_RFIXED.pack(REFINED_MAGIC, REFINED_FORMAT_VERSION, int(near), CLASSES, LADDER_ID,
@@ -759,6 +832,7 @@ def parse_refined(blob, check_tables=True):
     if _magic(base) not in (MAGIC, TILED_MAGIC):
         raise ValueError("base container: a residual layer goes over an LLDW or LLDT container (got magic %r)" % base[:4])
     bh = read_header(base)
+    _no_chroma(bh, "a residual layer (near)")
     pos += blen
     count = struct.unpack_from("<I", blob, pos)[0]
     pos += 4
@@ -811,6 +885,7 @@ def pack_layered(table_crc, base, layers):
     if _magic(base) not in (MAGIC, TILED_MAGIC):
         raise ValueError("base container: quality layers go over an LLDW or LLDT container")
     bh = read_header(base)
+    _no_chroma(bh, "quality layers (layers)")
     m = len(layers)
     _check_layered_base(bh, m)
     units, per = bh.get("ny", 1) * bh.get("nx", 1), _PLANES * (bh["dwtlevels"] - 1)
@@ -845,6 +920,7 @@ def parse_layered(blob, check_tables=True):
     if _magic(base) not in (MAGIC, TILED_MAGIC):
         raise ValueError("base container: quality layers go over an LLDW or LLDT container (got magic %r)" % base[:4])
     bh = read_header(base)
+    _no_chroma(bh, "quality layers (layers)")
     _check_layered_base(bh, m)
     pos += blen
     base_end = pos
@@ -924,11 +1000,12 @@ def reduce_bytes(hdr):
 
 
 # ------------------------------------------------------------------------------------------------ model identity
-def arithmetic_string(coder="host", step=None, qmap=None):
+def arithmetic_string(coder="host", step=None, qmap=None, chroma=None):
     """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path, plus the
     entropy coder: ``coder=irans32`` for coder="gpu", no key for the host coder (so the host string is unchanged), plus the
     quantisation step: ``step=<n>`` for step = n / 16 other than 1, no key for None or 1; or, for a step map,
-    ``qmap=<8 hex digits>`` of its CRC (qmap: the CRC as an int), which excludes a step.
+    ``qmap=<8 hex digits>`` of its CRC (qmap: the CRC as an int), which excludes a step; plus the chroma format:
+    ``chroma=420`` or ``chroma=400``, no key for None or "444" (DESIGN.md 7.1.11).
     Which reach which layer (the others are carried along, harmlessly):
       plc_mode, plc_fuse, plc_algo, plc_shape, storage -- the tree-context pair: conditioned2ZTsepSubbands, onlyEZWT;
       precision -- the split-fp16 pair and cgp chain (conditioned2ZTsepSubbands, onlyEZWT) and the lifting steps (all);
@@ -944,14 +1021,15 @@ def arithmetic_string(coder="host", step=None, qmap=None):
         kv.append(("coder", CODER_KEYS[coder]))
     if qmap is not None and check_step(step) != STEP_DENOM:
         raise ValueError("step and step_map: give one of them (the map holds every step)")
-    return _with_qmap(_with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step)), qmap)
+    return _with_chroma(_with_qmap(_with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step)), qmap), chroma)
 
 
 def _batch_invariant(arith):
     """True when the coding path is per image in this arithmetic, so images can be coded together.  Not so when the
     non-fused split-fp16 pair takes its operand scale from an absmax over the whole batch (plc_fuse=0), or with fp16
     storage (a bound over the batch's parents); the one-product precisions are not verified.  Otherwise: one image per call."""
-    arith = _split_qmap(_split_step(_split_coder(arith)[1])[1])[1]   # neither the coder nor the step(s) change what a batch shares
+    # neither the coder nor the step(s) nor the chroma format change what a batch shares
+    arith = _split_chroma(_split_qmap(_split_step(_split_coder(arith)[1])[1])[1])[1]
     d = dict(p.split("=") for p in arith.split(","))
     if d["precision"] != "f16x3" or d["storage"] != "fp32":
         return False
@@ -1021,11 +1099,12 @@ def describe(net):
 
 
 # ------------------------------------------------------------------------------------------------ public API
-def _check_images(images_u8):
+def _check_images(images_u8, chroma="444"):
     import torch
+    ch = 1 if chroma == "400" else 3
     if not (isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
-            and images_u8.shape[3] == 3):
-        raise ValueError("images must be a (B,H,W,3) uint8 tensor")
+            and images_u8.shape[3] == ch):
+        raise ValueError("images must be a (B,H,W,%d) uint8 tensor%s" % (ch, "" if chroma == "444" else " with chroma=%s" % chroma))
     B, H, W, _ = images_u8.shape
     if B < 1 or H < 1 or W < 1 or H >= 1 << 32 or W >= 1 << 32:
         raise ValueError("bad image batch shape %s" % (tuple(images_u8.shape),))
@@ -1111,6 +1190,22 @@ def _layer_args(layers, step, L, near=None, step_map=None, overlap=0, target_byt
                          "%d)" % L)
     check_step_divides(check_step(step), m)
     return m
+
+
+def _chroma_args(chroma, near=None, layers=None, step_map=None, overlap=0, target_psnr=None, target_msssim=None):
+    """The chroma argument of encode_images / encode_tiled, checked on the host before everything else -> "444", "420" or "400".
+    ValueError naming chroma and the other argument for what a chroma format does not compose with: each of
+    near, layers, step_map, overlap > 0, target_psnr and target_msssim needs a 4:2:0 form of its own kernel."""
+    ch = check_chroma(chroma)
+    if ch == "444":
+        return ch
+    for name, val in (("near", near), ("layers", layers), ("step_map", step_map), ("target_psnr", target_psnr),
+                      ("target_msssim", target_msssim)):
+        if val is not None and not (name == "layers" and not isinstance(val, bool) and val == 0):
+            raise ValueError("chroma and %s: chroma=%s does not compose with %s; use chroma=\"444\"" % (name, ch, name))
+    if overlap:
+        raise ValueError("chroma and overlap: chroma=%s over lapped tiles (overlap > 0) is not defined; use overlap=0" % ch)
+    return ch
 
 
 def _rate_args(step, target_bytes, near, L):
@@ -1314,7 +1409,7 @@ def _estimated_size(empty, estimates):
 
 
 def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None,
-                  layers=None, target_psnr=None, target_msssim=None):
+                  layers=None, chroma="444", target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -1339,10 +1434,15 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     ValueError naming the target and the best achievable value if the finest step misses it.
     layers = m in 1..4: LLDP containers holding the container of the other arguments byte for byte plus m
     quality layers, layer j refining the levels 0 .. L-2 to the step q / 3^j; decode_images(..., layers=j) decodes any prefix.
-    With coder, step (n / 3^m >= 1) and rdo; not with near, step_map or a target.  None and 0 write the bytes above."""
+    With coder, step (n / 3^m >= 1) and rdo; not with near, step_map or a target.  None and 0 write the bytes above.
+    chroma: "444" (the default) codes three full-size planes and writes the bytes above; "420" codes Y at full
+    and Cb, Cr at half size (the chroma is averaged over 2 x 2 pixels and interpolated back on decoding); "400" takes a
+    (B,H,W,1) greyscale tensor and codes one plane.  The format is one more key of the arithmetic string and the decoders read
+    it from the header.  With coder, step, target_bytes and rdo; not with near, layers, step_map or a quality target."""
     from .graphs.layers.lifting_dwt_nets import padded_size
+    ch = _chroma_args(chroma, near, layers, step_map, 0, target_psnr, target_msssim)
     layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8)
+    B, H, W = _check_images(images_u8, ch)
     m = _layer_args(layers, step, L, near, step_map, 0, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
@@ -1351,20 +1451,24 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     maps = _map_arg(step_map, step, target_bytes, B, H, W, L)
     n, T = _rate_args(step, target_bytes, near, L)
     rdo = _rdo_arg(rdo, L)
-    Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m)
+    if ch == "444":
+        Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
+    else:
+        Hp, Wp, _, _ = chroma_sizes(L, nettype == "CDF97", H, W, ch)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m, ch)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0):
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0, chroma="444"):
     """_encode at the step step_n / 16, or with a byte target T the search of _search_step, or with a quality target (the
     pair of _quality_args) that of _encode_at_quality, one image at a time.  walk: the (magic, grid, group, coder) of _encode.
-    rdo: probes and real encodes alike.  layers: the number of quality layers (_layer_args: no target then)."""
+    rdo: probes and real encodes alike.  layers: the number of quality layers (_layer_args: no target then).  chroma: the
+    format of _chroma_args (not "444": no near, maps, quality target or layers)."""
     if target is not None:
         return _encode_at_quality(net, images_u8, walk, rdo, target)
     if T is None:
-        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps, layers=layers)
-    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo)[0],
-                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo)[0], T)
+        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps, layers=layers, chroma=chroma)
+    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo, chroma=chroma)[0],
+                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo, chroma=chroma)[0], T)
             for b in range(images_u8.shape[0])]
 
 
@@ -1461,7 +1565,24 @@ def _gather_layers(units, k, L):
             for jj in range(len(units[0]))]
 
 
-def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None, layers=0):
+def _encode_chroma_planes(nets, img, chroma, grid, first, n, **kw):
+    """One group of tiles of a 4:2:0 or 4:0:0 encode -> (s_xe, s_xo) with one entry per coded plane, as
+    encode_strings_planes gives them for three planes.  Luma goes through nets[0:1] at (th, tw); Cb and Cr share one two-plane
+    call through nets[1:3] at (th / 2, tw / 2).  The coding path is per plane, so a plane's streams are those of coding it
+    alone, encode_strings_planes([nets[p]], x_p, ...) (tests/test_gpu_codec_chroma.py holds them to that).  kw: coder, step, rdo."""
+    from . import ops
+    from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
+    th, tw, ny, nx, _ = grid
+    if chroma == "400":
+        return encode_strings_planes(nets[0:1], ops.u8hw_to_y_tiles(img, th, tw, ny, nx, first, n), **kw)[:2]
+    luma, chr2 = ops.u8hwc_to_ycc420_tiles(img, th, tw, ny, nx, first, n)
+    y_xe, y_xo = encode_strings_planes(nets[0:1], luma, **kw)[:2]
+    c_xe, c_xo = encode_strings_planes(nets[1:3], chr2, **kw)[:2]
+    return list(y_xe) + list(c_xe), [list(a) + list(b) for a, b in zip(y_xo, c_xo)]
+
+
+def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None, layers=0,
+            chroma="444"):
     """The encode walk behind encode_images and encode_tiled (arguments checked there): the batch is cut into the tiles of
     grid = (th, tw, ny, nx, ov) -- the untiled codec is the 1 x 1 grid of one padded_size tile, which the untiled input and
     output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
@@ -1471,17 +1592,20 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     maps: the (B, hb, wb) array of _map_arg (None: the step alone): every unit is coded with its slice of its image's map
     (_unit_maps), every base carries the qmap key of its image's map, and the result is wrapped into LLDQ (pack_mapped).
     layers: m > 0 quality layers (without near, maps or estimate): every group's layer streams are coded right
-    after its base, from the group's own tensors, and the containers are wrapped into LLDP (pack_layered)."""
+    after its base, from the group's own tensors, and the containers are wrapped into LLDP (pack_layered).
+    chroma: "420" / "400" (without near, maps, layers or overlap): the same walk, each group cut and coded
+    plane by plane (_encode_chroma_planes), the streams interleaved into the LLDW order, the header carrying the chroma key."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
     from .graphs.models.entropy_coding import ESTIMATE
     layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8)
+    B, H, W = _check_images(images_u8, chroma)
     th, tw, ny, nx, ov = grid
     nets = net.nets()
     step = step_n / STEP_DENOM
-    arith = arithmetic_string(coder, step)
+    arith = arithmetic_string(coder, step, chroma=chroma)
+    planes = CHROMA_PLANES[chroma]
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov,
                numerics=CODING_NUMERICS_VERSION, arithmetic=arith, digest=weights_digest(net))
@@ -1489,13 +1613,18 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     hdrs = [hdr if maps is None else dict(hdr, arithmetic=_with_qmap(arith, map_crc(maps[b]))) for b in range(B)]
     dev = next(net.parameters()).device
     img = images_u8.to(dev).contiguous()
-    per, count = ny * nx, _PLANES * (L + 1)
+    per, count = ny * nx, planes * (L + 1)
     g = group if _batch_invariant(arith) else 1
     tiles, unit_layers = [], []
     xh = torch.empty_like(img) if near is not None else None
     with torch.no_grad():
         for first in range(0, B * per, g):
             n = min(g, B * per - first)
+            if chroma != "444":
+                s_xe, s_xo = _encode_chroma_planes(nets, img, chroma, grid, first, n, coder=ESTIMATE if estimate else coder,
+                                                   step=step, rdo=rdo)
+                tiles += [_tile_streams(s_xe, s_xo, j, planes) for j in range(n)]
+                continue
             if ov:
                 x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
             else:
@@ -1534,6 +1663,7 @@ def check_header(hdr, layer, nettype, L, digest, arith, qmap=None):
     set aside only when it equals that CRC: a base coded with a step map cannot be decoded without the map."""
     _, hdr_arith = _split_coder(hdr["arithmetic"])
     _, hdr_arith = _split_step(hdr_arith)
+    _, hdr_arith = _split_chroma(hdr_arith)             # the chroma format selects planes and sizes, not arithmetic
     key, hdr_arith = _split_qmap(hdr_arith)
     if key != qmap:
         if qmap is None:
@@ -1599,7 +1729,9 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
     An LLDP container over LLDW is decoded through its base plus its first ``layers`` quality layers (None:
     all it holds; 0: exactly the base decode); with reduce = k the levels k .. L-2 are refined and the streams of finer levels
     are never touched.  ``layers`` above a container's count, or other than None / 0 for a container without layers, is a
-    ValueError."""
+    ValueError.
+    A container coded with chroma="420" decodes to (H,W,3), one coded with chroma="400" to (H,W,1); the
+    format comes from the header, containers are grouped by it as well, and a mix comes back in input order."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
@@ -1639,14 +1771,24 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
     dev = next(net.parameters()).device
     by_size = {}
     for i, (hdr, _) in enumerate(parsed):
-        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"], i in maps, len(layered.get(i, ()))), []).append(i)
+        by_size.setdefault((hdr["H"], hdr["W"], hdr["coder"], hdr["step"], i in maps, len(layered.get(i, ())),
+                            hdr.get("chroma", "444")), []).append(i)
     out = [None] * len(parsed)
     with torch.no_grad():
         if k:
             inv_a, b = ll_norm(net, k)
-        for (H, W, coder, step, mapped, nlay), idx in by_size.items():
-            Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
+        for (H, W, coder, step, mapped, nlay, chroma), idx in by_size.items():
             units = [parsed[i][1] for i in idx]
+            if chroma != "444":                       # the 1 x 1 grid of the format's padded size
+                Hp, Wp, _, _ = chroma_sizes(L, nettype == "CDF97", H, W, chroma)
+                Hr, Wr = _reduced(H, k), _reduced(W, k)
+                for a, n, res in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k):
+                    img = _write_chroma(chroma, res, (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr), (inv_a, b) if k else None,
+                                        B=n).cpu()
+                    for j, i in enumerate(idx[a:a + n]):
+                        out[i] = img[j]
+                continue
+            Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             um = _unit_maps([maps[i] for i in idx], range(len(idx)), (Hp, Wp, 1, 1, 0), L, dev) if mapped else None
             ul = [layered[i] for i in idx] if nlay else None
             for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um, ul):
@@ -1678,6 +1820,28 @@ def tile_grid(nets, H, W, tile=512):
         raise ValueError("tile grid: tile, H and W must be positive (got %d, %d, %d)" % (tile, H, W))
     nx, ny = -(-W // tile), -(-H // tile)
     th, tw = padded_size(nets, -(-H // ny), -(-W // nx))
+    return th, tw, -(-H // th), -(-W // tw)
+
+
+def chroma_sizes(L, cdf97, H, W, chroma="444", tile=None):
+    """The coded sizes of an H x W image in a chroma format -> (th, tw, ny, nx): the luma (or only) plane of
+    a tile and the grid; tile=None is the untiled codec, the 1 x 1 grid of one padded image.  L, cdf97: the level count and the
+    transform kind (padded_dims).  With share = (ceil(H / ny0), ceil(W / nx0)) for the counts ny0 = ceil(H / tile), nx0 =
+    ceil(W / tile) of the target tile side (the image itself when untiled): "444" and "400" code planes of padded_dims(share),
+    as tile_grid; "420" codes chroma planes of (Hc, Wc) = padded_dims(ceil(share / 2)) and a luma plane of (2 Hc, 2 Wc), so both
+    are sizes the transform accepts.  The grid is recounted with the tile size, as tile_grid does."""
+    from .graphs.layers.lifting_dwt_nets import padded_dims
+    ch = check_chroma(chroma)
+    if H < 1 or W < 1 or (tile is not None and int(tile) < 1):
+        raise ValueError("tile grid: tile, H and W must be positive (got %r, %d, %d)" % (tile, H, W))
+    sh, sw = (H, W) if tile is None else (-(-H // -(-H // int(tile))), -(-W // -(-W // int(tile))))
+    if ch == "420":
+        hc, wc = padded_dims(L, cdf97, -(-sh // 2), -(-sw // 2))
+        th, tw = 2 * hc, 2 * wc
+    else:
+        th, tw = padded_dims(L, cdf97, sh, sw)
+    if tile is None:
+        return th, tw, 1, 1
     return th, tw, -(-H // th), -(-W // tw)
 
 
@@ -1722,13 +1886,13 @@ def tile_grid_lapped(nets, H, W, tile=512, overlap=0):
     return th, tw, count(H, th), count(W, tw)
 
 
-def _tile_streams(s_xe, s_xo, j):
-    """The 3 (L + 1) streams of image j of an encode_strings_planes result, in the LLDW order."""
-    return [s for p in range(_PLANES) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
+def _tile_streams(s_xe, s_xo, j, planes=_PLANES):
+    """The planes * (L + 1) streams of image j of an encode_strings_planes result, in the LLDW order."""
+    return [s for p in range(planes) for s in [s_xe[p][j]] + [lev[p][j] for lev in s_xo]]
 
 
 def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
-                 rdo=None, step_map=None, layers=None, target_psnr=None, target_msssim=None):
+                 rdo=None, step_map=None, layers=None, chroma="444", target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -1746,9 +1910,12 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     for the frame: the tiles' in-image rectangles, or with overlap > 0 the blended frame.  The result does
     not depend on tiles_per_call.
     layers: as encode_images, every tile being a unit with its own layer streams (LLDP over LLDT; not with overlap > 0), so a
-    region decodes the refinement of the tiles it touches only."""
+    region decodes the refinement of the tiles it touches only.
+    chroma: as encode_images; with "420" the tile grid is that of chroma_sizes (the half of a tile is a size the transform
+    accepts) and every tile's streams are those of encode_images(net, tile, chroma="420"); not with overlap > 0."""
+    ch = _chroma_args(chroma, near, layers, step_map, overlap, target_psnr, target_msssim)
     layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8)
+    B, H, W = _check_images(images_u8, ch)
     m = _layer_args(layers, step, L, near, step_map, overlap, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
@@ -1763,11 +1930,14 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     ov = int(overlap)
     if ov != overlap or ov < 0 or ov > 0xFFFF:
         raise ValueError("overlap must be an integer in [0, 65535] (got %r)" % (overlap,))
-    th, tw, ny, nx = tile_grid_lapped([m.autoencoder for m in net.nets()], H, W, int(tile), ov)
+    if ch == "444":
+        th, tw, ny, nx = tile_grid_lapped([m.autoencoder for m in net.nets()], H, W, int(tile), ov)
+    else:
+        th, tw, ny, nx = chroma_sizes(L, nettype == "CDF97", H, W, ch, int(tile))
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m, ch)
 
 
 def _tiles_per_call(tiles_per_call):
@@ -1786,13 +1956,23 @@ def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step
     return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, step=step, **kw)
 
 
-def _gather(units, k, L):
+def _gather(units, k, L, planes=_PLANES):
     """The stream lists of a group of units (images or tiles, each in the LLDW order) -> (s_xe, s_xo) as
     decode_strings_planes takes them at first_level = k: the xe streams and the xo streams of the levels k .. L-1."""
     per = L + 1                                       # streams per plane: xe, xo finest -> coarsest
-    s_xe = [[u[p * per] for u in units] for p in range(_PLANES)]
-    s_xo = [[[u[p * per + 1 + lev] for u in units] for p in range(_PLANES)] for lev in range(k, L)]
+    s_xe = [[u[p * per] for u in units] for p in range(planes)]
+    s_xo = [[[u[p * per + 1 + lev] for u in units] for p in range(planes)] for lev in range(k, L)]
     return s_xe, s_xo
+
+
+def _write_chroma(chroma, res, grid, region, affine=None, **kw):
+    """The output step of a 4:2:0 / 4:0:0 decode: res, what _decode_groups yields for the format -- (luma,
+    chroma planes) or the single plane -- -> the uint8 pixels of ops.ycc420_tiles_to_u8hwc / ops.y_tiles_to_u8hw.  affine: None,
+    or the (inv_a, b) of ll_norm at reduce > 0 (three values each; 4:0:0 takes plane 0's)."""
+    from . import ops
+    if chroma == "420":
+        return ops.ycc420_tiles_to_u8hwc(res[0], res[1], grid, region, affine=affine, **kw)
+    return ops.y_tiles_to_u8hw(res, grid, region, affine=None if affine is None else (affine[0][:1], affine[1][:1]), **kw)
 
 
 def _layers_arg(layers, m):
@@ -1815,8 +1995,21 @@ def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None, layers=None):
     7.1.10): each group's levels k .. L-2 are refined with its own streams before the inverse transform."""
     g = group if _batch_invariant(hdr["arithmetic"]) else 1
     L = hdr["dwtlevels"]
+    chroma = hdr.get("chroma", "444")
     for a in range(0, len(units), g):
         grp = units[a:a + g]
+        if chroma != "444":
+            # DESIGN.md 7.1.11: luma through nets[0:1] at the tile size (th, tw), Cb and Cr in one call through nets[1:3] at half
+            # of it, as the encoder coded them.  4:2:0 -> (luma (1,n,1,th>>k,tw>>k), chroma (2,n,1,th>>(k+1),tw>>(k+1))); 4:0:0 ->
+            # the plane.
+            s_xe, s_xo = _gather(grp, k, L, CHROMA_PLANES[chroma])
+            kw = dict(coder=hdr["coder"], first_level=k, step=hdr["step"])
+            res = _decode_tiles(nets[0:1], s_xe[0:1], [lev[0:1] for lev in s_xo], th, tw, len(grp), **kw).contiguous()
+            if chroma == "420":
+                res = (res, _decode_tiles(nets[1:3], s_xe[1:3], [lev[1:3] for lev in s_xo], th // 2, tw // 2, len(grp),
+                                          **kw).contiguous())
+            yield a, len(grp), res
+            continue
         s_xe, s_xo = _gather(grp, k, L)
         kw = {}
         if layers is not None:
@@ -1851,6 +2044,8 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     rectangles; refine=False, or reduce > 0, gives exactly the base decode.
     LLDP over LLDT: the touched tiles are decoded with their first ``layers`` quality layers (None: all, 0: the
     base decode), as decode_images; only those tiles' layer streams are read.
+    A container coded with chroma="420" / "400"  decodes to (h, w, 3) / (h, w, 1); the chroma of a tile is
+    upsampled from that tile alone, so a region still touches only the tiles it intersects.
     Every check (container, region, identity) runs on the host before any GPU work."""
     import torch
     from . import ops
@@ -1875,7 +2070,7 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
         if not refine or k:
             units = None
     hdr, tiles = _parse_base(LAPPED_MAGIC if _magic(blob) == LAPPED_MAGIC else TILED_MAGIC, blob)
-    ny, nx = hdr["ny"], hdr["nx"]
+    ny, nx, chroma = hdr["ny"], hdr["nx"], hdr.get("chroma", "444")
     # at reduce = k the tile side, the stride and the overlap are all shifted by k (they are multiples of 2^L)
     H, W, th, tw, ov = _reduced(hdr["H"], k), _reduced(hdr["W"], k), hdr["th"] >> k, hdr["tw"] >> k, hdr["overlap"] >> k
     y0, x0, h, w = _region(region, H, W)
@@ -1906,10 +2101,13 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
         if ov:
             acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
         else:
-            out = torch.empty(1, h, w, 3, device=dev, dtype=torch.uint8)
+            out = torch.empty(1, h, w, 1 if chroma == "400" else 3, device=dev, dtype=torch.uint8)
         ul = None if lay is None else [[lay[jj][t] for jj in range(len(lay))] for t in want]
         for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um, ul):
-            if ov:                   # lapped: the raw samples are blended, then written once as the tile of a 1 x 1 grid
+            if chroma != "444":      # the chroma is upsampled inside the tile, so no neighbour tile is needed
+                _write_chroma(chroma, xhat, (H, W, th, tw, ny, nx), (y0, x0, h, w), (inv_a, b) if k else None,
+                              tiles=want[a:a + n], out=out)
+            elif ov:                 # lapped: the raw samples are blended, then written once as the tile of a 1 x 1 grid
                 ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), want[a:a + n], acc)
             else:
                 write(xhat.contiguous(), (H, W, th, tw, ny, nx), (y0, x0, h, w), tiles=want[a:a + n], out=out)

@@ -275,6 +275,110 @@ def ycc_to_u8hwc_crop(y, H, W):
     return dst
 
 
+def u8hwc_to_ycc420_tiles(src, th, tw, ny, nx, first, n):
+    """u8hwc_to_ycc_tiles for 4:2:0: (B,H,W,3) uint8 RGB device tensor -> (luma (1,n,1,th,tw) with Y-0.5,
+    chroma (2,n,1,th/2,tw/2)) of the tiles first .. first+n-1; luma is bitwise plane 0 of u8hwc_to_ycc_tiles, a chroma sample
+    ((c00 + c01) + (c10 + c11)) * 0.25f over its 2 x 2 tile pixels (lldwt_u8hwc_to_ycc420_tiles).  th, tw even."""
+    who = "u8hwc_to_ycc420_tiles"
+    B, H, W = _u8hwc(src, who)
+    if n < 1 or th < 2 or tw < 2 or th % 2 or tw % 2:
+        raise _lib.LLDWTError("%s: n must be positive and th, tw even (got %r, %r, %r)" % (who, n, th, tw))
+    luma = torch.empty(1, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    chroma = torch.empty(2, n, 1, th // 2, tw // 2, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u8hwc_to_ycc420_tiles(C.c_void_p(src.data_ptr()), _chk(luma), _chk(chroma), B, H, W, th, tw, ny, nx,
+                                                  first, n, _stream()), who)
+    return luma, chroma
+
+
+def _tile_list(who, tiles, n, count, dev):
+    """The tile list argument of the chroma output wrappers -> (pointer, the device tensor that must outlive the call)."""
+    if tiles is None:
+        return C.c_void_p(0), None
+    if len(tiles) != n or any(t < 0 or t >= count for t in tiles):
+        raise _lib.LLDWTError("%s: need %d tile indexes in [0, %d)" % (who, n, count))
+    t = torch.tensor(list(tiles), dtype=torch.int32).to(dev)
+    return C.c_void_p(t.data_ptr()), t
+
+
+def _affine_arg(who, affine, count):
+    """affine = None or (inv_a, b) of ``count`` floats each -> two pointers (NULL, NULL for None) and their owners."""
+    if affine is None:
+        return C.c_void_p(0), C.c_void_p(0), None
+    if len(affine) != 2 or len(affine[0]) != count or len(affine[1]) != count:
+        raise _lib.LLDWTError("%s: inv_a and b need %d value(s) each" % (who, count))
+    ia = (C.c_float * count)(*[float(v) for v in affine[0]])
+    bb = (C.c_float * count)(*[float(v) for v in affine[1]])
+    return C.cast(ia, C.c_void_p), C.cast(bb, C.c_void_p), (ia, bb)
+
+
+def ycc420_tiles_to_u8hwc(luma, chroma, grid, region, affine=None, tiles=None, first=0, B=1, out=None):
+    """ycc_tiles_to_u8hwc for 4:2:0: luma (1,n,1,th,tw) and chroma (2,n,1,th/2,tw/2) decoded tiles -> the
+    uint8 RGB pixels of those tiles inside the image and the region, written into out (B,h,w,3) (allocated when None) and
+    returned; the chroma is upsampled in registers with the weights 3/4, 1/4 clamped at the tile's own plane.  grid, region,
+    tiles, first as ycc_tiles_to_u8hwc.  affine = (inv_a, b), 3 floats each: a reduced-resolution decode, every luma and chroma
+    sample of plane p becomes (s - b[p]) * inv_a[p] before the upsampling (lldwt_ycc420_tiles_to_u8hwc)."""
+    who = "ycc420_tiles_to_u8hwc"
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    if not (isinstance(luma, torch.Tensor) and luma.dim() == 5 and luma.shape[0] == 1 and luma.shape[2] == 1):
+        raise _lib.LLDWTError("%s: luma must be (1,n,1,th,tw)" % who)
+    n = luma.shape[1]
+    if tuple(luma.shape[3:]) != (th, tw) or th % 2 or tw % 2:
+        raise _lib.LLDWTError("%s: luma tiles are %d x %d, the grid says %d x %d (even sides)" % (who, luma.shape[3], luma.shape[4],
+                                                                                                  th, tw))
+    if not (isinstance(chroma, torch.Tensor) and tuple(chroma.shape) == (2, n, 1, th // 2, tw // 2)):
+        raise _lib.LLDWTError("%s: chroma must be (2,%d,1,%d,%d)" % (who, n, th // 2, tw // 2))
+    tptr, keep = _tile_list(who, tiles, n, B * ny * nx, luma.device)
+    ia, bb, keep_af = _affine_arg(who, affine, 3)
+    if out is None:
+        out = torch.empty(B, h, w, 3, device=luma.device, dtype=torch.uint8)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)):
+        raise _lib.LLDWTError("%s: out must be a contiguous (%d,%d,%d,3) uint8 device tensor" % (who, B, h, w))
+    check(_lib.load().lldwt_ycc420_tiles_to_u8hwc(_chk(luma, "luma"), _chk(chroma, "chroma"), tptr, first, n, B, H, W, th, tw, ny,
+                                                  nx, y0, x0, h, w, ia, bb, C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
+
+
+def u8hw_to_y_tiles(src, th, tw, ny, nx, first, n):
+    """u8hwc_to_ycc_tiles for greyscale (4:0:0): (B,H,W,1) uint8 device tensor -> (1,n,1,th,tw),
+    g / 255.0f - 0.5f, of the tiles first .. first+n-1, replicate-edge padded (lldwt_u8hw_to_y_tiles)."""
+    who = "u8hw_to_y_tiles"
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+            and src.dim() == 4 and src.shape[3] == 1):
+        raise _lib.LLDWTError("%s: expected a contiguous (B,H,W,1) uint8 device tensor" % who)
+    if n < 1 or th < 1 or tw < 1:
+        raise _lib.LLDWTError("%s: n, th, tw must be positive" % who)
+    B, H, W = src.shape[:3]
+    y = torch.empty(1, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u8hw_to_y_tiles(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, th, tw, ny, nx, first, n, _stream()),
+          who)
+    return y
+
+
+def y_tiles_to_u8hw(y, grid, region, affine=None, tiles=None, first=0, B=1, out=None):
+    """ycc_tiles_to_u8hwc for greyscale (4:0:0): y (1,n,1,th,tw) decoded tiles -> the uint8 pixels of those
+    tiles inside the image and the region, floor((clamp(s, -0.5, 0.5) + 0.5) * 255 + 0.5), written into out (B,h,w,1)
+    (allocated when None) and returned.  affine = (inv_a, b), 1 float each: s -> (s - b[0]) * inv_a[0] first, a reduced-resolution
+    decode (lldwt_y_tiles_to_u8hw)."""
+    who = "y_tiles_to_u8hw"
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    if not (isinstance(y, torch.Tensor) and y.dim() == 5 and y.shape[0] == 1 and y.shape[2] == 1):
+        raise _lib.LLDWTError("%s: y must be (1,n,1,th,tw)" % who)
+    n = y.shape[1]
+    if tuple(y.shape[3:]) != (th, tw):
+        raise _lib.LLDWTError("%s: tiles are %d x %d, the grid says %d x %d" % (who, y.shape[3], y.shape[4], th, tw))
+    tptr, keep = _tile_list(who, tiles, n, B * ny * nx, y.device)
+    ia, bb, keep_af = _affine_arg(who, affine, 1)
+    if out is None:
+        out = torch.empty(B, h, w, 1, device=y.device, dtype=torch.uint8)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 1)):
+        raise _lib.LLDWTError("%s: out must be a contiguous (%d,%d,%d,1) uint8 device tensor" % (who, B, h, w))
+    check(_lib.load().lldwt_y_tiles_to_u8hw(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, ia, bb,
+                                            C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
+
+
 RESID_MAX_NEAR = 32          # LLDWT_RESID_MAX_NEAR
 RESID_CONTEXTS = 24          # 3 channels x 8 activity classes
 

@@ -129,6 +129,32 @@ int lldwt_u8hwc_to_ycc_pad(const uint8_t* src, float* ycc, int64_t B, int64_t H,
                            void* stream);
 int lldwt_ycc_to_u8hwc_crop(const float* ycc, uint8_t* dst, int64_t B, int64_t H, int64_t W, int64_t Hp, int64_t Wp,
                             void* stream);
+/* Chroma formats 4:2:0 and 4:0:0 (codec.py chroma=; csrc/chroma.hip) on the plain tile grid above.  A 4:2:0
+ * tile is a luma plane (1,n,1,th,tw) and a chroma plane pair (2,n,1,th/2,tw/2) (Cb, Cr); th, tw even.  A 4:0:0 tile is one
+ * plane (1,n,1,th,tw) of a (B,H,W,1) uint8 image.  The limits of the 4:4:4 entry points hold (n, th <= 65535).
+ * lldwt_u8hwc_to_ycc420_tiles: the tiles first .. first+n-1 of src (B,H,W,3).  Per source pixel, coordinates clamped to the
+ *   image, Y-0.5, Cb, Cr are the values of lldwt_u8hwc_to_ycc_tiles; luma holds Y-0.5 (bitwise plane 0 of that entry point) and
+ *   chroma sample (i, j) of a tile is ((c00 + c01) + (c10 + c11)) * 0.25f over the tile pixels (2i..2i+1, 2j..2j+1), every
+ *   add separately rounded.  One pass; luma must be 8-byte aligned.
+ * lldwt_ycc420_tiles_to_u8hwc: the tiles tiles[0..n-1] (NULL: first .. first+n-1) -> the pixels inside the image and the
+ *   region, dst (B,h,w,3), as lldwt_ycc_tiles_to_u8hwc.  For tile pixel (y, x): cy = y >> 1, ny = cy + 1 if y is odd else
+ *   cy - 1, clamped to [0, th/2 - 1] (the tile's own plane; cx, nx alike); t(r) = 0.75f * c[r][cx] + 0.25f * c[r][nx];
+ *   v = 0.75f * t(cy) + 0.25f * t(ny), every product and sum separately rounded; (Y-0.5, v_cb, v_cr) then give the bytes of
+ *   lldwt_ycc_tiles_to_u8hwc.  inv_a, b: 3 host floats each or both NULL; given, every luma and chroma SAMPLE s of plane p
+ *   becomes (s - b[p]) * inv_a[p] before the upsampling (a reduced-resolution decode, as lldwt_ll_tiles_to_u8hwc).
+ * lldwt_u8hw_to_y_tiles: src (B,H,W,1) -> y (1,n,1,th,tw), g / 255.0f - 0.5f at the clamped source pixel.
+ * lldwt_y_tiles_to_u8hw: y (1,n,1,th,tw) -> dst (B,h,w,1), floor((clamp(s, -0.5, 0.5) + 0.5f) * 255.0f + 0.5f), tile list, grid
+ *   and region as above; inv_a, b: 1 host float each or both NULL, s -> (s - b[0]) * inv_a[0] first.                          */
+int lldwt_u8hwc_to_ycc420_tiles(const uint8_t* src, float* luma, float* chroma, int64_t B, int64_t H, int64_t W, int64_t th,
+                                int64_t tw, int64_t ny, int64_t nx, int64_t first, int64_t n, void* stream);
+int lldwt_ycc420_tiles_to_u8hwc(const float* luma, const float* chroma, const int32_t* tiles, int64_t first, int64_t n, int64_t B,
+                                int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
+                                int64_t h, int64_t w, const float* inv_a, const float* b, uint8_t* dst, void* stream);
+int lldwt_u8hw_to_y_tiles(const uint8_t* src, float* y, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny,
+                          int64_t nx, int64_t first, int64_t n, void* stream);
+int lldwt_y_tiles_to_u8hw(const float* y, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                          int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                          const float* inv_a, const float* b, uint8_t* dst, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * P/U block parameters (graphs/layers/P_block_v2.py:15-33) packed for the kernels.

@@ -42,6 +42,12 @@
     decode --layers J                      decodes the base plus the first J layers (default: all the container holds); info
                                            prints the bytes each prefix reads
 
+    encode --chroma {444,420,400}          the chroma format: 444 (default) codes three full-size planes; 420 codes Cb and Cr at
+                                           half size (1.5 planes of coefficients); 400 loads the file as greyscale (PIL mode L)
+                                           and codes one plane.  decode reads the format from the header and writes mode L for a
+                                           400 container; info prints it.  Not with --near / --lossless, --layers, --roi,
+                                           --overlap, --target-psnr / --target-msssim
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -128,6 +134,8 @@ def main(argv=None):
                                        help="code this rectangle at the step Q, the rest at --step (repeatable; writes LLDQ)")
     sub.choices["encode"].add_argument("--layers", type=int, metavar="M",
                                        help="add M quality layers (1..4) that refine the step by 3 each (writes LLDP)")
+    sub.choices["encode"].add_argument("--chroma", choices=("444", "420", "400"), default="444",
+                                       help="chroma format: 444 (default), 420 (half-size chroma) or 400 (greyscale, mode L)")
     sub.choices["decode"].add_argument("--layers", type=int, metavar="J",
                                        help="decode the base plus the first J quality layers of an LLDP container (default: all)")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
@@ -173,6 +181,9 @@ def main(argv=None):
             hdr = hdr["base"]
         for k, v in hdr.items():
             print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
+        fmt = hdr.get("chroma", "444")
+        print("%-15s %s (%d planes coded%s)" % ("chroma format", fmt, codec.CHROMA_PLANES[fmt],
+                                              ", Cb and Cr at half size" if fmt == "420" else ""))
         if "ny" in hdr:
             print("%-15s %d x %d tiles of %d x %d (rows x columns)" % ("grid", hdr["ny"], hdr["nx"], hdr["th"], hdr["tw"]))
             if hdr["overlap"]:
@@ -196,8 +207,10 @@ def main(argv=None):
     from PIL import Image
     net = build_net(a.config, a.checkpoint)
     if a.cmd == "encode":
-        img = np.asarray(Image.open(a.src).convert("RGB"), dtype=np.uint8)
+        img = np.asarray(Image.open(a.src).convert("L" if a.chroma == "400" else "RGB"), dtype=np.uint8)
         x = torch.from_numpy(np.ascontiguousarray(img))[None]
+        if a.chroma == "400":
+            x = x[..., None]                                    # (1,H,W,1)
         if a.lossless and a.near not in (None, 0):
             print("--lossless is --near 0; give one of them", file=sys.stderr)
             return 2
@@ -216,6 +229,8 @@ def main(argv=None):
             kw["rdo"] = a.rdo
         if a.layers is not None:
             kw["layers"] = a.layers
+        if a.chroma != "444":
+            kw["chroma"] = a.chroma
         if a.roi:
             if a.target_bytes is not None or a.target_bpp is not None:
                 print("--roi cannot be combined with --target-bytes / --target-bpp (a byte target over a step map is not defined)",
@@ -300,9 +315,13 @@ def main(argv=None):
             img = codec.decode_images(net, [blob], reduce=a.reduce, **kw)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        Image.fromarray(img.numpy()).save(a.dst)
-        print("decoded %dx%d: %.3f s" % (img.shape[1], img.shape[0], dt))
+        grey = img.shape[2] == 1                                # a chroma=400 container: mode L
+        Image.fromarray(img[..., 0].numpy() if grey else img.numpy()).save(a.dst)
+        print("decoded %dx%d%s: %.3f s" % (img.shape[1], img.shape[0], " (greyscale)" if grey else "", dt))
         if a.compare is not None:
+            if grey:
+                print("--compare: PSNR / MS-SSIM of single-channel images are not defined here", file=sys.stderr)
+                return 2
             src = _load_rgb(a.compare)
             if src.shape != img.shape:
                 print("--compare: %s is %dx%d, the decoded image %dx%d" % (a.compare, src.shape[1], src.shape[0], img.shape[1],
