@@ -106,7 +106,9 @@ void split_set_precision(int p);
 // diagnostics (lldwt_set_diagnostics): debug mask of the fused step (bit i = skip phase i+1, 16 = sequential conv3 / conv4,
 // 32 = no vertical reuse, 64 = the border tiles' strip correction in its earlier form: every k-step of the strips, half a wave
 // per corrected pixel; same output bits, 128 = correction sums behind the composite loop's barrier and no skipped MFMA tiles
-// at the image's top / bottom; same output bits) and the stamp buffers of the three split-fp16 kernel families
+// at the image's top / bottom; same output bits, 256 = conv2's weight fragments requested at the head of P2 instead of during P1: the
+// earlier form; same output bits, 512 = with a registered stamp buffer, the f16x3 eval kernels that also stamp inside P2)
+// and the stamp buffers of the three split-fp16 kernel families (the fused step's: 32 slots per wave and tile)
 void lift_f16_set_debug(int dbg);
 void lift_f16_set_stamps(void* p, int64_t nbytes);
 void f3_set_stamps(void* p, int64_t nbytes);

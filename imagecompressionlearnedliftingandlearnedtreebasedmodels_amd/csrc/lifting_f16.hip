@@ -303,7 +303,7 @@ struct LfArgs {
     int batch, h, w, vertical;
     float sign, rw;
     int dbg;              // diagnostics only (lldwt_set_diagnostics flags): bit i set = skip the tile loop of phase P(i+1); results are then wrong
-    unsigned long long* stamps;   // diagnostics only (lldwt_set_diagnostics kind 0): [tile][wave][16] s_memtime stamps
+    unsigned long long* stamps;   // diagnostics only (lldwt_set_diagnostics kind 0): [tile][wave][LF_NSTAMP] s_memtime stamps
     int tiles_x, tiles_y;
     int rl, nseg;                 // run length (tiles a workgroup walks down before it moves to another column) and runs per column
     int nitems;                   // runs of the launch: Z * tiles_x * nseg
@@ -326,10 +326,18 @@ struct LfArgs {
 // launches on different streams do not share one).
 __device__ int g_lf_queue[64][2];
 // in-kernel clock stamps of a diagnostic run (tools/lift_stamps.py); a null pointer (always, outside that tool) skips them
+// slots 0..13 and 16..: s_memtime, 14 and 15: s_memrealtime; slots 16.. lie inside P2 and are compiled into the P2ST kernels only
+constexpr int LF_NSTAMP = 32;
 #define LF_STAMP(i)                                                                                                     \
     if (a.stamps && lane == 0)                                                                                          \
-        a.stamps[(stamp_tile * NWAVE + wave) * 16 + (i)] =                                                              \
-            (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
+        a.stamps[(stamp_tile * NWAVE + wave) * LF_NSTAMP + (i)] =                                                       \
+            ((i) == 14 || (i) == 15) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
+#define LF_STAMP2(i)                                                                                                    \
+    if constexpr (P2ST) {                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+        LF_STAMP(i)                                                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+    }
 
 // 13 k-steps of one 16-pixel tile: B fragments from a T-image (input region width WIN, NIN pixels), A fragments in registers
 template <int WIN, int NIN, int PREC = 0>
@@ -417,10 +425,12 @@ __device__ __forceinline__ floatx4 conv16_tile_need(const uint8_t* __restrict__ 
 // read from LDS into a second register set BEFORE the 6 MFMAs of k-step ks (the sched_group_barrier sequence pins that
 // order and leaves room for 2 vector instructions of a neighbouring epilogue after every MFMA), so the matrix pipe never
 // waits for an LDS round trip.
-template <int WIN, int NIN, int PREC, class Piece>
+// WST (diagnostics, tools/lift_stamps.py): the cycles from the head of each k-step until every LDS operation of the wave has
+// returned, i.e. the wait for the k-step's operands, are added to wsum
+template <int WIN, int NIN, int PREC, bool WST = false, class Piece>
 __device__ __forceinline__ void conv16_tile2(const uint8_t* __restrict__ img, int base0, int base1, bool hi_tap,
                                              const half8 (&ah)[LF_KS], const half8 (&al)[LF_KS], floatx4& acc0, floatx4& acc1,
-                                             Piece&& piece) {
+                                             Piece&& piece, unsigned long long* wsum = nullptr) {
     acc0 = floatx4{0.f, 0.f, 0.f, 0.f};
     acc1 = floatx4{0.f, 0.f, 0.f, 0.f};
     half8 bh0[2], bl0[2], bh1[2], bl1[2];
@@ -446,6 +456,13 @@ __device__ __forceinline__ void conv16_tile2(const uint8_t* __restrict__ img, in
 #pragma unroll
     for (int ks = 0; ks < LF_KS; ++ks) {
         const int c = ks & 1;
+        if constexpr (WST) {
+            unsigned long long ta, tb;
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ta) : : "memory");
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tb) : : "memory");
+            *wsum += tb - ta;
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (ks + 1 < LF_KS) load(ks + 1, c ^ 1);
         if constexpr (PREC == 0) {
             acc0 = mma1<0>(al[ks], bh0[c], acc0);
@@ -598,8 +615,15 @@ struct LfPre {
 // transposed, mirrored weights (lift_f16_pack_bwd), no biases, the tanh replaced by the gates of the SAVED t2 / t1 (t2's gate is
 // staged into the T2 image before conv2' overwrites it pixel by pixel; t1's is loaded per tile in P3), and the gradient images
 // scaled by bounds (max|g| of the tile x the row L1 norms of the pack) instead of the fixed 2^14 of tanh outputs.
-template <bool SEQ, int PREC, bool TRAIN = false, bool BWD = false>
+// P2PRE: conv2's 26 weight fragments (104 VGPRs, 26 KB per wave, the same bytes for all eight waves: 213 KB per tile through
+// the CU's vector-memory path) are requested during P1, whose conv1 needs few registers, a sixth at a time between its
+// pieces, instead of at the head of P2, where the stamps found every wave held ~2.7k cycles with the matrix pipe idle.  The
+// eval path takes it; the sequential modes do not, nor does the eval path under diagnostics flag 256 (the A/B leg of
+// tools/lift_stamps.py and the reference of tests/test_gpu_lift_conv2_sched.py): same fragments, same MFMAs, same bits
+// P2ST (diagnostics flag 512 with a registered stamp buffer): stamps 16.. inside P2 (tools/lift_stamps.py --p2)
+template <bool SEQ, int PREC, bool TRAIN = false, bool BWD = false, bool P2PRE = false, bool P2ST = false>
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_lift_fused_f16(LfArgs a) {
+    static_assert(!P2ST || (!SEQ && PREC == 0), "the stamps inside P2 exist for the f16x3 eval path only");
     static_assert(!SEQ || PREC == 0, "the sequential check path exists for the fp32-accurate arithmetic only");
     static_assert(!TRAIN || SEQ, "the training forward needs t3: sequential path");
     static_assert(!BWD || (SEQ && !TRAIN), "backward-data runs on the sequential path");
@@ -927,10 +951,28 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             timg_store<N2, 0>(lds + LDS_T2, p, c4, gq);
         }
     }
+    half8 ah2[LF_KS], al2[LF_KS];             // conv2's weight fragments (P2)
+    if constexpr (P2PRE) {
+        // conv1's own operands are pinned in front: vector-memory loads return in order, and the compiler otherwise sinks them
+        // below the 26 requests, so that P1's first MFMA waits for all of them
+        asm volatile("" : "+v"(a1h), "+v"(a1l));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(b1c[q]));
+    }
+    // 26 requests of 1 KB hold the wave that issues them for as long as the CU's vector-memory path takes to accept them: ~2.7k
+    // cycles when all eight waves issue theirs together, in front of P1 (measured: P1 +1.9k) as much as at the head of P2.  So
+    // they go out in six chunks between the pieces of P1's first two iterations, which are written out for that; each chunk
+    // is defined on every path (a chunk under a condition, or inside the rolled loop, made the register allocator spill)
+    auto p2_fragments = [&](int chunk) {
+#pragma unroll
+        for (int ks = 0; ks < LF_KS; ++ks)
+            if ((ks < 10 ? ks / 2 : 5) == chunk) ldA<PREC>(frag, LF_H_C2 / LF_FRAG + ks, lane, ah2[ks], al2[ks]);
+    };
+    if constexpr (P2PRE) p2_fragments(0);
     // ---------------- P1: t1 = tanh(conv1(skip) + b1) on 28 x 44.  Two tiles per iteration (independent chains for the
     // scheduler: one tile alone is a latency chain LDS -> MFMA x3 -> tanh -> split -> store); tiles past the end repeat the
     // last one (same bytes stored again)
-    if (!(a.dbg & 1)) {
+    if (P2PRE || !(a.dbg & 1)) {            // (the skip flag is honoured by the form without the early requests only)
         // a continuing tile computes rows 12..27 only (tiles 33..76)
         // (sequential path: rows 8..27, tiles 22..76 -- T1 itself is not handed down there)
         int lo1, hi1;
@@ -939,8 +981,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int nit1 = (nt1 + 2 * NWAVE - 1) / (2 * NWAVE);           // 5, or 3 (sequential path: 4); fewer at the image's top / bottom
 
         float mx1 = 0.f;                        // BWD: max |dt3| x act1 over this wave's values (for the weight gradient's dY scale)
-#pragma unroll 1
-        for (int it = 0; it < nit1; ++it) {
+        auto p1_iter = [&](int it, int chunk) {       // chunk >= 0 (a constant): these requests go between conv1 and its epilogue
             floatx4 acc[2];
             int pq[2];
             float msk[2];
@@ -953,6 +994,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int gy = y0 - 6 + r, gx = x0 - 6 + c;
                 msk[t] = (gy >= 0 && gy < h && gx >= 0 && gx < w) ? act1 : 0.f;
                 pq[t] = p;
+            }
+            if (chunk >= 0) {
+                __builtin_amdgcn_sched_barrier(0);
+                p2_fragments(chunk);
+                __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -985,6 +1031,21 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     }
                 }
             }
+        };
+        if constexpr (P2PRE) {
+            p1_iter(0, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            p2_fragments(2);
+            __builtin_amdgcn_sched_barrier(0);
+            p1_iter(1, 3);                      // (with one iteration only, at the image's top / bottom: its tiles again, same bytes)
+            __builtin_amdgcn_sched_barrier(0);
+            p2_fragments(4);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll 1
+            for (int it = 2; it < nit1; ++it) p1_iter(it, -1);
+        } else {
+#pragma unroll 1
+            for (int it = 0; it < nit1; ++it) p1_iter(it, -1);
         }
         if constexpr (BWD) {
             if (a.mx) {
@@ -996,6 +1057,9 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
     }
+    if constexpr (P2PRE) {
+        p2_fragments(5);
+    }
     LF_STAMP(3)
     __syncthreads();
     LF_STAMP(4)
@@ -1004,9 +1068,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     {
         int lo2, hi2;
         tile_range(LDS_T2, T2A, R2W, NT2, 4, NT2 - NT2C, lo2, hi2);
-        half8 ah[LF_KS], al[LF_KS];
+        half8 (&ah)[LF_KS] = ah2, (&al)[LF_KS] = al2;
+        if constexpr (!P2PRE) {
 #pragma unroll
-        for (int ks = 0; ks < LF_KS; ++ks) ldA<PREC>(frag, LF_H_C2 / LF_FRAG + ks, lane, ah[ks], al[ks]);
+            for (int ks = 0; ks < LF_KS; ++ks) ldA<PREC>(frag, LF_H_C2 / LF_FRAG + ks, lane, ah[ks], al[ks]);
+        }
         float bv[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) bv[q] = bias[a.b2 + oc0 + q];
@@ -1085,6 +1151,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         };
         if (!(a.dbg & 2)) {
+            LF_STAMP2(16)
             {
                 const int b0 = tile_base(wave, pp[0]), b1 = tile_base(wave + NWAVE, pp[1]);
                 conv16_tile2<R1W, N1, PREC>(lds + LDS_T1, b0, b1, hi_tap, ah, al, pc[0], pc[1], [](int) {});
@@ -1093,23 +1160,55 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 pdup[0] = wave >= nt2;
                 pdup[1] = wave + NWAVE >= nt2;
             }
+            LF_STAMP2(17)
+            if constexpr (P2ST) {                   // what one wait stamp reads with nothing to wait for: the clock's own round trip
+                unsigned long long ta, tb;
+                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ta) : : "memory");
+                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tb) : : "memory");
+                if (a.stamps && lane == 0) a.stamps[(stamp_tile * NWAVE + wave) * LF_NSTAMP + 26] = tb - ta;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            unsigned long long wsum = 0;           // P2ST: operand waits at the k-step heads of the loop's pairs, and their number
+            int wpairs = 0;
 #pragma unroll 1
             for (int it = 1; it < nit2; ++it) {
                 floatx4 n0, n1;
                 int q0, q1;
                 const int b0 = tile_base(wave + 16 * it, q0), b1 = tile_base(wave + 16 * it + NWAVE, q1);
-                conv16_tile2<R1W, N1, PREC>(lds + LDS_T1, b0, b1, hi_tap, ah, al, n0, n1, slice);
+                if constexpr (P2ST && !P2PRE) {
+                    // every second tile of a column takes the wait stamps, the others run the pair as the production kernel does
+                    // (the earlier form only: with the fragments requested during P1 the second copy of the pair spills)
+                    if ((y0 / TH) & 1) {
+                        conv16_tile2<R1W, N1, PREC, true>(lds + LDS_T1, b0, b1, hi_tap, ah, al, n0, n1, slice, &wsum);
+                        ++wpairs;
+                    } else {
+                        conv16_tile2<R1W, N1, PREC>(lds + LDS_T1, b0, b1, hi_tap, ah, al, n0, n1, slice);
+                    }
+                } else {
+                    conv16_tile2<R1W, N1, PREC>(lds + LDS_T1, b0, b1, hi_tap, ah, al, n0, n1, slice);
+                }
                 pc[0] = n0; pc[1] = n1; pp[0] = q0; pp[1] = q1;
                 pin[0] = in_image(q0);
                 pin[1] = in_image(q1);
                 pdup[0] = wave + 16 * it >= nt2;
                 pdup[1] = wave + 16 * it + NWAVE >= nt2;
+                if constexpr (P2ST) {
+                    if (it <= 3) { LF_STAMP2(17 + it) }
+                }
             }
+            if constexpr (P2ST) {
+                if (a.stamps && lane == 0) {
+                    a.stamps[(stamp_tile * NWAVE + wave) * LF_NSTAMP + 24] = wsum;
+                    a.stamps[(stamp_tile * NWAVE + wave) * LF_NSTAMP + 25] = (unsigned long long)wpairs;
+                }
+            }
+            LF_STAMP2(21)
             if (single) {
                 floatx4 n0;
                 int q0;
                 const int b0 = tile_base(wave + 16 * nit2, q0);
                 conv16_tile1<R1W, N1, PREC>(lds + LDS_T1, b0, hi_tap, ah, al, n0, slice);
+                LF_STAMP2(22)
                 if constexpr (SEQ) {            // TRAIN / BWD: the single tile's epilogue is a pair's first half (gates, saved tensors, maxima)
                     pc[0] = n0; pp[0] = q0; pin[0] = in_image(q0); pdup[0] = false;
 #pragma unroll
@@ -1616,6 +1715,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         g_lf_queue[a.qslot][1] = 0;
     }
 }
+#undef LF_STAMP2
 #undef LF_STAMP
 
 }  // namespace
@@ -1704,6 +1804,11 @@ int lift_f16_launch(const LiftF16Call& c) {
         if (hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 2, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_lift_fused_f16<false, 0, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_lift_fused_f16<true, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL2) != hipSuccess) {
@@ -1750,7 +1855,7 @@ int lift_f16_launch(const LiftF16Call& c) {
         return LLDWT_EINVAL;
     }
     if (g_lf_stamps) {              // diagnostics (tools/lift_stamps.py): only when the registered buffer holds every tile's stamps
-        const int64_t need = (int64_t)a.tiles_x * a.tiles_y * Zl * NWAVE * 16 * 8;
+        const int64_t need = (int64_t)a.tiles_x * a.tiles_y * Zl * NWAVE * LF_NSTAMP * 8;
         if (g_lf_stamps_bytes >= need) a.stamps = g_lf_stamps;
     }
     static int ncu = 0;
@@ -1799,9 +1904,16 @@ int lift_f16_launch(const LiftF16Call& c) {
     if (bw) hipLaunchKernelGGL((k_lift_fused_f16<true, 0, false, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
     else if (sv) hipLaunchKernelGGL((k_lift_fused_f16<true, 0, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
     else if (seq) hipLaunchKernelGGL((k_lift_fused_f16<true, 0>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
-    else if (prec == 1) hipLaunchKernelGGL((k_lift_fused_f16<false, 1>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
-    else if (prec == 2) hipLaunchKernelGGL((k_lift_fused_f16<false, 2>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
-    else hipLaunchKernelGGL((k_lift_fused_f16<false, 0>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+    else if (a.dbg & 256) {         // diagnostics: conv2's weight fragments requested at the head of P2, as the sequential modes do
+        if (prec == 0 && (a.dbg & 512) && a.stamps) hipLaunchKernelGGL((k_lift_fused_f16<false, 0, false, false, false, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+        else if (prec == 1) hipLaunchKernelGGL((k_lift_fused_f16<false, 1>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+        else if (prec == 2) hipLaunchKernelGGL((k_lift_fused_f16<false, 2>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+        else hipLaunchKernelGGL((k_lift_fused_f16<false, 0>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+    }
+    else if (prec == 0 && (a.dbg & 512) && a.stamps) hipLaunchKernelGGL((k_lift_fused_f16<false, 0, false, false, true, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+    else if (prec == 1) hipLaunchKernelGGL((k_lift_fused_f16<false, 1, false, false, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+    else if (prec == 2) hipLaunchKernelGGL((k_lift_fused_f16<false, 2, false, false, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
+    else hipLaunchKernelGGL((k_lift_fused_f16<false, 0, false, false, true>), dim3(grid), dim3(NTH), LDS_TOTAL2, st, a);
     return check_launch("lift_f16_launch");
 }
 

@@ -186,7 +186,11 @@ int lldwt_get_precision(void);
  * convolutions, half a wave per corrected pixel): same output bits, kept for A/B timing and as a test reference;
  * 128 = the tile as it was before the correction sums left the critical path: the sums behind a barrier that follows the
  * composite loop (flag 64 implies this order too), and every MFMA tile of conv1 / conv2 computed at the top and bottom of the
- * image although all its pixels lie outside it: same output bits, the A/B leg of tools/lift_stamps.py and a test reference.
+ * image although all its pixels lie outside it: same output bits, a test reference;
+ * 256 = the eval kernels that request conv2's weight fragments at the head of P2 instead of between the pieces of P1 (the
+ * skip bit 0 is honoured by this form only): same fragments, same MFMA sequence and same output bits, the A/B leg of
+ * tools/lift_stamps.py and a test reference; 512 = with a registered buffer, the f16x3 eval kernels that also stamp inside P2 (tools/lift_stamps.py --p2).
+ * A buffer of kind 0 holds 32 stamps per wave and tile.
  * flags, kind 1: bit 0 = the Winograd pair kernel (k_plc_wino) in its earlier form -- the epilogue that loads each bias value
  * between the stores and waits for them, the first conv's ACT and STORE stages whole inside one unit of the chunk loop, eight
  * vector instructions offered per MFMA gap: same output bits, kept for A/B timing (tools/plc_stamps.py) and as a test reference.

@@ -5,8 +5,13 @@ a stamp buffer is registered through lldwt_set_diagnostics (this tool); a normal
 
 python tools/lift_stamps.py --ab [FILE]: the tile classes (border, top edge, bottom edge, left edge, interior first / continuing)
 at the level-0 row-pass shape (256 x 512) and at level 3's (32 x 64: four corner tiles per image, runs of one tile), once with
-diagnostics flag 128 (correction sums behind the composite loop's barrier, no skipped MFMA tiles at the image's top / bottom) and
-once without, in one process; written to FILE as JSON if given."""
+diagnostics flag 256 (conv2's weight fragments requested at the head of P2, the earlier form) and once without (requested in
+six chunks during P1), in one process, two launches per form; written to FILE as JSON if given.
+
+python tools/lift_stamps.py --p2 [FILE]: stamps INSIDE P2 (diagnostics flag 512: kernels of their own, no production launch holds
+them) of the interior continuing tiles at the level-0 shape, for both forms: cycles of the first pair, the loop's pair, the
+single tile and the tail per wave, the MFMA cycles a wave issues in them, the skew of the waves at P2's barrier and -- on every
+second tile row, for the earlier form -- the cycles each k-step of the loop's pair waits for its LDS operands."""
 import json
 import os
 import sys
@@ -16,6 +21,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+NSTAMP = 32                                    # LF_NSTAMP of csrc/lifting_f16.hip: stamp slots per wave and tile
+P2_OLD, P2_STAMPS = 256, 512                   # diagnostics flags: the earlier form of P2; the kernels that stamp inside P2
+MFMA_CYCLES = 16                               # v_mfma_f32_16x16x32_f16 on one SIMD
 NAMES = ["P0 load+filter", "P0 barrier", "P1 conv1+tanh", "P1 barrier", "P2 conv2+tanh", "P2 barrier",
          "PC composite", "PC barrier", "PC finish+store"]
 
@@ -37,7 +45,7 @@ def stamp(h, w, dbg, P=3, B=8):
     dout = ops.view_of(out, P * B, h, w)
     lib.lldwt_set_lift_mode(1)
     gx, gy = (w + 31) // 32, (h + 15) // 16
-    st = torch.zeros(gx * gy * P * B, 8, 16, dtype=torch.int64, device=dev)
+    st = torch.zeros(gx * gy * P * B, 8, NSTAMP, dtype=torch.int64, device=dev)
 
     def run():
         ops.lift_step(src, din, dout, P * B, B, h, w, taps, packed, 16, 5, True, 1.0, 0.1)
@@ -51,7 +59,7 @@ def stamp(h, w, dbg, P=3, B=8):
         torch.cuda.synchronize()
     finally:
         ops.set_diagnostics(0, None, 0)
-    return st.cpu().numpy().astype(np.int64).reshape(P * B, gy, gx, 8, 16)
+    return st.cpu().numpy().astype(np.int64).reshape(P * B, gy, gx, 8, NSTAMP)
 
 
 def classes(s, rl):
@@ -77,12 +85,12 @@ def classes(s, rl):
 
 def ab(path):
     res = {"what": "k_lift_fused_f16<false, 0>, one vertical step on 24 images; cycles from the tile's first stamp to its last, mean "
-                   "over the eight waves and the tiles of a class; 'parent_form' = diagnostics flag 128, 'change' = no flag; one process",
+                   "over the eight waves and the tiles of a class; 'parent_form' = diagnostics flag 256, 'change' = no flag; one process",
            "shapes": {}}
     for key, (h, w, rl) in (("level0_row_pass_256x512", (256, 512, int(os.environ.get("LLDWT_STAMPS_RL", "8")))),
                             ("level3_row_pass_32x64", (32, 64, 1))):
-        old, new = classes(stamp(h, w, 128), rl), classes(stamp(h, w, 0), rl)
-        old2, new2 = classes(stamp(h, w, 128), rl), classes(stamp(h, w, 0), rl)      # a second pair: what the stamps resolve
+        old, new = classes(stamp(h, w, P2_OLD), rl), classes(stamp(h, w, 0), rl)
+        old2, new2 = classes(stamp(h, w, P2_OLD), rl), classes(stamp(h, w, 0), rl)    # a second pair: what the stamps resolve
         res["shapes"][key] = {"run_length": rl, "parent_form": old, "change": new,
                               "total_cycles_mean": {c: {"parent_form": [old[c]["total_cycles_mean"], old2[c]["total_cycles_mean"]],
                                                         "change": [new[c]["total_cycles_mean"], new2[c]["total_cycles_mean"]]}
@@ -94,10 +102,71 @@ def ab(path):
             f.write(txt + "\n")
 
 
+def p2_of(s, rl):
+    """P2 of the interior continuing tiles of one stamped launch (flag 512), mean over tiles and waves unless named otherwise."""
+    gy, gx = s.shape[1:3]
+    ty = np.arange(gy)[:, None] * np.ones((1, gx), int)
+    tx = np.ones((gy, 1), int) * np.arange(gx)[None, :]
+    cont = (tx > 0) & (tx < gx - 1) & (ty > 0) & (ty < gy - 1) & (ty % rl != 0)
+    # the earlier form's stamping kernel drains the LDS queue at every k-step head of the loop's pair on odd tile rows (the wait
+    # stamps): those rows give the waits, the even rows everything else
+    waits = bool((s[:, cont & (ty % 2 == 1)][..., 25] > 0).any())
+    t = s[:, cont & (ty % 2 == 0)] if waits else s[:, cont]
+    d = lambda i, j: (t[..., i] - t[..., j]).astype(np.float64)
+    p2 = d(5, 4)
+    out = {"tiles": int(t.shape[0] * t.shape[1]),
+           "P2 (stamp 4 to 5)": round(float(p2.mean()), 1),
+           "set-up: the wait for the weight fragments, biases (4 to 16)": round(float(d(16, 4).mean()), 1),
+           "first pair, no epilogue beside it (16 to 17)": round(float(d(17, 16).mean()), 1),
+           "loop pair with the first pair's ten slices (17 to 18)": round(float(d(18, 17).mean()), 1),
+           "single tile with the loop pair's ten slices (21 to 22)": round(float(d(22, 21).mean()), 1),
+           "tail: the single tile's tanh, split, store (22 to 5)": round(float(d(5, 22).mean()), 1),
+           "single tile's share of P2": round(float((d(22, 21) / p2).mean()), 4),
+           "MFMA cycles a wave issues in P2 (195 x 16)": 195 * MFMA_CYCLES,
+           "MFMA cycles of both waves of a SIMD (the floor)": 2 * 195 * MFMA_CYCLES,
+           "MFMA cycles of both waves: a pair / the single tile": [2 * 78 * MFMA_CYCLES, 2 * 39 * MFMA_CYCLES],
+           "skew at P2's barrier: last wave minus first, mean over tiles": round(float((t[..., 5].max(-1) - t[..., 5].min(-1)).mean()), 1),
+           "P2 barrier wait (5 to 6)": round(float(d(6, 5).mean()), 1),
+           "per wave: P2": [round(float(p2[..., k].mean()), 1) for k in range(8)],
+           "per wave: P2 barrier wait": [round(float(d(6, 5)[..., k].mean()), 1) for k in range(8)]}
+    if not waits:
+        return out
+    o = s[:, cont & (ty % 2 == 1)]
+    n = o[..., 25].astype(np.float64)
+    ok = n > 0
+    per_pair = o[..., 24][ok] / n[ok]                      # 13 wait stamps per pair
+    base = float(np.median(o[..., 26][ok]))                # one wait stamp with nothing in flight
+    out["operand waits of the loop pair (odd tile rows)"] = {
+        "sum of the 13 wait stamps per pair": round(float(per_pair.mean()), 1),
+        "one wait stamp with nothing in flight (median)": base,
+        "waited beyond the stamp's own round trip, per pair": round(float(per_pair.mean()) - 13 * base, 1),
+        "per wave: sum of the 13 wait stamps": [round(float((o[..., k, 24][ok[..., k]] / n[..., k][ok[..., k]]).mean()), 1) for k in range(8)],
+        "loop pair on these rows, with its stamps (17 to 18)": round(float((o[..., 18] - o[..., 17]).mean()), 1)}
+    return out
+
+
+def p2(path):
+    h, w, rl = 256, 512, int(os.environ.get("LLDWT_STAMPS_RL", "8"))
+    res = {"what": "k_lift_fused_f16<false, 0>, stamps inside P2 (diagnostics flag 512), interior continuing tiles of one vertical step on "
+                   "24 images of 256 x 512; cycles per wave; 'parent_form' = flag 256 (weight fragments requested at P2's head), 'change' = during P1; "
+                   "two launches per form, one process.  A stamp is fenced and costs cycles: read shares and differences of like with like",
+           "run_length": rl, "parent_form": [], "change": []}
+    for _ in range(2):
+        res["parent_form"].append(p2_of(stamp(h, w, P2_OLD | P2_STAMPS), rl))
+        res["change"].append(p2_of(stamp(h, w, P2_STAMPS), rl))
+    txt = json.dumps(res, indent=1)
+    print(txt)
+    if path:
+        with open(path, "w") as f:
+            f.write(txt + "\n")
+
+
 def main():
     from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import ops
     if len(sys.argv) > 1 and sys.argv[1] == "--ab":
         return ab(sys.argv[2] if len(sys.argv) > 2 else "")
+    if len(sys.argv) > 1 and sys.argv[1] == "--p2":
+        return p2(sys.argv[2] if len(sys.argv) > 2 else "")
     P, B, h, w = 3, 8, 256, 512
     abl = None
     dbg = int(os.environ.get("LLDWT_LF_DBG", "0"))
