@@ -1,6 +1,8 @@
 """GPU: the irans32 device coder (csrc/rans_gpu.hip, irans.py) -- its bytes and symbols pinned to the
 Python definition tools/irans_ref.py, round trips of every coded layer against the host coder, tiles and regions, a fresh
-process, no host coder on the device path, stream size, and corrupt-stream refusal."""
+process, no host coder on the device path, stream size, and corrupt-stream refusal.  The pins here stop at 8 lanes, the
+Gaussian tables and sparse escapes; the coder's lane (16, 32), table and escape domain is pinned in
+tests/test_gpu_irans_domain.py on the cases of tests/irans_cases.py."""
 import os
 import subprocess
 import sys
