@@ -253,12 +253,86 @@ class DWTFactorizedEntropyLayer(_EntropyLayerBase):
         return bits, si_xo, q, q_xo
 
 
+class _CodedLayer(_EntropyLayerBase):
+    """An entropy layer with real entropy coding: the ONE level walk of compress_planes / decompress_planes, and test_planes /
+    test on top of them.  The walk codes xe, then the coarsest level, then the finer levels from the coarse end, each from its
+    DECODED parent; the entropy_coding functions it calls serve both directions (y = None plus strings: decode).  A layer states
+    only what is its own: _coding_setup (per call), _code_base (xe and the coarsest level) and _code_level (a finer level).
+    One rANS stream per (plane, image, tensor)."""
+
+    @staticmethod
+    def _coding_setup(layers):
+        """-> whatever the layer's hooks need per call (handed to them as ctx)."""
+
+    @staticmethod
+    def _code_base(layers, ctx, level, y, shape, strings, coder):
+        """xe (level None) or the coarsest level -> (strings or None, dequantised).  Here: the factorized priors ent_out_xe /
+        ent_out_xo (EntropyBottleneck; compressai's compress / decompress)."""
+        from . import entropy_coding as ec
+        return ec.code_factorized([l.ent_out_xe if level is None else l.ent_out_xo for l in layers], y, shape, strings, coder=coder)
+
+    @classmethod
+    def _walk(cls, layers, xe, xo, strings, coder, first_level, step, rdo):
+        """Encoder (strings None): xe, xo the coefficients -> (strings_xe, [strings_xo], xe_q, [xo_q]).  Decoder: xe, xo their
+        shapes, strings = (strings_xe, strings_xo_list) -> (xe, [xo_k .. xo_{L-1}]), k = first_level.  Lists finest first."""
+        L = len(xo)
+        step = _check_step(step, L, layers)
+        rdo = _check_rdo(rdo, L)
+        if strings is None:
+            s_xe, s_xo, ys, shapes = None, [None] * L, [xe] + list(xo), [xe.shape] + [t.shape for t in xo]
+        else:
+            s_xe, s_xo, ys, shapes = strings[0], _coarse_strings(strings[1], L, first_level), [None] * (L + 1), [xe] + list(xo)
+        ctx = cls._coding_setup(layers)
+        with torch.no_grad():
+            s_xe, xe_q = cls._code_base(layers, ctx, None, ys[0], shapes[0], s_xe, coder)
+            s_list, q_list = [], []
+            for i in range(L - 1, first_level - 1, -1):
+                y, shape = ys[i + 1], shapes[i + 1]
+                if i == L - 1:
+                    s, q = cls._code_base(layers, ctx, i, y, shape, s_xo[i], coder)
+                else:                                                                 # q: the decoded parent, level i + 1
+                    s, q = cls._code_level(layers, ctx, i, L, q, y, shape, s_xo[i], coder,
+                                           _level_step(step, L, i, shape, q.device), rdo)
+                s_list.append(s)
+                q_list.append(q)
+        s_list.reverse()
+        q_list.reverse()
+        return (s_xe, s_list, xe_q, q_list) if strings is None else (xe_q, q_list)
+
+    @classmethod
+    def compress_planes(cls, layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
+        """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first) with *_q the values the decoder
+        reconstructs.  step, rdo: DESIGN.md 7.1.6-7.1.8; they reach the levels below the coarsest."""
+        return cls._walk(layers, out_xe, out_xo_list, None, coder, 0, step, rdo)
+
+    @classmethod
+    def decompress_planes(cls, layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
+        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
+        xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]); shapes_xo has all L levels, strings_xo_list all L or the
+        levels k .. L-1 (_coarse_strings)."""
+        return cls._walk(layers, shape_xe, shapes_xo, (strings_xe, strings_xo_list), coder, first_level, step, None)
+
+    @classmethod
+    def test_planes(cls, layers, out_xe, out_xo_list):
+        """Encode, then decode FROM THE STRINGS (the reference returns the decoder's tensors, :419-456)."""
+        s_xe, s_xo, _, _ = cls.compress_planes(layers, out_xe, out_xo_list)
+        xe, xo = cls.decompress_planes(layers, s_xe, s_xo, out_xe.shape, [t.shape for t in out_xo_list])
+        return s_xe, s_xo, xe, xo
+
+    def test(self, out_xe, out_xo_list):
+        """Reference signature (:374): (B,C,h,w) tensors of ONE plane -> (string_xe, [string_xo per level, finest first],
+        decoded xe, [decoded xo]).  Strings are ``bytes`` at batch 1 (as in the reference), lists of per-image bytes else."""
+        s_xe, s_xo, xe, xo = self.test_planes([self], out_xe[None].contiguous(), [t[None].contiguous() for t in out_xo_list])
+        one = lambda rows: rows[0][0] if len(rows[0]) == 1 else rows[0]
+        return one(s_xe), [one(r) for r in s_xo], xe[0], [t[0] for t in xo]
+
+
 def _plc(so):
     o = so * 81
     return nn.Conv2d(so, o, kernel_size=3, stride=1, padding=1), nn.LeakyReLU(), nn.Conv2d(o, o, kernel_size=3, stride=1, padding=1)
 
 
-class onlyEZWT(_EntropyLayerBase):
+class onlyEZWT(_CodedLayer):
     """Inter-subband ("zero-tree") model only (LiftingBasedDWT_net.py:759-840)."""
 
     def __init__(self, config):
@@ -309,71 +383,17 @@ class onlyEZWT(_EntropyLayerBase):
         return _conv([s[4] for s in seqs], t)                                       # (P,B,6,h,w): sigma even, mu odd
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
-        """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first)."""
+    def _code_level(layers, ctx, i, L, parent, y, shape, strings, coder, step, rdo):
         from . import entropy_coding as ec
-        L = len(out_xo_list)
-        step = _check_step(step, L, layers)
-        rdo = _check_rdo(rdo, L)
-        with torch.no_grad():
-            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
-            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
-            s_list, q_list = [s], [q]
-            for i in range(L - 2, -1, -1):
-                tabs = ec._Tables(layers[0].ent_out_xo_list[i], get_scale_table())
-                for l in layers[1:]:
-                    l.ent_out_xo_list[i].update_scale_table(get_scale_table())
-                ms = onlyEZWT._level_params(layers, i, q)
-                s, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, out_xo_list[i],
-                                                 out_xo_list[i].shape, tabs, coder=coder,
-                                                 step=_level_step(step, L, i, out_xo_list[i].shape, ms.device), rdo=rdo)
-                s_list.append(s)
-                q_list.append(q)
-        s_list.reverse()
-        q_list.reverse()
-        return s_xe, s_list, xe_q, q_list
-
-    @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
-        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
-        xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]); shapes_xo has all L levels, strings_xo_list all L or the
-        levels k .. L-1 (_coarse_strings)."""
-        from . import entropy_coding as ec
-        L = len(shapes_xo)
-        step = _check_step(step, L, layers)
-        strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
-        with torch.no_grad():
-            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
-            if first_level == L:
-                return xe, []
-            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1], coder=coder)
-            q_list = [q]
-            for i in range(L - 2, first_level - 1, -1):
-                tabs = ec._Tables(layers[0].ent_out_xo_list[i], get_scale_table())
-                for l in layers[1:]:
-                    l.ent_out_xo_list[i].update_scale_table(get_scale_table())
-                ms = onlyEZWT._level_params(layers, i, q)
-                _, q = ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, None, shapes_xo[i], tabs,
-                                                 strings_xo_list[i], coder=coder,
-                                                 step=_level_step(step, L, i, shapes_xo[i], ms.device))
-                q_list.append(q)
-        q_list.reverse()
-        return xe, q_list
-
-    @staticmethod
-    def test_planes(layers, out_xe, out_xo_list):
-        """Encode, then decode FROM THE STRINGS (same contract as the conditioned2 layer's test_planes)."""
-        s_xe, s_xo, _, _ = onlyEZWT.compress_planes(layers, out_xe, out_xo_list)
-        xe, xo = onlyEZWT.decompress_planes(layers, s_xe, s_xo, out_xe.shape, [t.shape for t in out_xo_list])
-        return s_xe, s_xo, xe, xo
-
-    def test(self, out_xe, out_xo_list):
-        s_xe, s_xo, xe, xo = self.test_planes([self], out_xe[None].contiguous(), [t[None].contiguous() for t in out_xo_list])
-        one = lambda rows: rows[0][0] if len(rows[0]) == 1 else rows[0]
-        return one(s_xe), [one(r) for r in s_xo], xe[0], [t[0] for t in xo]
+        tabs = ec._Tables(layers[0].ent_out_xo_list[i], get_scale_table())
+        for l in layers[1:]:
+            l.ent_out_xo_list[i].update_scale_table(get_scale_table())
+        ms = onlyEZWT._level_params(layers, i, parent)
+        return ec.code_gaussian_parallel([l.ent_out_xo_list[i] for l in layers], ms, y, shape, tabs, strings, coder=coder,
+                                         step=step, rdo=rdo)
 
 
-class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
+class DWTConditioned2EntropyLayerZTsepSubbands(_CodedLayer):
     """Tree (parent level) + causal intra-subband context model (LiftingBasedDWT_net.py:233-372)."""
 
     def __init__(self, config):
@@ -472,22 +492,8 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return si_xe, si_list, xe_q, q_list
 
 
-    # ---------------------------------------------------------------- real entropy coding (:374-556)
-    def test(self, out_xe, out_xo_list):
-        """Reference signature (:374): (B,C,h,w) tensors of ONE plane -> (string_xe, [string_xo per level, finest first],
-        decoded xe, [decoded xo]).  Strings are ``bytes`` at batch 1 (as in the reference), lists of per-image bytes else."""
-        s_xe, s_xo, xe, xo = self.test_planes([self], out_xe[None].contiguous(), [t[None].contiguous() for t in out_xo_list])
-        one = lambda rows: rows[0][0] if len(rows[0]) == 1 else rows[0]
-        return one(s_xe), [one(r) for r in s_xo], xe[0], [t[0] for t in xo]
-
-    @staticmethod
-    def test_planes(layers, out_xe, out_xo_list):
-        """Encode, then decode FROM THE STRINGS (the reference returns the decoder's tensors, :419-456)."""
-        cls = DWTConditioned2EntropyLayerZTsepSubbands
-        s_xe, s_xo, _, _ = cls.compress_planes(layers, out_xe, out_xo_list)
-        xe, xo = cls.decompress_planes(layers, s_xe, s_xo, out_xe.shape, [t.shape for t in out_xo_list])
-        return s_xe, s_xo, xe, xo
-
+    # ---------------------------------------------------------------- real entropy coding (:374-556): compress_ar /
+    # decompress_ar for every tensor (:386-417 / :419-454), *_q = round(y - mu) + mu
     @staticmethod
     def _coding_setup(layers):
         from .entropy_coding import _Tables
@@ -515,71 +521,26 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_EntropyLayerBase):
         return plc, (packed, packed16), dims, cs[0].kernel_size[0], cs[0].tap_bits()
 
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
-        """compress_ar for every tensor (:386-417): -> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q])
-        with *_q = round(y - mu) + mu, the values the decoder reconstructs."""
+    def _code_base(layers, ctx, level, y, shape, strings, coder):
+        """The 3x3-crop stacks: csc_xe, and csc_list[L - 1] for the coarsest level."""
         from . import entropy_coding as ec
-        tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
-        L = len(out_xo_list)
-        step = _check_step(step, L, layers)
-        rdo = _check_rdo(rdo, L)
-        with torch.no_grad():
-            s_xe, xe_q = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], out_xe,
-                                            out_xe.shape, tabs, coder=coder)
-            s, q = ec.code_crop_stack(stack, [l.ent_out_xo_list[L - 1] for l in layers], [l.csc_list[L - 1] for l in layers],
-                                      out_xo_list[L - 1], out_xo_list[L - 1].shape, tabs, coder=coder)
-            s_list, q_list = [s], [q]
-            for i in range(L - 2, -1, -1):
-                x = out_xo_list[i]
-                plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, x.shape[2])
-                em_i = [l.ent_out_xo_list[i] for l in layers]
-                st_i = _level_step(step, L, i, x.shape, plc.device)
-                if packed[1] is not None:       # the reference's cgp widths: one fused launch per wavefront step
-                    s, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, x, x.shape, tabs, coder=coder, step=st_i,
-                                              rdo=rdo)
-                else:
-                    s, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, x, x.shape, tabs, coder=coder,
-                                                         step=st_i, rdo=rdo)
-                s_list.append(s)
-                q_list.append(q)
-        s_list.reverse()
-        q_list.reverse()
-        return s_xe, s_list, xe_q, q_list
+        tabs, stack = ctx
+        ems = [l.ent_out_xe if level is None else l.ent_out_xo_list[level] for l in layers]
+        seqs = [l.csc_xe if level is None else l.csc_list[level] for l in layers]
+        return ec.code_crop_stack(stack, ems, seqs, y, shape, tabs, strings, coder=coder)
 
     @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
-        """decompress_ar for every tensor (:419-454): strings -> (xe, [xo] finest first), bit-identical to compress_planes'
-        dequantised tensors.  first_level = k: decode xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}])
-        (_coarse_strings; onlyEZWT.decompress_planes)."""
+    def _code_level(layers, ctx, i, L, parent, y, shape, strings, coder, step, rdo):
         from . import entropy_coding as ec
-        tabs, stack = DWTConditioned2EntropyLayerZTsepSubbands._coding_setup(layers)
-        L = len(shapes_xo)
-        step = _check_step(step, L, layers)
-        strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
-        with torch.no_grad():
-            _, xe = ec.code_crop_stack(stack, [l.ent_out_xe for l in layers], [l.csc_xe for l in layers], None, shape_xe, tabs,
-                                       strings_xe, coder=coder)
-            if first_level == L:
-                return xe, []
-            _, q = ec.code_crop_stack(stack, [l.ent_out_xo_list[L - 1] for l in layers], [l.csc_list[L - 1] for l in layers],
-                                      None, shapes_xo[L - 1], tabs, strings_xo_list[L - 1], coder=coder)
-            q_list = [q]
-            for i in range(L - 2, first_level - 1, -1):
-                plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, q, shapes_xo[i][2])
-                em_i = [l.ent_out_xo_list[i] for l in layers]
-                st_i = _level_step(step, L, i, shapes_xo[i], plc.device)
-                if packed[1] is not None:
-                    _, q = ec.code_tree_level(em_i, plc, packed[1], K, bits, None, shapes_xo[i], tabs, strings_xo_list[i], coder=coder,
-                                              step=st_i)
-                else:
-                    _, q = ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, None, shapes_xo[i], tabs,
-                                                      strings_xo_list[i], coder=coder, step=st_i)
-                q_list.append(q)
-        q_list.reverse()
-        return xe, q_list
+        plc, packed, dims, K, bits = DWTConditioned2EntropyLayerZTsepSubbands._tree_context(layers, i, parent, shape[2])
+        em_i = [l.ent_out_xo_list[i] for l in layers]
+        if packed[1] is not None:       # the reference's cgp widths: one fused launch per wavefront step
+            return ec.code_tree_level(em_i, plc, packed[1], K, bits, y, shape, ctx[0], strings, coder=coder, step=step, rdo=rdo)
+        return ec.code_tree_level_generic(em_i, plc, packed[0], dims, K, bits, y, shape, ctx[0], strings, coder=coder, step=step,
+                                          rdo=rdo)
 
 
-class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
+class DWTConditioned2EntropyLayerZTBlock(_CodedLayer):
     """Block-wise variant (LiftingBasedDWT_net.py:558-757): the four polyphase phases of each subband are predicted in
     sequence from the (not upsampled) parent subband and the phases already coded, by eight 5-layer CNNs (mu / sigma)."""
 
@@ -698,67 +659,16 @@ class DWTConditioned2EntropyLayerZTBlock(_EntropyLayerBase):
             packs.append(cached(layers[0], ("ztblock", i, k), srcs, build))
         return packs
 
+    _coding_setup = _require_clrch1
+
     @staticmethod
-    def compress_planes(layers, out_xe, out_xo_list, coder="host", step=1.0, rdo=None):
-        """-> (strings_xe[p][b], [strings_xo[p][b]] finest first, xe_q, [xo_q] finest first), *_q the decoder's values."""
+    def _code_level(layers, ctx, i, L, parent, y, shape, strings, coder, step, rdo):
         from . import entropy_coding as ec
         cls = DWTConditioned2EntropyLayerZTBlock
-        cls._require_clrch1(layers)
-        L = len(out_xo_list)
-        step = _check_step(step, L, layers)
-        rdo = _check_rdo(rdo, L)
-        with torch.no_grad():
-            s_xe, xe_q = ec.code_factorized([l.ent_out_xe for l in layers], out_xe, out_xe.shape, coder=coder)
-            s, q = ec.code_factorized([l.ent_out_xo for l in layers], out_xo_list[L - 1], out_xo_list[L - 1].shape, coder=coder)
-            s_list, q_list = [s], [q]
-            for i in range(L - 1):
-                x = out_xo_list[L - i - 2]
-                ems, tabs = cls._level_models(layers, i, L)
-                s, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, x.contiguous(), x.shape, tabs, coder=coder,
-                                             step=_level_step(step, L, L - i - 2, x.shape, x.device), rdo=rdo)
-                s_list.append(s)
-                q_list.append(q)
-        s_list.reverse()
-        q_list.reverse()
-        return s_xe, s_list, xe_q, q_list
-
-    @staticmethod
-    def decompress_planes(layers, strings_xe, strings_xo_list, shape_xe, shapes_xo, coder="host", first_level=0, step=1.0):
-        """strings -> (xe, [xo] finest first), bit-identical to compress_planes' dequantised tensors.  first_level = k: decode
-        xe and the levels L-1 .. k only -> (xe, [xo_k .. xo_{L-1}]) (_coarse_strings; onlyEZWT.decompress_planes)."""
-        from . import entropy_coding as ec
-        cls = DWTConditioned2EntropyLayerZTBlock
-        cls._require_clrch1(layers)
-        L = len(shapes_xo)
-        step = _check_step(step, L, layers)
-        strings_xo_list = _coarse_strings(strings_xo_list, L, first_level)
-        with torch.no_grad():
-            _, xe = ec.code_factorized([l.ent_out_xe for l in layers], None, shape_xe, strings_xe, coder=coder)
-            if first_level == L:
-                return xe, []
-            _, q = ec.code_factorized([l.ent_out_xo for l in layers], None, shapes_xo[L - 1], strings_xo_list[L - 1], coder=coder)
-            q_list = [q]
-            for i in range(L - 1 - first_level):          # i counts from the coarse end: level L - i - 2 >= first_level
-                ems, tabs = cls._level_models(layers, i, L)
-                _, q = ec.code_ztblock_level(ems, cls._phase_packs(layers, i), q, None, shapes_xo[L - i - 2], tabs,
-                                             strings_xo_list[L - i - 2], coder=coder,
-                                             step=_level_step(step, L, L - i - 2, shapes_xo[L - i - 2], q.device))
-                q_list.append(q)
-        q_list.reverse()
-        return xe, q_list
-
-    @staticmethod
-    def test_planes(layers, out_xe, out_xo_list):
-        """Encode, then decode FROM THE STRINGS (same contract as the other coded layers' test_planes)."""
-        cls = DWTConditioned2EntropyLayerZTBlock
-        s_xe, s_xo, _, _ = cls.compress_planes(layers, out_xe, out_xo_list)
-        xe, xo = cls.decompress_planes(layers, s_xe, s_xo, out_xe.shape, [t.shape for t in out_xo_list])
-        return s_xe, s_xo, xe, xo
-
-    def test(self, out_xe, out_xo_list):
-        s_xe, s_xo, xe, xo = self.test_planes([self], out_xe[None].contiguous(), [t[None].contiguous() for t in out_xo_list])
-        one = lambda rows: rows[0][0] if len(rows[0]) == 1 else rows[0]
-        return one(s_xe), [one(r) for r in s_xo], xe[0], [t[0] for t in xo]
+        j = L - i - 2                                     # the reference counts the finer levels from the coarse end
+        ems, tabs = cls._level_models(layers, j, L)
+        return ec.code_ztblock_level(ems, cls._phase_packs(layers, j), parent, None if y is None else y.contiguous(), shape, tabs,
+                                     strings, coder=coder, step=step, rdo=rdo)
 
 
 # ------------------------------------------------------------------------------------------------ training path

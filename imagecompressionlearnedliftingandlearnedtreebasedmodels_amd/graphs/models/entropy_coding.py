@@ -89,18 +89,22 @@ class _Sink:
             self.idx.append(idx)
             self.sym.append(sym)
             return sym
-        import ctypes as C
-        from ... import _lib
         ih = np.ascontiguousarray(idx.cpu().numpy(), dtype=np.int32)
         out = np.empty(ih.shape, dtype=np.int32)
+        self.pop(ih.ctypes.data, int(ih.shape[2] * ih.shape[3]), out.ctypes.data)
+        return torch.from_numpy(out).to(idx.device)
+
+    def pop(self, idx_ptr, per, out_ptr):
+        """Decoder: ONE C call that pops the next `per` symbols of every (plane, image) stream.  idx_ptr / out_ptr: addresses of
+        the caller's host int32 buffers, (P*B, per) each (numpy or pinned torch memory)."""
+        import ctypes as C
+        from ... import _lib
         if self._handles is None:
             self._handles = (C.c_void_p * (self.P * self.B))(*[self.dec[p][b]._h for p in range(self.P) for b in range(self.B)])
-        per = int(ih.shape[2] * ih.shape[3])
         pv = lambda a_: a_.ctypes.data_as(C.c_void_p)
-        ops.check(_lib.load().lldwt_rans_decode_multi(self._handles, self.P * self.B, pv(ih), per, per, pv(self.t.cdf),
+        ops.check(_lib.load().lldwt_rans_decode_multi(self._handles, self.P * self.B, C.c_void_p(idx_ptr), per, per, pv(self.t.cdf),
                                                       self.t.cdf.shape[0], self.t.cdf.shape[1], pv(self.t.sizes),
-                                                      pv(self.t.offsets), pv(out)), "rans_decode_multi")
-        return torch.from_numpy(out).to(idx.device)
+                                                      pv(self.t.offsets), C.c_void_p(out_ptr)), "rans_decode_multi")
 
     def note(self, idx_host, sym_host):
         """Decoder of code_tree_level: called with every step's (indexes, symbols) as host int32 arrays once they are decoded.
@@ -223,50 +227,27 @@ def _rdo_args(rdo, tables, dev):
 
 
 def _finish_step(emodel, sink, sigma, mu, yv, step=1.0, rdo=None):
-    """sigma, mu (P,B,g,N); yv (P,B,g,N) or None when decoding -> dequantised values (P,B,g,N).  step != 1: the quantiser
-    of DESIGN.md 7.1.6 restated in fp32 tensor ops (the table entered with sigma / q, round((y - mu) / q), symbol * q + mu).
+    """sigma, mu (P,B,g,N); yv (P,B,g,N) or None when decoding -> dequantised values (P,B,g,N).  The quantiser of DESIGN.md 7.1.6
+    in fp32 tensor ops: the table entered with sigma * inv_q, symbol round((y - mu) * inv_q), value symbol * q + mu.
+    step: a number, or a pair (q, inv_q) of fp32 tensors that broadcast against (P,B,g,N) -- the per-pixel pairs gathered from a
+    step map (_pixel_pairs); the arithmetic is the same, elementwise.  At the unit step the multiplications by
+    1.0f (exact) are left out: the crop stacks always run there, and keep their launch count.
     rdo (encoder only): (k, cost, sizes, offsets) of _rdo_args -- the symbol is chosen by the rule of DESIGN.md 7.1.7, restated
-    in tensor ops (ops.rdo_lookup, ops.rdo_choose).
-    step may also be a pair (q, inv_q) of fp32 tensors that broadcast against (P,B,g,N): the per-pixel pairs gathered from a step
-    map (_pixel_pairs); the arithmetic is the same, elementwise."""
-    if isinstance(step, tuple):
-        q, inv_q = step
-        idx = emodel.build_indexes(sigma * inv_q)
-        sym = None
-        if yv is not None:
-            v = (yv - mu) * inv_q
-            sym = torch.round(v)
-            if rdo is not None:
-                k, cost, sizes, offsets = rdo
-                s1 = sym - torch.sign(sym)
-                sym = ops.rdo_choose(v, sym, ops.rdo_lookup(cost, sizes, offsets, idx, sym), ops.rdo_lookup(cost, sizes, offsets, idx, s1), k)
-            sym = sym.int().permute(0, 1, 3, 2).contiguous()
-        sym = sink.step(idx.permute(0, 1, 3, 2).contiguous(), sym)
-        return sym.permute(0, 1, 3, 2).float() * q + mu
-    if rdo is not None and yv is not None:
-        q, inv_q = ops.step_pair(step)
-        idx = emodel.build_indexes(sigma * inv_q)                                       # (P,B,g,N); does not depend on the choice
-        v = (yv - mu) * inv_q                                                           # the rounded fp32 product
-        s0 = torch.round(v)
-        s1 = s0 - torch.sign(s0)
-        k, cost, sizes, offsets = rdo
-        sym = ops.rdo_choose(v, s0, ops.rdo_lookup(cost, sizes, offsets, idx, s0), ops.rdo_lookup(cost, sizes, offsets, idx, s1), k)
-        sym = sink.step(idx.permute(0, 1, 3, 2).contiguous(), sym.int().permute(0, 1, 3, 2).contiguous())
-        return sym.permute(0, 1, 3, 2).float() * q + mu
-    if step == 1.0:
-        idx = emodel.build_indexes(sigma).permute(0, 1, 3, 2).contiguous()             # (P,B,N,g)
-        sym = None
-        if yv is not None:
-            sym = torch.round(yv - mu).int().permute(0, 1, 3, 2).contiguous()          # quantize(..., "symbols", mu)
-        sym = sink.step(idx, sym)
-        return sym.permute(0, 1, 3, 2).float() + mu                                     # dequantize: symbol + mu
-    q, inv_q = ops.step_pair(step)
-    idx = emodel.build_indexes(sigma * inv_q).permute(0, 1, 3, 2).contiguous()
+    in tensor ops (ops.rdo_lookup, ops.rdo_choose); the index does not depend on the choice."""
+    unit = not isinstance(step, tuple) and step == 1.0
+    q, inv_q = (1.0, 1.0) if unit else step if isinstance(step, tuple) else ops.step_pair(step)
+    idx = emodel.build_indexes(sigma if unit else sigma * inv_q)                       # (P,B,g,N)
     sym = None
     if yv is not None:
-        sym = torch.round((yv - mu) * inv_q).int().permute(0, 1, 3, 2).contiguous()
-    sym = sink.step(idx, sym)
-    return sym.permute(0, 1, 3, 2).float() * q + mu
+        v = yv - mu if unit else (yv - mu) * inv_q                                      # the rounded fp32 product
+        sym = torch.round(v)
+        if rdo is not None:
+            k, cost, sizes, offsets = rdo
+            s1 = sym - torch.sign(sym)
+            sym = ops.rdo_choose(v, sym, ops.rdo_lookup(cost, sizes, offsets, idx, sym), ops.rdo_lookup(cost, sizes, offsets, idx, s1), k)
+        sym = sym.int().permute(0, 1, 3, 2).contiguous()
+    sym = sink.step(idx.permute(0, 1, 3, 2).contiguous(), sym).permute(0, 1, 3, 2).float()      # the sink's layout: (P,B,N,g)
+    return sym + mu if unit else sym * q + mu
 
 
 def _pixel_pairs(smap, h, w):
@@ -323,91 +304,19 @@ def code_tree_level(emodels, plc, packed16, K, tap_bits, y, shape, tables, strin
     taps are gathered from the decoded-so-far tensor, the cgp chain runs on the matrix cores and the epilogue produces CDF
     index, symbol and dequantised value -- no per-step tensor ops on the host side.  Encoder: the launches are queued back to
     back (no synchronisation until the streams are written).  Decoder: per step one launch, the step's indexes down to the
-    host (pinned buffer), ONE C call that pops the step's symbols from every (plane, image) stream, the symbols up, one
-    small launch that writes symbol + mu.  With coder="gpu" the decoder never waits: per step the step kernel, the irans32 pop
-    of every stream and the apply launch are queued back to back, and the streams are checked once at the end of the level.
+    host (pinned buffer), ONE C call that pops the step's symbols from every (plane, image) stream (_Sink.pop), the symbols
+    up, one small launch that writes symbol * q + mu.  With coder="gpu" the decoder never waits: per step the step kernel, the
+    irans32 pop of every stream and the apply launch are queued back to back, and the streams are checked once at the end of
+    the level.  One encoder loop and one decoder loop serve every case; what differs is the pair of launchers chosen per level:
     step: the quantisation step q of DESIGN.md 7.1.6 (lldwt_cgp16_wavefront_step_q / lldwt_wavefront_apply_q; the unit step
     goes through them too and gives the bits of the entry points without a step).
     rdo: the Lagrangian of DESIGN.md 7.1.7 (None or 0: off); the encoder's steps then go through
     lldwt_cgp16_wavefront_step_rdo with the level's cost tables, the decoder ignores it.
     step may be an ops.StepMap over the level: every launch then goes through lldwt_cgp16_wavefront_step_map /
-    lldwt_wavefront_apply_map, with or without the cost tables; the schedule is the same."""
+    lldwt_wavefront_apply_map, with or without the cost tables."""
     import ctypes as C
     from ... import _lib
     lib = _lib.load()
-    P, B, G, H, W = shape
-    if isinstance(step, ops.StepMap):
-        return _code_tree_level_map(lib, emodels, plc, packed16, K, tap_bits, y, shape, tables, strings, coder, step, rdo)
-    q, inv_q = ops.step_pair(step)
-    dev = plc.device
-    slope = K // 2 + 1
-    starts = _step_offsets(H, W, slope)
-    nsteps, ntot = len(starts) - 1, H * W
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    table63 = emodels[0].scale_table.to(dev).float()[:63].contiguous()
-    yhat = torch.zeros(P, B, G, H, W, device=dev, dtype=torch.float32)
-    sink = _make_sink(coder, P, B, tables, strings, ntot * G, dev)
-    ptr = lambda t_: C.c_void_p(t_.data_ptr())
-    if not sink.decoding:
-        yc = y.contiguous()
-        idx_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
-        sym_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
-        ra = _rdo_args(rdo, tables, dev)
-        for t in range(nsteps):
-            if ra is not None:
-                k, cost, csizes, coffs = ra
-                ops.check(lib.lldwt_cgp16_wavefront_step_rdo(ptr(plc), ptr(yhat), ptr(yc), ptr(packed16), ptr(table63), ptr(idx_all),
-                                                             ptr(sym_all), None, None, P, B, H, W, G, K, int(tap_bits), t, ntot,
-                                                             starts[t], q, inv_q, ptr(cost), ptr(csizes), ptr(coffs), cost.shape[0],
-                                                             cost.shape[1], k, st), "cgp16_wavefront_step_rdo")
-                continue
-            ops.check(lib.lldwt_cgp16_wavefront_step_q(ptr(plc), ptr(yhat), ptr(yc), ptr(packed16), ptr(table63), ptr(idx_all),
-                                                       ptr(sym_all), None, None, P, B, H, W, G, K, int(tap_bits), t, ntot, starts[t],
-                                                       q, inv_q, st), "cgp16_wavefront_step")
-        sink.idx, sink.sym = [idx_all], [sym_all]
-        return sink.flush(), yhat
-    nmax = max(starts[t + 1] - starts[t] for t in range(nsteps))
-    Z = P * B
-    idx_d = torch.empty(Z * nmax * G, device=dev, dtype=torch.int32)
-    sym_d = torch.empty(Z * nmax * G, device=dev, dtype=torch.int32)
-    mu_d = torch.empty(Z * G * nmax, device=dev, dtype=torch.float32)
-    if coder == "gpu":
-        for t in range(nsteps):
-            n = starts[t + 1] - starts[t]
-            if n == 0:
-                continue
-            ops.check(lib.lldwt_cgp16_wavefront_step_q(ptr(plc), ptr(yhat), None, ptr(packed16), ptr(table63), ptr(idx_d), None,
-                                                       ptr(mu_d), None, P, B, H, W, G, K, int(tap_bits), t, n, 0, q, inv_q, st),
-                      "cgp16_wavefront_step")
-            sink.dec.pop(idx_d, n * G, n * G, sym_d)
-            ops.check(lib.lldwt_wavefront_apply_q(ptr(sym_d), ptr(mu_d), ptr(yhat), P, B, H, W, G, K, t, n, 0, q, inv_q, st), "wavefront_apply")
-        sink.finish()
-        return None, yhat
-    idx_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
-    sym_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
-    handles = (C.c_void_p * Z)(*[sink.dec[p][b]._h for p in range(P) for b in range(B)])
-    cdf, sizes, offs = tables.cdf, tables.sizes, tables.offsets
-    pv = lambda a_: a_.ctypes.data_as(C.c_void_p)
-    for t in range(nsteps):
-        n = starts[t + 1] - starts[t]
-        if n == 0:
-            continue
-        cnt = Z * n * G
-        ops.check(lib.lldwt_cgp16_wavefront_step_q(ptr(plc), ptr(yhat), None, ptr(packed16), ptr(table63), ptr(idx_d), None, ptr(mu_d),
-                                                   None, P, B, H, W, G, K, int(tap_bits), t, n, 0, q, inv_q, st), "cgp16_wavefront_step")
-        idx_h[:cnt].copy_(idx_d[:cnt], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        ops.check(lib.lldwt_rans_decode_multi(handles, Z, C.c_void_p(idx_h.data_ptr()), n * G, n * G, pv(cdf), cdf.shape[0],
-                                              cdf.shape[1], pv(sizes), pv(offs), C.c_void_p(sym_h.data_ptr())), "rans_decode_multi")
-        sink.note(idx_h[:cnt].numpy(), sym_h[:cnt].numpy())
-        sym_d[:cnt].copy_(sym_h[:cnt], non_blocking=True)
-        ops.check(lib.lldwt_wavefront_apply_q(ptr(sym_d), ptr(mu_d), ptr(yhat), P, B, H, W, G, K, t, n, 0, q, inv_q, st), "wavefront_apply")
-    return None, yhat
-
-
-def _code_tree_level_map(lib, emodels, plc, packed16, K, tap_bits, y, shape, tables, strings, coder, smap, rdo):
-    """code_tree_level with a step map: the same three schedules on the map entry points."""
-    import ctypes as C
     P, B, G, H, W = shape
     dev = plc.device
     starts = _step_offsets(H, W, K // 2 + 1)
@@ -417,23 +326,42 @@ def _code_tree_level_map(lib, emodels, plc, packed16, K, tap_bits, y, shape, tab
     yhat = torch.zeros(P, B, G, H, W, device=dev, dtype=torch.float32)
     sink = _make_sink(coder, P, B, tables, strings, ntot * G, dev)
     ptr = lambda t_: C.c_void_p(t_.data_ptr())
-    m = ops._map_args(smap, B, H, W)
-    no_rdo = (None, None, None, 0, 0, 0.0)
+    ra = None if sink.decoding else _rdo_args(rdo, tables, dev)
+    if ra is not None:
+        k, cost, csizes, coffs = ra
+        ra = (ptr(cost), ptr(csizes), ptr(coffs), cost.shape[0], cost.shape[1], k)
+    # the two launchers of the level.  step_launch: the step kernel on step t -- encoder (yc, sym: all n = ntot pixels of the level
+    # are addressed, the step's start at off) or decoder (mu: the step's n pixels, off = 0); apply_launch: symbol * q + mu
+    if isinstance(step, ops.StepMap):
+        m = ops._map_args(step, B, H, W)
+        rdo_or_none = ra or (None, None, None, 0, 0, 0.0)
 
-    def step_launch(yc, idx, sym, mu, t, n, off, ra):
-        ops.check(lib.lldwt_cgp16_wavefront_step_map(ptr(plc), ptr(yhat), yc, ptr(packed16), ptr(table63), ptr(idx), sym, mu, None, P, B,
-                                                     H, W, G, K, int(tap_bits), t, n, off, *m, *ra, st), "cgp16_wavefront_step_map")
+        def step_launch(yc, idx, sym, mu, t, n, off):
+            ops.check(lib.lldwt_cgp16_wavefront_step_map(ptr(plc), ptr(yhat), yc, ptr(packed16), ptr(table63), ptr(idx), sym, mu, None, P, B,
+                                                         H, W, G, K, int(tap_bits), t, n, off, *m, *rdo_or_none, st), "cgp16_wavefront_step_map")
+
+        def apply_launch(sym, mu, t, n):
+            ops.check(lib.lldwt_wavefront_apply_map(ptr(sym), ptr(mu), ptr(yhat), P, B, H, W, G, K, t, n, 0, *m, st), "wavefront_apply_map")
+    else:
+        q, inv_q = ops.step_pair(step)
+
+        def step_launch(yc, idx, sym, mu, t, n, off):
+            args = (ptr(plc), ptr(yhat), yc, ptr(packed16), ptr(table63), ptr(idx), sym, mu, None, P, B, H, W, G, K, int(tap_bits), t, n,
+                    off, q, inv_q)
+            if ra is not None:
+                ops.check(lib.lldwt_cgp16_wavefront_step_rdo(*args, *ra, st), "cgp16_wavefront_step_rdo")
+            else:
+                ops.check(lib.lldwt_cgp16_wavefront_step_q(*args, st), "cgp16_wavefront_step")
+
+        def apply_launch(sym, mu, t, n):
+            ops.check(lib.lldwt_wavefront_apply_q(ptr(sym), ptr(mu), ptr(yhat), P, B, H, W, G, K, t, n, 0, q, inv_q, st), "wavefront_apply")
 
     if not sink.decoding:
         yc = y.contiguous()
         idx_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
         sym_all = torch.empty(P, B, ntot, G, device=dev, dtype=torch.int32)
-        ra = _rdo_args(rdo, tables, dev)
-        if ra is not None:
-            k, cost, csizes, coffs = ra
-            ra = (ptr(cost), ptr(csizes), ptr(coffs), cost.shape[0], cost.shape[1], k)
         for t in range(nsteps):
-            step_launch(ptr(yc), idx_all, ptr(sym_all), None, t, ntot, starts[t], ra or no_rdo)
+            step_launch(ptr(yc), idx_all, ptr(sym_all), None, t, ntot, starts[t])
         sink.idx, sink.sym = [idx_all], [sym_all]
         return sink.flush(), yhat
     nmax = max(starts[t + 1] - starts[t] for t in range(nsteps))
@@ -445,27 +373,22 @@ def _code_tree_level_map(lib, emodels, plc, packed16, K, tap_bits, y, shape, tab
     if host:
         idx_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
         sym_h = torch.empty(Z * nmax * G, dtype=torch.int32).pin_memory()
-        handles = (C.c_void_p * Z)(*[sink.dec[p][b]._h for p in range(P) for b in range(B)])
-        cdf, sizes, offs = tables.cdf, tables.sizes, tables.offsets
-        pv = lambda a_: a_.ctypes.data_as(C.c_void_p)
     for t in range(nsteps):
         n = starts[t + 1] - starts[t]
         if n == 0:
             continue
-        step_launch(None, idx_d, None, ptr(mu_d), t, n, 0, no_rdo)
+        step_launch(None, idx_d, None, ptr(mu_d), t, n, 0)
         if host:
             cnt = Z * n * G
             idx_h[:cnt].copy_(idx_d[:cnt], non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            ops.check(lib.lldwt_rans_decode_multi(handles, Z, C.c_void_p(idx_h.data_ptr()), n * G, n * G, pv(cdf), cdf.shape[0],
-                                                  cdf.shape[1], pv(sizes), pv(offs), C.c_void_p(sym_h.data_ptr())), "rans_decode_multi")
+            sink.pop(idx_h.data_ptr(), n * G, sym_h.data_ptr())
             sink.note(idx_h[:cnt].numpy(), sym_h[:cnt].numpy())
             sym_d[:cnt].copy_(sym_h[:cnt], non_blocking=True)
         else:
             sink.dec.pop(idx_d, n * G, n * G, sym_d)
-        ops.check(lib.lldwt_wavefront_apply_map(ptr(sym_d), ptr(mu_d), ptr(yhat), P, B, H, W, G, K, t, n, 0, *m, st), "wavefront_apply_map")
-    if not host:
-        sink.finish()
+        apply_launch(sym_d, mu_d, t, n)
+    sink.finish()
     return None, yhat
 
 

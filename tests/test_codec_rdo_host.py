@@ -148,6 +148,42 @@ def test_restatement_equals_the_float64_lagrangian(m, n16):
     assert (got != s0n).any() and all((s0n[0, 0, j] != 0).any() for j in range(len(SIGMAS)))     # every sigma takes part
 
 
+def test_unit_step_is_the_literal_quantiser():
+    """At step 1 the one body of _finish_step gives what compressai's contract states without a step: build_indexes(sigma),
+    round(y - mu), symbol + mu -- no product with 1 is needed for that (it would be exact anyway)."""
+    em = _model()[0]
+    sigma, mu, y = (t[..., :5000] for t in _draws(16))
+    sink = _Keep()
+    val = ec._finish_step(em, sink, sigma, mu, y)
+    sym = torch.round(y - mu)
+    assert torch.equal(sink.idx, em.build_indexes(sigma).permute(0, 1, 3, 2))
+    assert sink.sym.dtype == torch.int32 and torch.equal(sink.sym, sym.int().permute(0, 1, 3, 2))
+    assert torch.equal(val, sym + mu)
+    again = _Keep()
+    assert torch.equal(ec._finish_step(em, again, sigma, mu, y, 1.0), val) and torch.equal(again.sym, sink.sym)
+
+
+@pytest.mark.parametrize("n16", [16, 23, 40])
+@pytest.mark.parametrize("rdo", [False, True])
+def test_scalar_step_equals_the_same_step_as_constant_pairs(n16, rdo):
+    """A number and the pair of constant tensors holding ops.step_pair of it go through the same arithmetic: equal indexes,
+    symbols and values, with the rule of 7.1.7 and without."""
+    em, _, (cost, sizes, offsets) = _model()
+    sigma, mu, y = (t[..., :20000] for t in _draws(n16))
+    ra = (ops.rdo_scale(13 / 64), cost, sizes, offsets) if rdo else None
+    q, inv_q = ops.step_pair(n16 / 16.0)
+    pair = (torch.full((1, 1, 1, y.shape[3]), q), torch.full((1, 1, 1, y.shape[3]), inv_q))
+    a, b = _Keep(), _Keep()
+    va = ec._finish_step(em, a, sigma, mu, y, n16 / 16.0, ra)
+    vb = ec._finish_step(em, b, sigma, mu, y, pair, ra)
+    assert torch.equal(a.idx, b.idx) and torch.equal(a.sym, b.sym) and torch.equal(va, vb)
+    assert bool((a.sym != 0).any())
+    if rdo:
+        plain = _Keep()
+        ec._finish_step(em, plain, sigma, mu, y, n16 / 16.0)
+        assert not torch.equal(plain.sym, a.sym)                                 # the rule took part
+
+
 def test_lookup_and_choice_on_a_small_table():
     """The lookup's four exits and the choice's sign handling, by hand: table 0 holds symbols -1 .. 2, table 1 symbol 5 only."""
     cost = torch.tensor([[3 << 16, 1 << 16, 2 << 16, 6 << 16, 0], [1 << 16, 0, 0, 0, 0]], dtype=torch.int32)
