@@ -63,6 +63,13 @@ SIGNATURES = {
     "lldwt_ycc420_tiles_to_u8hwc": (_i, [_p, _p, _p] + [_i64] * 13 + [_p, _p, _p, _p]),
     "lldwt_u8hw_to_y_tiles": (_i, [_p, _p] + [_i64] * 9 + [_p]),
     "lldwt_y_tiles_to_u8hw": (_i, [_p, _p] + [_i64] * 13 + [_p, _p, _p, _p]),
+    "lldwt_u16hwc_to_ycc_tiles": (_i, [_p, _p] + [_i64] * 9 + [_i, _p, _p]),
+    "lldwt_ycc_tiles_to_u16hwc": (_i, [_p, _p] + [_i64] * 13 + [_p, _p, _i, _p, _p]),
+    "lldwt_u16hwc_to_ycc420_tiles": (_i, [_p, _p, _p] + [_i64] * 9 + [_i, _p, _p]),
+    "lldwt_ycc420_tiles_to_u16hwc": (_i, [_p, _p, _p] + [_i64] * 13 + [_p, _p, _i, _p, _p]),
+    "lldwt_u16hw_to_y_tiles": (_i, [_p, _p] + [_i64] * 9 + [_i, _p, _p]),
+    "lldwt_y_tiles_to_u16hw": (_i, [_p, _p] + [_i64] * 13 + [_p, _p, _i, _p, _p]),
+    "lldwt_u16hwc_to_f32chw": (_i, [_p, _p] + [_i64] * 3 + [_i, _p, _p]),
     "lldwt_pblock_packed_floats": (_i64, [_i, _i]),
     "lldwt_set_lift_mode": (_i, [_i]),
     "lldwt_set_diagnostics": (_i, [_i, _p, _i64, _i]),

@@ -164,6 +164,18 @@ header holds ``chroma`` only when the key is present (readers use ``hdr.get("chr
 ``step``, ``target_bytes``, ``rdo``, tiles, ``region``, ``tiles_per_call`` and ``reduce``; excludes ``near``, ``layers``,
 ``step_map``, ``overlap > 0`` and the quality targets, and LLDR / LLDQ / LLDP / LLDO containers over such a base are refused.
 
+Sample depth (``encode_images(..., depth=d)``, the same on ``encode_tiled``): d in 9..16 codes ``torch.uint16``
+tensors of d-bit samples, (B,H,W,3) or with ``chroma="400"`` (B,H,W,1).  A sample is v / M with M = 2^d - 1 in fp32, a true
+division, followed by exactly the colour expressions of the uint8 kernels; the decoder stores floor((c + 0.5) * M + 0.5) as
+uint16 (csrc/depth.hip; tests/depth_ref.py states both in torch).  A sample above M is a ValueError naming depth, found by the
+input kernels.  The depth is one more key of the arithmetic string, ``depth=<d>``, absent for 8: ``depth=None`` and ``8`` take
+uint8 and write the containers above byte for byte, and a parsed header holds ``depth`` only when the key is present (readers
+use ``hdr.get("depth", 8)``; the pinned header fixtures hold exactly the keys they held).  Nothing below
+the image boundary changes, so a depth-16 image holding v8 * 257 has the streams of the uint8 image v8 (65535 = 255 * 257).
+Composes with ``coder``, ``step``, ``target_bytes``, ``rdo``, ``chroma``, tiles, ``region``, ``tiles_per_call`` and ``reduce``;
+excludes ``near``, ``layers``, ``step_map``, ``overlap > 0`` and the quality targets, and LLDR / LLDQ / LLDP / LLDO containers
+over such a base are refused.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -340,6 +352,50 @@ def _no_chroma(bh, what):
         raise ValueError("chroma: the base container is coded with chroma=%s, which does not compose with %s" % (bh["chroma"], what))
 
 
+# sample depth: 8 is the uint8 path and writes no key; the arithmetic string's "depth" key holds 9 .. 16
+DEPTH_MIN, DEPTH_MAX = 9, 16
+
+
+def check_depth(depth):
+    """The depth argument of the API -> 8 (None or 8: uint8 samples) or the bit depth 9 .. 16 of uint16 samples.  ValueError
+    naming depth otherwise."""
+    if depth is None:
+        return 8
+    if isinstance(depth, bool) or not isinstance(depth, int) or not (depth == 8 or DEPTH_MIN <= depth <= DEPTH_MAX):
+        raise ValueError("depth must be None or an integer in [8, %d] (got %r)" % (DEPTH_MAX, depth))
+    return depth
+
+
+def _split_depth(arith):
+    """arithmetic string -> (depth, the string without the depth key); 8 when the key is absent.  ValueError naming depth if the
+    key occurs twice or its value is not a canonical decimal integer in [9, 16] (8 bits are written by leaving the key out)."""
+    parts = arith.split(",") if arith else []
+    vals = [p[len("depth="):] for p in parts if p.startswith("depth=")]
+    if not vals:
+        return 8, arith
+    ok = len(vals) == 1 and vals[0].isascii() and vals[0].isdigit() and vals[0] == str(int(vals[0])) \
+        and DEPTH_MIN <= int(vals[0]) <= DEPTH_MAX
+    if not ok:
+        raise ValueError("depth: bad sample depth %r in the arithmetic string (an integer in [%d, %d], once; 8 bits have no key)"
+                         % (",".join(vals), DEPTH_MIN, DEPTH_MAX))
+    return int(vals[0]), ",".join(p for p in parts if not p.startswith("depth="))
+
+
+def _with_depth(arith, depth):
+    """The arithmetic string (without a depth key) with the key of the depth merged in at its sorted place; None and 8: unchanged."""
+    d = check_depth(depth)
+    if d == 8:
+        return arith
+    return ",".join(sorted((arith.split(",") if arith else []) + ["depth=%d" % d]))
+
+
+def _no_depth(bh, what):
+    """Refuses a base header that carries a depth key under a wrapper or lapped container (``what`` names it and the argument
+    it stands for): those layers are built for 8-bit samples."""
+    if bh.get("depth", 8) != 8:
+        raise ValueError("depth: the base container is coded with depth=%d, which does not compose with %s" % (bh["depth"], what))
+
+
 def _blocks(v, L):
     """ceil(v / 2^L): blocks of a step map along a side of v pixels."""
     return -(-int(v) >> L)
@@ -416,6 +472,7 @@ def pack_mapped(map_n, inner):
         raise ValueError("inner container: a step map goes over an LLDW, LLDT, LLDO or LLDR container")
     bh = _base_header(read_header(inner))
     _no_chroma(bh, "a step map (step_map)")
+    _no_depth(bh, "a step map (step_map)")
     L, hb, wb = bh["dwtlevels"], a.shape[0], a.shape[1]
     if (hb, wb) != (_blocks(bh["H"], L), _blocks(bh["W"], L)) or hb > 0xFFFF or wb > 0xFFFF:
         raise ValueError("hb, wb: a %d x %d map for an inner container of %d x %d pixels at %d levels" % (hb, wb, bh["H"], bh["W"], L))
@@ -491,6 +548,7 @@ def parse_mapped(blob):
     ih = parse_refined(inner, check_tables=False)[0] if _magic(inner) == REFINED_MAGIC else _parse_base(_magic(inner), inner)[0]
     bh = _base_header(ih)
     _no_chroma(bh, "a step map (step_map)")
+    _no_depth(bh, "a step map (step_map)")
     if block != bh["dwtlevels"]:
         raise ValueError("block log2: the container holds %d, the inner container has dwtlevels %d" % (block, bh["dwtlevels"]))
     if block < 2:
@@ -691,6 +749,9 @@ def _pack_base(magic, hdr, units):
     version, fixed = _BASE[magic]
     L, grid = hdr["dwtlevels"], ()
     chroma = _split_chroma(hdr["arithmetic"])[0]
+    depth = _split_depth(hdr["arithmetic"])[0]
+    if magic == LAPPED_MAGIC and depth != 8:
+        raise ValueError("depth: depth=%d does not compose with lapped tiles (overlap)" % depth)
     if magic == MAGIC:
         count = len(units[0])
     else:
@@ -722,6 +783,9 @@ def _parse_base(magic, blob):
     _check_model_fields(layer, nettype, L, H, W)
     arith, digest, count, pos = _parse_identity(blob, fixed.size, end)
     chroma, _ = _split_chroma(arith)
+    depth, _ = _split_depth(arith)
+    if magic == LAPPED_MAGIC and depth != 8:
+        raise ValueError("depth: the container is coded with depth=%d, which does not compose with lapped tiles (overlap)" % depth)
     if magic == LAPPED_MAGIC and chroma != "444":
         raise ValueError("chroma: the container is coded with chroma=%s, which does not compose with lapped tiles (overlap)"
                          % chroma)
@@ -738,6 +802,8 @@ def _parse_base(magic, blob):
     hdr = dict(version=version, layer=_LAYER_NAMES[layer], netType=_NETTYPE_NAMES[nettype], dwtlevels=L, H=H, W=W,
                numerics=numerics, arithmetic=arith, coder=coder, step=step_n / STEP_DENOM, digest=digest,
                stream_lengths=lengths, header_bytes=end - sum(lengths))
+    if depth != 8:                                    # only with the key, like chroma: a key-less header is what it was
+        hdr["depth"] = depth
     if chroma != "444":                               # only with the key: a key-less header is what it was
         hdr["chroma"] = chroma
     if grid:
@@ -790,6 +856,7 @@ def pack_refined(near, table_crc, base, units):
         raise ValueError("base container: a residual layer goes over an LLDW or LLDT container")
     bh = read_header(base)
     _no_chroma(bh, "a residual layer (near)")
+    _no_depth(bh, "a residual layer (near)")
     if len(units) != bh.get("ny", 1) * bh.get("nx", 1):
         raise ValueError("unit count: %d units for a base of %d" % (len(units), bh.get("ny", 1) * bh.get("nx", 1)))
     body = bytearray(_RFIXED.pack(REFINED_MAGIC, REFINED_FORMAT_VERSION, int(near), CLASSES, LADDER_ID,
@@ -833,6 +900,7 @@ def parse_refined(blob, check_tables=True):
         raise ValueError("base container: a residual layer goes over an LLDW or LLDT container (got magic %r)" % base[:4])
     bh = read_header(base)
     _no_chroma(bh, "a residual layer (near)")
+    _no_depth(bh, "a residual layer (near)")
     pos += blen
     count = struct.unpack_from("<I", blob, pos)[0]
     pos += 4
@@ -886,6 +954,7 @@ def pack_layered(table_crc, base, layers):
         raise ValueError("base container: quality layers go over an LLDW or LLDT container")
     bh = read_header(base)
     _no_chroma(bh, "quality layers (layers)")
+    _no_depth(bh, "quality layers (layers)")
     m = len(layers)
     _check_layered_base(bh, m)
     units, per = bh.get("ny", 1) * bh.get("nx", 1), _PLANES * (bh["dwtlevels"] - 1)
@@ -921,6 +990,7 @@ def parse_layered(blob, check_tables=True):
         raise ValueError("base container: quality layers go over an LLDW or LLDT container (got magic %r)" % base[:4])
     bh = read_header(base)
     _no_chroma(bh, "quality layers (layers)")
+    _no_depth(bh, "quality layers (layers)")
     _check_layered_base(bh, m)
     pos += blen
     base_end = pos
@@ -1000,12 +1070,13 @@ def reduce_bytes(hdr):
 
 
 # ------------------------------------------------------------------------------------------------ model identity
-def arithmetic_string(coder="host", step=None, qmap=None, chroma=None):
+def arithmetic_string(coder="host", step=None, qmap=None, chroma=None, depth=None):
     """Canonical "key=value,..." of every process switch that selects the arithmetic of the coding context path, plus the
     entropy coder: ``coder=irans32`` for coder="gpu", no key for the host coder (so the host string is unchanged), plus the
     quantisation step: ``step=<n>`` for step = n / 16 other than 1, no key for None or 1; or, for a step map,
     ``qmap=<8 hex digits>`` of its CRC (qmap: the CRC as an int), which excludes a step; plus the chroma format:
-    ``chroma=420`` or ``chroma=400``, no key for None or "444" (DESIGN.md 7.1.11).
+    ``chroma=420`` or ``chroma=400``, no key for None or "444" (DESIGN.md 7.1.11); plus the sample depth: ``depth=<d>`` for
+    d in 9 .. 16, no key for None or 8.
     Which reach which layer (the others are carried along, harmlessly):
       plc_mode, plc_fuse, plc_algo, plc_shape, storage -- the tree-context pair: conditioned2ZTsepSubbands, onlyEZWT;
       precision -- the split-fp16 pair and cgp chain (conditioned2ZTsepSubbands, onlyEZWT) and the lifting steps (all);
@@ -1021,15 +1092,16 @@ def arithmetic_string(coder="host", step=None, qmap=None, chroma=None):
         kv.append(("coder", CODER_KEYS[coder]))
     if qmap is not None and check_step(step) != STEP_DENOM:
         raise ValueError("step and step_map: give one of them (the map holds every step)")
-    return _with_chroma(_with_qmap(_with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step)), qmap), chroma)
+    return _with_depth(_with_chroma(_with_qmap(_with_step(",".join("%s=%s" % p for p in sorted(kv)), check_step(step)), qmap),
+                                    chroma), depth)
 
 
 def _batch_invariant(arith):
     """True when the coding path is per image in this arithmetic, so images can be coded together.  Not so when the
     non-fused split-fp16 pair takes its operand scale from an absmax over the whole batch (plc_fuse=0), or with fp16
     storage (a bound over the batch's parents); the one-product precisions are not verified.  Otherwise: one image per call."""
-    # neither the coder nor the step(s) nor the chroma format change what a batch shares
-    arith = _split_chroma(_split_qmap(_split_step(_split_coder(arith)[1])[1])[1])[1]
+    # neither the coder nor the step(s) nor the chroma format nor the sample depth change what a batch shares
+    arith = _split_depth(_split_chroma(_split_qmap(_split_step(_split_coder(arith)[1])[1])[1])[1])[1]
     d = dict(p.split("=") for p in arith.split(","))
     if d["precision"] != "f16x3" or d["storage"] != "fp32":
         return False
@@ -1099,12 +1171,21 @@ def describe(net):
 
 
 # ------------------------------------------------------------------------------------------------ public API
-def _check_images(images_u8, chroma="444"):
+def _check_images(images_u8, chroma="444", depth=8):
+    """The image batch of an encode or of ``quality`` -> (B, H, W).  depth: 8 takes uint8, 9 .. 16 take uint16 (DESIGN.md 7.1.12);
+    a tensor of the other type is a ValueError naming depth."""
     import torch
     ch = 1 if chroma == "400" else 3
-    if not (isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
+    if isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint16 and depth == 8:
+        raise ValueError("depth: a uint16 tensor needs depth=<bits per sample> in [%d, %d]" % (DEPTH_MIN, DEPTH_MAX))
+    if isinstance(images_u8, torch.Tensor) and images_u8.dtype == torch.uint8 and depth != 8:
+        raise ValueError("depth: depth=%d takes a uint16 tensor (got uint8; 8-bit samples need no depth)" % depth)
+    dt = torch.uint8 if depth == 8 else torch.uint16
+    if not (isinstance(images_u8, torch.Tensor) and images_u8.dtype == dt and images_u8.dim() == 4
             and images_u8.shape[3] == ch):
-        raise ValueError("images must be a (B,H,W,%d) uint8 tensor%s" % (ch, "" if chroma == "444" else " with chroma=%s" % chroma))
+        raise ValueError("images must be a (B,H,W,%d) %s tensor%s%s" % (ch, "uint8" if depth == 8 else "uint16",
+                                                                        "" if chroma == "444" else " with chroma=%s" % chroma,
+                                                                        "" if depth == 8 else " with depth=%d" % depth))
     B, H, W, _ = images_u8.shape
     if B < 1 or H < 1 or W < 1 or H >= 1 << 32 or W >= 1 << 32:
         raise ValueError("bad image batch shape %s" % (tuple(images_u8.shape),))
@@ -1119,24 +1200,41 @@ def msssim_db(m):
     return float("inf") if m >= 1.0 else -10.0 * math.log10(1.0 - m)
 
 
-def quality(a_u8, b_u8):
+def _check_range(flag, depth):
+    """Reads the range flag of the uint16 input kernels (a synchronisation): ValueError naming depth when one of them met a
+    sample above 2^depth - 1 (an error, not a clamp)."""
+    if int(flag.item()):
+        raise ValueError("depth: the images hold a sample above %d = 2^%d - 1, the largest of depth=%d"
+                         % ((1 << depth) - 1, depth, depth))
+
+
+def quality(a_u8, b_u8, depth=None):
     """PSNR and MS-SSIM of image pairs: (B,H,W,3) or (H,W,3) uint8 RGB tensors of one shape, on the host or the device.
     -> {"psnr": ..., "msssim": ...} with one Python float per image (lists for a batch, plain values for a single (H,W,3)
     pair).  PSNR is 10 log10(1 / mse) on values in [0,1] over the three channels, inf for identical images; MS-SSIM is the
-    mean over the channels (ops.ms_ssim, five scales), None when a side is below its minimum of 161."""
+    mean over the channels (ops.ms_ssim, five scales), None when a side is below its minimum of 161.
+    depth = d in 9..16: uint16 tensors of d-bit samples, v / (2^d - 1) in [0,1], so the PSNR is
+    10 log10(M^2 3 H W / SSE) of the samples; a sample above 2^d - 1 is a ValueError naming depth."""
     import math
     import torch
     from . import ops
     single = isinstance(a_u8, torch.Tensor) and a_u8.dim() == 3
     if single:
         a_u8, b_u8 = a_u8[None], (b_u8[None] if isinstance(b_u8, torch.Tensor) and b_u8.dim() == 3 else b_u8)
-    B, H, W = _check_images(a_u8)
-    _check_images(b_u8)
+    d = check_depth(depth)
+    B, H, W = _check_images(a_u8, depth=d)
+    _check_images(b_u8, depth=d)
     if tuple(a_u8.shape) != tuple(b_u8.shape):
         raise ValueError("quality: the images differ in shape: %s and %s" % (tuple(a_u8.shape), tuple(b_u8.shape)))
     dev = a_u8.device if a_u8.is_cuda else (b_u8.device if b_u8.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    a = ops.u8hwc_to_f32chw(a_u8.to(dev).contiguous())                                # (B,3,H,W) in [0,1]
-    b = ops.u8hwc_to_f32chw(b_u8.to(dev).contiguous())
+    if d == 8:
+        a = ops.u8hwc_to_f32chw(a_u8.to(dev).contiguous())                            # (B,3,H,W) in [0,1]
+        b = ops.u8hwc_to_f32chw(b_u8.to(dev).contiguous())
+    else:
+        flag = ops.depth_flag(dev)
+        a = ops.u16hwc_to_f32chw(a_u8.to(dev).contiguous(), d, flag)
+        b = ops.u16hwc_to_f32chw(b_u8.to(dev).contiguous(), d, flag)
+        _check_range(flag, d)
     sq = torch.zeros(B, dtype=torch.float64, device=dev)
     for i in range(B):
         ops.sq_err_sum(a[i], b[i], sq[i:i + 1])
@@ -1206,6 +1304,23 @@ def _chroma_args(chroma, near=None, layers=None, step_map=None, overlap=0, targe
     if overlap:
         raise ValueError("chroma and overlap: chroma=%s over lapped tiles (overlap > 0) is not defined; use overlap=0" % ch)
     return ch
+
+
+def _depth_args(depth, near=None, layers=None, step_map=None, overlap=0, target_psnr=None, target_msssim=None):
+    """The depth argument of encode_images / encode_tiled, checked on the host before any GPU work -> 8, or d in 9 .. 16.
+    ValueError naming depth and the other argument for what more than 8 bits do not compose with: near (the
+    residual ladder and its histogram are built for 511 bins), layers, step_map, overlap > 0, target_psnr and target_msssim
+    (their kernels measure and blend bytes)."""
+    d = check_depth(depth)
+    if d == 8:
+        return d
+    for name, val in (("near", near), ("layers", layers), ("step_map", step_map), ("target_psnr", target_psnr),
+                      ("target_msssim", target_msssim)):
+        if val is not None and not (name == "layers" and not isinstance(val, bool) and val == 0):
+            raise ValueError("depth and %s: depth=%d does not compose with %s; it is defined for 8-bit samples" % (name, d, name))
+    if overlap:
+        raise ValueError("depth and overlap: depth=%d over lapped tiles (overlap > 0) is not defined; use overlap=0" % d)
+    return d
 
 
 def _rate_args(step, target_bytes, near, L):
@@ -1409,7 +1524,7 @@ def _estimated_size(empty, estimates):
 
 
 def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None,
-                  layers=None, chroma="444", target_psnr=None, target_msssim=None):
+                  layers=None, chroma="444", depth=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -1438,11 +1553,15 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     chroma: "444" (the default) codes three full-size planes and writes the bytes above; "420" codes Y at full
     and Cb, Cr at half size (the chroma is averaged over 2 x 2 pixels and interpolated back on decoding); "400" takes a
     (B,H,W,1) greyscale tensor and codes one plane.  The format is one more key of the arithmetic string and the decoders read
-    it from the header.  With coder, step, target_bytes and rdo; not with near, layers, step_map or a quality target."""
+    it from the header.  With coder, step, target_bytes and rdo; not with near, layers, step_map or a quality target.
+    depth: None and 8 take uint8 and write the bytes above; d in 9..16 takes a uint16 tensor of d-bit samples
+    (a sample above 2^d - 1 is a ValueError naming depth), recorded as one more key of the arithmetic string; the decoders then
+    return uint16.  With coder, step, target_bytes, rdo and chroma; not with near, layers, step_map or a quality target."""
     from .graphs.layers.lifting_dwt_nets import padded_size
     ch = _chroma_args(chroma, near, layers, step_map, 0, target_psnr, target_msssim)
+    d = _depth_args(depth, near, layers, step_map, 0, target_psnr, target_msssim)
     layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8, ch)
+    B, H, W = _check_images(images_u8, ch, d)
     m = _layer_args(layers, step, L, near, step_map, 0, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
@@ -1455,20 +1574,21 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
         Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
     else:
         Hp, Wp, _, _ = chroma_sizes(L, nettype == "CDF97", H, W, ch)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m, ch)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m, ch, d)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0, chroma="444"):
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0, chroma="444", depth=8):
     """_encode at the step step_n / 16, or with a byte target T the search of _search_step, or with a quality target (the
     pair of _quality_args) that of _encode_at_quality, one image at a time.  walk: the (magic, grid, group, coder) of _encode.
     rdo: probes and real encodes alike.  layers: the number of quality layers (_layer_args: no target then).  chroma: the
-    format of _chroma_args (not "444": no near, maps, quality target or layers)."""
+    format of _chroma_args (not "444": no near, maps, quality target or layers).  depth: that of _depth_args (not 8: the same)."""
     if target is not None:
         return _encode_at_quality(net, images_u8, walk, rdo, target)
+    kw = dict(rdo=rdo, chroma=chroma, depth=depth)
     if T is None:
-        return _encode(net, images_u8, *walk, near, step_n, rdo=rdo, maps=maps, layers=layers, chroma=chroma)
-    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, rdo=rdo, chroma=chroma)[0],
-                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, rdo=rdo, chroma=chroma)[0], T)
+        return _encode(net, images_u8, *walk, near, step_n, maps=maps, layers=layers, **kw)
+    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, **kw)[0],
+                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, **kw)[0], T)
             for b in range(images_u8.shape[0])]
 
 
@@ -1565,24 +1685,39 @@ def _gather_layers(units, k, L):
             for jj in range(len(units[0]))]
 
 
-def _encode_chroma_planes(nets, img, chroma, grid, first, n, **kw):
+def _cut_tiles(img, chroma, grid, first, n, depth=8, flag=None):
+    """The input step of every encode: the tiles first .. first+n-1 of the grid cut out of the image batch as the nets' fp32
+    planes -- (3,n,1,th,tw) for "444", (luma, chroma planes) for "420", (1,n,1,th,tw) for "400" -- by the uint8 kernels, or at
+    depth 9 .. 16 by their uint16 siblings with the encode's range flag."""
+    from . import ops
+    th, tw, ny, nx, ov = grid
+    deep = () if depth == 8 else (depth, flag)
+    if ov:
+        return ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)      # _depth_args: 8 bits only
+    if chroma == "400":
+        return (ops.u16hw_to_y_tiles if deep else ops.u8hw_to_y_tiles)(img, th, tw, ny, nx, first, n, *deep)
+    if chroma == "420":
+        return (ops.u16hwc_to_ycc420_tiles if deep else ops.u8hwc_to_ycc420_tiles)(img, th, tw, ny, nx, first, n, *deep)
+    return (ops.u16hwc_to_ycc_tiles if deep else ops.u8hwc_to_ycc_tiles)(img, th, tw, ny, nx, first, n, *deep)
+
+
+def _encode_chroma_planes(nets, planes, chroma, **kw):
     """One group of tiles of a 4:2:0 or 4:0:0 encode -> (s_xe, s_xo) with one entry per coded plane, as
     encode_strings_planes gives them for three planes.  Luma goes through nets[0:1] at (th, tw); Cb and Cr share one two-plane
     call through nets[1:3] at (th / 2, tw / 2).  The coding path is per plane, so a plane's streams are those of coding it
-    alone, encode_strings_planes([nets[p]], x_p, ...) (tests/test_gpu_codec_chroma.py holds them to that).  kw: coder, step, rdo."""
-    from . import ops
+    alone, encode_strings_planes([nets[p]], x_p, ...) (tests/test_gpu_codec_chroma.py holds them to that).  planes: the
+    group's tiles as _cut_tiles gives them for the format.  kw: coder, step, rdo."""
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
-    th, tw, ny, nx, _ = grid
     if chroma == "400":
-        return encode_strings_planes(nets[0:1], ops.u8hw_to_y_tiles(img, th, tw, ny, nx, first, n), **kw)[:2]
-    luma, chr2 = ops.u8hwc_to_ycc420_tiles(img, th, tw, ny, nx, first, n)
+        return encode_strings_planes(nets[0:1], planes, **kw)[:2]
+    luma, chr2 = planes
     y_xe, y_xo = encode_strings_planes(nets[0:1], luma, **kw)[:2]
     c_xe, c_xo = encode_strings_planes(nets[1:3], chr2, **kw)[:2]
     return list(y_xe) + list(c_xe), [list(a) + list(b) for a, b in zip(y_xo, c_xo)]
 
 
 def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=False, rdo=None, maps=None, layers=0,
-            chroma="444"):
+            chroma="444", depth=8):
     """The encode walk behind encode_images and encode_tiled (arguments checked there): the batch is cut into the tiles of
     grid = (th, tw, ny, nx, ov) -- the untiled codec is the 1 x 1 grid of one padded_size tile, which the untiled input and
     output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
@@ -1594,17 +1729,19 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     layers: m > 0 quality layers (without near, maps or estimate): every group's layer streams are coded right
     after its base, from the group's own tensors, and the containers are wrapped into LLDP (pack_layered).
     chroma: "420" / "400" (without near, maps, layers or overlap): the same walk, each group cut and coded
-    plane by plane (_encode_chroma_planes), the streams interleaved into the LLDW order, the header carrying the chroma key."""
+    plane by plane (_encode_chroma_planes), the streams interleaved into the LLDW order, the header carrying the chroma key.
+    depth: 9 .. 16 (without near, maps, layers or overlap): the same walk on uint16 samples, cut by the uint16
+    input kernels (_cut_tiles), whose range flag is read after every cut, before the group is coded."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
     from .graphs.models.entropy_coding import ESTIMATE
     layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8, chroma)
+    B, H, W = _check_images(images_u8, chroma, depth)
     th, tw, ny, nx, ov = grid
     nets = net.nets()
     step = step_n / STEP_DENOM
-    arith = arithmetic_string(coder, step, chroma=chroma)
+    arith = arithmetic_string(coder, step, chroma=chroma, depth=depth)
     planes = CHROMA_PLANES[chroma]
     _prepare(net)
     hdr = dict(layer=layer, netType=nettype, dwtlevels=L, H=H, W=W, th=th, tw=tw, ny=ny, nx=nx, overlap=ov,
@@ -1617,18 +1754,17 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     g = group if _batch_invariant(arith) else 1
     tiles, unit_layers = [], []
     xh = torch.empty_like(img) if near is not None else None
+    flag = None if depth == 8 else ops.depth_flag(dev)
     with torch.no_grad():
         for first in range(0, B * per, g):
             n = min(g, B * per - first)
+            x = _cut_tiles(img, chroma, grid, first, n, depth, flag)                  # "444": (3,n,1,th,tw)
+            if flag is not None:                      # before the nets see the group: a sample past the range is an error
+                _check_range(flag, depth)
             if chroma != "444":
-                s_xe, s_xo = _encode_chroma_planes(nets, img, chroma, grid, first, n, coder=ESTIMATE if estimate else coder,
-                                                   step=step, rdo=rdo)
+                s_xe, s_xo = _encode_chroma_planes(nets, x, chroma, coder=ESTIMATE if estimate else coder, step=step, rdo=rdo)
                 tiles += [_tile_streams(s_xe, s_xo, j, planes) for j in range(n)]
                 continue
-            if ov:
-                x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
-            else:
-                x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)             # (3,n,1,th,tw)
             st = step if maps is None else _unit_maps(maps, range(first, first + n), grid, L, dev)
             if layers:
                 s_xe, s_xo, lay = encode_strings_planes(nets, x, coder=coder, step=st, rdo=rdo, layers=(step_n, layers))
@@ -1664,6 +1800,7 @@ def check_header(hdr, layer, nettype, L, digest, arith, qmap=None):
     _, hdr_arith = _split_coder(hdr["arithmetic"])
     _, hdr_arith = _split_step(hdr_arith)
     _, hdr_arith = _split_chroma(hdr_arith)             # the chroma format selects planes and sizes, not arithmetic
+    _, hdr_arith = _split_depth(hdr_arith)              # the sample depth selects the boundary kernels, not arithmetic
     key, hdr_arith = _split_qmap(hdr_arith)
     if key != qmap:
         if qmap is None:
@@ -1731,7 +1868,9 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
     are never touched.  ``layers`` above a container's count, or other than None / 0 for a container without layers, is a
     ValueError.
     A container coded with chroma="420" decodes to (H,W,3), one coded with chroma="400" to (H,W,1); the
-    format comes from the header, containers are grouped by it as well, and a mix comes back in input order."""
+    format comes from the header, containers are grouped by it as well, and a mix comes back in input order.
+    A container coded with depth=d decodes to a uint16 tensor of d-bit samples; the depth comes from the
+    header, and containers of different depths in one call are a ValueError naming depth (a list of one dtype comes back)."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
@@ -1763,6 +1902,11 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
             if refine and k == 0:
                 refined[i] = (rhdr["near"], units)
     parsed = [parse_container(b) for b in blobs]
+    depths = sorted({hdr.get("depth", 8) for hdr, _ in parsed})
+    if len(depths) > 1:
+        raise ValueError("depth: the containers hold samples of %s bits; decode one depth per call"
+                         % " and ".join(str(d) for d in depths))
+    depth = depths[0] if depths else 8
     digest, arith = weights_digest(net), arithmetic_string()
     for i, (hdr, _) in enumerate(parsed):
         check_header(hdr, layer, nettype, L, digest, arith, qmap=map_crc(maps[i]) if i in maps else None)
@@ -1781,14 +1925,16 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
             units = [parsed[i][1] for i in idx]
             if chroma != "444":                       # the 1 x 1 grid of the format's padded size
                 Hp, Wp, _, _ = chroma_sizes(L, nettype == "CDF97", H, W, chroma)
+            else:
+                Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
+            if chroma != "444" or depth != 8:         # no step map, layers or residual here (_chroma_args, _depth_args)
                 Hr, Wr = _reduced(H, k), _reduced(W, k)
                 for a, n, res in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k):
-                    img = _write_chroma(chroma, res, (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr), (inv_a, b) if k else None,
-                                        B=n).cpu()
+                    img = _write_tiles(chroma, depth, res, (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr),
+                                       (inv_a, b) if k else None, B=n).cpu()
                     for j, i in enumerate(idx[a:a + n]):
                         out[i] = img[j]
                 continue
-            Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             um = _unit_maps([maps[i] for i in idx], range(len(idx)), (Hp, Wp, 1, 1, 0), L, dev) if mapped else None
             ul = [layered[i] for i in idx] if nlay else None
             for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um, ul):
@@ -1892,7 +2038,7 @@ def _tile_streams(s_xe, s_xo, j, planes=_PLANES):
 
 
 def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
-                 rdo=None, step_map=None, layers=None, chroma="444", target_psnr=None, target_msssim=None):
+                 rdo=None, step_map=None, layers=None, chroma="444", depth=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -1912,10 +2058,12 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     layers: as encode_images, every tile being a unit with its own layer streams (LLDP over LLDT; not with overlap > 0), so a
     region decodes the refinement of the tiles it touches only.
     chroma: as encode_images; with "420" the tile grid is that of chroma_sizes (the half of a tile is a size the transform
-    accepts) and every tile's streams are those of encode_images(net, tile, chroma="420"); not with overlap > 0."""
+    accepts) and every tile's streams are those of encode_images(net, tile, chroma="420"); not with overlap > 0.
+    depth: as encode_images (uint16 samples of 9..16 bits); not with overlap > 0."""
     ch = _chroma_args(chroma, near, layers, step_map, overlap, target_psnr, target_msssim)
+    d = _depth_args(depth, near, layers, step_map, overlap, target_psnr, target_msssim)
     layer, nettype, L = describe(net)
-    B, H, W = _check_images(images_u8, ch)
+    B, H, W = _check_images(images_u8, ch, d)
     m = _layer_args(layers, step, L, near, step_map, overlap, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
     if near is not None:
@@ -1937,7 +2085,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m, ch)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m, ch, d)
 
 
 def _tiles_per_call(tiles_per_call):
@@ -1965,14 +2113,21 @@ def _gather(units, k, L, planes=_PLANES):
     return s_xe, s_xo
 
 
-def _write_chroma(chroma, res, grid, region, affine=None, **kw):
-    """The output step of a 4:2:0 / 4:0:0 decode: res, what _decode_groups yields for the format -- (luma,
-    chroma planes) or the single plane -- -> the uint8 pixels of ops.ycc420_tiles_to_u8hwc / ops.y_tiles_to_u8hw.  affine: None,
-    or the (inv_a, b) of ll_norm at reduce > 0 (three values each; 4:0:0 takes plane 0's)."""
+def _write_tiles(chroma, depth, res, grid, region, affine=None, **kw):
+    """The output step of a 4:2:0 / 4:0:0 decode and of every decode at more than 8 bits:
+    res, what _decode_groups yields for the format -- the three planes, (luma, chroma planes) or the single plane -- -> the
+    uint8 pixels of ops.ycc420_tiles_to_u8hwc / ops.y_tiles_to_u8hw, or at depth 9 .. 16 the uint16 samples of their siblings
+    and of ops.ycc_tiles_to_u16hwc.  affine: None, or the (inv_a, b) of ll_norm at reduce > 0 (three values each; 4:0:0 takes
+    plane 0's).  The 8-bit 4:4:4 decode keeps its own calls (decode_images, decode_tiled)."""
     from . import ops
+    deep = () if depth == 8 else (depth,)
     if chroma == "420":
-        return ops.ycc420_tiles_to_u8hwc(res[0], res[1], grid, region, affine=affine, **kw)
-    return ops.y_tiles_to_u8hw(res, grid, region, affine=None if affine is None else (affine[0][:1], affine[1][:1]), **kw)
+        return (ops.ycc420_tiles_to_u16hwc if deep else ops.ycc420_tiles_to_u8hwc)(res[0], res[1], grid, region, *deep,
+                                                                                  affine=affine, **kw)
+    if chroma == "400":
+        return (ops.y_tiles_to_u16hw if deep else ops.y_tiles_to_u8hw)(
+            res, grid, region, *deep, affine=None if affine is None else (affine[0][:1], affine[1][:1]), **kw)
+    return ops.ycc_tiles_to_u16hwc(res.contiguous(), grid, region, depth, affine=affine, **kw)
 
 
 def _layers_arg(layers, m):
@@ -2046,6 +2201,7 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     base decode), as decode_images; only those tiles' layer streams are read.
     A container coded with chroma="420" / "400"  decodes to (h, w, 3) / (h, w, 1); the chroma of a tile is
     upsampled from that tile alone, so a region still touches only the tiles it intersects.
+    A container coded with depth=d decodes to uint16 samples of d bits.
     Every check (container, region, identity) runs on the host before any GPU work."""
     import torch
     from . import ops
@@ -2070,7 +2226,7 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
         if not refine or k:
             units = None
     hdr, tiles = _parse_base(LAPPED_MAGIC if _magic(blob) == LAPPED_MAGIC else TILED_MAGIC, blob)
-    ny, nx, chroma = hdr["ny"], hdr["nx"], hdr.get("chroma", "444")
+    ny, nx, chroma, depth = hdr["ny"], hdr["nx"], hdr.get("chroma", "444"), hdr.get("depth", 8)
     # at reduce = k the tile side, the stride and the overlap are all shifted by k (they are multiples of 2^L)
     H, W, th, tw, ov = _reduced(hdr["H"], k), _reduced(hdr["W"], k), hdr["th"] >> k, hdr["tw"] >> k, hdr["overlap"] >> k
     y0, x0, h, w = _region(region, H, W)
@@ -2101,12 +2257,14 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
         if ov:
             acc = torch.zeros(3, 1, 1, h, w, device=dev, dtype=torch.float32)
         else:
-            out = torch.empty(1, h, w, 1 if chroma == "400" else 3, device=dev, dtype=torch.uint8)
+            out = torch.empty(1, h, w, 1 if chroma == "400" else 3, device=dev,
+                              dtype=torch.uint8 if depth == 8 else torch.uint16)
         ul = None if lay is None else [[lay[jj][t] for jj in range(len(lay))] for t in want]
         for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um, ul):
-            if chroma != "444":      # the chroma is upsampled inside the tile, so no neighbour tile is needed
-                _write_chroma(chroma, xhat, (H, W, th, tw, ny, nx), (y0, x0, h, w), (inv_a, b) if k else None,
-                              tiles=want[a:a + n], out=out)
+            if chroma != "444" or depth != 8:
+                # the chroma is upsampled inside the tile, so no neighbour tile is needed
+                _write_tiles(chroma, depth, xhat, (H, W, th, tw, ny, nx), (y0, x0, h, w), (inv_a, b) if k else None,
+                             tiles=want[a:a + n], out=out)
             elif ov:                 # lapped: the raw samples are blended, then written once as the tile of a 1 x 1 grid
                 ops.ycc_tiles_blend(xhat.contiguous(), (H, W, th, tw, ov, ny, nx), (y0, x0, h, w), want[a:a + n], acc)
             else:

@@ -379,6 +379,158 @@ def y_tiles_to_u8hw(y, grid, region, affine=None, tiles=None, first=0, B=1, out=
     return out
 
 
+# ---- samples of 9 to 16 bits (csrc/depth.hip): the uint16 siblings of the wrappers above, same argument checks
+def _u16(src, ch, depth, who):
+    """The input check of the uint16 image kernels -> (B, H, W).  depth: 8 .. 16 at this level, always on uint16 storage."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint16 and src.is_contiguous()
+            and src.dim() == 4 and src.shape[3] == ch):
+        raise _lib.LLDWTError("%s: expected a contiguous (B,H,W,%d) uint16 device tensor" % (who, ch))
+    _depth(depth, who)
+    return tuple(src.shape[:3])
+
+
+def _depth(depth, who):
+    if isinstance(depth, bool) or not isinstance(depth, int) or not 8 <= depth <= 16:
+        raise _lib.LLDWTError("%s: depth must be an integer in [8, 16] (got %r)" % (who, depth))
+
+
+def depth_flag(device):
+    """A zeroed int32 device scalar for the range flag of the uint16 input kernels: they store 1 there when they meet a sample
+    above 2^depth - 1 and never write it otherwise, so one flag may serve every call of an encode."""
+    return torch.zeros(1, device=device, dtype=torch.int32)
+
+
+def _flag(flag, src, who):
+    if flag is None:
+        return depth_flag(src.device)
+    if not (isinstance(flag, torch.Tensor) and flag.is_cuda and flag.dtype == torch.int32 and flag.numel() == 1):
+        raise _lib.LLDWTError("%s: flag must be an int32 device scalar" % who)
+    return flag
+
+
+def _out_u16(who, out, shape, dev):
+    if out is None:
+        out = torch.empty(*shape, device=dev, dtype=torch.uint16)
+    if not (out.is_cuda and out.dtype == torch.uint16 and out.is_contiguous() and tuple(out.shape) == tuple(shape)):
+        raise _lib.LLDWTError("%s: out must be a contiguous (%d,%d,%d,%d) uint16 device tensor" % ((who,) + tuple(shape)))
+    return out
+
+
+def u16hwc_to_f32chw(src, depth, flag=None):
+    """u8hwc_to_f32chw on uint16: (B,H,W,3) uint16 device tensor -> (B,3,H,W) fp32, v / (2^depth - 1).  flag: as
+    u16hwc_to_ycc_tiles (lldwt_u16hwc_to_f32chw)."""
+    who = "u16hwc_to_f32chw"
+    B, H, W = _u16(src, 3, depth, who)
+    flag = _flag(flag, src, who)
+    dst = torch.empty(B, 3, H, W, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u16hwc_to_f32chw(C.c_void_p(src.data_ptr()), _chk(dst), B, H, W, depth, C.c_void_p(flag.data_ptr()),
+                                             _stream()), who)
+    return dst
+
+
+def u16hwc_to_ycc_tiles(src, th, tw, ny, nx, first, n, depth, flag=None):
+    """u8hwc_to_ycc_tiles on (B,H,W,3) uint16 samples of ``depth`` bits: v / (2^depth - 1), then the same expressions, so depth 8
+    gives the uint8 wrapper's floats bit for bit.  flag: an int32 device scalar (depth_flag) that receives 1 when a sample exceeds
+    2^depth - 1; None: a private one nobody reads (lldwt_u16hwc_to_ycc_tiles)."""
+    who = "u16hwc_to_ycc_tiles"
+    B, H, W = _u16(src, 3, depth, who)
+    flag = _flag(flag, src, who)
+    y = torch.empty(3, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u16hwc_to_ycc_tiles(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, th, tw, ny, nx, first, n, depth,
+                                                C.c_void_p(flag.data_ptr()), _stream()), who)
+    return y
+
+
+def ycc_tiles_to_u16hwc(y, grid, region, depth, affine=None, tiles=None, first=0, B=1, out=None):
+    """ycc_tiles_to_u8hwc (affine=None) and ll_tiles_to_u8hwc (affine = (inv_a, b), 3 floats each) for samples of ``depth`` bits:
+    floor((c + 0.5) * (2^depth - 1) + 0.5) stored as uint16 into out (B,h,w,3) (lldwt_ycc_tiles_to_u16hwc)."""
+    who = "ycc_tiles_to_u16hwc"
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    _depth(depth, who)
+    if not (isinstance(y, torch.Tensor) and y.dim() == 5 and y.shape[0] == 3 and y.shape[2] == 1):
+        raise _lib.LLDWTError("%s: y must be (3,n,1,th,tw)" % who)
+    n = y.shape[1]
+    if tuple(y.shape[3:]) != (th, tw):
+        raise _lib.LLDWTError("%s: tiles are %d x %d, the grid says %d x %d" % (who, y.shape[3], y.shape[4], th, tw))
+    tptr, keep = _tile_list(who, tiles, n, B * ny * nx, y.device)
+    ia, bb, keep_af = _affine_arg(who, affine, 3)
+    out = _out_u16(who, out, (B, h, w, 3), y.device)
+    check(_lib.load().lldwt_ycc_tiles_to_u16hwc(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, ia, bb, depth,
+                                                C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
+
+
+def u16hwc_to_ycc420_tiles(src, th, tw, ny, nx, first, n, depth, flag=None):
+    """u8hwc_to_ycc420_tiles on (B,H,W,3) uint16 samples of ``depth`` bits -> (luma, chroma); flag as u16hwc_to_ycc_tiles
+    (lldwt_u16hwc_to_ycc420_tiles).  th, tw even."""
+    who = "u16hwc_to_ycc420_tiles"
+    B, H, W = _u16(src, 3, depth, who)
+    if n < 1 or th < 2 or tw < 2 or th % 2 or tw % 2:
+        raise _lib.LLDWTError("%s: n must be positive and th, tw even (got %r, %r, %r)" % (who, n, th, tw))
+    flag = _flag(flag, src, who)
+    luma = torch.empty(1, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    chroma = torch.empty(2, n, 1, th // 2, tw // 2, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u16hwc_to_ycc420_tiles(C.c_void_p(src.data_ptr()), _chk(luma), _chk(chroma), B, H, W, th, tw, ny, nx,
+                                                   first, n, depth, C.c_void_p(flag.data_ptr()), _stream()), who)
+    return luma, chroma
+
+
+def ycc420_tiles_to_u16hwc(luma, chroma, grid, region, depth, affine=None, tiles=None, first=0, B=1, out=None):
+    """ycc420_tiles_to_u8hwc for samples of ``depth`` bits, stored as uint16 into out (B,h,w,3) (lldwt_ycc420_tiles_to_u16hwc)."""
+    who = "ycc420_tiles_to_u16hwc"
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    _depth(depth, who)
+    if not (isinstance(luma, torch.Tensor) and luma.dim() == 5 and luma.shape[0] == 1 and luma.shape[2] == 1):
+        raise _lib.LLDWTError("%s: luma must be (1,n,1,th,tw)" % who)
+    n = luma.shape[1]
+    if tuple(luma.shape[3:]) != (th, tw) or th % 2 or tw % 2:
+        raise _lib.LLDWTError("%s: luma tiles are %d x %d, the grid says %d x %d (even sides)" % (who, luma.shape[3], luma.shape[4],
+                                                                                                  th, tw))
+    if not (isinstance(chroma, torch.Tensor) and tuple(chroma.shape) == (2, n, 1, th // 2, tw // 2)):
+        raise _lib.LLDWTError("%s: chroma must be (2,%d,1,%d,%d)" % (who, n, th // 2, tw // 2))
+    tptr, keep = _tile_list(who, tiles, n, B * ny * nx, luma.device)
+    ia, bb, keep_af = _affine_arg(who, affine, 3)
+    out = _out_u16(who, out, (B, h, w, 3), luma.device)
+    check(_lib.load().lldwt_ycc420_tiles_to_u16hwc(_chk(luma, "luma"), _chk(chroma, "chroma"), tptr, first, n, B, H, W, th, tw, ny,
+                                                   nx, y0, x0, h, w, ia, bb, depth, C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
+
+
+def u16hw_to_y_tiles(src, th, tw, ny, nx, first, n, depth, flag=None):
+    """u8hw_to_y_tiles on (B,H,W,1) uint16 samples of ``depth`` bits: v / (2^depth - 1) - 0.5f; flag as u16hwc_to_ycc_tiles
+    (lldwt_u16hw_to_y_tiles)."""
+    who = "u16hw_to_y_tiles"
+    B, H, W = _u16(src, 1, depth, who)
+    if n < 1 or th < 1 or tw < 1:
+        raise _lib.LLDWTError("%s: n, th, tw must be positive" % who)
+    flag = _flag(flag, src, who)
+    y = torch.empty(1, n, 1, th, tw, device=src.device, dtype=torch.float32)
+    check(_lib.load().lldwt_u16hw_to_y_tiles(C.c_void_p(src.data_ptr()), _chk(y), B, H, W, th, tw, ny, nx, first, n, depth,
+                                             C.c_void_p(flag.data_ptr()), _stream()), who)
+    return y
+
+
+def y_tiles_to_u16hw(y, grid, region, depth, affine=None, tiles=None, first=0, B=1, out=None):
+    """y_tiles_to_u8hw for samples of ``depth`` bits, stored as uint16 into out (B,h,w,1) (lldwt_y_tiles_to_u16hw)."""
+    who = "y_tiles_to_u16hw"
+    H, W, th, tw, ny, nx = grid
+    y0, x0, h, w = region
+    _depth(depth, who)
+    if not (isinstance(y, torch.Tensor) and y.dim() == 5 and y.shape[0] == 1 and y.shape[2] == 1):
+        raise _lib.LLDWTError("%s: y must be (1,n,1,th,tw)" % who)
+    n = y.shape[1]
+    if tuple(y.shape[3:]) != (th, tw):
+        raise _lib.LLDWTError("%s: tiles are %d x %d, the grid says %d x %d" % (who, y.shape[3], y.shape[4], th, tw))
+    tptr, keep = _tile_list(who, tiles, n, B * ny * nx, y.device)
+    ia, bb, keep_af = _affine_arg(who, affine, 1)
+    out = _out_u16(who, out, (B, h, w, 1), y.device)
+    check(_lib.load().lldwt_y_tiles_to_u16hw(_chk(y, "y"), tptr, first, n, B, H, W, th, tw, ny, nx, y0, x0, h, w, ia, bb, depth,
+                                             C.c_void_p(out.data_ptr()), _stream()), who)
+    return out
+
+
 RESID_MAX_NEAR = 32          # LLDWT_RESID_MAX_NEAR
 RESID_CONTEXTS = 24          # 3 channels x 8 activity classes
 

@@ -155,6 +155,32 @@ int lldwt_u8hw_to_y_tiles(const uint8_t* src, float* y, int64_t B, int64_t H, in
 int lldwt_y_tiles_to_u8hw(const float* y, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
                           int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
                           const float* inv_a, const float* b, uint8_t* dst, void* stream);
+/* Samples of 9 to 16 bits (codec.py depth=; csrc/depth.hip): the uint16 siblings of the tile entry points
+ * above, with their tile grid, tile list or first / n, region, limits and refusals.  src and dst hold uint16_t samples (passed as
+ * void*; 2-byte aligned, HWC) and depth is 8 .. 16 with M = 2^depth - 1 as an fp32 constant.  Input: v / M, a true fp32 division,
+ * then exactly the expressions of the uint8 entry point (greyscale: v / M - 0.5f).  Output: the expressions of the uint8 entry
+ * point with floorf((c + 0.5f) * M + 0.5f) stored as uint16_t.  So depth 8 gives the floats and values of the uint8 entry
+ * points bit for bit.  flag: a 4-byte aligned device int32 the caller zeroes; an input kernel that meets a sample above M stores
+ * 1 there (the floats written are then meaningless) and never writes it otherwise.  inv_a, b: host floats (3 each; 1 each for
+ * y_tiles) or both NULL, as lldwt_ll_tiles_to_u8hwc / lldwt_ycc420_tiles_to_u8hwc: one output entry point serves the full and
+ * the reduced decode.  lldwt_u16hwc_to_f32chw: lldwt_u8hwc_to_f32chw on uint16, v / M.                                         */
+int lldwt_u16hwc_to_ycc_tiles(const void* src, float* ycc, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny,
+                              int64_t nx, int64_t first, int64_t n, int depth, int32_t* flag, void* stream);
+int lldwt_ycc_tiles_to_u16hwc(const float* ycc, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                              int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                              const float* inv_a, const float* b, int depth, void* dst, void* stream);
+int lldwt_u16hwc_to_ycc420_tiles(const void* src, float* luma, float* chroma, int64_t B, int64_t H, int64_t W, int64_t th,
+                                 int64_t tw, int64_t ny, int64_t nx, int64_t first, int64_t n, int depth, int32_t* flag,
+                                 void* stream);
+int lldwt_ycc420_tiles_to_u16hwc(const float* luma, const float* chroma, const int32_t* tiles, int64_t first, int64_t n, int64_t B,
+                                 int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0,
+                                 int64_t h, int64_t w, const float* inv_a, const float* b, int depth, void* dst, void* stream);
+int lldwt_u16hw_to_y_tiles(const void* src, float* y, int64_t B, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t ny,
+                           int64_t nx, int64_t first, int64_t n, int depth, int32_t* flag, void* stream);
+int lldwt_y_tiles_to_u16hw(const float* y, const int32_t* tiles, int64_t first, int64_t n, int64_t B, int64_t H, int64_t W,
+                           int64_t th, int64_t tw, int64_t ny, int64_t nx, int64_t y0, int64_t x0, int64_t h, int64_t w,
+                           const float* inv_a, const float* b, int depth, void* dst, void* stream);
+int lldwt_u16hwc_to_f32chw(const void* src, float* dst, int64_t B, int64_t H, int64_t W, int depth, int32_t* flag, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * P/U block parameters (graphs/layers/P_block_v2.py:15-33) packed for the kernels.

@@ -48,6 +48,13 @@
                                            400 container; info prints it.  Not with --near / --lossless, --layers, --roi,
                                            --overlap, --target-psnr / --target-msssim
 
+    encode --depth D                       samples of D bits in 9..16: reads a .npy file of shape (H,W,3) or (H,W) (greyscale, with
+                                           --chroma 400) or a binary PPM / PGM (P6 / P5) whose maxval is 2^D - 1 (16-bit samples
+                                           big-endian, per Netpbm).  decode reads the depth from the header and writes .npy, .ppm
+                                           or .pgm by the output's extension; info prints it.  compare --depth D takes two such
+                                           files.  Not with --near / --lossless, --layers, --roi, --overlap, --target-psnr /
+                                           --target-msssim
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -85,9 +92,9 @@ def build_net(config_path, checkpoint=None, device="cuda:0"):
     return net.to(device).eval()
 
 
-def print_quality(a_u8, b_u8):
-    """PSNR / MS-SSIM lines of two (H,W,3) uint8 tensors (codec.quality)."""
-    q = codec.quality(a_u8, b_u8)
+def print_quality(a_u8, b_u8, depth=None):
+    """PSNR / MS-SSIM lines of two (H,W,3) uint8 tensors, or uint16 ones of ``depth`` bits (codec.quality)."""
+    q = codec.quality(a_u8, b_u8, depth=depth)
     print("psnr     %.4f dB" % q["psnr"])
     if q["msssim"] is None:
         print("ms-ssim  n/a (a side is below 161)")
@@ -101,6 +108,91 @@ def _load_rgb(path):
     import torch
     from PIL import Image
     return torch.from_numpy(np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)))
+
+
+def read_pnm(path):
+    """A binary PPM (P6) or PGM (P5) file -> (numpy array (H,W,3) or (H,W), maxval): uint8 for maxval < 256, else uint16 read
+    from big-endian 16-bit samples (Netpbm).  Comments (# to the end of the line) may stand between the header's tokens."""
+    import numpy as np
+    with open(path, "rb") as f:
+        data = f.read()
+    pos, tokens = 0, []
+    while len(tokens) < 4:
+        while pos < len(data) and data[pos:pos + 1].isspace():
+            pos += 1
+        if data[pos:pos + 1] == b"#":
+            while pos < len(data) and data[pos:pos + 1] != b"\n":
+                pos += 1
+            continue
+        start = pos
+        while pos < len(data) and not data[pos:pos + 1].isspace():
+            pos += 1
+        if start == pos:
+            raise ValueError("%s: truncated PNM header" % path)
+        tokens.append(data[start:pos])
+    pos += 1                                               # the single whitespace byte after maxval
+    if tokens[0] not in (b"P5", b"P6"):
+        raise ValueError("%s: not a binary PGM / PPM file (magic %r)" % (path, tokens[0]))
+    try:
+        W, H, maxval = (int(t) for t in tokens[1:])
+    except ValueError:
+        raise ValueError("%s: bad PNM header %r" % (path, tokens)) from None
+    if W < 1 or H < 1 or not 1 <= maxval <= 65535:
+        raise ValueError("%s: bad PNM header: %d x %d, maxval %d" % (path, W, H, maxval))
+    ch = 3 if tokens[0] == b"P6" else 1
+    dt = np.dtype(">u2") if maxval > 255 else np.dtype("u1")
+    if len(data) - pos < H * W * ch * dt.itemsize:
+        raise ValueError("%s: %d sample bytes, the header announces %d" % (path, len(data) - pos, H * W * ch * dt.itemsize))
+    a = np.frombuffer(data, dtype=dt, count=H * W * ch, offset=pos).astype(np.uint16 if maxval > 255 else np.uint8)
+    return (a.reshape(H, W, 3) if ch == 3 else a.reshape(H, W)), maxval
+
+
+def write_pnm(path, a, maxval):
+    """(H,W,3) -> binary PPM (P6), (H,W) -> binary PGM (P5), with the given maxval; samples above 255 as big-endian 16 bits."""
+    import numpy as np
+    a = np.asarray(a)
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or not 1 <= maxval <= 65535:
+        raise ValueError("write_pnm: an (H,W,3) or (H,W) array and a maxval in [1, 65535]")
+    with open(path, "wb") as f:
+        f.write(b"%s\n%d %d\n%d\n" % (b"P6" if a.ndim == 3 else b"P5", a.shape[1], a.shape[0], maxval))
+        f.write(np.ascontiguousarray(a.astype(">u2" if maxval > 255 else "u1")).tobytes())
+
+
+def load_deep(path, depth, grey=False):
+    """A .npy, .ppm or .pgm file of ``depth``-bit samples -> (H,W,3) (or (H,W,1) with grey) uint16 torch tensor.  A PNM file's
+    maxval must be 2^depth - 1; the range of a .npy file is checked by the encoder."""
+    import numpy as np
+    import torch
+    if path.lower().endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+        if a.dtype != np.uint16:
+            raise ValueError("%s: --depth takes a uint16 array (got %s)" % (path, a.dtype))
+    else:
+        a, maxval = read_pnm(path)
+        if maxval != (1 << depth) - 1:
+            raise ValueError("%s: maxval %d, --depth %d needs %d" % (path, maxval, depth, (1 << depth) - 1))
+        a = a.astype(np.uint16)
+    if a.ndim != (2 if grey else 3) or (not grey and a.shape[2] != 3):
+        raise ValueError("%s: expected %s, got shape %s" % (path, "(H,W) greyscale samples" if grey else "(H,W,3) RGB samples",
+                                                           a.shape))
+    x = torch.from_numpy(np.ascontiguousarray(a))
+    return x[..., None] if grey else x
+
+
+def save_deep(path, img, depth):
+    """A decoded (H,W,3) / (H,W,1) uint16 tensor -> .npy, or .ppm / .pgm with maxval 2^depth - 1, by the extension."""
+    import numpy as np
+    a = img.numpy()
+    a = a[..., 0] if a.shape[2] == 1 else a
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        with open(path, "wb") as f:
+            np.save(f, a)
+    elif ext == (".pgm" if a.ndim == 2 else ".ppm"):
+        write_pnm(path, a, (1 << depth) - 1)
+    else:
+        raise ValueError("%s: a %d-bit %s image is written as .npy or %s" % (path, depth, "greyscale" if a.ndim == 2 else "RGB",
+                                                                             ".pgm" if a.ndim == 2 else ".ppm"))
 
 
 def main(argv=None):
@@ -136,6 +228,8 @@ def main(argv=None):
                                        help="add M quality layers (1..4) that refine the step by 3 each (writes LLDP)")
     sub.choices["encode"].add_argument("--chroma", choices=("444", "420", "400"), default="444",
                                        help="chroma format: 444 (default), 420 (half-size chroma) or 400 (greyscale, mode L)")
+    sub.choices["encode"].add_argument("--depth", type=int, metavar="D",
+                                       help="samples of D bits in 9..16 from a .npy, .ppm or .pgm file (default: 8-bit image files)")
     sub.choices["decode"].add_argument("--layers", type=int, metavar="J",
                                        help="decode the base plus the first J quality layers of an LLDP container (default: all)")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
@@ -150,6 +244,7 @@ def main(argv=None):
     p = sub.add_parser("compare")
     p.add_argument("a")
     p.add_argument("b")
+    p.add_argument("--depth", type=int, metavar="D", help="compare two .npy / .ppm files of D-bit samples (9..16)")
     a = ap.parse_args(argv)
 
     if a.cmd == "info":
@@ -181,6 +276,7 @@ def main(argv=None):
             hdr = hdr["base"]
         for k, v in hdr.items():
             print("%-15s %s" % (k, v.hex() if isinstance(v, bytes) else v))
+        print("%-15s %d bits per sample" % ("sample depth", hdr.get("depth", 8)))
         fmt = hdr.get("chroma", "444")
         print("%-15s %s (%d planes coded%s)" % ("chroma format", fmt, codec.CHROMA_PLANES[fmt],
                                               ", Cb and Cr at half size" if fmt == "420" else ""))
@@ -194,12 +290,13 @@ def main(argv=None):
         return 0
 
     if a.cmd == "compare":
-        xa, xb = _load_rgb(a.a), _load_rgb(a.b)
+        deep = a.depth is not None and codec.check_depth(a.depth) != 8
+        xa, xb = (load_deep(a.a, a.depth), load_deep(a.b, a.depth)) if deep else (_load_rgb(a.a), _load_rgb(a.b))
         if xa.shape != xb.shape:
             print("compare: the images differ in size: %dx%d and %dx%d" % (xa.shape[1], xa.shape[0], xb.shape[1], xb.shape[0]),
                   file=sys.stderr)
             return 2
-        print_quality(xa, xb)
+        print_quality(xa, xb, a.depth if deep else None)
         return 0
 
     import numpy as np
@@ -207,10 +304,15 @@ def main(argv=None):
     from PIL import Image
     net = build_net(a.config, a.checkpoint)
     if a.cmd == "encode":
-        img = np.asarray(Image.open(a.src).convert("L" if a.chroma == "400" else "RGB"), dtype=np.uint8)
-        x = torch.from_numpy(np.ascontiguousarray(img))[None]
-        if a.chroma == "400":
-            x = x[..., None]                                    # (1,H,W,1)
+        deep = a.depth is not None and codec.check_depth(a.depth) != 8
+        if deep:
+            x = load_deep(a.src, a.depth, a.chroma == "400")[None]
+            img = x[0]
+        else:
+            img = np.asarray(Image.open(a.src).convert("L" if a.chroma == "400" else "RGB"), dtype=np.uint8)
+            x = torch.from_numpy(np.ascontiguousarray(img))[None]
+            if a.chroma == "400":
+                x = x[..., None]                                # (1,H,W,1)
         if a.lossless and a.near not in (None, 0):
             print("--lossless is --near 0; give one of them", file=sys.stderr)
             return 2
@@ -231,6 +333,8 @@ def main(argv=None):
             kw["layers"] = a.layers
         if a.chroma != "444":
             kw["chroma"] = a.chroma
+        if deep:
+            kw["depth"] = a.depth
         if a.roi:
             if a.target_bytes is not None or a.target_bpp is not None:
                 print("--roi cannot be combined with --target-bytes / --target-bpp (a byte target over a step map is not defined)",
@@ -316,18 +420,22 @@ def main(argv=None):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         grey = img.shape[2] == 1                                # a chroma=400 container: mode L
-        Image.fromarray(img[..., 0].numpy() if grey else img.numpy()).save(a.dst)
+        depth = inner.get("base", inner).get("depth", 8)
+        if depth != 8:
+            save_deep(a.dst, img, depth)
+        else:
+            Image.fromarray(img[..., 0].numpy() if grey else img.numpy()).save(a.dst)
         print("decoded %dx%d%s: %.3f s" % (img.shape[1], img.shape[0], " (greyscale)" if grey else "", dt))
         if a.compare is not None:
             if grey:
                 print("--compare: PSNR / MS-SSIM of single-channel images are not defined here", file=sys.stderr)
                 return 2
-            src = _load_rgb(a.compare)
+            src = load_deep(a.compare, depth) if depth != 8 else _load_rgb(a.compare)
             if src.shape != img.shape:
                 print("--compare: %s is %dx%d, the decoded image %dx%d" % (a.compare, src.shape[1], src.shape[0], img.shape[1],
                                                                          img.shape[0]), file=sys.stderr)
                 return 2
-            print_quality(src, img.cpu())
+            print_quality(src, img.cpu(), depth if depth != 8 else None)
     return 0
 
 
