@@ -318,6 +318,17 @@ struct LfArgs {
     const float* gate1; const float* gate2;
     float* mx;                  // BWD: (planes, 2, 64) |.|-max slots of dt3 and dpre2 (atomic max; zeroed by the host), or null
 };
+// The kernel's own argument segment (LfArgs is its only parameter) through a pointer the compiler cannot see through.  A field
+// read through `a` is loaded once in front of the tile loop and stays live around it; the scalars that do not fit are parked in
+// vector lanes (v_writelane / v_readlane: they issue on the vector port, and every 64 parked scalars cost a vector register).
+// The view sets -- 34 scalars that only the operand fetch and the final store touch -- are read through this pointer where
+// they are used instead: scalar loads from the constant cache, and nothing to keep.
+typedef const __attribute__((address_space(4))) LfArgs* LfArgsK;
+__device__ __forceinline__ LfArgsK lf_kernarg() {
+    LfArgsK k = (LfArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
 // Work queue of the runs.  A workgroup starts with run blockIdx.x and takes every further one from an atomic counter, so the
 // workgroups that drew border columns (their tiles cost ~25 % more) simply take fewer runs; the border runs come first in the
 // item order (longest processing time first).  A static deal left the CUs 13 % idle at the level-0 shape (in-kernel stamps).
@@ -635,37 +646,44 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tpi = a.tiles_x * a.tiles_y;                     // tiles per image
 
     // image z of the launch -> its view set and its image index inside that set
-    auto view_of_z = [&](int64_t z, int64_t& zz) -> LiftF16Views {          // by value: scalar selects, no stack
+    // (read through k = lf_kernarg() of the place that needs the views: the operand fetch, the final store)
+    auto view_of_z = [&](LfArgsK k, int64_t z, int64_t& zz) -> LiftF16Views {          // by value: scalar selects, no stack
         const bool second = z >= a.zsplit;
         zz = second ? z - a.zsplit : z;
-        LiftF16Views r = a.v;
-        r.src = second ? a.src2 : a.v.src;     r.src_sz = second ? a.src2_sz : a.v.src_sz;
-        r.din = second ? a.din2 : a.v.din;     r.din_sz = second ? a.din2_sz : a.v.din_sz;
-        r.dout = second ? a.dout2 : a.v.dout;  r.dout_sz = second ? a.dout2_sz : a.v.dout_sz;
+        LiftF16Views r;
+        r.src = second ? k->src2 : k->v.src;     r.src_sz = second ? k->src2_sz : k->v.src_sz;
+        r.din = second ? k->din2 : k->v.din;     r.din_sz = second ? k->din2_sz : k->v.din_sz;
+        r.dout = second ? k->dout2 : k->v.dout;  r.dout_sz = second ? k->dout2_sz : k->v.dout_sz;
+        r.src_sy = k->v.src_sy;   r.src_sx = k->v.src_sx;
+        r.din_sy = k->v.din_sy;   r.din_sx = k->v.din_sx;
+        r.dout_sy = k->v.dout_sy; r.dout_sx = k->v.dout_sx;
         return r;
     };
     // work item = a RUN: rl vertically consecutive tiles of one column strip of one image (the last run of a column may be
     // shorter).  Item order: the runs of the first / last column strip of every image (border tiles), then the others.
     const int bcols = a.tiles_x >= 2 ? 2 : 1;
+    // (every quantity is non-negative: UNSIGNED divisions, whose loop-invariant reciprocals -- hoisted out of the tile loop and
+    // parked in vector lanes like the arguments -- take fewer scalar registers than the signed ones)
     auto decode = [&](int item, int j, int64_t& z, int& y0, int& x0, int& seglen) {
-        int zi, sx, seg;
+        unsigned zi, sx, seg;
+        const unsigned nseg = (unsigned)a.nseg;
         if (item < a.nborder) {
-            const int per = bcols * a.nseg;
-            zi = item / per;
-            const int r = item - zi * per, c = r / a.nseg;
-            seg = r - c * a.nseg;
-            sx = c ? a.tiles_x - 1 : 0;
-        } else {
-            const int per = (a.tiles_x - bcols) * a.nseg, it2 = item - a.nborder;
+            const unsigned per = (unsigned)bcols * nseg, it2 = (unsigned)item;
             zi = it2 / per;
-            const int r = it2 - zi * per, c = r / a.nseg;
-            seg = r - c * a.nseg;
+            const unsigned r = it2 - zi * per, c = r / nseg;
+            seg = r - c * nseg;
+            sx = c ? (unsigned)a.tiles_x - 1 : 0;
+        } else {
+            const unsigned per = (unsigned)(a.tiles_x - bcols) * nseg, it2 = (unsigned)(item - a.nborder);
+            zi = it2 / per;
+            const unsigned r = it2 - zi * per, c = r / nseg;
+            seg = r - c * nseg;
             sx = 1 + c;
         }
         z = zi;
-        y0 = (seg * a.rl + j) * TH;
-        x0 = sx * TW;
-        seglen = min(a.rl, a.tiles_y - seg * a.rl);
+        y0 = (int)(seg * (unsigned)a.rl + (unsigned)j) * TH;
+        x0 = (int)sx * TW;
+        seglen = min(a.rl, a.tiles_y - (int)seg * a.rl);
     };
     // branch-free: every load goes to a clamped (valid) address; P0 applies the zero padding when it consumes the values
     auto fetch = [&](int item, int j, int tid, LfPre& pr) {
@@ -674,7 +692,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int y0, x0, seglen_;
         decode(item, j, z, y0, x0, seglen_);
         int64_t zz;
-        const LiftF16Views vw = view_of_z(z, zz);
+        const LiftF16Views vw = view_of_z(lf_kernarg(), z, zz);
         const float* sp = vw.src + zz * vw.src_sz;
         const int ssy = (int)vw.src_sy, ssx = (int)vw.src_sx;   // per-image offsets fit 32 bits (checked on the host)
         const int dyv = a.vertical ? 1 : 0;
@@ -778,8 +796,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
     const int64_t stamp_tile = (z * a.tiles_y + y0 / TH) * a.tiles_x + x0 / TW;
-    int64_t zv;
-    const LiftF16Views vout = view_of_z(z, zv);
+    const int64_t zv = z >= a.zsplit ? z - a.zsplit : z;       // the image's index inside its view set
     const int plane = (int)(zv / a.batch);
     const float* pk = a.packed + (int64_t)plane * a.pstride;
     const float* bias = pk + a.orient_fp32;
@@ -1541,6 +1558,8 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int oy = tid / TW, ox = tid - oy * TW;
             const int gy = y0 + oy, gx = x0 + ox;
             const float invc = (1.f / ACT_SCALE) * tail[12];
+            int64_t zo;
+            const LiftF16Views vout = view_of_z(lf_kernarg(), z, zo);    // requested in front of the sums, needed at the store
             float net = 0.f;
             const float* drow = Dp(oy * R2W) + ox * DP;          // a row of the D image lies inside one quarter
 #pragma unroll
@@ -1563,7 +1582,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const float skip = S[(oy + 8) * SW + ox + 8];
             const float din = din_pre;
             if (valid)      // per-image offsets fit 32 bits (checked on the host)
-                (vout.dout + zv * vout.dout_sz)[gy * (int)vout.dout_sy + gx * (int)vout.dout_sx] = din + a.sign * (skip + a.rw * net);
+                (vout.dout + zo * vout.dout_sz)[gy * (int)vout.dout_sy + gx * (int)vout.dout_sx] = din + a.sign * (skip + a.rw * net);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (more) stage(tid, nxt);
@@ -1698,7 +1717,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const float skip = S[(oy + 8) * SW + ox + 8];
             const float din = din_pre;
             if constexpr (BWD) a.sv_skip[zv * (int64_t)h * w + (int64_t)gy * w + gx] = net;       // dsk = conv1^T(dr)
-            else vout.dout[zv * vout.dout_sz + (int64_t)gy * vout.dout_sy + (int64_t)gx * vout.dout_sx] = din + a.sign * (skip + a.rw * net);
+            else {
+                int64_t zo;
+                const LiftF16Views vout = view_of_z(lf_kernarg(), z, zo);
+                vout.dout[zo * vout.dout_sz + (int64_t)gy * vout.dout_sy + (int64_t)gx * vout.dout_sx] = din + a.sign * (skip + a.rw * net);
+            }
         }
     }
     __builtin_amdgcn_sched_barrier(0);

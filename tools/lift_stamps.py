@@ -11,7 +11,11 @@ six chunks during P1), in one process, two launches per form; written to FILE as
 python tools/lift_stamps.py --p2 [FILE]: stamps INSIDE P2 (diagnostics flag 512: kernels of their own, no production launch holds
 them) of the interior continuing tiles at the level-0 shape, for both forms: cycles of the first pair, the loop's pair, the
 single tile and the tail per wave, the MFMA cycles a wave issues in them, the skew of the waves at P2's barrier and -- on every
-second tile row, for the earlier form -- the cycles each k-step of the loop's pair waits for its LDS operands."""
+second tile row, for the earlier form -- the cycles each k-step of the loop's pair waits for its LDS operands.
+
+python tools/lift_stamps.py --classes [FILE]: the same tile classes and shapes for the library as built, no flag, two launches per
+shape, with the launch's span in real time and the in-kernel clock: for comparing two BUILDS (a change that touches code all
+diagnostics forms share has no flag to compare against), one process per build, run back to back on one box."""
 import json
 import os
 import sys
@@ -102,6 +106,29 @@ def ab(path):
             f.write(txt + "\n")
 
 
+def classes_of_build(path):
+    res = {"what": "k_lift_fused_f16 as built (no diagnostics flag), one vertical step on 24 images; cycles from the tile's first stamp to "
+                   "its last, mean over the eight waves and the tiles of a class; two launches per shape; launch_span_us = last end "
+                   "stamp minus first start stamp of the launch (s_memrealtime, 100 MHz)",
+           "shapes": {}}
+    for key, (h, w, rl) in (("level0_row_pass_256x512", (256, 512, int(os.environ.get("LLDWT_STAMPS_RL", "8")))),
+                            ("level3_row_pass_32x64", (32, 64, 1))):
+        runs = []
+        for _ in range(2):
+            s = stamp(h, w, 0)
+            c = classes(s, rl)
+            real = (s[..., 15] - s[..., 14]).astype(np.float64)
+            ok = real > 0
+            runs.append({"launch_span_us": float((s[..., 15].max() - s[..., 14].min()) / 100.0),
+                         "in_kernel_clock_GHz": float(np.median((s[..., 9] - s[..., 0])[ok] / real[ok]) * 0.1), "classes": c})
+        res["shapes"][key] = {"run_length": rl, "launches": runs}
+    txt = json.dumps(res, indent=1)
+    print(txt)
+    if path:
+        with open(path, "w") as f:
+            f.write(txt + "\n")
+
+
 def p2_of(s, rl):
     """P2 of the interior continuing tiles of one stamped launch (flag 512), mean over tiles and waves unless named otherwise."""
     gy, gx = s.shape[1:3]
@@ -165,6 +192,8 @@ def main():
     from imagecompressionlearnedliftingandlearnedtreebasedmodels_amd import ops
     if len(sys.argv) > 1 and sys.argv[1] == "--ab":
         return ab(sys.argv[2] if len(sys.argv) > 2 else "")
+    if len(sys.argv) > 1 and sys.argv[1] == "--classes":
+        return classes_of_build(sys.argv[2] if len(sys.argv) > 2 else "")
     if len(sys.argv) > 1 and sys.argv[1] == "--p2":
         return p2(sys.argv[2] if len(sys.argv) > 2 else "")
     P, B, h, w = 3, 8, 256, 512
