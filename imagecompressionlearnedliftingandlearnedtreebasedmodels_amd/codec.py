@@ -176,6 +176,16 @@ Composes with ``coder``, ``step``, ``target_bytes``, ``rdo``, ``chroma``, tiles,
 excludes ``near``, ``layers``, ``step_map``, ``overlap > 0`` and the quality targets, and LLDR / LLDQ / LLDP / LLDO containers
 over such a base are refused.
 
+Centroid reconstruction (``decode_images`` / ``decode_tiled(..., recon="centroid")``): a decoder's choice that
+costs no bits and changes no container.  Every decoder above puts a coefficient at the centre of its bin, sym * q + mu; under
+the Gaussian (sigma, mu) the entropy model assigns to it the mean-square-optimal value is the bin's conditional mean, which
+lies toward mu.  For every level 0 .. L-2 the decode reaches, ``quality_layers.level_params`` on the decoded base gives (sigma,
+mu) and ``ops.gauss_centroid`` (csrc/recon.hip) moves the values, never out of their bins, with the step in force: the header's
+step, the step of the last quality layer decoded, or the block's step of an LLDQ map.  xe and the coarsest level stay as
+decoded.  ``recon=None`` and ``"centre"`` are the decode as ever, bit for bit.  Composes with every container and decoder
+argument above except a residual layer that is applied: LLDR with ``refine=True`` at full resolution is a ValueError naming
+recon and near (the residual was taken against the centre reconstruction); ``refine=False`` is allowed.
+
 ``decode_images`` / ``decode_tiled`` take LLDR over LLDW / LLDT; ``refine=False`` returns the base decode, and reduce > 0
 decodes the base only (the residual lives at full resolution).  A region decodes the base and residual streams of the tiles it
 touches only.  The decoder compares cs(xh) with its own reconstruction before it applies anything and raises
@@ -1854,7 +1864,7 @@ def ll_norm(net, k):
     return torch.tensor(inv, dtype=torch.float32).tolist(), torch.tensor(b, dtype=torch.float32).tolist()
 
 
-def decode_images(net, blobs, reduce=0, refine=True, layers=None):
+def decode_images(net, blobs, reduce=0, refine=True, layers=None, recon=None):
     """List of containers -> list of (H,W,3) uint8 CPU tensors, in input order.  Every container is checked on the host
     first; then containers of equal (H, W), coder and quantisation step are decoded together (both come from each header).
     reduce = k in [0, L]: the image at 1/2^k of each side, (ceil(H / 2^k), ceil(W / 2^k), 3), decoded from the xe streams
@@ -1870,10 +1880,16 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
     A container coded with chroma="420" decodes to (H,W,3), one coded with chroma="400" to (H,W,1); the
     format comes from the header, containers are grouped by it as well, and a mix comes back in input order.
     A container coded with depth=d decodes to a uint16 tensor of d-bit samples; the depth comes from the
-    header, and containers of different depths in one call are a ValueError naming depth (a list of one dtype comes back)."""
+    header, and containers of different depths in one call are a ValueError naming depth (a list of one dtype comes back).
+    recon="centroid" (DESIGN.md 7.1.13): every coefficient of the levels 0 .. L-2 that the decode reaches is put at the mean of
+    its quantisation bin under the entropy model's Gaussian instead of the bin's centre -- after the quality layers, with the
+    step of the last layer decoded, and with the step map of an LLDQ container.  A decoder's choice: no container records it, and
+    None or "centre" is the decode as ever.  Over an LLDR container whose residual would be applied (refine=True, reduce=0) it is
+    a ValueError naming recon and near: the residual was taken against the centre reconstruction."""
     import torch
     from . import ops
     from .graphs.layers.lifting_dwt_nets import padded_size
+    rc = _recon_arg(recon)
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
     refined, maps, layered = {}, {}, {}
@@ -1894,6 +1910,8 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
             _, maps[i], b = parse_mapped(b)
             blobs[i] = b
         if _magic(b) == REFINED_MAGIC:
+            if refine and k == 0:
+                _recon_refined(rc)
             rhdr, base, units = parse_refined(b)
             if _magic(base) != MAGIC:
                 raise ValueError("base container: decode_images takes an LLDR over LLDW; this one is over %s (decode_tiled)"
@@ -1929,7 +1947,7 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
                 Hp, Wp = padded_size([n.autoencoder for n in nets], H, W)
             if chroma != "444" or depth != 8:         # no step map, layers or residual here (_chroma_args, _depth_args)
                 Hr, Wr = _reduced(H, k), _reduced(W, k)
-                for a, n, res in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k):
+                for a, n, res in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, recon=rc):
                     img = _write_tiles(chroma, depth, res, (Hr, Wr, Hp >> k, Wp >> k, 1, 1), (0, 0, Hr, Wr),
                                        (inv_a, b) if k else None, B=n).cpu()
                     for j, i in enumerate(idx[a:a + n]):
@@ -1937,7 +1955,7 @@ def decode_images(net, blobs, reduce=0, refine=True, layers=None):
                 continue
             um = _unit_maps([maps[i] for i in idx], range(len(idx)), (Hp, Wp, 1, 1, 0), L, dev) if mapped else None
             ul = [layered[i] for i in idx] if nlay else None
-            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um, ul):
+            for a, n, xhat in _decode_groups(nets, units, Hp, Wp, len(idx), parsed[idx[0]][0], k, um, ul, rc):
                 g = idx[a:a + n]
                 if k == 0:
                     img = ops.ycc_to_u8hwc_crop(xhat.contiguous(), H, W)
@@ -2095,12 +2113,15 @@ def _tiles_per_call(tiles_per_call):
     return int(tiles_per_call)
 
 
-def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step=1.0, layers=None):
+def _decode_tiles(nets, s_xe, s_xo, th, tw, n, coder="host", first_level=0, step=1.0, layers=None, recon=None):
     """One group of n tiles -> xhat (3,n,1,th,tw), or at first_level = k the LL band (3,n,1,th>>k,tw>>k)
     (decode_strings_planes; a module-level hook so the number of tiles a decode touches can be counted).  layers: the
-    (streams, n of the base step, layer count) of decode_strings_planes, given only for a decode with quality layers."""
+    (streams, n of the base step, layer count) of decode_strings_planes, given only for a decode with quality layers; recon:
+    given only for a centroid decode."""
     from .graphs.models.LiftingBasedDWT_net import decode_strings_planes
     kw = {} if layers is None else {"layers": layers}
+    if recon is not None:
+        kw["recon"] = recon
     return decode_strings_planes(nets, s_xe, s_xo, th, tw, n, coder=coder, first_level=first_level, step=step, **kw)
 
 
@@ -2130,6 +2151,20 @@ def _write_tiles(chroma, depth, res, grid, region, affine=None, **kw):
     return ops.ycc_tiles_to_u16hwc(res.contiguous(), grid, region, depth, affine=affine, **kw)
 
 
+def _recon_arg(recon):
+    """The recon argument of the decoders -> "centroid" or None (None and "centre": the decode as ever).
+    ValueError naming recon; host only."""
+    from .ops import check_recon
+    return "centroid" if check_recon(recon) == "centroid" else None
+
+
+def _recon_refined(rc):
+    """A centroid decode under a residual layer that is about to be applied: ValueError naming recon and near."""
+    if rc is not None:
+        raise ValueError("recon and near: the residual layer of an LLDR container was taken against the centre reconstruction "
+                         "and its checksum would refuse any other; decode with refine=False (or reduce > 0) for recon=%r" % rc)
+
+
 def _layers_arg(layers, m):
     """The layers argument of a decode against a container of m quality layers (0: none) -> the count to decode (None: all).
     ValueError naming layers."""
@@ -2140,15 +2175,17 @@ def _layers_arg(layers, m):
     return layers
 
 
-def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None, layers=None):
+def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None, layers=None, recon=None):
     """The decode walk behind decode_images and decode_tiled: the units (stream lists of images or tiles of th x tw, all of
     the coder and step of hdr) are decoded ``group`` at a time, one per call in the arithmetics that are not batch invariant,
     through the _decode_tiles hook -> yields (index of the group's first unit, its size n, the hook's result).
     maps: the units' step maps (_unit_maps, one per unit) when the units were coded with one; each group then decodes with its
     slice in place of the header's step.
     layers: (per unit its layer streams in the LLDP order, truncated to the count j > 0 to decode) of a layered decode (DESIGN.md
-    7.1.10): each group's levels k .. L-2 are refined with its own streams before the inverse transform."""
+    7.1.10): each group's levels k .. L-2 are refined with its own streams before the inverse transform.
+    recon: "centroid" for a centroid decode, else None; it goes to every call of the hook, chroma planes too."""
     g = group if _batch_invariant(hdr["arithmetic"]) else 1
+    rk = {} if recon is None else {"recon": recon}
     L = hdr["dwtlevels"]
     chroma = hdr.get("chroma", "444")
     for a in range(0, len(units), g):
@@ -2158,7 +2195,7 @@ def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None, layers=None):
             # of it, as the encoder coded them.  4:2:0 -> (luma (1,n,1,th>>k,tw>>k), chroma (2,n,1,th>>(k+1),tw>>(k+1))); 4:0:0 ->
             # the plane.
             s_xe, s_xo = _gather(grp, k, L, CHROMA_PLANES[chroma])
-            kw = dict(coder=hdr["coder"], first_level=k, step=hdr["step"])
+            kw = dict(coder=hdr["coder"], first_level=k, step=hdr["step"], **rk)
             res = _decode_tiles(nets[0:1], s_xe[0:1], [lev[0:1] for lev in s_xo], th, tw, len(grp), **kw).contiguous()
             if chroma == "420":
                 res = (res, _decode_tiles(nets[1:3], s_xe[1:3], [lev[1:3] for lev in s_xo], th // 2, tw // 2, len(grp),
@@ -2166,7 +2203,7 @@ def _decode_groups(nets, units, th, tw, group, hdr, k, maps=None, layers=None):
             yield a, len(grp), res
             continue
         s_xe, s_xo = _gather(grp, k, L)
-        kw = {}
+        kw = dict(rk)
         if layers is not None:
             lay = _gather_layers(layers[a:a + g], k, L)
             kw["layers"] = (lay, int(round(hdr["step"] * STEP_DENOM)), len(lay))
@@ -2186,7 +2223,7 @@ def _region(region, H, W):
     return y0, x0, h, w
 
 
-def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True, layers=None):
+def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=True, layers=None, recon=None):
     """LLDT or LLDO container (or an LLDQ over one, DESIGN.md 7.1.8: each tile decodes with its slice of the step map) ->
     (h, w, 3) uint8 CPU tensor: the whole image, or region = (y0, x0, h, w).  Only the tiles that
     intersect the region are decoded, tiles_per_call at a time, and written into the region by lldwt_ycc_tiles_to_u8hwc.
@@ -2202,9 +2239,12 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     A container coded with chroma="420" / "400"  decodes to (h, w, 3) / (h, w, 1); the chroma of a tile is
     upsampled from that tile alone, so a region still touches only the tiles it intersects.
     A container coded with depth=d decodes to uint16 samples of d bits.
+    recon="centroid" (DESIGN.md 7.1.13): the touched tiles are decoded to their bins' centroids, as decode_images does; lapped
+    tiles are blended afterwards as ever.  Refused over an LLDR container whose residual would be applied.
     Every check (container, region, identity) runs on the host before any GPU work."""
     import torch
     from . import ops
+    rc = _recon_arg(recon)
     layer, nettype, L = describe(net)
     k = _reduce(reduce, L)
     units = smap = lay = None
@@ -2219,6 +2259,8 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
     if _magic(blob) == MAPPED_MAGIC:           # the inner container with its step map
         _, smap, blob = parse_mapped(blob)
     if _magic(blob) == REFINED_MAGIC:
+        if refine and not k:
+            _recon_refined(rc)
         rhdr, blob, units = parse_refined(blob)
         if _magic(blob) != TILED_MAGIC:
             raise ValueError("base container: decode_tiled takes an LLDR over LLDT; this one is over %s (decode_images)"
@@ -2260,7 +2302,7 @@ def decode_tiled(net, blob, region=None, tiles_per_call=32, reduce=0, refine=Tru
             out = torch.empty(1, h, w, 1 if chroma == "400" else 3, device=dev,
                               dtype=torch.uint8 if depth == 8 else torch.uint16)
         ul = None if lay is None else [[lay[jj][t] for jj in range(len(lay))] for t in want]
-        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um, ul):
+        for a, n, xhat in _decode_groups(nets, [tiles[t] for t in want], hdr["th"], hdr["tw"], group, hdr, k, um, ul, rc):
             if chroma != "444" or depth != 8:
                 # the chroma is upsampled inside the tile, so no neighbour tile is needed
                 _write_tiles(chroma, depth, xhat, (H, W, th, tw, ny, nx), (y0, x0, h, w), (inv_a, b) if k else None,

@@ -1061,14 +1061,18 @@ def encode_strings_planes(nets, x, coder="host", recon=False, step=1.0, rdo=None
     return res
 
 
-def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0, step=1.0, layers=None):
+def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host", first_level=0, step=1.0, layers=None, recon=None):
     """The decoder half: strings of B images of Hp x Wp (as encode_strings_planes returns them, with the same coder) ->
     xhat (P,B,C,Hp,Wp).
     Needs nothing from the encoder's process: the coded shapes come from the transform (encode_shapes).
     first_level = k: strings_xo holds all L levels or only the levels k .. L-1, which are the only ones decoded, and the result
     is the decoded LL band at level k, (P,B,C,Hp>>k,Wp>>k) (decode_planes; lifting_dwt_nets.ll_affine gives its scale).
     layers = (lay, n, j): the first j quality layers of encode_strings_planes(..., layers=(n, m)), lay[jj - 1][i][p][b], refine
-    the decoded levels k .. L-2 before the inverse transform; the entries of finer levels are never read."""
+    the decoded levels k .. L-2 before the inverse transform; the entries of finer levels are never read.
+    recon = "centroid": every coefficient of the levels k .. L-2 is moved from the centre of its quantisation bin to the bin's
+    mean under the Gaussian of quality_layers.level_params on the decoded base, after the quality layers and
+    before the inverse transform; None or "centre": the decode as ever.  Nothing in the strings says which."""
+    centroid = ops.check_recon(recon) == "centroid"
     em = [n.entropymodel for n in nets]
     if not hasattr(type(em[0]), "decompress_planes"):
         raise NotImplementedError(_NOT_CODED)
@@ -1079,10 +1083,35 @@ def decode_strings_planes(nets, strings_xe, strings_xo, Hp, Wp, B, coder="host",
     kw = {"step": step} if isinstance(step, torch.Tensor) or step != 1.0 else {}
     xe, xo = type(em[0]).decompress_planes(em, strings_xe, strings_xo, shape_xe, shapes_xo, coder=coder, first_level=k, **kw)
     assert [tuple(t.shape) for t in xo] == [tuple(sh) for sh in shapes_xo[k:]]
+    base = [None] * k + list(xo)                                    # the decoded base, indexed by level
     if layers is not None and layers[2] > 0:
         from ... import quality_layers
-        xo = quality_layers.decode_units(em, [None] * k + list(xo), layers[0], layers[1], layers[2], coder, first_level=k)[k:]
+        xo = quality_layers.decode_units(em, base, layers[0], layers[1], layers[2], coder, first_level=k)[k:]
+    if centroid:
+        xo = _centroid_levels(em, base, list(xo), k, step, layers)
     return decode_planes(aenc, xe, xo, first_level=k)
+
+
+def _centroid_levels(em, base, xo, k, step, layers):
+    """The centroid reconstruction of a decode.  base: the decoded base indexed by level (entries below k are
+    None); xo: the levels k .. L-1 as they go into the inverse transform (after the quality layers, if any); step, layers: as
+    decode_strings_planes takes them -> xo with the levels k .. L-2 moved to their bins' centroids: per level ONE evaluation of
+    the model on the base (quality_layers.level_params, the call the quality layers make) and ONE ops.gauss_centroid with the
+    step in force -- the pair of layer j, the header's pair, or the level's view of a step map.  The coarsest level and the
+    levels a reduced decode does not reach are never touched."""
+    from ... import quality_layers
+    L = len(base)
+    smap = _check_step(step, L, em)
+    for i in range(k, L - 1):
+        v = xo[i - k].contiguous()
+        if layers is not None and layers[2] > 0:
+            pair = ops.layer_pair(layers[1], layers[2])
+        elif isinstance(smap, torch.Tensor):
+            pair = _level_step(smap, L, i, v.shape, v.device)
+        else:
+            pair = ops.step_pair(smap)
+        xo[i - k] = ops.gauss_centroid(v, quality_layers.level_params(em, i, base), pair)
+    return xo
 
 
 class LiftingBasedDWTNet(PackedOwnerMixin, nn.Module):

@@ -1522,6 +1522,41 @@ def layer_apply(v_prev, sym, sign, cur, out=None):
     return v
 
 
+RECONS = ("centre", "centroid")      # the decoders' recon argument; None is "centre"
+
+
+def check_recon(recon):
+    """The ``recon`` argument of the decoders -> "centre" (None too) or "centroid".  ValueError naming recon otherwise."""
+    if recon is None:
+        return RECONS[0]
+    if not (isinstance(recon, str) and recon in RECONS):
+        raise ValueError("recon must be None or one of %s: where a decoder puts a coefficient inside its quantisation bin (got %r)"
+                         % (", ".join(repr(r) for r in RECONS), recon))
+    return recon
+
+
+def gauss_centroid(v, params, pair, out=None):
+    """Centroid reconstruction of a level (lldwt_gauss_centroid).  v (P,B,C,h,w): the decoded values; params
+    (P,B,2C,h,w): sigma on the even, mu on the odd channels (quality_layers.level_params); pair: the step in force, (q, inv_q)
+    of step_pair / layer_pair, or a StepMap over the level (one map per image b of B; lldwt_gauss_centroid_map) -> every value
+    moved from the centre of its bin to the bin's mean under N(mu, sigma^2), never out of the bin (out: where to write it, v
+    itself allowed)."""
+    if v.dim() != 5 or params.dim() != 5 or tuple(params.shape) != (v.shape[0], v.shape[1], 2 * v.shape[2], v.shape[3], v.shape[4]):
+        raise _lib.LLDWTError("gauss_centroid: level %s and params %s do not belong together" % (tuple(v.shape), tuple(params.shape)))
+    P, B, G, h, w = v.shape
+    o = torch.empty_like(v) if out is None else out
+    if o.shape != v.shape:
+        raise _lib.LLDWTError("gauss_centroid: out %s and the level %s differ in shape" % (tuple(o.shape), tuple(v.shape)))
+    if isinstance(pair, StepMap):
+        check(_lib.load().lldwt_gauss_centroid_map(_chk(params, "params"), _chk(v, "v"), _chk(o, "out"), P * B, B, G, h, w,
+                                                   *_map_args(pair, B, h, w), _stream()), "gauss_centroid_map")
+        return o
+    q, inv_q = pair
+    check(_lib.load().lldwt_gauss_centroid(_chk(params, "params"), _chk(v, "v"), _chk(o, "out"), P * B, G, h, w, float(q),
+                                           float(inv_q), _stream()), "gauss_centroid")
+    return o
+
+
 def cost_table(cdf, sizes):
     """Quantised CDF tables (host int32 arrays: cdf (T, width), sizes (T)) -> (T, width) int32 numpy array for code_cost:
     round(-log2(freq / 65536) * 2^16) for the sizes[t] - 2 symbols of table t, COST_ESCAPE elsewhere."""

@@ -933,6 +933,25 @@ int lldwt_layer_rows(const float* v_prev, const float* params, const float* tabl
 int lldwt_layer_apply(const float* v_prev, const int32_t* sym, const int32_t* sign, float* v_out, int64_t streams, int channels,
                       int64_t h, int64_t w, float q, float inv_q, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Centroid reconstruction of the levels that carry a step (a decoder's choice; DESIGN.md 7.1.13, csrc/recon.hip).
+ * Element-wise over a level v (streams, channels, h, w) fp32 with its Gaussian parameters (streams, 2 channels, h, w), sigma of
+ * channel c on 2c and mu on 2c + 1 (the layout of lldwt_gauss_quantise), all fp32 with every product rounded:
+ *   u   = (v - mu) * inv_q,  a = |u|,  s = max(sigma * inv_q, 0.11)
+ *   out = clamp(v - copysign(q * delta(a, s), u), v - q / 2, v + q / 2)
+ *   delta(a, s) = a - E[X | a - 1/2 <= X <= a + 1/2], X ~ N(0, s^2), to the tolerance DESIGN.md 7.1.13 states (not to bits)
+ * and out = v wherever u, sigma * inv_q or delta is not a finite number.  out may be v.
+ * lldwt_gauss_centroid takes the step in force as a pair (q, fp32(1 / q)) formed on the host (the division in double; q in
+ * (0, 64]), else LLDWT_EINVAL; lldwt_gauss_centroid_map takes the pair of every element from a step map as
+ * lldwt_gauss_quantise_map does: qpairs (units, mh, mw, 2), stream z reads the map of unit z % units and position (i, j) the
+ * pair at (i >> shift, j >> shift); the map must cover the h x w level and be 8-byte aligned, else LLDWT_EINVAL.
+ * One 16-byte access per array and thread where w % 4 == 0 and every array is 16-byte aligned, one element per thread
+ * otherwise.  streams * channels <= 65535.  Nothing synchronises. */
+int lldwt_gauss_centroid(const float* params, const float* v, float* out, int64_t streams, int channels, int64_t h, int64_t w,
+                         float q, float inv_q, void* stream);
+int lldwt_gauss_centroid_map(const float* params, const float* v, float* out, int64_t streams, int64_t units, int channels,
+                             int64_t h, int64_t w, const float* qpairs, int64_t mh, int64_t mw, int shift, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

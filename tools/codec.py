@@ -55,6 +55,12 @@
                                            files.  Not with --near / --lossless, --layers, --roi, --overlap, --target-psnr /
                                            --target-msssim
 
+    decode --recon {centre,centroid}       centroid puts every coefficient of the levels that carry a step at the mean of its
+                                           quantisation bin under the entropy model's Gaussian instead of the bin's centre: no
+                                           bits, no container change, a little less error at large steps, behind --roi and under
+                                           truncated --layers.  Not over a refined (LLDR) container without --base-only.  With
+                                           --compare SRC the two reconstructions can be told apart by PSNR / MS-SSIM
+
 The config is a JSON object of LiftingBasedDWTNetWrapper keys (utils/config.py DEFAULTS fill the rest).  The checkpoint is
 read with the weights-only unpickler and must match the model's key set exactly (agents/base.py load_checkpoint).
 Without a checkpoint the net gets seeded default-initialised weights -- for trying the tool out only: encoder and
@@ -232,6 +238,9 @@ def main(argv=None):
                                        help="samples of D bits in 9..16 from a .npy, .ppm or .pgm file (default: 8-bit image files)")
     sub.choices["decode"].add_argument("--layers", type=int, metavar="J",
                                        help="decode the base plus the first J quality layers of an LLDP container (default: all)")
+    sub.choices["decode"].add_argument("--recon", choices=("centre", "centroid"), default="centre",
+                                       help="where a coefficient goes inside its quantisation bin: the centre (default) or the "
+                                            "bin's mean under the entropy model's Gaussian")
     sub.choices["decode"].add_argument("--base-only", action="store_true",
                                        help="decode the base layer of a refined (LLDR) container only")
     sub.choices["decode"].add_argument("--region", help="y0,x0,h,w: decode only this region (tiled containers only)")
@@ -403,6 +412,8 @@ def main(argv=None):
         kw = {"refine": False} if a.base_only else {}
         if a.layers is not None:
             kw["layers"] = a.layers
+        if a.recon != "centre":
+            kw["recon"] = a.recon
         inner = codec.read_header(blob)["inner"] if blob[:4] == codec.MAPPED_MAGIC else codec.read_header(blob)
         tiled = "ny" in inner.get("base", inner)
         region = None
