@@ -217,6 +217,8 @@ SIGNATURES = {
     "lldwt_layer_apply": (_i, [_p] * 4 + [_i64, _i, _i64, _i64, _f, _f, _p]),
     "lldwt_gauss_centroid": (_i, [_p] * 3 + [_i64, _i, _i64, _i64, _f, _f, _p]),
     "lldwt_gauss_centroid_map": (_i, [_p] * 3 + [_i64, _i64, _i, _i64, _i64, _p, _i64, _i64, _i, _p]),
+    "lldwt_aq_activity": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _p]),
+    "lldwt_aq_steps": (_i, [_p, _p, _p, _i64, _i64, _i, _i, _p]),
 }
 
 _lib = None

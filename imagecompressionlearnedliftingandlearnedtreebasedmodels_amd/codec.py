@@ -278,6 +278,27 @@ def check_rdo(rdo):
     return int(m)
 
 
+# adaptive quantisation: the strength aq = m / AQ_DENOM of the activity-derived step map
+AQ_DENOM, AQ_M_MAX = 16, 32
+
+
+def check_aq(aq):
+    """The strength of adaptive quantisation of the API -> m, the integer with aq == m / 16 (None and 0 -> 0: off).  ValueError
+    naming aq unless the value is exactly m / 16 with m in [1, 32]."""
+    if aq is None:
+        return 0
+    try:
+        m = float(aq) * AQ_DENOM
+    except (TypeError, ValueError):
+        raise ValueError("aq must be a number (got %r)" % (aq,)) from None
+    if m == 0:
+        return 0
+    if not (m == m and 1 <= m <= AQ_M_MAX and m == int(m)):
+        raise ValueError("aq must be m / %d with an integer m in [1, %d], i.e. a multiple of %g in [%g, %g], or 0 / None for off "
+                         "(got %r)" % (AQ_DENOM, AQ_M_MAX, 1.0 / AQ_DENOM, 1.0 / AQ_DENOM, AQ_M_MAX / AQ_DENOM, aq))
+    return int(m)
+
+
 def _split_step(arith):
     """arithmetic string -> (n, the string without the step key); n = 16 when the key is absent.  ValueError naming step if
     the key occurs twice or its value is not a decimal integer in [4, 1024] other than 16 (the unit step is written by
@@ -1395,6 +1416,61 @@ def _unit_maps(maps, units, grid, L, dev):
     return torch.from_numpy(np.stack(out).astype(np.int32)).to(dev)
 
 
+def _aq_args(aq, L, step_map=None, layers=None, chroma="444", depth=None):
+    """The aq argument of encode_images / encode_tiled, checked on the host before any GPU work -> m (0: off).  ValueError naming
+    aq and the other argument for what adaptive quantisation does not compose with: step_map (two sources of
+    a map), layers (a layer's step is one number per level), a chroma format other than "444" and depth > 8 (the analysis reads
+    uint8 RGB); also without a level that carries a step (dwtlevels < 2)."""
+    m = check_aq(aq)
+    if m == 0:
+        return 0
+    if step_map is not None:
+        raise ValueError("aq and step_map: give one of them (each is a source of the step map)")
+    if layers is not None and not (not isinstance(layers, bool) and layers == 0):
+        raise ValueError("aq and layers: quality layers do not compose with a step map, so not with aq")
+    if check_chroma(chroma) != "444":
+        raise ValueError("aq and chroma: aq analyses uint8 RGB, it does not compose with chroma=%s; use chroma=\"444\"" % chroma)
+    if check_depth(depth) != 8:
+        raise ValueError("aq and depth: aq analyses uint8 RGB, it does not compose with depth=%d" % check_depth(depth))
+    if L < 2:
+        raise ValueError("aq: a step map needs dwtlevels >= 2 (it applies to the levels below the coarsest; the net has %d)" % L)
+    if L > 8:
+        raise ValueError("aq: the analysis is defined for blocks of up to 256 pixels, dwtlevels <= 8 (the net has %d)" % L)
+    return m
+
+
+class _Activity:
+    """The activity of a batch, computed ONCE on the device (ops.aq_activity); maps(n_q) -> the (B, hb, wb)
+    uint16 array of n at the base step n_q / 16, maps(n_q, b) -> that of image b alone as (1, hb, wb): only ops.aq_steps runs."""
+
+    def __init__(self, images_u8, L, m, dev):
+        from . import ops
+        self.m = m
+        self.a, self.A = ops.aq_activity(images_u8.to(dev).contiguous(), L)
+
+    def maps(self, n_q, b=None):
+        import numpy as np
+        from . import ops
+        a, A = (self.a, self.A) if b is None else (self.a[b:b + 1], self.A[b:b + 1])
+        return ops.aq_steps(a, A, self.m / AQ_DENOM, n_q).cpu().numpy().astype(np.uint16)
+
+
+def activity_step_map(images_u8, L, aq, step=1.0):
+    """The step map of adaptive quantisation -> (B, hb, wb) float64 numpy array of steps, which step_map=
+    accepts: encode_*(..., aq=aq, step=step) writes the bytes of encode_*(..., step_map=activity_step_map(images, L, aq, step)).
+    images_u8: (B,H,W,3) uint8 (CPU or device; analysed on the current device); L: the net's dwtlevels (2 .. 8); aq: the strength
+    m / 16, m in 1..32; step: the base step n / 16.  Flat blocks get finer and busy blocks coarser steps around the base, a
+    quarter octave per octave of (luma variance + 4)^(aq / 4), centred on the image's own mean."""
+    import numpy as np
+    import torch
+    m = _aq_args(aq, L)
+    if m == 0:
+        raise ValueError("aq: activity_step_map needs a strength m / 16 with m in [1, 32] (got %r)" % (aq,))
+    _check_images(images_u8)
+    dev = images_u8.device if images_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return _Activity(images_u8, L, m, dev).maps(check_step(step)).astype(np.float64) / STEP_DENOM
+
+
 def psnr_sse_bound(psnr, H, W):
     """The largest sum of squared byte errors over the 3 H W samples of an H x W uint8 RGB image at which its PSNR,
     10 log10(255^2 * 3 H W / SSE) as ``quality`` reports it, is still at least ``psnr`` dB: floor(3 H W * 65025 / 10^(psnr / 10))
@@ -1534,7 +1610,7 @@ def _estimated_size(empty, estimates):
 
 
 def encode_images(net, images_u8, coder="host", near=None, step=None, target_bytes=None, rdo=None, step_map=None,
-                  layers=None, chroma="444", depth=None, target_psnr=None, target_msssim=None):
+                  layers=None, chroma="444", depth=None, aq=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor (CPU or device, one size per call) -> list of B containers (bytes).  coder: "host" (the
     default; rans64 on the host) or "gpu" (irans32 on the device, recorded in the arithmetic string).
     near: None -> LLDW as ever; 0 -> lossless, d in 1..32 -> every decoded sample within d of the original: LLDR containers
@@ -1566,11 +1642,18 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
     it from the header.  With coder, step, target_bytes and rdo; not with near, layers, step_map or a quality target.
     depth: None and 8 take uint8 and write the bytes above; d in 9..16 takes a uint16 tensor of d-bit samples
     (a sample above 2^d - 1 is a ValueError naming depth), recorded as one more key of the arithmetic string; the decoders then
-    return uint16.  With coder, step, target_bytes, rdo and chroma; not with near, layers, step_map or a quality target."""
+    return uint16.  With coder, step, target_bytes, rdo and chroma; not with near, layers, step_map or a quality target.
+    aq = m / 16, m in 1..32: adaptive quantisation, a step map derived from the image on the device -- flat
+    blocks of 2^L x 2^L pixels get finer steps, busy ones coarser, around a base step, with the image's mean log-step held.
+    With step = q (or none) the bytes are those of step_map=activity_step_map(images, L, aq, q): an LLDQ container, nothing new
+    to a decoder.  With target_bytes, target_psnr or target_msssim the searches above move the BASE step along STEP_GRID (the map
+    is the rule's at every base) and SEARCH_STATS reports the base.  With coder, rdo and near (no target then); not with
+    step_map, layers, chroma other than "444", depth > 8 or dwtlevels < 2.  None and 0 write the bytes above."""
     from .graphs.layers.lifting_dwt_nets import padded_size
     ch = _chroma_args(chroma, near, layers, step_map, 0, target_psnr, target_msssim)
     d = _depth_args(depth, near, layers, step_map, 0, target_psnr, target_msssim)
     layer, nettype, L = describe(net)
+    aq = _aq_args(aq, L, step_map, layers, chroma, depth)
     B, H, W = _check_images(images_u8, ch, d)
     m = _layer_args(layers, step, L, near, step_map, 0, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
@@ -1584,32 +1667,47 @@ def encode_images(net, images_u8, coder="host", near=None, step=None, target_byt
         Hp, Wp = padded_size([m.autoencoder for m in net.nets()], H, W)
     else:
         Hp, Wp, _, _ = chroma_sizes(L, nettype == "CDF97", H, W, ch)
-    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m, ch, d)
+    return _encode_at_rate(net, images_u8, (MAGIC, (Hp, Wp, 1, 1, 0), B, coder), near, n, T, rdo, maps, target, m, ch, d, aq)
 
 
-def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0, chroma="444", depth=8):
+def _encode_at_rate(net, images_u8, walk, near, step_n, T, rdo=None, maps=None, target=None, layers=0, chroma="444", depth=8, aq=0):
     """_encode at the step step_n / 16, or with a byte target T the search of _search_step, or with a quality target (the
     pair of _quality_args) that of _encode_at_quality, one image at a time.  walk: the (magic, grid, group, coder) of _encode.
     rdo: probes and real encodes alike.  layers: the number of quality layers (_layer_args: no target then).  chroma: the
-    format of _chroma_args (not "444": no near, maps, quality target or layers).  depth: that of _depth_args (not 8: the same)."""
+    format of _chroma_args (not "444": no near, maps, quality target or layers).  depth: that of _depth_args (not 8: the same).
+    aq: the m of _aq_args ("444", 8 bits, no maps or layers): the batch's activity is taken once, step_n / 16
+    is the BASE step of the activity's map, which is coded as any step map (the unit step in the arithmetic string), and a
+    target moves that base along STEP_GRID -- per probe only the map is formed again."""
+    act = None
+    if aq:
+        act = _Activity(images_u8, describe(net)[2], aq, next(net.parameters()).device)
     if target is not None:
-        return _encode_at_quality(net, images_u8, walk, rdo, target)
+        return _encode_at_quality(net, images_u8, walk, rdo, target, act)
     kw = dict(rdo=rdo, chroma=chroma, depth=depth)
     if T is None:
+        if act is not None:
+            step_n, maps = STEP_DENOM, act.maps(step_n)
         return _encode(net, images_u8, *walk, near, step_n, maps=maps, layers=layers, **kw)
-    return [_search_step(lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, estimate=True, **kw)[0],
-                         lambda m, i=images_u8[b:b + 1]: _encode(net, i, *walk, None, m, **kw)[0], T)
-            for b in range(images_u8.shape[0])]
+
+    def coded(b, estimate):
+        """n -> image b's container (or its estimated size) at the step n / 16, with aq at the BASE step n / 16."""
+        img = images_u8[b:b + 1]
+        if act is None:
+            return lambda n: _encode(net, img, *walk, None, n, estimate=estimate, **kw)[0]
+        return lambda n: _encode(net, img, *walk, None, STEP_DENOM, estimate=estimate, maps=act.maps(n, b), **kw)[0]
+    return [_search_step(coded(b, True), coded(b, False), T) for b in range(images_u8.shape[0])]
 
 
-def _probe_quality(net, image_u8, magic, grid, group, step_n, rdo, kind):
+def _probe_quality(net, image_u8, magic, grid, group, step_n, rdo, kind, maps=None):
     """One probe of a quality target: ONE image (1,H,W,3) goes through the encode walk of _encode at the step
     step_n / 16 with the estimating sink (no range coder runs) and the encoder's own reconstruction, which is the decoder's
     (encode_strings_planes(..., recon=True)), and the image decode_images / decode_tiled would return for that container is
     measured on the device: kind "psnr" -> its exact integer SSE against the original (lldwt_ycc_tiles_sq_err; no image is
     written), kind "msssim" -> the channel mean of ops.ms_ssim on the u8 pair, as ``quality`` computes it.  Plain tiles are
     measured on their in-image rectangles; lapped tiles are blended in ascending tile index into an fp32 frame
-    (ops.ycc_tiles_blend), which is then taken as the tile of a 1 x 1 grid, as decode_tiled finishes such a frame."""
+    (ops.ycc_tiles_blend), which is then taken as the tile of a 1 x 1 grid, as decode_tiled finishes such a frame.
+    maps: the image's (1, hb, wb) array of n instead of the one step (step_n is then 16): every tile is quantised with its slice
+    (_unit_maps), as _encode codes it and the decoders read it from an LLDQ container."""
     import torch
     from . import ops
     from .graphs.models.LiftingBasedDWT_net import encode_strings_planes
@@ -1633,7 +1731,8 @@ def _probe_quality(net, image_u8, magic, grid, group, step_n, rdo, kind):
                 x = ops.u8hwc_to_ycc_tiles_lapped(img, th, tw, ov, ny, nx, first, n)
             else:
                 x = ops.u8hwc_to_ycc_tiles(img, th, tw, ny, nx, first, n)
-            xhat = encode_strings_planes(nets, x, coder=ESTIMATE, recon=True, step=step, rdo=rdo)[2].contiguous()
+            st = step if maps is None else _unit_maps(maps, range(first, first + n), grid, describe(net)[2], dev)
+            xhat = encode_strings_planes(nets, x, coder=ESTIMATE, recon=True, step=st, rdo=rdo)[2].contiguous()
             if ov:
                 ops.ycc_tiles_blend(xhat, (H, W, th, tw, ov, ny, nx), (0, 0, H, W), list(range(first, first + n)), acc)
             elif kind == "psnr":
@@ -1649,10 +1748,12 @@ def _probe_quality(net, image_u8, magic, grid, group, step_n, rdo, kind):
         return float(ops.ms_ssim(ops.u8hwc_to_f32chw(img), ops.u8hwc_to_f32chw(rec), offset=0.0).mean(1).item())
 
 
-def _encode_at_quality(net, images_u8, walk, rdo, target):
+def _encode_at_quality(net, images_u8, walk, rdo, target, act=None):
     """The quality target of DESIGN.md 7.1.9, one image (or one tiled frame) at a time: _search_quality over probes of
     _probe_quality, then ONE real encode at the chosen step -- the container of encode_*(..., step=<chosen>) byte for byte.
-    walk: the (magic, grid, group, coder) of _encode; target: the pair of _quality_args; rdo: probes and the encode alike."""
+    walk: the (magic, grid, group, coder) of _encode; target: the pair of _quality_args; rdo: probes and the encode alike.
+    act: the batch's _Activity (adaptive quantisation): the search moves the BASE step of the activity's map,
+    and the container is that of encode_*(..., step_map=<the map at the chosen base>)."""
     magic, grid, group, coder = walk
     kind, want = target
     B, H, W = _check_images(images_u8)
@@ -1661,8 +1762,14 @@ def _encode_at_quality(net, images_u8, walk, rdo, target):
     for b in range(B):
         img, vals = images_u8[b:b + 1], {}
 
+        def at(k):
+            """Grid index k -> (step_n, maps) of _probe_quality and _encode: the step alone, or with aq the unit step and the
+            activity's map at the base STEP_GRID[k] / 16."""
+            return (STEP_GRID[k], None) if act is None else (STEP_DENOM, act.maps(STEP_GRID[k], b))
+
         def meets(k):
-            vals[k] = _probe_quality(net, img, magic, grid, group, STEP_GRID[k], rdo, kind)
+            step_n, maps = at(k)
+            vals[k] = _probe_quality(net, img, magic, grid, group, step_n, rdo, kind, maps=maps)
             return vals[k] <= bound if kind == "psnr" else vals[k] >= want
 
         def fail():
@@ -1672,7 +1779,8 @@ def _encode_at_quality(net, images_u8, walk, rdo, target):
                                   % (want, q0, sse_psnr(vals[0], H, W)))
             return ValueError("target_msssim: %g cannot be met; at the finest step %g the best is %.6f" % (want, q0, vals[0]))
         k, probes = _search_quality(meets, fail)
-        blob = _encode(net, img, magic, grid, group, coder, None, STEP_GRID[k], rdo=rdo)[0]
+        step_n, maps = at(k)
+        blob = _encode(net, img, magic, grid, group, coder, None, step_n, rdo=rdo, maps=maps)[0]
         blobs.append(blob)
         stats.append({"probes": probes, "encodes": 1, "step": STEP_GRID[k] / STEP_DENOM, "bytes": len(blob),
                       "sse" if kind == "psnr" else "msssim": vals[k]})
@@ -1733,10 +1841,11 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
     output kernels serve -- and coded ``group`` tiles at a time (over all images of the batch; one per call in the
     arithmetics that are not batch invariant) at the step step_n / 16 -> the B containers of ``magic``, with near the LLDR
     containers over them.  estimate: -> the estimated container sizes (ints) from the code-length kernel instead; no range
-    coder runs.  rdo: the Lagrangian of DESIGN.md 7.1.7 (None: off), which only the encoder's symbols see.
+    coder runs (with maps the estimate counts the qmap key and the LLDQ wrapper too).  rdo: the Lagrangian of DESIGN.md 7.1.7
+    (None: off), which only the encoder's symbols see.
     maps: the (B, hb, wb) array of _map_arg (None: the step alone): every unit is coded with its slice of its image's map
     (_unit_maps), every base carries the qmap key of its image's map, and the result is wrapped into LLDQ (pack_mapped).
-    layers: m > 0 quality layers (without near, maps or estimate): every group's layer streams are coded right
+    layers: m > 0 quality layers (without near or maps, and not estimated): every group's layer streams are coded right
     after its base, from the group's own tensors, and the containers are wrapped into LLDP (pack_layered).
     chroma: "420" / "400" (without near, maps, layers or overlap): the same walk, each group cut and coded
     plane by plane (_encode_chroma_planes), the streams interleaved into the LLDW order, the header carrying the chroma key.
@@ -1787,8 +1896,14 @@ def _encode(net, images_u8, magic, grid, group, coder, near, step_n, estimate=Fa
                 ops.ycc_tiles_to_u8hwc(xhat.contiguous(), (H, W, th, tw, ny, nx), (0, 0, H, W), first=first, B=B, out=xh)
             tiles += [_tile_streams(s_xe, s_xo, j) for j in range(n)]
         if estimate:
-            empty = _pack_base(magic, hdr, [[b""] * count] * per)
-            return [_estimated_size(empty, [e for t in tiles[b * per:(b + 1) * per] for e in t]) for b in range(B)]
+            sizes = []
+            for b in range(B):
+                empty = _pack_base(magic, hdrs[b], [[b""] * count] * per)
+                size = _estimated_size(empty, [e for t in tiles[b * per:(b + 1) * per] for e in t])
+                if maps is not None:         # the LLDQ wrapper, whose inner length field grows with the inner container
+                    size += len(pack_mapped(maps[b], empty)) - len(empty) + len(leb128_encode(size)) - len(leb128_encode(len(empty)))
+                sizes.append(size)
+            return sizes
         blobs = [_pack_base(magic, hdrs[b], tiles[b * per:(b + 1) * per]) for b in range(B)]
         if near is not None:
             blobs = _refine(blobs, img, xh, (H, W, th, tw, ny, nx), near, coder)
@@ -2056,7 +2171,7 @@ def _tile_streams(s_xe, s_xo, j, planes=_PLANES):
 
 
 def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", overlap=0, near=None, step=None, target_bytes=None,
-                 rdo=None, step_map=None, layers=None, chroma="444", depth=None, target_psnr=None, target_msssim=None):
+                 rdo=None, step_map=None, layers=None, chroma="444", depth=None, aq=None, target_psnr=None, target_msssim=None):
     """(B,H,W,3) uint8 RGB tensor -> list of B LLDT containers, or with overlap > 0 LLDO containers of lapped tiles
     (tile_grid_lapped; the tiles are cut by lldwt_u8hwc_to_ycc_tiles_lapped and coded exactly as below).
     Every tile is coded as an independent image: its streams
@@ -2077,10 +2192,13 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     region decodes the refinement of the tiles it touches only.
     chroma: as encode_images; with "420" the tile grid is that of chroma_sizes (the half of a tile is a size the transform
     accepts) and every tile's streams are those of encode_images(net, tile, chroma="420"); not with overlap > 0.
-    depth: as encode_images (uint16 samples of 9..16 bits); not with overlap > 0."""
+    depth: as encode_images (uint16 samples of 9..16 bits); not with overlap > 0.
+    aq: as encode_images; the map is that of the whole frame and a tile takes its slice as with step_map, for plain and lapped
+    tiles alike; a target moves the one base step of the frame."""
     ch = _chroma_args(chroma, near, layers, step_map, overlap, target_psnr, target_msssim)
     d = _depth_args(depth, near, layers, step_map, overlap, target_psnr, target_msssim)
     layer, nettype, L = describe(net)
+    aq = _aq_args(aq, L, step_map, layers, chroma, depth)
     B, H, W = _check_images(images_u8, ch, d)
     m = _layer_args(layers, step, L, near, step_map, overlap, target_bytes, target_psnr, target_msssim)
     target = _quality_args(target_psnr, target_msssim, target_bytes, step, step_map, near, L, H, W)
@@ -2103,7 +2221,7 @@ def encode_tiled(net, images_u8, tile=512, tiles_per_call=32, coder="host", over
     if ny > 0xFFFF or nx > 0xFFFF:
         raise ValueError("tile grid %d x %d: ny, nx must fit 16 bits" % (ny, nx))
     walk = (LAPPED_MAGIC if ov else TILED_MAGIC, (th, tw, ny, nx, ov), group, coder)
-    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m, ch, d)
+    return _encode_at_rate(net, images_u8, walk, near, n, T, rdo, maps, target, m, ch, d, aq)
 
 
 def _tiles_per_call(tiles_per_call):

@@ -14,7 +14,7 @@ mkdir -p "$HERE/obj"
 HDRS="$HERE/common.h $HERE/lifting_f16.h $HERE/split_f16.h $HERE/plc_fold.h $HERE/../../include/lldwt.h"
 pids=()
 names=()
-for f in ops subband_mlp_f16 lifting lifting_f16 cdf97 conv_mfma conv_f16x3 conv_wgrad_f16x3 cgp_fused cgp_f16x3 conv_bwd rans rans_gpu ztblock msssim residual quant layers chroma depth recon; do
+for f in ops subband_mlp_f16 lifting lifting_f16 cdf97 conv_mfma conv_f16x3 conv_wgrad_f16x3 cgp_fused cgp_f16x3 conv_bwd rans rans_gpu ztblock msssim residual quant layers chroma depth recon aq; do
   [ -f "$HERE/$f.hip" ] || continue
   EXTRA=""
   # the 36-unit chunk loop of the split-fp16 conv must unroll completely (register rings indexed by the unit number)

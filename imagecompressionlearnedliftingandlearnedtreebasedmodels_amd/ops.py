@@ -1557,6 +1557,44 @@ def gauss_centroid(v, params, pair, out=None):
     return o
 
 
+AQ_DENOM = 16                        # a strength of adaptive quantisation is m / AQ_DENOM, m in [1, AQ_M_MAX]
+AQ_M_MAX = 32
+AQ_L_MIN, AQ_L_MAX = 2, 8            # blocks of 2^L x 2^L pixels
+
+
+def aq_activity(images_u8, L):
+    """The activity of every block of 2^L x 2^L pixels of a (B,H,W,3) uint8 device batch (lldwt_aq_activity)
+    -> (a, A): a (B, ceil(H / 2^L), ceil(W / 2^L)) int32, the eighth-octave logarithm of the block's luma AC energy plus its
+    floor, and A (B,) int64, the sum of a over each image.  Integers: exact and reproducible."""
+    B, H, W = _u8hwc(images_u8, "aq_activity")
+    if not (isinstance(L, int) and AQ_L_MIN <= L <= AQ_L_MAX):
+        raise _lib.LLDWTError("aq_activity: L must be an integer in [%d, %d] (got %r)" % (AQ_L_MIN, AQ_L_MAX, L))
+    a = torch.empty(B, -(-H >> L), -(-W >> L), device=images_u8.device, dtype=torch.int32)
+    A = torch.empty(B, device=images_u8.device, dtype=torch.int64)
+    check(_lib.load().lldwt_aq_activity(C.c_void_p(images_u8.data_ptr()), C.c_void_p(a.data_ptr()), C.c_void_p(A.data_ptr()),
+                                        B, H, W, L, _stream()), "aq_activity")
+    return a, A
+
+
+def aq_steps(a, A, aq, step_n):
+    """The step map of adaptive quantisation (lldwt_aq_steps): a (B,hb,wb) int32 and A (B,) int64 of
+    aq_activity, the strength aq = m / 16 (m in 1..32) and the base step step_n / 16 (step_n in [4, 1024]) -> (B,hb,wb) int32
+    device tensor of n, n / 16 the step of each block.  A byte or quality target reruns only this for every base it tries."""
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.int32 and a.is_contiguous() and a.dim() == 3
+            and isinstance(A, torch.Tensor) and A.is_cuda and A.dtype == torch.int64 and A.is_contiguous()
+            and tuple(A.shape) == (a.shape[0],)):
+        raise _lib.LLDWTError("aq_steps: a must be a contiguous (B,hb,wb) int32 and A a (B,) int64 device tensor")
+    m = float(aq) * AQ_DENOM
+    if not (1 <= m <= AQ_M_MAX and m == int(m)):
+        raise _lib.LLDWTError("aq_steps: aq must be m / %d with an integer m in [1, %d] (got %r)" % (AQ_DENOM, AQ_M_MAX, aq))
+    if not (isinstance(step_n, int) and STEP_N_MIN <= step_n <= STEP_N_MAX):
+        raise _lib.LLDWTError("aq_steps: step_n must be an integer in [%d, %d] (got %r)" % (STEP_N_MIN, STEP_N_MAX, step_n))
+    n = torch.empty_like(a)
+    check(_lib.load().lldwt_aq_steps(C.c_void_p(a.data_ptr()), C.c_void_p(A.data_ptr()), C.c_void_p(n.data_ptr()), a.shape[0],
+                                     a.shape[1] * a.shape[2], int(m), step_n, _stream()), "aq_steps")
+    return n
+
+
 def cost_table(cdf, sizes):
     """Quantised CDF tables (host int32 arrays: cdf (T, width), sizes (T)) -> (T, width) int32 numpy array for code_cost:
     round(-log2(freq / 65536) * 2^16) for the sizes[t] - 2 symbols of table t, COST_ESCAPE elsewhere."""

@@ -952,6 +952,24 @@ int lldwt_gauss_centroid(const float* params, const float* v, float* out, int64_
 int lldwt_gauss_centroid_map(const float* params, const float* v, float* out, int64_t streams, int64_t units, int channels,
                              int64_t h, int64_t w, const float* qpairs, int64_t mh, int64_t mw, int shift, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Adaptive quantisation: a step map derived from the image (csrc/aq.hip).  Integers only: defined to the bit.
+ * lldwt_aq_activity: img (B, H, W, 3) uint8 RGB -> a (B, hb, wb) int32 with hb = ceil(H / 2^L), wb = ceil(W / 2^L), and sums (B)
+ * int64, the sum of a over each image (zeroed here, then added to with integer atomics: exact in any order).  Per block of
+ * 2^L x 2^L pixels, coordinates clamped to the image:
+ *   Y = (77 R + 150 G + 29 B + 128) >> 8
+ *   S = sum over the block's 4 x 4 cells of 16 sum(Y^2) - (sum Y)^2,  x = S + (1 << (6 + 2 L))
+ *   a = lg(x) = 8 e + #{j in 1..7 : m >= T_j},  e = floor(log2 x),  m = x >> (e - 15) (x << (15 - e) below 2^15),
+ *   T = 35734, 38968, 42495, 46341, 50536, 55109, 60097  (T_j the smallest integer with T_j^8 >= 2^(120 + j))
+ * One pass over the image; nothing else is written.  L in [2, 8], B <= 65535, hb * wb < 2^22; a 4-byte and sums 8-byte aligned.
+ * lldwt_aq_steps: a (B, N) int32 and sums (B) int64 as above, N = hb * wb -> n (B, N) int32, n / 16 the step of each block at the
+ * strength m / 16 (m in [1, 32]) around the base step n_q / 16 (n_q in [4, 1024]):
+ *   d = clamp(floor((2 m (N a - sums) + 128 N) / (256 N)), -8, 24),  n = clamp((n_q * G(d) + 8) >> 4, 4, 1024)
+ * with G(d) = round(16 * 2^(d / 4)), the step grid of a byte target.  N < 2^31; a, n 4-byte and sums 8-byte aligned.
+ * Anything else is LLDWT_EINVAL.  Nothing synchronises. */
+int lldwt_aq_activity(const uint8_t* img, int32_t* a, int64_t* sums, int64_t B, int64_t H, int64_t W, int L, void* stream);
+int lldwt_aq_steps(const int32_t* a, const int64_t* sums, int32_t* n, int64_t B, int64_t N, int m, int n_q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

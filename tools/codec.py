@@ -36,6 +36,13 @@
                                            select.  Not with --target-bytes / --target-bpp.  decode needs no option; info
                                            prints the map's size, its steps and the share of blocks at each
 
+    encode --aq S                          adaptive quantisation at the strength S = m / 16 in (0, 2] (try 1): a step map derived
+                                           from the image -- flat blocks of 2^dwtlevels pixels get finer steps, busy ones coarser,
+                                           around --step (default 1) -- in an LLDQ container, which decode and info read as any
+                                           step map.  With --target-bytes / --target-bpp / --target-psnr / --target-msssim the
+                                           search moves the base step of that map and prints it.  With --tile and --overlap.
+                                           Not with --roi, --layers, --chroma other than 444 or --depth
+
     encode --layers M                      adds M quality layers (1..4) over the container of --step Q: layer j refines the levels
                                            below the coarsest to the step Q / 3^j (Q * 16 / 3^M >= 1), writing an LLDP container.
                                            Not with --near / --lossless, --roi, --overlap or a target
@@ -230,6 +237,9 @@ def main(argv=None):
                                        help="rate-distortion optimised quantisation, Lagrangian m / 64 in (0, 4] (default off)")
     sub.choices["encode"].add_argument("--roi", action="append", metavar="Y0,X0,H,W:Q",
                                        help="code this rectangle at the step Q, the rest at --step (repeatable; writes LLDQ)")
+    sub.choices["encode"].add_argument("--aq", type=float, metavar="S",
+                                       help="adaptive quantisation, strength m / 16 in (0, 2]: an activity-derived step map around "
+                                            "the step, or around the base step a target chooses (writes LLDQ)")
     sub.choices["encode"].add_argument("--layers", type=int, metavar="M",
                                        help="add M quality layers (1..4) that refine the step by 3 each (writes LLDP)")
     sub.choices["encode"].add_argument("--chroma", choices=("444", "420", "400"), default="444",
@@ -344,6 +354,14 @@ def main(argv=None):
             kw["chroma"] = a.chroma
         if deep:
             kw["depth"] = a.depth
+        if a.aq is not None:
+            for flag, given in (("--roi", bool(a.roi)), ("--layers", a.layers is not None), ("--chroma " + a.chroma, a.chroma != "444"),
+                                ("--depth", a.depth is not None)):
+                if given and codec.check_aq(a.aq):
+                    print("--aq cannot be combined with %s (the activity map is defined for 8-bit 4:4:4 images and is the only "
+                          "source of the step map)" % flag, file=sys.stderr)
+                    return 2
+            kw["aq"] = a.aq
         if a.roi:
             if a.target_bytes is not None or a.target_bpp is not None:
                 print("--roi cannot be combined with --target-bytes / --target-bpp (a byte target over a step map is not defined)",
@@ -394,6 +412,8 @@ def main(argv=None):
             hdr = hdr["base"]
         if hdr["step"] != 1.0:
             print("step: %g" % hdr["step"])
+        if a.aq and (a.target_bytes is not None or a.target_bpp is not None):
+            print("aq %g: base step %g" % (a.aq, codec.SEARCH_STATS["step"]))
         if a.target_psnr is not None:
             st = codec.SEARCH_STATS
             print("target %g dB: step %g, %.4f dB (SSE %d), %d probes, %d encode"
