@@ -26,7 +26,7 @@ class LiftOp(C.Structure):
                 ("off_din", C.c_int64), ("sz_din", C.c_int64), ("sy_din", C.c_int64), ("sx_din", C.c_int64),
                 ("off_dout", C.c_int64), ("sz_dout", C.c_int64), ("sy_dout", C.c_int64), ("sx_dout", C.c_int64),
                 ("h", C.c_int32), ("w", C.c_int32), ("vertical", C.c_int32), ("tap", C.c_int32), ("block", C.c_int32),
-                ("is_u", C.c_int32), ("sign", C.c_float), ("pad_", C.c_int32), ("saved_off", C.c_int64)]
+                ("is_u", C.c_int32), ("sign", C.c_float), ("level", C.c_int32), ("saved_off", C.c_int64)]
 
 
 class ConvDesc(C.Structure):
@@ -105,6 +105,9 @@ SIGNATURES = {
     "lldwt_lifting_ws_bytes": (_i64, [_i64, _i64, _i64, _i]),
     "lldwt_lifting_forward": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _f, _i,
                                    _p, _p, _p, _i64, _p]),
+    "lldwt_lifting_forward_split": (_i, [_p, _p, C.POINTER(_p), _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _f, _i,
+                                         _p, _p, _p, _i64, _i, _p, _p, _p]),
+    "lldwt_lift_split_level": (_i, [_i64, _i64, _i64, _i, _i]),
     "lldwt_lifting_inverse": (_i, [_p, C.POINTER(_p), _p, _i64, _i64, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _f, _i,
                                    _p, _p, _p, _i64, _p]),
     "lldwt_lifting_program": (_i, [C.POINTER(LiftOp), _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),

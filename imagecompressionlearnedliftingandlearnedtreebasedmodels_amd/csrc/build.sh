@@ -11,7 +11,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-u
 FORCE="${LLDWT_FORCE_BUILD:-0}"
 [ "$1" = "--force" ] && FORCE=1
 mkdir -p "$HERE/obj"
-HDRS="$HERE/common.h $HERE/lifting_f16.h $HERE/split_f16.h $HERE/plc_fold.h $HERE/../../include/lldwt.h"
+HDRS="$HERE/common.h $HERE/lifting_f16.h $HERE/split_f16.h $HERE/plc_fold.h $HERE/lift_split.h $HERE/../../include/lldwt.h"
 pids=()
 names=()
 for f in ops subband_mlp_f16 lifting lifting_f16 cdf97 conv_mfma conv_f16x3 conv_wgrad_f16x3 cgp_fused cgp_f16x3 conv_bwd rans rans_gpu ztblock msssim residual quant layers chroma depth recon aq; do

@@ -9,6 +9,7 @@
 // pass uses the (kh,kw)-transposed weights instead of transposing the data.
 #include "common.h"
 #include "lifting_f16.h"
+#include "lift_split.h"     // lift_split_level(): where the eval step forks the transform, or 0
 #include <string.h>
 
 namespace lldwt {
@@ -1283,7 +1284,7 @@ static inline SymView sv(int buf, int64_t off, int64_t sz, int64_t sy, int64_t s
 
 static void push_op(lldwt_lift_op* ops, int& n, int max_ops, int kind, SymView src, SymView din, SymView dout, int64_t h,
                     int64_t w, int vertical, int tap, int block, int is_u, float sign, int64_t& saved_off, int64_t Z,
-                    int C) {
+                    int C, int lev) {
     if (n < max_ops) {
         lldwt_lift_op& o = ops[n];
         o.kind = kind;
@@ -1291,7 +1292,7 @@ static void push_op(lldwt_lift_op* ops, int& n, int max_ops, int kind, SymView s
         o.buf_din = din.buf; o.off_din = din.off; o.sz_din = din.sz; o.sy_din = din.sy; o.sx_din = din.sx;
         o.buf_dout = dout.buf; o.off_dout = dout.off; o.sz_dout = dout.sz; o.sy_dout = dout.sy; o.sx_dout = dout.sx;
         o.h = (int32_t)h; o.w = (int32_t)w; o.vertical = vertical; o.tap = tap; o.block = block; o.is_u = is_u;
-        o.sign = sign; o.saved_off = saved_off;
+        o.sign = sign; o.level = lev; o.saved_off = saved_off;
     }
     saved_off += kind == 0 ? saved_step_floats(Z, h, w, C) : Z * h * w;      // a scale op keeps its input
     ++n;
@@ -1300,24 +1301,24 @@ static void push_op(lldwt_lift_op* ops, int& n, int max_ops, int kind, SymView s
 // 2-stage lifting on symbolic (L,H) -> (Lout,Hout) (wavelet_forward_v2.py:58-74 / wavelet_inverse_v2.py:76-90)
 static void two_stage(lldwt_lift_op* ops, int& n, int max_ops, bool inverse, SymView L, SymView H, SymView Lout,
                       SymView Hout, SymView tL, SymView tH, int64_t hh, int64_t ww, int vertical, int blk,
-                      int64_t& so, int64_t Z, int C) {
+                      int64_t& so, int64_t Z, int C, int lev) {
     if (!inverse) {
-        push_op(ops, n, max_ops, 0, L, H, tH, hh, ww, vertical, 0, blk + 0, 0, 1.f, so, Z, C);        // :60-62
-        push_op(ops, n, max_ops, 0, tH, L, tL, hh, ww, vertical, 1, blk + 0, 1, 1.f, so, Z, C);       // :64-66
-        push_op(ops, n, max_ops, 0, tL, tH, Hout, hh, ww, vertical, 2, blk + 1, 0, 1.f, so, Z, C);    // :68-70
-        push_op(ops, n, max_ops, 0, Hout, tL, Lout, hh, ww, vertical, 3, blk + 1, 1, 1.f, so, Z, C);  // :72-74
+        push_op(ops, n, max_ops, 0, L, H, tH, hh, ww, vertical, 0, blk + 0, 0, 1.f, so, Z, C, lev);        // :60-62
+        push_op(ops, n, max_ops, 0, tH, L, tL, hh, ww, vertical, 1, blk + 0, 1, 1.f, so, Z, C, lev);       // :64-66
+        push_op(ops, n, max_ops, 0, tL, tH, Hout, hh, ww, vertical, 2, blk + 1, 0, 1.f, so, Z, C, lev);    // :68-70
+        push_op(ops, n, max_ops, 0, Hout, tL, Lout, hh, ww, vertical, 3, blk + 1, 1, 1.f, so, Z, C, lev);  // :72-74
     } else {
-        push_op(ops, n, max_ops, 0, H, L, tL, hh, ww, vertical, 3, blk + 1, 1, -1.f, so, Z, C);       // :76-78
-        push_op(ops, n, max_ops, 0, tL, H, tH, hh, ww, vertical, 2, blk + 1, 0, -1.f, so, Z, C);      // :80-82
-        push_op(ops, n, max_ops, 0, tH, tL, Lout, hh, ww, vertical, 1, blk + 0, 1, -1.f, so, Z, C);   // :84-86
-        push_op(ops, n, max_ops, 0, Lout, tH, Hout, hh, ww, vertical, 0, blk + 0, 0, -1.f, so, Z, C); // :88-90
+        push_op(ops, n, max_ops, 0, H, L, tL, hh, ww, vertical, 3, blk + 1, 1, -1.f, so, Z, C, lev);       // :76-78
+        push_op(ops, n, max_ops, 0, tL, H, tH, hh, ww, vertical, 2, blk + 1, 0, -1.f, so, Z, C, lev);      // :80-82
+        push_op(ops, n, max_ops, 0, tH, tL, Lout, hh, ww, vertical, 1, blk + 0, 1, -1.f, so, Z, C, lev);   // :84-86
+        push_op(ops, n, max_ops, 0, Lout, tH, Hout, hh, ww, vertical, 0, blk + 0, 0, -1.f, so, Z, C, lev); // :88-90
     }
 }
 
 // scale ops (config.scale == 1): kind 1 = dout = src * nh, 2 = * nl, 3 = / nh, 4 = / nl (per plane)
 static void push_scale(lldwt_lift_op* ops, int& n, int max_ops, int kind, SymView src, SymView dout, int64_t h, int64_t w,
-                       int64_t& so, int64_t Z) {
-    push_op(ops, n, max_ops, kind, src, src, dout, h, w, 0, 0, 0, 0, 1.f, so, Z, 0);
+                       int64_t& so, int64_t Z, int lev) {
+    push_op(ops, n, max_ops, kind, src, src, dout, h, w, 0, 0, 0, 0, 1.f, so, Z, 0, lev);
 }
 
 static int build_program(lldwt_lift_op* ops, int max_ops, int64_t Z, int64_t H, int64_t W, int levels, int different,
@@ -1334,21 +1335,21 @@ static int build_program(lldwt_lift_op* ops, int max_ops, int64_t Z, int64_t H, 
             SymView A = sv(bin, 0, h * w, 2 * w, 1), Bv = sv(bin, w, h * w, 2 * w, 1);         // rows (wavelet_forward_v2.py:27-29)
             SymView vL = sv(B_LROW, 0, hh * w, w, 1), vH = sv(B_HROW, 0, hh * w, w, 1);
             SymView tL = sv(B_TMPL, 0, hh * w, w, 1), tH = sv(B_TMPH, 0, hh * w, w, 1);
-            two_stage(ops, n, max_ops, false, A, Bv, vL, vH, tL, tH, hh, w, 1, blk, so, Z, C);
-            if (scale) { push_scale(ops, n, max_ops, 1, vH, vH, hh, w, so, Z); push_scale(ops, n, max_ops, 2, vL, vL, hh, w, so, Z); }
+            two_stage(ops, n, max_ops, false, A, Bv, vL, vH, tL, tH, hh, w, 1, blk, so, Z, C, lev);
+            if (scale) { push_scale(ops, n, max_ops, 1, vH, vH, hh, w, so, Z, lev); push_scale(ops, n, max_ops, 2, vL, vL, hh, w, so, Z, lev); }
             SymView vLL = sv(bll, 0, sub, wh, 1);
             SymView vLH = sv(byh, 0, 3 * sub, wh, 1), vHL = sv(byh, sub, 3 * sub, wh, 1), vHH = sv(byh, 2 * sub, 3 * sub, wh, 1);
             SymView t2L = sv(B_TMPL, 0, sub, wh, 1), t2H = sv(B_TMPH, 0, sub, wh, 1);
             SymView Le = sv(B_LROW, 0, hh * w, w, 2), Lo = sv(B_LROW, 1, hh * w, w, 2);          // columns of L (:32-39)
-            two_stage(ops, n, max_ops, false, Le, Lo, vLL, vHL, t2L, t2H, hh, wh, 0, blk, so, Z, C);
-            if (scale) { push_scale(ops, n, max_ops, 1, vHL, vHL, hh, wh, so, Z); push_scale(ops, n, max_ops, 2, vLL, vLL, hh, wh, so, Z); }
+            two_stage(ops, n, max_ops, false, Le, Lo, vLL, vHL, t2L, t2H, hh, wh, 0, blk, so, Z, C, lev);
+            if (scale) { push_scale(ops, n, max_ops, 1, vHL, vHL, hh, wh, so, Z, lev); push_scale(ops, n, max_ops, 2, vLL, vLL, hh, wh, so, Z, lev); }
             SymView He = sv(B_HROW, 0, hh * w, w, 2), Ho = sv(B_HROW, 1, hh * w, w, 2);          // columns of H (:43-51)
             // its own temporaries (the second halves of tmpL / tmpH, free during the column passes): the L and H column
             // passes are independent, and the eval executor runs step k of both in ONE launch (run_program)
             const int64_t toff = scale ? 0 : Z * sub;
             SymView u2L = sv(B_TMPL, toff, sub, wh, 1), u2H = sv(B_TMPH, toff, sub, wh, 1);
-            two_stage(ops, n, max_ops, false, He, Ho, vLH, vHH, u2L, u2H, hh, wh, 0, blk, so, Z, C);
-            if (scale) { push_scale(ops, n, max_ops, 1, vHH, vHH, hh, wh, so, Z); push_scale(ops, n, max_ops, 2, vLH, vLH, hh, wh, so, Z); }
+            two_stage(ops, n, max_ops, false, He, Ho, vLH, vHH, u2L, u2H, hh, wh, 0, blk, so, Z, C, lev);
+            if (scale) { push_scale(ops, n, max_ops, 1, vHH, vHH, hh, wh, so, Z, lev); push_scale(ops, n, max_ops, 2, vLH, vLH, hh, wh, so, Z, lev); }
         }
     } else {
         const int blk = block_offset;       // lifting_dwt_nets.py:718-722: every inverse level uses the same pair
@@ -1363,20 +1364,20 @@ static int build_program(lldwt_lift_op* ops, int max_ops, int64_t Z, int64_t H, 
             SymView inL = vLL, inH = vHL;
             // scratch for the scaled copies (config.scale == 1, wavelet_inverse_v2.py:70-74): second halves of tmpL/tmpH
             SymView sL = sv(B_TMPL, Z * (H / 2) * W / 2, sub, wh, 1), sH = sv(B_TMPH, Z * (H / 2) * W / 2, sub, wh, 1);
-            if (scale) { push_scale(ops, n, max_ops, 4, vLL, sL, hh, wh, so, Z); push_scale(ops, n, max_ops, 3, vHL, sH, hh, wh, so, Z); inL = sL; inH = sH; }
+            if (scale) { push_scale(ops, n, max_ops, 4, vLL, sL, hh, wh, so, Z, lev); push_scale(ops, n, max_ops, 3, vHL, sH, hh, wh, so, Z, lev); inL = sL; inH = sH; }
             SymView Le = sv(B_LROW, 0, hh * w, w, 2), Lo = sv(B_LROW, 1, hh * w, w, 2);          // (LL,HL) -> L (:21-26)
-            two_stage(ops, n, max_ops, true, inL, inH, Le, Lo, t2L, t2H, hh, wh, 0, blk, so, Z, C);
+            two_stage(ops, n, max_ops, true, inL, inH, Le, Lo, t2L, t2H, hh, wh, 0, blk, so, Z, C, lev);
             inL = vLH; inH = vHH;
-            if (scale) { push_scale(ops, n, max_ops, 4, vLH, sL, hh, wh, so, Z); push_scale(ops, n, max_ops, 3, vHH, sH, hh, wh, so, Z); inL = sL; inH = sH; }
+            if (scale) { push_scale(ops, n, max_ops, 4, vLH, sL, hh, wh, so, Z, lev); push_scale(ops, n, max_ops, 3, vHH, sH, hh, wh, so, Z, lev); inL = sL; inH = sH; }
             SymView He = sv(B_HROW, 0, hh * w, w, 2), Ho = sv(B_HROW, 1, hh * w, w, 2);          // (LH,HH) -> H (:28-33)
             const int64_t toff = scale ? 0 : Z * sub;                                              // see the forward program
             SymView u2L = sv(B_TMPL, toff, sub, wh, 1), u2H = sv(B_TMPH, toff, sub, wh, 1);
-            two_stage(ops, n, max_ops, true, inL, inH, He, Ho, u2L, u2H, hh, wh, 0, blk, so, Z, C);
+            two_stage(ops, n, max_ops, true, inL, inH, He, Ho, u2L, u2H, hh, wh, 0, blk, so, Z, C, lev);
             SymView vL = sv(B_LROW, 0, hh * w, w, 1), vH = sv(B_HROW, 0, hh * w, w, 1);
             SymView tL = sv(B_TMPL, 0, hh * w, w, 1), tH = sv(B_TMPH, 0, hh * w, w, 1);
             SymView A = sv(bout, 0, h * w, 2 * w, 1), Bv = sv(bout, w, h * w, 2 * w, 1);        // (L,H) -> rows (:35-37)
-            if (scale) { push_scale(ops, n, max_ops, 4, vL, vL, hh, w, so, Z); push_scale(ops, n, max_ops, 3, vH, vH, hh, w, so, Z); }
-            two_stage(ops, n, max_ops, true, vL, vH, A, Bv, tL, tH, hh, w, 1, blk, so, Z, C);
+            if (scale) { push_scale(ops, n, max_ops, 4, vL, vL, hh, w, so, Z, lev); push_scale(ops, n, max_ops, 3, vH, vH, hh, w, so, Z, lev); }
+            two_stage(ops, n, max_ops, true, vL, vH, A, Bv, tL, tH, hh, w, 1, blk, so, Z, C, lev);
         }
     }
     if (saved_total) *saved_total = so;
@@ -1399,6 +1400,10 @@ struct RunCtx {
     float* step_ws;
     float* saved;          // training: per-step intermediates, or null
     hipStream_t st;
+    // forked run (lldwt_lifting_forward_split): the ops of the levels >= split go to `tail` behind `fork`; split 0 = one stream
+    int split;
+    hipStream_t tail;
+    hipEvent_t fork;
 };
 
 // ops[i .. i+3] and ops[i+4 .. i+7] are the two independent column passes (L and H) of one level: same geometry, same
@@ -1428,8 +1433,23 @@ static bool column_pass_pair(const lldwt_lift_op* ops, int n, int i) {
 
 static int run_program(const lldwt_lift_op* ops, int n, float* const* bases, const RunCtx& c) {
     const bool fused_eval = g_lift_mode == 1 && !c.linear && c.saved == nullptr && c.C == LF_C && c.K == LF_K;
+    // Every op runs on the stream of the level whose buffers it writes (o.level): the gain ops and the last level's ll included.
+    // The forward program is in level order, so there is ONE switch: the first op of level `split` records `fork` behind the
+    // last op of level split - 1 (which wrote the LL buffer it reads) and the tail stream waits for it.  The temporaries
+    // (Lrow, Hrow, tmpL, tmpH, the step workspace) are shared by all levels; after the switch only the tail touches them.
+    hipStream_t st = c.st;
+    bool forked = false;
     for (int i = 0; i < n; ++i) {
         const lldwt_lift_op& o = ops[i];
+        if (c.split > 0 && !forked && o.level >= c.split) {
+            if (hipEventRecord(c.fork, c.st) != hipSuccess || hipStreamWaitEvent(c.tail, c.fork, 0) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("lifting program: cannot order the tail stream behind level %d", c.split - 1);
+                return LLDWT_EHIP;
+            }
+            st = c.tail;
+            forked = true;
+        }
         if (fused_eval && o.kind == 0 && column_pass_pair(ops, n, i)) {
             // step k of the L pass and step k of the H pass in one launch (twice the tiles: the deep levels' launches are
             // too small to fill the chip on their own)
@@ -1447,7 +1467,7 @@ static int run_program(const lldwt_lift_op* ops, int n, float* const* bases, con
                 fc.v = views(a); fc.v2 = &vb;
                 fc.Z = c.Z; fc.batch = c.batch; fc.h = a.h; fc.w = a.w;
                 fc.taps = c.taps + (int64_t)a.tap * c.planes * 3; fc.packed = pk; fc.pstride = c.pstride;
-                fc.vertical = a.vertical; fc.sign = a.sign; fc.rw = c.rw; fc.st = c.st;
+                fc.vertical = a.vertical; fc.sign = a.sign; fc.rw = c.rw; fc.st = st;
                 int r = lift_f16_launch(fc);
                 if (r) return r;
             }
@@ -1459,7 +1479,7 @@ static int run_program(const lldwt_lift_op* ops, int n, float* const* bases, con
         if (o.kind != 0) {
             const float* f = (o.kind == 1 || o.kind == 3) ? c.nh : c.nl;
             dim3 grid((unsigned)cdiv(o.w, 256), (unsigned)(o.h < 1024 ? o.h : 1024), (unsigned)c.Z);
-            hipLaunchKernelGGL(k_scale_view, grid, dim3(256), 0, c.st, cv(src), dout, (int)c.batch, o.h, o.w, f, o.kind >= 3,
+            hipLaunchKernelGGL(k_scale_view, grid, dim3(256), 0, st, cv(src), dout, (int)c.batch, o.h, o.w, f, o.kind >= 3,
                                c.saved ? c.saved + o.saved_off : nullptr);
             continue;
         }
@@ -1467,7 +1487,7 @@ static int run_program(const lldwt_lift_op* ops, int n, float* const* bases, con
         const float* pk = c.packed + ((int64_t)o.block * 2 + o.is_u) * c.total;
         const StepBufs b = c.saved ? saved_bufs(c.saved + o.saved_off, c.Z, o.h, o.w, c.C) : ws_bufs(c.step_ws, c.Z, o.h, o.w, c.C);
         int r = dispatch_step(src, din, dout, c.Z, c.batch, o.h, o.w, c.taps + (int64_t)o.tap * c.planes * 3, pk, c.pstride,
-                              c.C, c.K, o.vertical, o.sign, c.rw, c.linear, b, c.st);
+                              c.C, c.K, o.vertical, o.sign, c.rw, c.linear, b, st);
         if (r) return r;
     }
     return check_launch("lifting program");
@@ -1795,9 +1815,12 @@ extern "C" int lldwt_lifting_program(lldwt_lift_op* ops, int max_ops, int64_t Z,
 static int lifting_run(const char* who, int inverse, float* x, float* ll, float* const* yh, int64_t planes, int64_t batch,
                        int64_t H, int64_t W, int levels, const float* taps, const float* packed, int nblocks,
                        int block_offset, int different, int C, int K, float res_weight, int linear, const float* scale_nh,
-                       const float* scale_nl, void* ws, int64_t ws_bytes, float* saved, void* stream) {
+                       const float* scale_nl, void* ws, int64_t ws_bytes, float* saved, void* stream, int split = 0,
+                       void* tail = nullptr, void* fork = nullptr) {
     int r = lifting_args_ok(who, planes, batch, H, W, levels);
     if (r) return r;
+    if (split <= 0 || split >= levels) split = 0;          // nothing on one side: the unsplit call
+    LLDWT_REQUIRE(split == 0 || (!inverse && fork != nullptr && tail != stream), "%s: a split needs an event and a second stream", who);
     LLDWT_REQUIRE(x && ll && yh && taps && packed && ws, "%s: null pointer", who);
     LLDWT_REQUIRE(nblocks >= 2 && block_offset >= 0 && block_offset + ((different && !inverse) ? 2 * levels : 2) <= nblocks,
                   "%s: block_offset=%d exceeds nblocks=%d", who, block_offset, nblocks);
@@ -1822,7 +1845,8 @@ static int lifting_run(const char* who, int inverse, float* x, float* ll, float*
     const int n = build_program(ops, (int)(sizeof(ops) / sizeof(ops[0])), Z, H, W, levels, different, block_offset, inverse,
                                 scale_nh != nullptr, C, nullptr);
     RunCtx c{Z, batch, planes, taps, packed, (int64_t)nblocks * 2 * pack_off(C, K).total, pack_off(C, K).total, C, K,
-             linear, res_weight, scale_nh, scale_nl, base + 4 * half + 2 * quarter, saved, (hipStream_t)stream};
+             linear, res_weight, scale_nh, scale_nl, base + 4 * half + 2 * quarter, saved, (hipStream_t)stream, split,
+             (hipStream_t)tail, (hipEvent_t)fork};
     return run_program(ops, n, bases, c);
 }
 
@@ -1834,6 +1858,29 @@ extern "C" int lldwt_lifting_forward(const float* x, float* ll, float* const* yh
     return lifting_run("lifting_forward", 0, const_cast<float*>(x), ll, yh, planes, batch, H, W, levels, taps, packed,
                        nblocks, block_offset, different, C, K, res_weight, linear, scale_nh, scale_nl, ws, ws_bytes,
                        nullptr, stream);
+}
+
+// The forward transform forked at a level (include/lldwt.h): levels < split_level on `stream`, the rest on `tail_stream`
+extern "C" int lldwt_lifting_forward_split(const float* x, float* ll, float* const* yh, int64_t planes, int64_t batch,
+                                           int64_t H, int64_t W, int levels, const float* taps, const float* packed,
+                                           int nblocks, int block_offset, int different, int C, int K, float res_weight,
+                                           int linear, const float* scale_nh, const float* scale_nl, void* ws,
+                                           int64_t ws_bytes, int split_level, void* stream, void* tail_stream,
+                                           void* fork_event) {
+    return lifting_run("lifting_forward_split", 0, const_cast<float*>(x), ll, yh, planes, batch, H, W, levels, taps, packed,
+                       nblocks, block_offset, different, C, K, res_weight, linear, scale_nh, scale_nl, ws, ws_bytes,
+                       nullptr, stream, split_level, tail_stream, fork_event);
+}
+
+extern "C" int lldwt_lift_split_level(int64_t Z, int64_t H, int64_t W, int levels, int cus) {
+    if (cus <= 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        LLDWT_REQUIRE(hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess,
+                      "lift_split_level: cannot read the device's CU count");
+        cus = prop.multiProcessorCount;
+    }
+    return lift_split_level(Z, H, W, levels, cus);
 }
 
 extern "C" int lldwt_lifting_inverse(const float* ll, const float* const* yh, float* x, int64_t planes, int64_t batch,

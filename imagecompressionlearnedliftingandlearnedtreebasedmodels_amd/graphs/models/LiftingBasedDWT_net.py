@@ -25,8 +25,9 @@ from ... import ops
 from ...entropy_models import EntropyBottleneck, GaussianConditional
 from ...packed_cache import PackedOwnerMixin, cached
 from ... import param_arena
-from ..layers.lifting_dwt_nets import (DWTPytorchWaveletsLayer, LiftingBasedNeuralWaveletv4, _stack,
-                                       decode_planes, encode_planes, encode_shapes, lifting_coeff)
+from ..layers.lifting_dwt_nets import (DWTPytorchWaveletsLayer, LiftingBasedNeuralWaveletv4, _stack, ae_planes,
+                                       decode_planes, encode_planes, encode_shapes, lifting_coeff,
+                                       lifting_forward_planes)
 from ..layers.masked_conv2d import MaskedConv2d
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
@@ -327,6 +328,21 @@ class _CodedLayer(_EntropyLayerBase):
         return one(s_xe), [one(r) for r in s_xo], xe[0], [t[0] for t in xo]
 
 
+def _forward_levels(cls, layers, out_xe, out_xo_list, training):
+    """forward_planes of the layers with a tree pair: xe and the coarsest level (cls._base), then the finer levels from the
+    coarse end, each from its parent (cls._level) -> (si_xe, [si_xo], xe_q, [xo_q]), lists finest first."""
+    L = len(out_xo_list)
+    si_xe, bits, xe_q, parent = cls._base(layers, out_xe, out_xo_list[L - 1], training)
+    si_list, q_list = [bits], [parent]
+    for i in range(L - 2, -1, -1):
+        bits, parent = cls._level(layers, i, out_xo_list[i], parent, training)
+        si_list.append(bits)
+        q_list.append(parent)
+    q_list.reverse()
+    si_list.reverse()
+    return si_xe, si_list, xe_q, q_list
+
+
 def _plc(so):
     o = so * 81
     return nn.Conv2d(so, o, kernel_size=3, stride=1, padding=1), nn.LeakyReLU(), nn.Conv2d(o, o, kernel_size=3, stride=1, padding=1)
@@ -349,27 +365,28 @@ class onlyEZWT(_CodedLayer):
         self.ent_out_xe = EntropyBottleneck(channels=1)
         self.ent_out_xo = EntropyBottleneck(channels=3)
 
+    # the parent of level i is the level i + 1 as the DECODER has it (:832), which hangs on level i + 2 in turn: the levels form
+    # one chain, and the forked eval step (_forward_overlap) has no pair to run before its join
+    PARENT_IS_QUANTISED_INPUT = False
+
     @staticmethod
-    def forward_planes(layers, out_xe, out_xo_list, training):
-        L = len(out_xo_list)
-        si_list, q_list = [], []
+    def _base(layers, out_xe, xo_top, training):
+        """xe and the coarsest level -> (si_xe, bits, xe_q, xo_q)."""
         si_xe, xe_q = ops.factorized_rate(out_xe, _eb_packed([l.ent_out_xe for l in layers]), _noise(out_xe, training))
-        bits, q = ops.factorized_rate(out_xo_list[L - 1], _eb_packed([l.ent_out_xo for l in layers]),
-                                      _noise(out_xo_list[L - 1], training))
-        si_list.append(bits)
-        q_list.append(q)
-        parent = q
-        for i in range(L - 2, -1, -1):
-            seqs = [l.plc_list[i] for l in layers]
-            t = _plc_pair([s[0] for s in seqs], [s[2] for s in seqs], parent, ops.ACT_LRELU)   # :822,835 + :793-794
-            ms = _conv([s[4] for s in seqs], t)
-            bits, q = ops.gauss_rate(out_xo_list[i], ms, _noise(out_xo_list[i], training), want_q=True)   # :832
-            si_list.append(bits)
-            q_list.append(q)
-            parent = q
-        q_list.reverse()
-        si_list.reverse()
-        return si_xe, si_list, xe_q, q_list
+        bits, q = ops.factorized_rate(xo_top, _eb_packed([l.ent_out_xo for l in layers]), _noise(xo_top, training))
+        return si_xe, bits, xe_q, q
+
+    @staticmethod
+    def _level(layers, i, x, parent, training, xo_q=None):
+        """Level i < L - 1 from its parent, the level i + 1 as decoded -> (bits, xo_q)."""
+        seqs = [l.plc_list[i] for l in layers]
+        t = _plc_pair([s[0] for s in seqs], [s[2] for s in seqs], parent, ops.ACT_LRELU)   # :822,835 + :793-794
+        ms = _conv([s[4] for s in seqs], t)
+        return ops.gauss_rate(x, ms, _noise(x, training), want_q=True)                      # :832
+
+    @classmethod
+    def forward_planes(cls, layers, out_xe, out_xo_list, training):
+        return _forward_levels(cls, layers, out_xe, out_xo_list, training)
 
     # ---------------------------------------------------------------- real entropy coding (EXTENSION: the reference's
     # onlyEZWT defines only forward, :759-840; this is what its compress would be with compressai's own
@@ -436,60 +453,63 @@ class DWTConditioned2EntropyLayerZTsepSubbands(_CodedLayer):
         self.csc_xe = stack(self.ses[L - 1])
         self.ent_out_xe = GaussianConditional(scale_table=None, scale_bound=0.11)
 
+    # the parent of level i is quantize(out_xo[i + 1]) (:348), whatever the coarser levels' models say: the forked eval step
+    # (_forward_overlap) runs the pairs of the finest levels before it has anything from the coarse end
+    PARENT_IS_QUANTISED_INPUT = True
+
     @staticmethod
-    def forward_planes(layers, out_xe, out_xo_list, training):
-        L = len(out_xo_list)
+    def _base(layers, out_xe, xo_top, training):
+        """xe and the coarsest level, i = L - 1 -> (si_xe, bits, xe_q, xo_q)."""
+        i = len(layers[0].csc_list) - 1
         idx5 = (0, 2, 4, 6, 8)
         # xe: decoder / context see quantize(x) WITHOUT means (:330); the rate uses an independent noise sample (:334)
         xe_q = ops.quantize(out_xe, _noise(out_xe, training))
-        q_list, si_list = [], []
-        i = L - 1
-        if not training and ops.tail_mode() != "legacy" and out_xe.shape[3:] == out_xo_list[i].shape[3:]:
+        if not training and ops.tail_mode() != "legacy" and out_xe.shape[3:] == xo_top.shape[3:]:
             # the two stacks are independent and each leaves most of the chip idle: one launch per layer for both
-            xo_q = ops.quantize(out_xo_list[i])
+            xo_q = ops.quantize(xo_top)
             ms, ms_xe = _seq_stack_pair([l.csc_list[i] for l in layers], [l.csc_xe for l in layers], xo_q, xe_q, idx5)
             si_xe, _ = ops.gauss_rate(out_xe, ms_xe)
-            bits, _ = ops.gauss_rate(out_xo_list[i], ms)
+            bits, _ = ops.gauss_rate(xo_top, ms)
         else:
             ms = _seq_stack([l.csc_xe for l in layers], xe_q, idx5)
             si_xe, _ = ops.gauss_rate(out_xe, ms, _noise(out_xe, training))
-            xo_q = ops.quantize(out_xo_list[i], _noise(out_xo_list[i], training))
+            xo_q = ops.quantize(xo_top, _noise(xo_top, training))
             ms = _seq_stack([l.csc_list[i] for l in layers], xo_q, idx5)
-            bits, _ = ops.gauss_rate(out_xo_list[i], ms, _noise(out_xo_list[i], training))
-        si_list.append(bits)
-        q_list.append(xo_q)
-        parent = xo_q
-        for i in range(L - 2, -1, -1):
-            x = out_xo_list[i]
-            P, B, so, h, w = x.shape
+            bits, _ = ops.gauss_rate(xo_top, ms, _noise(xo_top, training))
+        return si_xe, bits, xe_q, xo_q
+
+    @staticmethod
+    def _level(layers, i, x, parent, training, xo_q=None):
+        """Level i < L - 1 from its parent, the quantised level i + 1 -> (bits, xo_q).  xo_q: quantize(x), if the caller has it."""
+        P, B, so, h, w = x.shape
+        if xo_q is None:
             xo_q = ops.quantize(x, _noise(x, training))
-            seqs = [l.plc_list[i] for l in layers]
-            plc = _plc_pair([s[0] for s in seqs], [s[2] for s in seqs], parent, ops.ACT_NONE)                # :348,355
-            cg = [l.cgp_out_xo_list[i] for l in layers]
-            cs = [l.csc_list[i] for l in layers]
-            convs = [[s[n] for s in cg] for n in (0, 2, 4, 6)]
-            for m in cs:
-                m.apply_mask_()
-            # The masked csc conv (:275-277,353) feeds cgp layer 0 (:282) with no nonlinearity in between and the regroup
-            # (:357-359) is pure data movement, so its 81 channels per subband are folded into layer 0:
-            #   W0[:, csc half] . Wcsc -> 12 extra input columns = the live taps of the quantised subband itself,
-            # gathered inside the fused kernel.  The csc conv, its 243-channel output and half of layer 0's MACs disappear.
-            packed, dims, packed16 = cached(cg[0], ("cgp_ctx",),
-                                            [p for layer in convs for m in layer for p in (m.weight, m.bias)] +
-                                            [p for m in cs for p in (m.weight, m.bias)],
-                                            lambda: _fold_csc_into_cgp(convs, cs, so))
-            if packed16 is not None and not training and ops.cgp_mode() == "f16x3":
-                # split-fp16 register chain -> (sigma, mu), then the fused Gaussian rate kernel
-                params = ops.cgp16_params(plc, xo_q, packed16, cs[0].kernel_size[0], cs[0].tap_bits())
-                bits, _ = ops.gauss_rate(x, params)
-            else:
-                bits = ops.cgp_rate_ctx(plc, xo_q, x, packed, dims, cs[0].kernel_size[0], cs[0].tap_bits(), _noise(x, training))
-            si_list.append(bits)
-            q_list.append(xo_q)
-            parent = xo_q
-        q_list.reverse()
-        si_list.reverse()
-        return si_xe, si_list, xe_q, q_list
+        seqs = [l.plc_list[i] for l in layers]
+        plc = _plc_pair([s[0] for s in seqs], [s[2] for s in seqs], parent, ops.ACT_NONE)                # :348,355
+        cg = [l.cgp_out_xo_list[i] for l in layers]
+        cs = [l.csc_list[i] for l in layers]
+        convs = [[s[n] for s in cg] for n in (0, 2, 4, 6)]
+        for m in cs:
+            m.apply_mask_()
+        # The masked csc conv (:275-277,353) feeds cgp layer 0 (:282) with no nonlinearity in between and the regroup
+        # (:357-359) is pure data movement, so its 81 channels per subband are folded into layer 0:
+        #   W0[:, csc half] . Wcsc -> 12 extra input columns = the live taps of the quantised subband itself,
+        # gathered inside the fused kernel.  The csc conv, its 243-channel output and half of layer 0's MACs disappear.
+        packed, dims, packed16 = cached(cg[0], ("cgp_ctx",),
+                                        [p for layer in convs for m in layer for p in (m.weight, m.bias)] +
+                                        [p for m in cs for p in (m.weight, m.bias)],
+                                        lambda: _fold_csc_into_cgp(convs, cs, so))
+        if packed16 is not None and not training and ops.cgp_mode() == "f16x3":
+            # split-fp16 register chain -> (sigma, mu), then the fused Gaussian rate kernel
+            params = ops.cgp16_params(plc, xo_q, packed16, cs[0].kernel_size[0], cs[0].tap_bits())
+            bits, _ = ops.gauss_rate(x, params)
+        else:
+            bits = ops.cgp_rate_ctx(plc, xo_q, x, packed, dims, cs[0].kernel_size[0], cs[0].tap_bits(), _noise(x, training))
+        return bits, xo_q
+
+    @classmethod
+    def forward_planes(cls, layers, out_xe, out_xo_list, training):
+        return _forward_levels(cls, layers, out_xe, out_xo_list, training)
 
 
     # ---------------------------------------------------------------- real entropy coding (:374-556): compress_ar /
@@ -994,18 +1014,93 @@ _TRANSFORM = {"CDF97": DWTPytorchWaveletsLayer, "LiftingBasedNeuralWaveletv4": L
 
 
 # ------------------------------------------------------------------------------------------------ nets
-def forward_planes(nets, x, training):
-    """encode -> entropymodel -> decode for a list of per-plane nets; x (P,B,C,H,W) plane-major.
-    (LiftingBasedDWTNet.forward, LiftingBasedDWT_net.py:154-170)"""
-    out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
+def overlap_level(nets, x, training, overlap=None):
+    """The level at which the eval step forks the lifting transform (_forward_overlap), 0 = the serial path.  Serial: training,
+    CDF 9/7, an entropy layer without the tree pair, fewer than 3 levels, a stream under capture -- whatever ``overlap`` says.
+    overlap: None = the rule (ops.lift_split_level, csrc/lift_split.h; it prices the level-0 pair and context MLP as the main
+    stream's block, so it is asked for conditioned2ZTsepSubbands only: onlyEZWT's levels form one chain and leave the main
+    stream the subband MLPs alone), False = serial, True = the rule's level whatever the sizes, an int = that level."""
+    aenc, em = nets[0].autoencoder, nets[0].entropymodel
+    if training or overlap is False or not isinstance(aenc, LiftingBasedNeuralWaveletv4) or \
+            type(em) not in (DWTConditioned2EntropyLayerZTsepSubbands, onlyEZWT):
+        return 0
+    L = aenc.waveletLevel
+    if L < 3 or not x.is_cuda or torch.cuda.is_current_stream_capturing():
+        return 0
+    if overlap is None:
+        if type(em) is not DWTConditioned2EntropyLayerZTsepSubbands:
+            return 0
+        P, B, _, H, W = x.shape
+        return ops.lift_split_level(P * B, H, W, L)
+    k = 2 if overlap is True else int(overlap)
+    return k if 0 < k < L else 0
+
+
+def _forward_overlap(nets, x, k):
+    """encode_planes + the entropy layer's forward_planes (eval) with the coarse end on a second stream:
+      tail stream: lifting levels >= k, the subband MLPs of those levels and of ll, cls._base (xe and the coarsest level: the
+                   context stacks and their rates) and, where the parents are quantised inputs, quantize of the levels k .. L-2
+      main stream: lifting levels < k, their subband MLPs and quantize, then cls._level of the levels 0 .. k-2, whose parents
+                   are the main stream's own
+      join, then cls._level of the levels L-2 .. k-1 (for a layer whose levels form one chain: of all of them).
+    -> (si_xe, [si_xo], xe_q, [xo_q]) as forward_planes returns them, every tensor with the bits of the serial path and ready
+    on the caller's stream.  Tensors made on one stream and read on the other are recorded there (record_stream) or, the
+    transform's ll / yh, held until the join."""
+    aenc = [n.autoencoder for n in nets]
     em = [n.entropymodel for n in nets]
-    si_xe, si_xo, xe_q, xo_q = type(em[0]).forward_planes(em, out_xe, out_xo, training)
+    cls = type(em[0])
+    L = aenc[0].waveletLevel
+    early = cls.PARENT_IS_QUANTISED_INPUT
+    main = torch.cuda.current_stream()
+    out_xo, q, si = [None] * L, [None] * L, [None] * L
+    with ops.eval_overlap(k, x.device) as ov:
+        ll, yh = lifting_forward_planes(aenc, x)
+        with torch.cuda.stream(ov.tail):
+            out_xe = ae_planes([n.Yl_ae for n in aenc], ll, False)
+            for i in range(k, L):
+                out_xo[i] = ae_planes([n.Yh_ae[i] for n in aenc], yh[i], False)
+            si_xe, si[L - 1], xe_q, q[L - 1] = cls._base(em, out_xe, out_xo[L - 1], False)
+            if early:
+                for i in range(L - 2, k - 1, -1):
+                    q[i] = ops.quantize(out_xo[i])
+        for i in range(k):
+            out_xo[i] = ae_planes([n.Yh_ae[i] for n in aenc], yh[i], False)
+        if early:
+            for i in range(k):
+                q[i] = ops.quantize(out_xo[i])
+            for i in range(k - 1):                       # finest first: the largest block starts at once
+                si[i], _ = cls._level(em, i, out_xo[i], q[i + 1], False, q[i])
+        ov.join()
+        for t in [si_xe, xe_q, si[L - 1]] + out_xo[k:] + q[k:]:
+            if t is not None:
+                t.record_stream(main)
+        for i in range(L - 2, -1, -1):
+            if si[i] is None:
+                si[i], q[i] = cls._level(em, i, out_xo[i], q[i + 1], False, q[i])
+    return si_xe, si, xe_q, q
+
+
+def forward_planes(nets, x, training, overlap=None):
+    """encode -> entropymodel -> decode for a list of per-plane nets; x (P,B,C,H,W) plane-major.
+    (LiftingBasedDWTNet.forward, LiftingBasedDWT_net.py:154-170)  overlap: see overlap_level."""
+    k = overlap_level(nets, x, training, overlap)
+    if k:
+        si_xe, si_xo, xe_q, xo_q = _forward_overlap(nets, x, k)
+    else:
+        out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
+        em = [n.entropymodel for n in nets]
+        si_xe, si_xo, xe_q, xo_q = type(em[0]).forward_planes(em, out_xe, out_xo, training)
     xhat = decode_planes([n.autoencoder for n in nets], xe_q, xo_q)
     return xhat, si_xe, si_xo
 
 
-def rate_planes(nets, x, training=False):
-    """The metric's path: lifting DWT encode + entropy-model forward (no decode) -> (si_xe, si_xo_list)."""
+def rate_planes(nets, x, training=False, overlap=None):
+    """The metric's path: lifting DWT encode + entropy-model forward (no decode) -> (si_xe, si_xo_list).  overlap: see
+    overlap_level (None: the eval step forks where the rule says it pays)."""
+    k = overlap_level(nets, x, training, overlap)
+    if k:
+        si_xe, si_xo, _, _ = _forward_overlap(nets, x, k)
+        return si_xe, si_xo
     out_xe, out_xo = encode_planes([n.autoencoder for n in nets], x)
     em = [n.entropymodel for n in nets]
     si_xe, si_xo, _, _ = type(em[0]).forward_planes(em, out_xe, out_xo, training)

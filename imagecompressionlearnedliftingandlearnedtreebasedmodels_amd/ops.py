@@ -6,6 +6,7 @@ Tensor convention: "plane-major" (P, B, C, h, w) fp32 contiguous CUDA(HIP) tenso
 import collections
 import ctypes as C
 import os
+import threading
 
 import torch
 
@@ -86,13 +87,102 @@ def _opt(t, name="tensor"):
 
 
 def workspace(nbytes, device):
-    """Grow-only scratch buffer per device (the library never allocates: include/lldwt.h conventions)."""
+    """Grow-only scratch buffer per device (the library never allocates: include/lldwt.h conventions).  While a forked
+    lifting_forward has it in use on the tail stream (eval_overlap), nobody else gets it: asking is an error."""
     key = (device.type, device.index)
+    ov = current_overlap()
+    if ov is not None and ov.lent and ov.ws_key == key:
+        raise _lib.LLDWTError("workspace: lent to the tail stream of a forked lifting transform until the join")
     buf = _ws.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
         _ws[key] = buf
     return buf
+
+
+# ---- the forked eval step (DESIGN.md 9 item 7): the coarse end of the transform on a second stream ---------------------------
+class _Overlap:
+    """State of one eval_overlap context: the level the next lifting_forward forks at, the tail stream and the fork / join
+    events; ``lent``: the workspace is with the tail stream, from the forked call until join()."""
+
+    def __init__(self, split, device, tail, fork, done):
+        self.split, self.tail, self.fork, self.done, self.lent = int(split), tail, fork, done, False
+        self.ws_key = (device.type, device.index)       # the workspace() this context lends
+
+    def join(self):
+        """The current stream waits for everything enqueued on the tail so far; the workspace comes back."""
+        if self.lent:
+            self.done.record(self.tail)
+            torch.cuda.current_stream().wait_event(self.done)
+            self.lent = False
+
+
+# One context per host thread (a thread drives one device at a time); the streams and events are per (thread, device), so two
+# threads that run eval steps on two devices share nothing here.  workspace() itself is one buffer per device, as ever: two
+# host threads on ONE device were never served by it (INTEGRATION.md, ownership and threading).
+_tls = threading.local()
+_tail_priority = [-1]           # -1: the highest priority the device offers, 0: the default (DESIGN.md 9 item 7 has both measured)
+
+
+def current_overlap():
+    """The eval_overlap context the calling thread is inside, or None."""
+    return getattr(_tls, "ov", None)
+
+
+def lift_split_level(Z, H, W, levels, cus=0):
+    """The rule of the forked eval step (csrc/lift_split.h through lldwt_lift_split_level): the level to fork at, or 0."""
+    r = _lib.load().lldwt_lift_split_level(int(Z), int(H), int(W), int(levels), int(cus))
+    check(min(r, 0), "lift_split_level")
+    return r
+
+
+def set_tail_priority(priority):
+    """Priority of the tail stream (torch.cuda.Stream's: -1 high, 0 default) for the streams created from now on; the
+    calling thread's existing ones are dropped.  Diagnostics: tools/bench_tail_priority.py, the priority comparison of
+    DESIGN.md 9 item 7."""
+    if current_overlap() is not None:
+        raise _lib.LLDWTError("set_tail_priority: inside an eval_overlap context")
+    _tail_priority[0] = int(priority)
+    _tls.tail = {}
+
+
+def tail_stream(device):
+    """The second stream of the forked eval step and its two events, created once per device (and host thread)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    tails = _tls.__dict__.setdefault("tail", {})
+    ent = tails.get(idx)
+    if ent is None:
+        with torch.cuda.device(idx):
+            st = torch.cuda.Stream(priority=_tail_priority[0])
+            fork, done = torch.cuda.Event(), torch.cuda.Event()
+            fork.record()           # torch creates the HIP event at its first record; the library is handed the handle
+        ent = tails[idx] = (st, fork, done)
+    return ent
+
+
+class eval_overlap:
+    """``with ops.eval_overlap(k, device) as ov:`` -- a lifting_forward inside forks at level k (lldwt_lifting_forward_split):
+    levels < k on the current stream, the rest on ov.tail, where the caller continues their work under
+    torch.cuda.stream(ov.tail).  ov.join() makes the current stream wait for the tail; leaving the context joins if the caller
+    has not.  Not for a stream under capture, and not re-entrant."""
+
+    def __init__(self, split_level, device):
+        self.args = (split_level, device)
+
+    def __enter__(self):
+        if current_overlap() is not None:
+            raise _lib.LLDWTError("eval_overlap: already inside one")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.LLDWTError("eval_overlap: the current stream is under capture")
+        _tls.ov = _Overlap(self.args[0], self.args[1], *tail_stream(self.args[1]))
+        return _tls.ov
+
+    def __exit__(self, *exc):
+        try:
+            _tls.ov.join()
+        finally:
+            _tls.ov = None
+        return False
 
 
 def rgb_to_ycc(x):
@@ -684,6 +774,21 @@ def lifting_forward(x, taps, packed, levels, Cc, K, res_weight, linear=False, di
     yh = [torch.empty(P, B, 3, H >> (i + 1), W >> (i + 1), device=dev, dtype=torch.float32) for i in range(levels)]
     nb = lib.lldwt_lifting_ws_bytes(P * B, H, W, Cc)
     ws = workspace(nb, dev)
+    ov = current_overlap()
+    if ov is not None and 0 < ov.split < levels:
+        # forked (eval_overlap): yh[:split] are ordered on the current stream, yh[split:] and ll on ov.tail; the workspace
+        # stays with the tail until ov.join()
+        fork = ov.fork.cuda_event
+        if not fork or ov.tail.cuda_stream == torch.cuda.current_stream().cuda_stream:
+            raise _lib.LLDWTError("lifting_forward: the overlap context has no event handle or no second stream")
+        ov.lent = True          # before the call: if it fails behind the fork, leaving the context still joins the tail
+        check(lib.lldwt_lifting_forward_split(_chk(x, "x"), _chk(ll), _ptr_array(yh), P, B, H, W, levels, _chk(taps, "taps"),
+                                              _chk(packed, "packed"), int(packed.shape[1]), int(block_offset),
+                                              int(bool(different)), Cc, K, float(res_weight), int(bool(linear)),
+                                              _opt(scale_nh), _opt(scale_nl), C.c_void_p(ws.data_ptr()), nb, ov.split,
+                                              _stream(), C.c_void_p(ov.tail.cuda_stream), C.c_void_p(fork)),
+              "lifting_forward_split")
+        return ll, yh
     check(lib.lldwt_lifting_forward(_chk(x, "x"), _chk(ll), _ptr_array(yh), P, B, H, W, levels, _chk(taps, "taps"),
                                     _chk(packed, "packed"), int(packed.shape[1]), int(block_offset),
                                     int(bool(different)), Cc, K, float(res_weight), int(bool(linear)), _opt(scale_nh),

@@ -276,6 +276,25 @@ int lldwt_lifting_forward(const float* x, float* ll, float* const* yh, int64_t p
                           int64_t W, int levels, const float* taps, const float* packed, int nblocks,
                           int block_offset, int different, int C, int K, float res_weight, int linear,
                           const float* scale_nh, const float* scale_nl, void* ws, int64_t ws_bytes, void* stream);
+/* lldwt_lifting_forward forked at a level: the ops of the levels < split_level (lldwt_lift_op.level) are enqueued on `stream`,
+ * then `fork_event` (a hipEvent_t of the caller's, as void*; the library creates none) is recorded there, `tail_stream` waits
+ * for it, and the ops of the levels >= split_level -- their gain ops and the final ll included -- are enqueued on `tail_stream`.
+ * Plain stream and event calls only; no kernel waits for another.  The results have the bits of the unsplit call.
+ *   ordered on `stream`:      yh[0 .. split_level-1]
+ *   ordered on `tail_stream`: yh[split_level .. levels-1] and ll
+ *   `ws` (the LL ping-pong of the levels below the fork, the row / column temporaries, the step workspace) is read and
+ *   written by the tail stream's launches: it must not be handed to any other work, on either stream, until the tail
+ *   stream's work of this call is done (the caller joins: an event recorded on `tail_stream` that `stream` waits for).
+ *   x is read on `stream` only when split_level >= 1.
+ * split_level <= 0 or >= levels: the unsplit call on `stream` (tail_stream and fork_event are not touched).
+ * lldwt_lift_split_level: where the eval step of the tree-pair layers forks the transform (csrc/lift_split.h, the one rule):
+ *   0 = do not fork, else the split_level.  Z = planes*batch; cus = compute units, <= 0: those of the current device. */
+int lldwt_lifting_forward_split(const float* x, float* ll, float* const* yh, int64_t planes, int64_t batch, int64_t H,
+                                int64_t W, int levels, const float* taps, const float* packed, int nblocks,
+                                int block_offset, int different, int C, int K, float res_weight, int linear,
+                                const float* scale_nh, const float* scale_nl, void* ws, int64_t ws_bytes,
+                                int split_level, void* stream, void* tail_stream, void* fork_event);
+int lldwt_lift_split_level(int64_t Z, int64_t H, int64_t W, int levels, int cus);
 /* Inverse (LiftingBasedNeuralWaveletv4.decode, lifting_dwt_nets.py:762-781; wavelet_inverse_v2.py:20-92).  */
 int lldwt_lifting_inverse(const float* ll, const float* const* yh, float* x, int64_t planes, int64_t batch,
                           int64_t H, int64_t W, int levels, const float* taps, const float* packed, int nblocks,
@@ -296,7 +315,7 @@ typedef struct lldwt_lift_op {
     int64_t off_dout, sz_dout, sy_dout, sx_dout;
     int32_t h, w, vertical, tap, block, is_u;
     float sign;
-    int32_t pad_;
+    int32_t level;      /* the transform level whose buffers the op writes (0 = finest) */
     int64_t saved_off;
 } lldwt_lift_op;
 int lldwt_lifting_program(lldwt_lift_op* ops, int max_ops, int64_t Z, int64_t H, int64_t W, int levels, int different,
